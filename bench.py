@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- aligned frames/sec on synthetic video + bgr_image_warp HBM roofline (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--clips-per-gpu C]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--clips-per-gpu C] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline and nothing else: set-up, --warmup steps, the untimed pre-roll, exactly --steps timed steps, the
+outputs (--dump-outputs), the JSON line.  Everything else the line can carry -- the other warp forms, the reference's own pipeline,
+the CPU baseline and the parity gate riding on it, the isolated 4K roofline, live counter passes, the host-fed / drop-in legs, the
+c3 / c5 / c4_strong legs, the repeats of the timed loop and the clock probe -- runs only with --full (the --no-* switches prune it).
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64): the align +
+warp workloads `aligned` (1 / 0 per frame), `transforms` (A, B, TX, TY per frame) and `warped`, the stabilizer workload
+`has_output` and `stabilized`; image outputs are a fixed seeded sample of 2^22 values when larger (rank 0's clips).
 
 A "step" is one pass of the hot path over the rank's clips, which are already resident in HBM:
   c2 (default, BASELINE configs[1]): one 240-frame 1080p BGR clip, pyramid_min_width=256 (3 levels): every frame is
@@ -17,15 +25,16 @@ barriers that bracket the timed region and one max/sum all-reduce for the report
 The warp of the timed step is bgr_image_warp in its SEPARABLE form (VS_WARP_LANCZOS2_SEP, `value_warp_mode`: the contracted weights
 and taps, summed rows first, then columns, over the product of the two 1-D weight sums -- equal to generators.cpp:687-697 in real
 arithmetic, a reassociation inside the slack of the reference's own non-strict_float build), admitted as `value` by SURVEY 8(d)'s
-integer gate, which every run re-checks against the UN-contracted oracle (`parity.separable_vs_exact`: max 1 LSB, >= 99.99 % of the
-samples identical; a broken gate fails the run).  The same step with the un-contracted sampler is `exact_warp` (the figure to compare
+integer gate, which every --full run re-checks against the UN-contracted oracle (`parity.separable_vs_exact`: max 1 LSB, >= 99.99 % of
+the samples identical; a broken gate fails the run).  The same step with the un-contracted sampler is `exact_warp` (the figure to compare
 across rounds: rounds 1-3 reported it as `value`), with the contracted one (round 4's `value`) `contracted_warp`.
 Timing: after the driver's --warmup steps an UNTIMED pre-roll keeps stepping until >= 150 ms of launches have run (the shader clock
 needs ~40 ms of continuous work to settle: tools/clock_settling.py); then the driver's loop -- exactly --steps steps between barrier +
-synchronize -- runs three times back to back: `value` / `ms_per_step` are the MEDIAN repeat, `value_spread` has min / median / max,
-`shader_clock_mhz` the clock a probe kernel issued directly behind the loops sees (s_memtime / s_memrealtime).
+synchronize -- runs once: `value` / `ms_per_step` are its figures.  With --full it runs three times back to back: `value` / `ms_per_step`
+are the MEDIAN repeat, `value_spread` has min / median / max, `shader_clock_mhz` the clock a probe kernel issued directly behind the
+loops sees (s_memtime / s_memrealtime).
 
-The JSON line also carries
+The JSON line also carries (`roofline` -- its live traffic aside -- and `ranks` in every run, the rest with --full)
   roofline      the dominant kernel of the timed region (bgr_image_warp): algorithmic bytes / mean launch time, HIP
                 events on the launch stream, against the 8 TB/s HBM peak; `traffic` scaled from the committed PMC passes
   default_warp  (in the headline's object and in c3) the reference's OWN pipeline on the workload: align + cv::warpAffine's fixed-point bilinear
@@ -79,7 +88,9 @@ WARP_MODES = {
 }
 WARP_BENCH_NAME = {"separable": "sep", "contracted": "fast", "exact": "lanczos2", "bilinear_cv": "cv"}          # tools/warp_bench.py --mode
 PREROLL_SECONDS = 0.15
-REPEATS = 3
+REPEATS = 3                 # repeats of the timed loop with --full (a plain run times it once)
+DUMP_SAMPLES = 1 << 22      # --dump-outputs: values per image output at most (16 MB as float32) ...
+DUMP_SEED = 20251015        # ... drawn with this seed when the output is larger
 
 WORKLOADS = {
     "c2": dict(name="1080p single clip, 3-level pyramid (pyramid_min_width=256), align + bgr_image_warp Lanczos2",
@@ -511,6 +522,7 @@ class AlignWarp:
                                     **params_kw)
         self.warped = None if args.no_warp else torch.empty_like(self.frames)
         self.ev = []
+        self.last = None                  # (status, transforms) of the latest step: what --dump-outputs writes
         self.shared(True)
 
     def shared(self, on):
@@ -536,6 +548,7 @@ class AlignWarp:
 
     def step(self, timed=False, mode=None, border=None):
         status, ts = self.align()
+        self.last = (status, ts)
         if not self.args.no_warp:
             if mode is None:
                 mode = getattr(self.capi, WARP_MODES[self.args.warp_mode][0])
@@ -587,6 +600,29 @@ class AlignWarp:
         self.frames = self.warped = self.clips = None
         self.aligner = None
         self.torch.cuda.empty_cache()
+
+
+def sample_frames(torch, t, frames):
+    """float32 values of the frames `frames` (indices into the first axis) of device tensor t: all of them when they number at most
+    DUMP_SAMPLES, else DUMP_SAMPLES positions drawn with DUMP_SEED (sorted: the same positions in every run with the same arguments)"""
+    import numpy as np
+    frames = np.asarray(frames, dtype=np.int64)
+    per = t[0].numel()
+    total = len(frames) * per
+    if total <= DUMP_SAMPLES:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLES, dtype=np.int64))
+    flat = frames[pos // per] * per + pos % per                 # < t.numel(): frame index < t.shape[0], offset < per
+    return t.reshape(-1).index_select(0, torch.from_numpy(flat).to(t.device)).cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    sys.stderr.write("bench.py: outputs of the last timed step in %s: %s\n" % (d, ", ".join("%s %s" % (k, a.shape) for k, a in arrays.items())))
 
 
 def stage_table(t, steps):
@@ -703,6 +739,12 @@ def main():
     ap.add_argument("--no-c4-strong", action="store_true", help="skip the strong-scaling leg")
     ap.add_argument("--c4-clips", type=int, default=64, help="total clips of the strong-scaling leg (rehearsals use fewer)")
     ap.add_argument("--c4-frames", type=int, default=120)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the other warp forms and the reference's own pipeline, the CPU baseline and the "
+                         "parity gate, the 4K roofline, live counter passes, the host-fed / drop-in legs, c3 / c5 / c4_strong, three repeats of the "
+                         "timed loop (the --no-* switches above prune these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     default_run = args.workload is None
     if default_run:
@@ -836,11 +878,12 @@ def main():
                                **params_kw)
         out_buf = torch.empty((n_clips * n, H - 2 * crop, W - 2 * crop, 3), dtype=clips[0].dtype, device=dev)
         aw = None
+        stab_has = []
 
         def step(timed):
             # all clips of the rank in one call (vs_stabilizer_process_clips): each clip through a fresh stabilizer,
             # alignment and warps of all clips batched together
-            r, _ = stab.process_clips_device(all_frames.data_ptr(), n_clips, n, W, H, fmt, out_buf.data_ptr())
+            r, stab_has[:] = stab.process_clips_device(all_frames.data_ptr(), n_clips, n, W, H, fmt, out_buf.data_ptr())
             return r
     else:
         aw = AlignWarp(torch, capi, synth, dev, wl, n, n_clips, seeds, params_kw, args, wl["seed"] + 1000 * rank)
@@ -863,23 +906,38 @@ def main():
     preroll_s = time.perf_counter() - t_pre
     if aw:
         aw.aligner.enable_timing(True)
-    # the driver's loop, REPEATS times back to back; whole-job numbers per repeat: max seconds over ranks, frames summed over ranks (the only
-    # collectives of the run)
+    # the driver's loop (REPEATS times back to back with --full); whole-job numbers per repeat: max seconds over ranks, frames summed over
+    # ranks (the only collectives of the run)
+    repeats = REPEATS if args.full else 1
     reps = []
-    for _ in range(REPEATS):
+    for _ in range(repeats):
         dt_r, good = timed_loop(lambda: step(True), args.steps)
         reps.append(vsdist.aggregate(dt_r, n * n_clips * args.steps, int(good) * args.steps, device=red_dev))
+    if args.dump_outputs and rank == 0:
+        # what the timed path returned in its last step, before any other leg reuses the buffers
+        import numpy as np
+        if aw:
+            status, ts = aw.last
+            arrays = {"aligned": np.array(list(status), dtype=np.float32),
+                      "transforms": np.array([t.tup() for t in ts], dtype=np.float64).reshape(-1, 4)}
+            if aw.warped is not None:
+                arrays["warped"] = sample_frames(torch, aw.warped, range(aw.N))
+        else:
+            arrays = {"has_output": np.array(stab_has, dtype=np.float32),
+                      "stabilized": sample_frames(torch, out_buf, [i for i, h in enumerate(stab_has) if h])}
+        dump_outputs(args.dump_outputs, arrays)
     shader_mhz = None
-    try:
-        shader_mhz = round(capi.shader_clock_probe(stream.cuda_stream), 1)      # issued directly behind the timed loops
-    except Exception:                                        # noqa: BLE001 -- a diagnostic must not cost the line its headline
-        pass
-    order = sorted(range(REPEATS), key=lambda i: reps[i][0])
-    dt, total_frames, total_good = reps[order[REPEATS // 2]]
+    if args.full:
+        try:
+            shader_mhz = round(capi.shader_clock_probe(stream.cuda_stream), 1)      # issued directly behind the timed loops
+        except Exception:                                        # noqa: BLE001 -- a diagnostic must not cost the line its headline
+            pass
+    order = sorted(range(repeats), key=lambda i: reps[i][0])
+    dt, total_frames, total_good = reps[order[repeats // 2]]
     tm = aw.aligner.timings() if aw else None
 
     align_only = None
-    if aw and not args.no_warp:
+    if args.full and aw and not args.no_warp:
         # second, separately reported figure: the alignment stages alone (BASELINE configs[1] read literally)
         aw.shared(False)                                       # nothing else runs: one 512-thread workgroup per pair
         aw.aligner.enable_timing(True)
@@ -890,7 +948,7 @@ def main():
 
     others = {}
     default_leg = None
-    if aw and not args.no_warp:
+    if args.full and aw and not args.no_warp:
         # beside `value`: the same step with the OTHER members of the sampler family -- `exact_warp` (VS_WARP_LANCZOS2: the reference's
         # written, un-contracted rounding order; rounds 1-3's `value`), `contracted_warp` (round 4's `value`), `separable_warp`
         for name, (gname, _, _) in WARP_MODES.items():
@@ -906,7 +964,7 @@ def main():
                                           aggregate=lambda dt_, fr_, gd_: vsdist.aggregate(dt_, fr_, gd_, device=red_dev))
 
     stable = None
-    if aw and not args.no_warp and args.select == "device":
+    if args.full and aw and not args.no_warp and args.select == "device":
         # fourth figure: the same step with the selection under the documented STL-independent rule (VS_SELECT_STABLE, SURVEY 8(f)
         # rank 1; bit-identical to the oracle's select rule 1: tests/test_select_stable_gpu.py) -- beside `value`, never as `value`
         aw.aligner.set_select_mode(capi.SELECT_STABLE)
@@ -918,6 +976,7 @@ def main():
 
     rc = 0
     out = None
+    gate_runs = args.full and not args.no_cpu_baseline and world == 1        # the parity gate rides on the CPU baseline
     if rank == 0:
         out = {
             "metric": "aligned frames/sec", "value": round((total_good if not wl["stabilizer"] else total_frames) / dt, 2), "unit": "frames/s",
@@ -927,14 +986,14 @@ def main():
             "dist_backend": (backend_used if dist is not None else None), "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak",
             "value_warp_mode": None if (args.no_warp and not wl["stabilizer"]) else args.warp_mode,
-            "value_spread": {"repeats": REPEATS, "value_is": "median",
-                             "values": [round((reps[i][2] if not wl["stabilizer"] else reps[i][1]) / reps[i][0], 2) for i in reversed(order)],
-                             "ms_per_step": [round(1e3 * reps[i][0] / args.steps, 4) for i in order],
-                             "note": "the driver's loop (exactly --steps steps between barrier + synchronize) run %d times back to back; "
-                                     "`values` ascending: min, median, max" % REPEATS},
+            **({"value_spread": {"repeats": REPEATS, "value_is": "median",
+                                 "values": [round((reps[i][2] if not wl["stabilizer"] else reps[i][1]) / reps[i][0], 2) for i in reversed(order)],
+                                 "ms_per_step": [round(1e3 * reps[i][0] / args.steps, 4) for i in order],
+                                 "note": "the driver's loop (exactly --steps steps between barrier + synchronize) run %d times back to back; "
+                                         "`values` ascending: min, median, max" % REPEATS}} if args.full else {}),
             "preroll": {"steps": preroll_steps, "seconds": round(preroll_s, 4),
                         "note": "untimed steps after --warmup until >= %.2f s of launches have run (clock settling)" % PREROLL_SECONDS},
-            "shader_clock_mhz": shader_mhz,
+            **({"shader_clock_mhz": shader_mhz} if args.full else {}),
             "vs_baseline": None, "dtype": "u8" if bits == 8 else "u16", "data": "synthetic",
             "config": {"workload": wl["name"] if not args.default_levels else
                        wl["name"].split(",")[0] + ", reference default pyramid (pyramid_min_width = pyramid_min_height = 20)",
@@ -951,7 +1010,8 @@ def main():
                        "warp": None if (args.no_warp and not wl["stabilizer"]) else
                        ("bgr_image_warp lanczos2, un-contracted (VS_WARP_LANCZOS2)" if args.warp_mode == "exact" else
                         "bgr_image_warp %s: <= 1 LSB from the un-contracted order, >= 99.99 %% identical "
-                        "(SURVEY 8(d) integer gate, checked in this run: parity.%s_vs_exact)" % (WARP_MODES[args.warp_mode][2], args.warp_mode)),
+                        "(SURVEY 8(d) integer gate, checked %s: parity.%s_vs_exact)"
+                        % (WARP_MODES[args.warp_mode][2], "in this run" if gate_runs else "by bench.py --full", args.warp_mode)),
                        "resident": "HBM",
                        "select_mode_in_force": (aw.aligner.select_mode() if aw else stab.select_mode())},
             "frames_per_step": total_frames // args.steps,
@@ -962,7 +1022,7 @@ def main():
         if backend_note:
             out["dist_backend_note"] = "RCCL could not be initialised (%s): the report scalars were reduced over gloo on the host" % backend_note
         if tm:
-            out["stages"] = stage_table(tm, args.steps * REPEATS)
+            out["stages"] = stage_table(tm, args.steps * repeats)
             out["gn_iterations_per_frame"] = round(tm["gn_iterations"] / max(1, tm["frames"]), 2)
         if align_only:
             dt_a, frames_a, tm_a = align_only
@@ -987,7 +1047,7 @@ def main():
                                             "bit-identical to the oracle's select rule 1"}
         if aw and aw.ev:
             out["roofline"] = roofline_of(aw, n * n_clips)
-            if default_run and world == 1 and not args.no_live_traffic and args.warp_mode != "exact" and not args.no_warp:
+            if args.full and default_run and world == 1 and not args.no_live_traffic and args.warp_mode != "exact" and not args.no_warp:
                 # the HBM-side bytes of the dominant kernel, measured live (child processes; the figure from the committed passes stays
                 # beside it, so a regression shows as a disagreement between the two)
                 live, how = measure_traffic_live(aw.W, aw.H, n * n_clips, aw.bits, mode=args.warp_mode)
@@ -1004,7 +1064,7 @@ def main():
                     out["default_warp"]["roofline"]["traffic_source"] = how_cv
 
     # ---- parity gate + CPU baseline (rank 0 of a one-GPU run; the oracle is the checker, never the thing measured) ----------
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and gate_runs:
         fh = clips[0][: min(n, 64)].cpu().numpy()
         if bits != 8:
             fh = fh.view("uint16")
@@ -1020,19 +1080,19 @@ def main():
                 out["parity"] = {"pass": False, "error": repr(e)}
                 rc = 3
 
-    if rank == 0 and not args.no_roofline_4k:
+    if rank == 0 and args.full and not args.no_roofline_4k:
         out["roofline_4k"] = roofline_4k(torch, capi, dev, stream)
-    if rank == 0 and not args.no_host_fed and aw is not None:
+    if rank == 0 and args.full and not args.no_host_fed and aw is not None:
         out["host_fed"] = host_fed(torch, capi, dev, clips[0], W, H, fmt, params_kw)
-    if rank == 0 and world == 1 and not args.no_drop_in and aw is not None:
+    if rank == 0 and args.full and world == 1 and not args.no_drop_in and aw is not None:
         try:
             fh = clips[0][: min(n, 48)].cpu().numpy()
             out["drop_in"] = {"%dp" % H: drop_in(capi, dev.index, fh.view("uint16") if bits != 8 else fh, params_kw)}
         except Exception as e:
             out["drop_in"] = {"error": repr(e)}
 
-    # ---- the 4K half of the metric (default one-GPU run): BASELINE configs[2] through the same step --------------------------
-    if default_run and world == 1 and not args.no_c3 and aw is not None:
+    # ---- the 4K half of the metric (--full, default one-GPU run): BASELINE configs[2] through the same step -------------------
+    if args.full and default_run and world == 1 and not args.no_c3 and aw is not None:
         aw.free()
         aw = None
         clips = None
@@ -1092,8 +1152,8 @@ def main():
         except Exception as e:
             out["c3"] = {"error": repr(e)}
 
-    # ---- BASELINE configs[4] (default one-GPU run): 4K 10-bit clips through the full stabilizer loop ----------------------------
-    if default_run and world == 1 and not args.no_c5:
+    # ---- BASELINE configs[4] (--full, default one-GPU run): 4K 10-bit clips through the full stabilizer loop ---------------------
+    if args.full and default_run and world == 1 and not args.no_c5:
         if aw is not None:
             aw.free()
             aw = None
@@ -1151,10 +1211,10 @@ def main():
             out["c5"] = {"error": repr(e)}
             torch.cuda.empty_cache()
 
-    # ---- BASELINE configs[3] as a strong-scaling leg: 64 clips in total, clip i -> rank i mod N --------------------------------
+    # ---- BASELINE configs[3] as a strong-scaling leg (--full): 64 clips in total, clip i -> rank i mod N -----------------------
     # (on one GPU the leg is the N = 1 point of the strong curve: 64 clips = 48 GB of frames + 48 GB of output; it runs when the
     # card has the room, and a failure there must not cost the line its headline)
-    want_c4 = default_run and not args.no_c4_strong and not args.no_warp
+    want_c4 = args.full and default_run and not args.no_c4_strong and not args.no_warp
     if want_c4 and world == 1 and not args.c4_strong:
         need = 2.3 * args.c4_clips * args.c4_frames * 1920 * 1080 * 3
         want_c4 = torch.cuda.mem_get_info(dev)[0] > need

@@ -1,5 +1,6 @@
-"""bench.py contract on the GPU box: one JSON line with the driver's keys, the roofline and cpu_baseline objects;
-and the N > 1 flow rehearsed with two gloo ranks sharing the one GPU (the real run uses nccl = RCCL, one GPU per rank)."""
+"""bench.py contract on a machine with a GPU: one JSON line with the driver's keys; with --full the roofline and cpu_baseline objects and every
+other leg, without it the headline alone; --dump-outputs; and the N > 1 flow rehearsed with two gloo ranks sharing the one GPU (the real run
+uses nccl = RCCL, one GPU per rank)."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ def _last_json(out):
 
 
 def test_bench_line_contract(gpu_vs):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "8", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--frames", "8", "--steps", "2", "--warmup", "1",
                           "--c4-clips", "3", "--c4-frames", "6", "--c5-clips", "2"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json(out.stdout)
@@ -106,13 +107,66 @@ def test_bench_line_contract(gpu_vs):
     assert hf["identical_to_device_resident"] is True and hf["value"] > 0 and 0 < hf["of_pinned_h2d"] <= 1.05
 
 
+FULL_ONLY = {"value_spread", "shader_clock_mhz", "align_only", "exact_warp", "contracted_warp", "default_warp", "stable_select", "cpu_baseline",
+             "parity", "roofline_4k", "roofline_4k_summary", "host_fed", "drop_in", "c3", "c5", "c4_strong"}
+
+
+def _plain(*extra, dump=None):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] + list(extra)
+    if dump is not None:
+        cmd += ["--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return _last_json(out.stdout)
+
+
+def _load(d):
+    import numpy as np
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()), {k: a.dtype for k, a in got.items()}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    return got
+
+
+def test_plain_bench_line_is_the_headline_alone(gpu_vs, tmp_path):
+    """without --full: the headline's keys, exactly --steps timed steps once, none of the other legs; its outputs written, and written the same
+    by a second run with the same arguments"""
+    import numpy as np
+    j = _plain("--frames", "8", dump=tmp_path / "a")
+    assert KEYS <= set(j) and not (FULL_ONLY & set(j)), sorted(FULL_ONLY & set(j))
+    assert j["metric"] == "aligned frames/sec" and j["unit"] == "frames/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["frames_per_step"] == 8 and j["aligned_per_step"] == 7
+    assert j["value"] > 0 and abs(j["value"] - 7 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-3 * j["value"]
+    assert j["roofline"]["bytes_per_launch"] == 1920 * 1080 * 3 * 2 * 8 and "not measured in this run" in j["roofline"]["traffic_source"]
+    a = _load(tmp_path / "a")
+    assert set(a) == {"aligned", "transforms", "warped"}
+    assert a["aligned"].shape == (8,) and a["aligned"].sum() == 7 and a["aligned"][0] == 0
+    assert a["transforms"].shape == (8, 4) and a["transforms"].dtype == np.float64 and np.isfinite(a["transforms"]).all()
+    assert a["warped"].shape == (1 << 22,) and 0 <= a["warped"].min() and a["warped"].max() <= 255 and a["warped"].std() > 10
+    _plain("--frames", "8", dump=tmp_path / "b")
+    b = _load(tmp_path / "b")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_outputs_of_the_stabilizer_workload(gpu_vs, tmp_path):
+    """c5's step returns stabilized frames only where has_output says so: the sample is drawn from those frames"""
+    import numpy as np
+    j = _plain("--workload", "c5", "--frames", "12", "--clips-per-gpu", "1", dump=tmp_path)
+    assert j["dtype"] == "u16" and j["outputs_per_step"] == 2 and not (FULL_ONLY & set(j))
+    a = _load(tmp_path)
+    assert set(a) == {"has_output", "stabilized"}
+    assert a["has_output"].tolist() == [0.0] * 10 + [1.0] * 2
+    assert a["stabilized"].shape == (1 << 22,) and a["stabilized"].max() <= 1023 and a["stabilized"].std() > 10
+
+
 RANKS = 5      # the box's process guard allows six GPU processes at once; this pytest process is one of them
 
 
 def _spawn(extra_env=None, clips=64, frames=4):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(RANKS), "--frames", "6", "--steps", "2", "--warmup", "1",
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(RANKS), "--frames", "6", "--steps", "2", "--warmup", "1",
                            "--no-cpu-baseline", "--no-roofline-4k", "--no-host-fed", "--dist-backend", "gloo", "--device", "0",
                            "--c4-clips", str(clips), "--c4-frames", str(frames), "--c4-strong"],
                           capture_output=True, text=True, timeout=900, env=env)

@@ -5,14 +5,23 @@ import numpy as np
 import pytest
 
 
-def test_optimal_dft_size(oracle, vs):
-    # cv::getOptimalDFTSize: smallest 2^a 3^b 5^c >= n
-    want = {1: 1, 2: 2, 7: 8, 11: 12, 13: 15, 17: 18, 61: 64, 80: 80, 97: 100, 120: 120, 135: 135, 270: 270, 271: 288,
-            480: 480, 481: 486, 540: 540, 960: 960, 1081: 1125, 4097: 4320}
-    for n, w in want.items():
+# cv::getOptimalDFTSize: smallest 2^a 3^b 5^c >= n
+OPTIMAL_DFT_SIZE = {1: 1, 2: 2, 7: 8, 11: 12, 13: 15, 17: 18, 61: 64, 80: 80, 97: 100, 120: 120, 135: 135, 270: 270, 271: 288,
+                    480: 480, 481: 486, 540: 540, 960: 960, 1081: 1125, 4097: 4320}
+
+
+def test_optimal_dft_size(oracle):
+    for n, w in OPTIMAL_DFT_SIZE.items():
         assert oracle.optimal_dft_size(n) == w, n
-        assert vs.optimal_dft_size(n) == w, n          # host-side function of the product library, same rule
-    assert oracle.optimal_dft_size(0) == -1 and vs.optimal_dft_size(0) == -1
+    assert oracle.optimal_dft_size(0) == -1
+
+
+def test_optimal_dft_size_of_the_product_library(vs):
+    # host-side function of the product library, same rule (a test of its own: tests/test_oracle_sanitizers.py runs this file's oracle
+    # tests in a sanitizer process that must not load the product library and its HIP runtime)
+    for n, w in OPTIMAL_DFT_SIZE.items():
+        assert vs.optimal_dft_size(n) == w, n
+    assert vs.optimal_dft_size(0) == -1
 
 
 def test_radix_plan_rule(oracle):

@@ -11,7 +11,7 @@ echo "stats c2 headline rc=$?"
 cp "$(find $O/stats_c2 -name '*kernel_stats.csv' | head -1)" $O/keep/r06_bench_c2_kernel_stats.csv
 python3 tools/step_trace.py "$(find $O/stats_c2 -name '*kernel_trace.csv' | head -1)" 40 110 > $O/keep/r06_step_trace_shared.md
 # (b) the driver's own command, every leg
-$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-live-traffic > $O/keep/r06_bench_default_line.json 2> $O/stats_default.err
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-live-traffic > $O/keep/r06_bench_default_line.json 2> $O/stats_default.err
 echo "stats default rc=$?"
 cp "$(find $O/stats_default -name '*kernel_stats.csv' | head -1)" $O/keep/r06_bench_default_kernel_stats.csv
 # (c) ONE kernel-stats file per warp mode and depth for the roofline_4k launch shape (32 x 4K frames per launch): bytes / AverageNs can be recomputed per kernel
