@@ -1,7 +1,8 @@
 // grid_runner.hpp -- the worker pool of the two grid searches (grid_search_align.cpp:150-205,
 // grid_search_smoother.cpp:190-262): every parameter combination stabilizes the whole clip with a fresh stabilizer and
 // is scored by output jitter / input jitter.  Here the clip, the stabilized output and the scoring all stay on the GPU;
-// a worker thread owns its stabilizer, its scoring aligner and its output buffer (handles are independent).
+// a worker thread owns its stabilizer, its scoring aligner and its output buffer (handles are independent).  With --score flow the
+// scoring is dense flow through one vs_flow handle per device slot (its scratch is up to ~2 GiB), taken by one worker at a time.
 // Several GPUs (--devices a,b,...|all): the clip is uploaded once per device slot, worker t works on slot t mod G with handles
 // created on that slot's device -- the reference's independence model (grid_search_align.cpp:159-210: one stabilizer per worker,
 // halide_set_num_threads(1); here one stream per handle), no exchange between devices, one shared work counter on the host.
@@ -31,7 +32,8 @@ struct GridResult {
     std::vector<size_t> slot_done;       // per device slot: combinations evaluated
 };
 
-inline GridResult run_grid(const std::vector<std::unique_ptr<DeviceClip>>& clips, double input_jitter, const std::vector<GridCombo>& combos, int jobs) {
+inline GridResult run_grid(const std::vector<std::unique_ptr<DeviceClip>>& clips, double input_jitter, const std::vector<GridCombo>& combos, int jobs,
+                           bool flow_score = false) {
     GridResult res;
     const int G = (int)clips.size();
     res.ratios.assign(combos.size(), std::nan(""));
@@ -45,6 +47,16 @@ inline GridResult run_grid(const std::vector<std::unique_ptr<DeviceClip>>& clips
     const int w = clip.fmt.w, h = clip.fmt.h, fmt = vs_format_of(clip.fmt), n = clip.frames;
     const size_t esz = clip.fmt.bits > 8 ? 2 : 1;
     std::string failure;
+    // --score flow: one flow handle per device slot, used under the slot's lock (a handle is single-threaded)
+    std::vector<vs_flow*> flows((size_t)G, nullptr);
+    std::unique_ptr<std::mutex[]> flow_mu(new std::mutex[(size_t)G]);
+    struct FlowGuard { std::vector<vs_flow*>& f; ~FlowGuard() { for (vs_flow* h : f) vs_flow_destroy(h); } } flow_guard{flows};
+    if (flow_score)
+        for (int g = 0; g < G; g++) {
+            hip_check(hipSetDevice(clips[(size_t)g]->device), "hipSetDevice");
+            flows[(size_t)g] = vs_flow_create(nullptr, clips[(size_t)g]->device);
+            if (!flows[(size_t)g]) throw std::runtime_error(std::string("vs_flow_create: ") + vs_last_error());
+        }
 
     auto worker = [&](int t) {
         const int slot = t % G;
@@ -86,8 +98,14 @@ inline GridResult run_grid(const std::vector<std::unique_ptr<DeviceClip>>& clips
                 if (produced < 2) { skipped++; continue; }          // grid_search_align.cpp:173
                 int first = 0;
                 while (first < n && !has_output[first]) first++;     // outputs start after `lag` frames and are contiguous
-                const double out_jitter = measure_jitter(scorer, static_cast<const uint8_t*>(out.ptr) + (size_t)first * out_elems * esz,
-                                                         out_elems, produced, ow, oh, fmt);
+                const void* scored = static_cast<const uint8_t*>(out.ptr) + (size_t)first * out_elems * esz;
+                double out_jitter;
+                if (flow_score) {
+                    std::lock_guard<std::mutex> lk(flow_mu[(size_t)slot]);
+                    out_jitter = measure_flow_jitter(flows[(size_t)slot], scored, out_elems, produced, ow, oh, fmt);
+                } else {
+                    out_jitter = measure_jitter(scorer, scored, out_elems, produced, ow, oh, fmt);
+                }
                 const double ratio = out_jitter / input_jitter;
                 const size_t finished = ++done;
                 std::lock_guard<std::mutex> lk(mu);
@@ -149,10 +167,19 @@ inline bool prepare(const GridArgs& args, std::vector<std::unique_ptr<DeviceClip
     }
     const DeviceClip& clip = *clips[0];
     hip_check(hipSetDevice(clip.device), "hipSetDevice");
-    vs_aligner* a = vs_aligner_create(nullptr, clip.device);
-    if (!a) { std::cerr << "vs_aligner_create: " << vs_last_error() << std::endl; return false; }
-    input_jitter = measure_jitter(a, clip.buf.ptr, clip.frame_elems(), clip.frames, clip.fmt.w, clip.fmt.h, vs_format_of(clip.fmt));
-    vs_aligner_destroy(a);
+    if (args.flow_score) {
+        vs_flow* f = vs_flow_create(nullptr, clip.device);
+        if (!f) { std::cerr << "vs_flow_create: " << vs_last_error() << std::endl; return false; }
+        try {
+            input_jitter = measure_flow_jitter(f, clip.buf.ptr, clip.frame_elems(), clip.frames, clip.fmt.w, clip.fmt.h, vs_format_of(clip.fmt));
+        } catch (...) { vs_flow_destroy(f); throw; }
+        vs_flow_destroy(f);
+    } else {
+        vs_aligner* a = vs_aligner_create(nullptr, clip.device);
+        if (!a) { std::cerr << "vs_aligner_create: " << vs_last_error() << std::endl; return false; }
+        input_jitter = measure_jitter(a, clip.buf.ptr, clip.frame_elems(), clip.frames, clip.fmt.w, clip.fmt.h, vs_format_of(clip.fmt));
+        vs_aligner_destroy(a);
+    }
     std::cout << "Input median jitter: " << input_jitter << " px" << std::endl;
     return true;
 }

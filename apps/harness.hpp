@@ -77,6 +77,22 @@ inline double measure_jitter(vs_aligner* a, const void* d_frames, size_t frame_s
     return vsjit::jitter(t.data(), n, w, h);
 }
 
+// The reference's own score (--score flow): dense flow between successive frames of the same n device-resident frames, this
+// build's Farneback (vs_flow_jitter), with the reference's parameters.
+inline double measure_flow_jitter(vs_flow* f, const void* d_frames, size_t frame_stride, int n, int w, int h, int format) {
+    if (n < 2) return 0.0;
+    std::vector<float> pairs((size_t)n - 1);
+    double med = 0.0;
+    vs_check(vs_flow_jitter(f, d_frames, frame_stride, n, w, h, w * 3, format, VS_MEM_DEVICE, pairs.data(), &med), "vs_flow_jitter");
+    return med;
+}
+// --score similarity|flow; false for anything else
+inline bool parse_score(const std::string& v, bool& flow) {
+    if (v == "similarity") { flow = false; return true; }
+    if (v == "flow") { flow = true; return true; }
+    return false;
+}
+
 // `video [-j N] [--device D | --devices a,b,...|all] [--frames M]` as the grid searches take it (grid_search_align.cpp:62-90)
 struct GridArgs {
     std::string video;
@@ -112,10 +128,12 @@ struct GridArgs {
             }
             else if (a == "--frames") { if (!value(v)) return false; max_frames = (size_t)std::max(0, v); }
             else if (a == "--dump-ratios") dump = true;
+            else if (a == "--score") { if (i + 1 >= argc || !parse_score(argv[++i], flow_score)) return false; }
             else video = a;
         }
         return !video.empty();
     }
+    bool flow_score = false;    // --score flow: the reference's dense-flow score instead of the similarity stand-in
     bool dump = false;          // print every combination's ratio in index order after the search (tests compare device splits)
     std::vector<int> slots() const { return devices.empty() ? std::vector<int>{device} : devices; }
 };

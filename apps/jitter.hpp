@@ -16,7 +16,11 @@
 namespace vsjit {
 
 // printed once by every tool that reports the score (the score must say what it is where it is read)
-inline const char* score_note() {
+inline const char* score_note(bool flow = false) {
+    if (flow)
+        return "note: jitter score = median over frame pairs of the median dense-flow magnitude (eval_jitter.cpp:43-70), the flow from "
+               "THIS build's specification of Farneback's algorithm (vs_flow.hip, OpenCV's parameter meanings and the reference's "
+               "parameters), not OpenCV's binary: values are close to, not equal to, numbers printed by the reference's tools";
     return "note: jitter score = median flow magnitude of the similarity THIS library measures between successive frames (not OpenCV's "
            "Farneback flow, eval_jitter.cpp:43-70): it sees global camera motion only, and a grid search over aligner parameters scores "
            "an aligner with an aligner -- failures that fool the measuring aligner as well go unseen; compare scores of this tool only";

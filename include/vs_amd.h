@@ -244,6 +244,44 @@ int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int cha
 int vs_bgr_to_gray(const void* src, int w, int h, int src_stride, int bits, int shift_to_8,
                    uint8_t* dst, int dst_stride, int mem, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dense optical flow and the flow-based jitter score (eval_jitter.cpp:43-70, grid_search_align.cpp:27-60)
+ * ------------------------------------------------------------------------------------------
+ * Two-frame polynomial-expansion flow (Farneback 2003) with cv::calcOpticalFlowFarneback's parameter meanings.  OpenCV is not
+ * part of this build: the arithmetic (layer sizes, pyramid blur, border rule, regularisation of the 2x2 solve) is this build's
+ * own specification, stated in the header comment of vs_flow.hip and restated in numpy by tests/_flow_ref.py, which the kernels
+ * equal bit for bit.  Scores are this build's Farneback, not OpenCV's binary.
+ * Fields as OpenCV names them; levels counts the layers ABOVE the frame (levels + 1 layers in all).  flags: 0 only (box window,
+ * no initial flow); anything else is VS_ERR_UNSUPPORTED.  Limits: winsize 1..31, poly_n 1..7, levels 0..15. */
+typedef struct vs_flow_params {
+    double pyr_scale;
+    int    levels;
+    int    winsize;
+    int    iterations;
+    int    poly_n;
+    double poly_sigma;
+    int    flags;
+} vs_flow_params;
+/* the reference's call: 0.5, 3, 15, 3, 5, 1.2, 0 */
+void vs_flow_params_default(vs_flow_params* p);
+/* A handle owns one HIP stream and its device scratch (grown on demand, at most about 2 GiB per chunk of frames: clips are
+ * processed in chunks sharing one frame).  Single-threaded like the other handles.  NULL on failure (vs_last_error).
+ * The handle's stream is not ordered against the caller's: VS_MEM_DEVICE inputs must be complete before a call (see
+ * vs_aligner_wait_stream); every call returns after its device work has finished. */
+typedef struct vs_flow vs_flow;
+vs_flow* vs_flow_create(const vs_flow_params* params /* NULL = defaults */, int device);
+void     vs_flow_destroy(vs_flow* f);
+/* Dense flow from prev to next (u8 gray, w x h, row stride `stride`): flow[y*flow_stride + 2x + {0,1}] = (dx, dy) with
+ * prev(x, y) ~ next(x + dx, y + dy); flow_stride in floats (>= 2w).  Both images and the flow live in `mem`.  Synchronises. */
+int vs_flow_compute(vs_flow* f, const uint8_t* prev, const uint8_t* next, int w, int h, int stride, int mem, float* flow,
+                    int flow_stride);
+/* The reference's jitter statistic of n >= 2 frames (frame i at frames + i*frame_stride ELEMENTS; any VS_FMT_*, BGR reduced to
+ * gray by vs_bgr_to_gray's rule shifted to 8 bits): pair_medians[i] (host, n-1 values) = element (w*h)/2 of the magnitudes of
+ * the flow from frame i to frame i+1, selected exactly on the device; *median = their median (mean of the two middle values
+ * for an even count).  Synchronises. */
+int vs_flow_jitter(vs_flow* f, const void* frames, size_t frame_stride, int n, int w, int h, int stride, int format, int mem,
+                   float* pair_medians, double* median);
+
 /* Test hook, not part of the reference's surface: fault injection for the library's own device / pinned-host allocations.
  * vs_test_fail_alloc(k), k > 0: the k-th allocation the library makes from now on (any handle, any thread) fails once with
  * out-of-memory, and the call it belongs to returns VS_ERR_HIP; k < 0: the |k|-th allocation THROWS std::bad_alloc instead -- a host

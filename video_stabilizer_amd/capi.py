@@ -67,6 +67,15 @@ class StageTimings(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_int64 * 8), ("frames", C.c_int64), ("gn_iterations", C.c_int64)]
 
 
+class FlowParams(C.Structure):
+    """vs_flow_params: cv::calcOpticalFlowFarneback's parameters (levels = layers above the frame)"""
+    _fields_ = [("pyr_scale", C.c_double), ("levels", C.c_int), ("winsize", C.c_int), ("iterations", C.c_int),
+                ("poly_n", C.c_int), ("poly_sigma", C.c_double), ("flags", C.c_int)]
+
+    def tup(self):
+        return (self.pyr_scale, self.levels, self.winsize, self.iterations, self.poly_n, self.poly_sigma, self.flags)
+
+
 class VsError(RuntimeError):
     pass
 
@@ -128,6 +137,11 @@ SIGNATURES = {
                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
+    "vs_flow_create": (_vp, [C.POINTER(FlowParams), _i32]),
+    "vs_flow_destroy": (None, [_vp]),
+    "vs_flow_compute": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "vs_flow_jitter": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.POINTER(C.c_double)]),
     "vs_aligner_create": (_vp, [C.POINTER(AlignerParams), _i32]),
     "vs_aligner_destroy": (None, [_vp]),
     "vs_aligner_set_select_mode": (_i32, [_vp, _i32]),
@@ -531,6 +545,79 @@ def _fmt_of(frame_dtype, ndim_tail):
     if ndim_tail == 2:
         return FMT_GRAY8
     return FMT_BGR8 if frame_dtype == np.uint8 else FMT_BGR10      # u16 numpy frames are 10-bit unless the caller passes fmt=
+
+
+# ---- dense optical flow (this build's Farneback specification, vs_flow.hip) -------------------
+def flow_params(**kw):
+    """FlowParams with the reference's defaults (0.5, 3, 15, 3, 5, 1.2, 0), fields overridden by keyword"""
+    p = FlowParams()
+    lib().vs_flow_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("FlowParams has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class Flow:
+    """a vs_flow handle: its own stream and scratch, reused by every call"""
+
+    def __init__(self, params=None, device=0):
+        self.params = params if params is not None else flow_params()
+        self.h = lib().vs_flow_create(C.byref(self.params), device)
+        if not self.h:
+            raise VsError("vs_flow_create failed: %s" % lib().vs_last_error().decode())
+
+    def compute(self, prev, next_):
+        """(h, w, 2) float32 flow (dx, dy) from prev to next (u8 gray, or any 2-D array with row stride = its strides[0])"""
+        a = np.asarray(prev)
+        b = np.asarray(next_)
+        if a.dtype != np.uint8 or b.dtype != np.uint8 or a.ndim != 2 or a.shape != b.shape:
+            raise ValueError("dense_flow takes two u8 gray images of the same shape")
+        if a.strides[1] != 1 or b.strides[1] != 1 or a.strides[0] != b.strides[0]:
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        h, w = a.shape
+        out = np.empty((h, w, 2), np.float32)
+        _check(lib().vs_flow_compute(self.h, _p(a), _p(b), w, h, a.strides[0], MEM_HOST, _p(out), 2 * w))
+        return out
+
+    def jitter(self, frames, fmt=None):
+        """frames: numpy (n, h, w) u8 gray or (n, h, w, 3) BGR u8 / u16 (10-bit unless fmt says otherwise).
+        returns (median, pair medians (n-1) float32)"""
+        frames = np.ascontiguousarray(frames)
+        n = frames.shape[0]
+        fmt = _fmt_of(frames.dtype, frames.ndim - 1) if fmt is None else fmt
+        hh, ww = frames.shape[1:3]
+        ch = 1 if fmt == FMT_GRAY8 else 3
+        pm = np.zeros(max(n - 1, 0), np.float32)
+        med = C.c_double(0.0)
+        _check(lib().vs_flow_jitter(self.h, _p(frames), hh * ww * ch, n, ww, hh, ww * ch, fmt, MEM_HOST, _p(pm), C.byref(med)))
+        return med.value, pm
+
+    def jitter_device(self, ptr, n, w, h, fmt, stride=None, frame_stride=None):
+        """device-resident frames (raw device pointer; strides in elements): (median, pair medians)"""
+        ch = 1 if fmt == FMT_GRAY8 else 3
+        stride = stride or w * ch
+        frame_stride = frame_stride or h * stride
+        pm = np.zeros(max(n - 1, 0), np.float32)
+        med = C.c_double(0.0)
+        _check(lib().vs_flow_jitter(self.h, _p(ptr), frame_stride, n, w, h, stride, fmt, MEM_DEVICE, _p(pm), C.byref(med)))
+        return med.value, pm
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.vs_flow_destroy(self.h)
+            self.h = None
+
+
+def dense_flow(prev, next_, params=None, device=0):
+    """cv::calcOpticalFlowFarneback(prev, next, flow, ...) under this build's specification: (h, w, 2) float32 (dx, dy)"""
+    return Flow(params, device).compute(prev, next_)
+
+
+def flow_jitter(frames, params=None, fmt=None, device=0):
+    """the reference's jitter score of a clip (eval_jitter.cpp:43-70): (median over pairs, per-pair medians)"""
+    return Flow(params, device).jitter(frames, fmt)
 
 
 class Aligner:
