@@ -1,7 +1,7 @@
 #!/bin/bash
-# Builds video_stabilizer_amd/variants/libvs_amd_<name>.so = the library with vs_warp.hip compiled under extra -D flags
-# (tuning experiments: select one with VS_AMD_LIB=... ; the other objects come from the regular build).
-# usage: tools/build_variant.sh <name> "<flags>" [file.hip ...]   (default file: vs_warp.hip)
+# Builds video_stabilizer_amd/variants/libvs_amd_<name>.so = the library with some files compiled under extra compiler flags
+# (select one with VS_AMD_LIB=... ; the other objects come from the regular build).
+# usage: tools/build_variant.sh <name> "<compiler flags>" [file.hip ...]   (default file: vs_warp.hip)
 #        tools/build_variant.sh bounds      the debug build with bounds-checked LDS / scratch indexing (-DVS_DEBUG_BOUNDS: vs_device.hpp,
 #                                           include/vs_amd.h vs_debug_bounds_check) -> variants/libvs_amd_bounds.so, tests/test_bounds_build_gpu.py
 set -euo pipefail

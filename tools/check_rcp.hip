@@ -1,4 +1,4 @@
-// tools/check_rcp.hip -- exhaustive check of the reciprocal sequences the separable warp may use (vs_warp.hip rcp_rn), against the IEEE
+// tools/check_rcp.hip -- exhaustive check of the reciprocal sequences the separable warp may use (vs_warp.hip sep_rows_pipelined), against the IEEE
 // quotient 1.0f / den (hipcc's full division expansion, -fno-fast-math) for EVERY float in [0.5, 2).
 //   seq A: v_rcp, one Newton step, two residual corrections (the compiler's own sequence without scaling / fix-up) -- 7 instructions
 //   seq B: v_rcp, one Newton step, ONE residual correction                                                         -- 5 instructions

@@ -7,9 +7,6 @@
 // carries the (identical) fp64 transform in registers; the only exchange per iteration is the block
 // sum.  T is updated in place (including the x2 of TX,TY when moving to a finer level).
 // Returns 0 ok / 2 max iterations / 3 over displacement; *iters_out, *cond_out as the reference logs.
-#ifndef VS_GN_FLIGHT
-#define VS_GN_FLIGHT 2
-#endif
 #define VS_LDS_AS __attribute__((address_space(3)))
 // Virtual threads.  Every fp64 sum of a pair is defined over kGnVirt threads (which records a thread adds, in which order, and
 // the fixed trees that combine lanes and waves).  A build whose workgroup has fewer hardware threads (kGnThreads < kGnVirt: the
@@ -80,17 +77,7 @@ __device__ __noinline__ void gn_hessian_partials(GnShared& sh, const PointRecs& 
 // On entry sh.red[0] holds the Hessian partials (gn_hessian_partials or the fused kernel's gather) and a barrier has passed.
 __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__ key, const uint8_t* key_lds, int w, int h, int nsel,
                                         const PointRecs& rc, int level, const GnParams& gp_in, double T_io[4], int* iters_out,
-                                        double* cond_out
-#ifdef VS_PROFILE_STAMPS
-                                        , unsigned long long* gtk
-#endif
-                                        ) {
-#ifdef VS_PROFILE_STAMPS
-    gtk[0] = __builtin_amdgcn_s_memtime();
-#define VS_GSTAMP(k) gtk[k] = __builtin_amdgcn_s_memtime()
-#else
-#define VS_GSTAMP(k)
-#endif
+                                        double* cond_out) {
     // This function is not inlined, so its arguments arrive as per-lane values and generic pointers.  They are the same
     // in every lane and all point to device memory: say so (readfirstlane -> SGPRs; address space 1 -> global_load with a
     // scalar base instead of flat_load with a 64-bit address per lane; address space 3 for the shared block).  The
@@ -312,9 +299,7 @@ __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__
         if (threadIdx.x == 0) { sh.seq = 0; sh.ctl[0] = 0; sh.ctl[1] = 0; }
         // iteration 0 needs no sampling: its sums are in red[1] already (all waves'); wave 0 solves the 4x4 problem (red[0]).
         if (w0) solve_hessian();
-        VS_GSTAMP(1); VS_GSTAMP(2);
         __syncthreads();
-        VS_GSTAMP(3); VS_GSTAMP(4);
         for (int k = 0;; k++) {
             // the partial sums of iteration k are in red[(k + 1) & 1]; those of k + 1 go to red[k & 1]
             if (w0) {
@@ -328,30 +313,16 @@ __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__
                 const int f = corner_test(Tn, k);
                 if (threadIdx.x == 0) __hip_atomic_store(&sh.ctl[k & 1], ((k + 1) << 2) | f, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             } else {
-#ifdef VS_PIPE_STAMPS
-                const unsigned long long q0 = __builtin_amdgcn_s_memtime();
-#endif
                 while (__hip_atomic_load(&sh.seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != k + 1) __builtin_amdgcn_s_sleep(1);
-#ifdef VS_PIPE_STAMPS
-                const unsigned long long q1 = __builtin_amdgcn_s_memtime();
-#endif
                 const VS_LDS_AS double* Tp = sh.Tp[k & 1];
                 const double Ts[4] = {Tp[0], Tp[1], Tp[2], Tp[3]};
                 float Ps[4];
                 ul_params_sparse(Ts, w, h, Ps);
                 double a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
                 sample_regs(Ps, a8, k + 1);
-#ifdef VS_PIPE_STAMPS
-                const unsigned long long q2 = __builtin_amdgcn_s_memtime();
-#endif
                 wave_partials8_butterfly(a8, sh.red[k & 1], wave);
-#ifdef VS_PIPE_STAMPS
-                const unsigned long long q3 = __builtin_amdgcn_s_memtime();
-                if (k == 2 && lane == 0 && blockIdx.x == 0) printf("[pipe] wave %d: wait for T %llu, sample %llu, butterfly %llu\n", wave, q1 - q0, q2 - q1, q3 - q2);
-#endif
             }
             __syncthreads();
-            if (k == 0) { VS_GSTAMP(5); VS_GSTAMP(6); VS_GSTAMP(7); VS_GSTAMP(8); }
             T[0] = sh.Tp[k & 1][0]; T[1] = sh.Tp[k & 1][1]; T[2] = sh.Tp[k & 1][2]; T[3] = sh.Tp[k & 1][3];
             flag = sh.ctl[k & 1] & 3;
             iters = k + 1;
@@ -362,7 +333,6 @@ __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__
         // Iteration 0 needs no sampling (its sums are in red[1] already, all waves'); the Hessian partials are in red[0] until
         // wave 0 has read them.
         if (w0) solve_hessian();
-        VS_GSTAMP(1); VS_GSTAMP(2);
         for (int iter = 0; iter < max_iters; iter++) {
             iters++;
             VS_LDS_AS double* red = sh.red[iter == 0 ? 1 : 0];
@@ -376,11 +346,7 @@ __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__
                     wave_partials8_butterfly(a8, red, wave);
                 }
             }
-            if (iter == 0) VS_GSTAMP(3);
-            if (iter == 1) VS_GSTAMP(6);
             __syncthreads();
-            if (iter == 0) VS_GSTAMP(4);
-            if (iter == 1) VS_GSTAMP(7);
             if (w0) {
                 double Tn[4];
                 next_transform(red, iter == 0 ? 0 : 1, T, Tn);
@@ -391,8 +357,6 @@ __device__ __noinline__ int gn_level(GnShared& sh_g, const uint8_t* __restrict__
                 }
             }
             __syncthreads();
-            if (iter == 0) VS_GSTAMP(5);
-            if (iter == 1) VS_GSTAMP(8);
             T[0] = sh.T[0]; T[1] = sh.T[1]; T[2] = sh.T[2]; T[3] = sh.T[3];
             flag = sh.flag;
             if (flag) break;
@@ -426,12 +390,7 @@ __global__ VS_GN_FUSED_BOUNDS __attribute__((unused)) void vs_k_gn_level(PairSta
     double cond;
     gn_hessian_partials(sh, rc, nsel);
     __syncthreads();
-#ifdef VS_PROFILE_STAMPS
-    unsigned long long gtk[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int fail = gn_level(sh, key, nullptr, w, h, nsel, rc, level, gp, T, &iters, &cond, gtk);
-#else
     const int fail = gn_level(sh, key, nullptr, w, h, nsel, rc, level, gp, T, &iters, &cond);
-#endif
     __syncthreads();   // every thread has read st.T before thread 0 rewrites it
     if (threadIdx.x == 0) {
         st.iterations[level] = iters;
@@ -457,14 +416,9 @@ __global__ VS_GN_FUSED_BOUNDS __attribute__((unused)) void vs_k_gn_level(PairSta
 // prefix counts, so one partition is a few block-wide scans.  tests/test_select_gpu.py checks the
 // permutation against the host's std::nth_element on tie-heavy inputs.
 // Elements are packed (abs_delta << 16) | tile_index; only abs_delta takes part in comparisons.
-// selection tuning (tools/select_bench.py): ranges up to VS_SEL_WAVE_RANGE elements are finished by one wave; the
-// block-wide rounds give elements to VS_SEL_THREADS threads (more only when a 32-element chunk would not cover the range)
-#ifndef VS_SEL_WAVE_RANGE
-#define VS_SEL_WAVE_RANGE 256
-#endif
-#ifndef VS_SEL_THREADS
-#define VS_SEL_THREADS 256
-#endif
+// selection tuning (tools/select_bench.py): ranges up to kWaveRange elements are finished by one wave; the
+// block-wide rounds give elements to kSelThreadsSmall threads (more only when a 32-element chunk would not cover the range)
+constexpr int kWaveRange = 256, kSelThreadsSmall = 256;
 struct SelShared {
     int wl[kGnThreads / 64], wr[kGnThreads / 64];   // per-wave stopper counts
     int red_k[kGnThreads / 64], red_c[kGnThreads / 64];
@@ -653,8 +607,6 @@ __device__ __noinline__ int introselect_block(uint32_t* __restrict__ a_g, uint16
     depth_cap = uni(depth_cap);
     if (depth_cap > 0) depth = min(depth, depth_cap); // test hook (GnParams::sel_depth_cap)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int kWaveRange = VS_SEL_WAVE_RANGE;
-    constexpr int kSelThreadsSmall = VS_SEL_THREADS;   // threads that own elements in the block-wide rounds ...
     bool fail = false;
     // block-wide rounds while the range is large.  Round structure: [median swap by thread 0] barrier
     // [classify + count] barrier [rank table] barrier [swaps + reduce] barrier; the next round's median swap
@@ -669,7 +621,7 @@ __device__ __noinline__ int introselect_block(uint32_t* __restrict__ a_g, uint16
         }
         const uint32_t pv = a[first] >> 16;
         const int f0 = first + 1, m = last - f0;
-        // ... unless a 32-element chunk per thread would not cover the range; then every thread of the block takes part, with
+        // kSelThreadsSmall threads own elements, unless a 32-element chunk per thread would not cover the range; then every thread of the block takes part, with
         // chunks of up to 64 elements (the masks are 64 bits wide)
         const int kSelThreads = m > 32 * kSelThreadsSmall ? kGnThreads : kSelThreadsSmall;
         const int chunk = (m + kSelThreads - 1) / kSelThreads;   // <= 64: the caller caps n at 64*kGnThreads
@@ -751,7 +703,7 @@ __device__ __noinline__ int introselect_block(uint32_t* __restrict__ a_g, uint16
 // rounds, same pivots, same swaps, same cut as introselect_block -- the permutation is a function of the values alone -- with
 // * up to 128 elements per thread (two 64-bit masks per side), so that 256 threads cover 32768 elements;
 // * a thread's loads issued in batches of eight (every access is an L2 round trip; nothing else hides it);
-// * the tail (<= VS_SEL_WAVE_RANGE + 1 elements) copied into `lds_tail` (>= 6 B x (VS_SEL_WAVE_RANGE + 1) bytes of LDS), finished
+// * the tail (<= kWaveRange + 1 elements) copied into `lds_tail` (>= 6 B x (kWaveRange + 1) bytes of LDS), finished
 //   there by introselect_wave, and copied back.
 // Stores of one thread are read by other threads of the workgroup only behind a workgroup barrier (which waits for vmcnt),
 // on the same CU (same L1): the pattern the record arrays of the fused kernel already use.
@@ -769,7 +721,6 @@ __device__ __noinline__ int introselect_block_g(uint32_t* __restrict__ a_g, uint
     depth_cap = uni(depth_cap);
     if (depth_cap > 0) depth = min(depth, depth_cap); // test hook (GnParams::sel_depth_cap)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int kWaveRange = VS_SEL_WAVE_RANGE;
     bool fail = false;
     auto median_to_first_g = [&](int f, int l) {      // __move_median_to_first(first, first+1, mid, last-1), thread 0
         const int mid = f + (l - f) / 2, ia = f + 1, ib = mid, ic = l - 1;
@@ -897,8 +848,8 @@ __device__ __noinline__ int introselect_dual(uint32_t* __restrict__ aX, uint16_t
     VS_SPAN(lds_u32*, a, a_g, n, 110);
     VS_SPAN(lds_u16*, posR, posR_g, n, 111);
     VS_LDS_AS SelShared& ss = *(VS_LDS_AS SelShared*)&ss2[half];
-    constexpr int kWaveRange = VS_SEL_WAVE_RANGE, kHalf = kGnThreads / 2, kHalfWaves = kHalf / 64;
-    constexpr int kSmall = VS_SEL_THREADS < kHalf ? VS_SEL_THREADS : kHalf;
+    constexpr int kHalf = kGnThreads / 2, kHalfWaves = kHalf / 64;
+    constexpr int kSmall = kSelThreadsSmall < kHalf ? kSelThreadsSmall : kHalf;
     int first = 0, last = n;
     int depth = 2 * (31 - __clz(n));
     depth_cap = uni(depth_cap);
@@ -1044,9 +995,6 @@ __device__ __noinline__ void stable_select(uint32_t* __restrict__ a0_g, uint16_t
         VS_BOUNDS_CHECK(sub + (int)(bin >> 1), S * kSub, 116);
         __hip_atomic_fetch_add((s ? hb1 : hb0) + sub + (bin >> 1), 1u << (16 * (bin & 1u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-#ifdef VS_PROFILE_STAMPS
-    unsigned long long q[6]; q[0] = __builtin_amdgcn_s_memtime();
-#endif
     auto clear_hist = [&]() {
         for (int s = 0; s < nsets; s++)
             for (int i = tid; i < S * kSub; i += kGnThreads) (s ? hb1 : hb0)[i] = 0u;
@@ -1104,9 +1052,6 @@ __device__ __noinline__ void stable_select(uint32_t* __restrict__ a0_g, uint16_t
         if (__any(seen) && lane == 0) ss.any_hi[s] = 1u;
     }
     __syncthreads();
-#ifdef VS_PROFILE_STAMPS
-    q[1] = __builtin_amdgcn_s_memtime();
-#endif
     const bool general = ss.any_hi[0] != 0u || (nsets > 1 && ss.any_hi[1] != 0u);     // (uniform)
     uint32_t hi0 = 0u, hi1 = 0u, k0 = (uint32_t)nsel, k1 = (uint32_t)nsel;
     if (general) {
@@ -1137,9 +1082,6 @@ __device__ __noinline__ void stable_select(uint32_t* __restrict__ a0_g, uint16_t
     }
     scan_pick(k0, k1);
     __syncthreads();
-#ifdef VS_PROFILE_STAMPS
-    q[2] = __builtin_amdgcn_s_memtime();
-#endif
     const uint32_t D0 = (hi0 << 8) | ss.cut_d[0], R0 = ss.cut_r[0];
     const uint32_t D1 = nsets > 1 ? ((hi1 << 8) | ss.cut_d[1]) : 0u, R1 = nsets > 1 ? ss.cut_r[1] : 0u;
     // ---- placement: wave w owns tiles [w * per, (w + 1) * per) of every set (per a multiple of 64), a lane one tile of every
@@ -1170,14 +1112,8 @@ __device__ __noinline__ void stable_select(uint32_t* __restrict__ a0_g, uint16_t
         }
         mine |= ((unsigned long long)(less | (eq << 16))) << (32 * s);
     }
-#ifdef VS_PROFILE_STAMPS
-    q[3] = __builtin_amdgcn_s_memtime();
-#endif
     if (lane == 0) ss.wsum[wave] = mine;
     __syncthreads();
-#ifdef VS_PROFILE_STAMPS
-    q[4] = __builtin_amdgcn_s_memtime();
-#endif
     unsigned long long before = 0ull;
     for (int w = 0; w < wave; w++) before += ss.wsum[w];
     for (int s = 0; s < nsets; s++) {
@@ -1202,10 +1138,6 @@ __device__ __noinline__ void stable_select(uint32_t* __restrict__ a0_g, uint16_t
         }
     }
     __syncthreads();                                                         // the survivors are placed
-#ifdef VS_PROFILE_STAMPS
-    q[5] = __builtin_amdgcn_s_memtime();
-    if (tid == 0 && blockIdx.x == 0) printf("[stable] nt %d sets %d: clear+count %llu pick %llu wave totals %llu barrier %llu place %llu\n", nt, nsets, q[1] - q[0], q[2] - q[1], q[3] - q[2], q[4] - q[3], q[5] - q[4]);
-#endif
 }
 
 
@@ -1249,7 +1181,7 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
     __shared__ GnShared sh;
     __shared__ int s_coop[2];
     // tail of a selection that runs on global arrays (introselect_block_g): values + rank table of the last <= 257 elements
-    __shared__ __attribute__((aligned(16))) uint32_t sel_tail[(VS_SEL_WAVE_RANGE + 1) + (VS_SEL_WAVE_RANGE + 2) / 2 + 32];
+    __shared__ __attribute__((aligned(16))) uint32_t sel_tail[(kWaveRange + 1) + (kWaveRange + 2) / 2 + 32];
     static_assert(sizeof(StableShared) <= sizeof(sel_tail), "VS_SELECT_STABLE keeps its histograms in the tail block (unused in that mode)");
     // dynamic LDS: the selection arrays (a | posR) at the start -- except at the coarsest level when its image AND its arrays
     // fit: then the image comes first and stays for the whole level (sparse_warpdiff and every Gauss-Newton pass sample it
@@ -1265,12 +1197,9 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
     // pairs read every other frame as their template), and workgroups go to the XCDs round-robin: a full batch gives every
     // XCD a contiguous run of pairs (workgroup b = the (b >> 3)-th pair of XCD b & 7's run), so that the second user of a
     // line finds it in that XCD's L2.
-#ifndef VS_GN_XCD_RUNS
-#define VS_GN_XCD_RUNS 1
-#endif
     int p = blockIdx.x / group;
     const int g = blockIdx.x % group;
-    if (VS_GN_XCD_RUNS && group == 1) {
+    if (group == 1) {
         const int n = (int)gridDim.x, x = (int)blockIdx.x & 7;
         p = (n >> 3) * x + min(x, n & 7) + ((int)blockIdx.x >> 3);
     }
@@ -1329,13 +1258,6 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
         float P[4];
         ul_params_sparse(T, w, h, P);
         const float A1 = 1.0f + P[0];
-#ifdef VS_PROFILE_STAMPS
-        unsigned long long tk[6];
-        tk[0] = __builtin_amdgcn_s_memtime();
-#define VS_STAMP(k) tk[k] = __builtin_amdgcn_s_memtime()
-#else
-#define VS_STAMP(k)
-#endif
         const uint16_t* lm0 = lm_tab + (size_t)d.key_slot * lm_frame + fl.lm_off[l];
         const float* jac0 = jac_tab + (size_t)d.key_slot * jac_frame + fl.jac_off[l];
         // The coarsest level's image is copied into the dynamic LDS block when it fits: most of a pair's Gauss-Newton iterations
@@ -1516,10 +1438,7 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
         // upper triangle of sum j j^T in fp64) is accumulated on the way: thread t sums records t, t + kGnThreads, ... in
         // that order, exactly as gn_hessian_partials does over the finished records (the per-level kernel of the host-selection
         // path), so H is the same bit for bit without the second pass.
-#ifndef VS_GA_FLIGHT
-#define VS_GA_FLIGHT 4
-#endif
-        constexpr int kGaFlight = VS_GA_FLIGHT;
+        constexpr int kGaFlight = 4;
         double hacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         double fa8[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the first Gauss-Newton pass, from the residuals as they are written
         auto gather_fill = [&](const uint32_t* sel, const uint16_t* sel16, int count, bool both, const uint16_t* __restrict__ lmb,
@@ -1666,31 +1585,9 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
             if (shared_now) { read_exchange(gkeys, a, 0, 2 * nt); read_exchange((const uint32_t*)gvals, (uint32_t*)wv, 0, 2 * nt); read_exchange((const uint32_t*)gtpx, (uint32_t*)wt, 0, 2 * nt); }
             else if (img_first) warpdiff_fill(lkey_img, a, lm0, 2 * nt, true, 0);
             else warpdiff_fill((vs_gbytes)key, a, lm0, 2 * nt, true, 0);
-#ifdef VS_COOP_DEBUG
-            if (shared_now) {
-                __syncthreads();
-                // diagnostic build: recompute every tile locally and compare with what came through the exchange buffers
-                int badk = 0, badv = 0, firstbad = -1;
-                for (int i = threadIdx.x; i < 2 * nt; i += kGnThreads) {
-                    const uint32_t xy = ((const uint32_t*)lm0)[i];
-                    const int tile_x = min((int)(xy & 0xffffu), w - 1), tile_y = min((int)(xy >> 16), h - 1);
-                    const float ox = (float)tile_x, oy = (float)tile_y;
-                    const float v = lanczos_sample_u8_fast(key, w, h, w, A1 * ox - P[1] * oy + P[2], P[1] * ox + A1 * oy + P[3]);
-                    float diff = fabsf(v - (float)tmpl[(size_t)tile_y * w + tile_x]);
-                    diff = fminf(fmaxf(diff, 0.0f), 65535.0f);
-                    const uint32_t k = ((uint32_t)(uint16_t)diff << 16) | (uint32_t)(i - (i >= nt ? nt : 0));
-                    if (k != a[i]) badk++;
-                    if (__float_as_uint(v) != __float_as_uint(wv[i])) { badv++; if (firstbad < 0) firstbad = i; }
-                }
-                if (badk || badv) printf("[coop debug] thread %d: %d bad keys, %d bad values, first bad value at %d\n", (int)threadIdx.x, badk, badv, firstbad);
-                __syncthreads();
-            }
-#endif
             __syncthreads();
-            VS_STAMP(1);
             if (gp.sel_stable) stable_select<true>(aX, pRX, aY, pRY, 2, nt, nsel, *reinterpret_cast<StableShared*>(sel_tail));
             else if (introselect_dual(aX, pRX, aY, pRY, ss2, nt, nsel, gp.sel_depth_cap)) { fail = 100; fail_level = l; }
-            VS_STAMP(2);
             gather_fill(a, gp.sel_stable ? pRX : nullptr, 2 * nsel, true, lm0, jac0, 0, 0);
         } else {
             for (int set = 0; set < 2 && !fail; set++) {
@@ -1726,22 +1623,9 @@ __global__ VS_GN_FUSED_BOUNDS void vs_k_align_pairs(PairState* __restrict__ stat
             if (!img_first) { stage_image(); __syncthreads(); }   // (the selection arrays in the block are dead now)
             key_lds = dyn;
         }
-        VS_STAMP(3);
         int iters;
         double cond;
-#ifdef VS_PROFILE_STAMPS
-        unsigned long long gtk[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const int f = gn_level(sh, key, key_lds, w, h, nsel, rc, l, gp, T, &iters, &cond, gtk);
-        if (threadIdx.x == 0)
-            printf("[gn stamps] level %d (thread 0): eigen-solve %llu wait for sample0 + partials + barrier %llu update+barrier %llu; second iteration: sample %llu partials+barrier %llu update+barrier %llu\n", l,
-                   gtk[1] - gtk[0], gtk[4] - gtk[3], gtk[5] - gtk[4], gtk[6] - gtk[5], gtk[7] - gtk[6], gtk[8] - gtk[7]);
-#else
         const int f = gn_level(sh, key, key_lds, w, h, nsel, rc, l, gp, T, &iters, &cond);
-#endif
-        VS_STAMP(4);
-#ifdef VS_PROFILE_STAMPS
-        if (threadIdx.x == 0) for (int k = 0; k < 5; k++) st.stamps[l][k] = tk[k];
-#endif
         if (threadIdx.x == 0) {
             st.iterations[l] = iters; st.condition[l] = cond;
             if (f != 2) {    // the estimate the level ended on, before gn_level's x2 of TX,TY (halving undoes it exactly)

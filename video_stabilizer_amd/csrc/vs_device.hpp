@@ -278,36 +278,12 @@ __device__ __forceinline__ LanczosFetch lanczos_fetch(P img, int w, int h, int s
     }
     return f;
 }
-// the scalar form of lanczos2_pk (same operations per value)
-template <bool EDGE>
-__device__ __forceinline__ float lanczos2_s(float x) {
-    const float x2 = x * x;
-    float v = 0.000858519f;
-    v = -0.0158853f + v * x2;
-    v = 0.128693f + v * x2;
-    v = -0.583468f + v * x2;
-    v = 1.52229f + v * x2;
-    v = -2.05238f + v * x2;
-    v = 0.999861f + v * x2;
-    if (EDGE) v = fabsf(x) >= 2.0f ? 0.0f : v;
-    return v;
-}
-#ifndef VS_SAMPLE_SCALAR_WEIGHTS
-#define VS_SAMPLE_SCALAR_WEIGHTS 0
-#endif
 __device__ __forceinline__ float lanczos_finish(const LanczosFetch& f, int w) {
     const int ix = f.ix;
-#if VS_SAMPLE_SCALAR_WEIGHTS
-    const float wx[4] = {lanczos2_s<true>(-1.0f - f.frx), lanczos2_s<false>(0.0f - f.frx), lanczos2_s<false>(1.0f - f.frx),
-                         lanczos2_s<true>(2.0f - f.frx)};
-    const float wy[4] = {lanczos2_s<true>(-1.0f - f.fry), lanczos2_s<false>(0.0f - f.fry), lanczos2_s<false>(1.0f - f.fry),
-                         lanczos2_s<true>(2.0f - f.fry)};
-#else
     const f2v fr = {f.frx, f.fry};
     const f2v w0 = lanczos2_pk<true>(f2v{-1.0f, -1.0f} - fr), w1 = lanczos2_pk<false>(f2v{0.0f, 0.0f} - fr),
               w2 = lanczos2_pk<false>(f2v{1.0f, 1.0f} - fr), w3 = lanczos2_pk<true>(f2v{2.0f, 2.0f} - fr);
     const float wx[4] = {w0.x, w1.x, w2.x, w3.x}, wy[4] = {w0.y, w1.y, w2.y, w3.y};
-#endif
     uint32_t r[4] = {f.r[0], f.r[1], f.r[2], f.r[3]};
     const bool edge = ix < 1 || ix + 2 >= w;
     if (__any(edge)) {                                        // wave-uniform branch
@@ -580,12 +556,10 @@ __device__ __forceinline__ void jacobi_eig4(const double* Hin, double* eval, dou
     for (int i = 0; i < 4; i++) eval[i] = a[i][i];
 }
 
-#ifndef VS_COND_INLINE
-#define VS_COND_INLINE __forceinline__   // (out of line its 32 doubles travel through scratch memory)
-#endif
 // cond = smax/(smin+1e-10); cond > 1e6 => H += 1e-6*smax*I (alignment.cpp:561-572);
 // Hinv = V diag(1/w) V^T dropping w <= 2*eps*sum(w) (OpenCV's DECOMP_SVD back-substitution).
-__device__ VS_COND_INLINE double condition_and_invert(double* Hio, double* Hinv_out) {
+// Inlined: out of line its 32 doubles travel through scratch memory.
+__device__ __forceinline__ double condition_and_invert(double* Hio, double* Hinv_out) {
     double H[16], Hinv[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) H[i] = Hio[i];

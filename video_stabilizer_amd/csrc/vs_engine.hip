@@ -61,9 +61,6 @@ struct PairState {
     int32_t iterations[kMaxLevels];
     double condition[kMaxLevels];
     double level_T[kMaxLevels][4];   // the estimate each level ended on (vs_align_info::level_transform)
-#ifdef VS_PROFILE_STAMPS
-    unsigned long long stamps[kMaxLevels][6];   // diagnostic build only: shader-clock ticks per phase of a level
-#endif
 };
 
 struct PairDesc {
@@ -216,10 +213,7 @@ constexpr int kCoopGroup = 16;         // workgroups per pair in latency mode (1
 constexpr int kCoopMaxGroup = 16;
 constexpr int kCoopMaxPairs = 128;     // helpers for launches of at most this many pairs (16 per pair up to 16 pairs, then as many as keep the launch within one workgroup per CU)
 constexpr int kChipCUs = 256;
-#ifndef VS_COOP_MIN_TILES
-#define VS_COOP_MIN_TILES 4096
-#endif
-constexpr int kCoopMinTiles = VS_COOP_MIN_TILES;    // levels with at least this many tiles are shared
+constexpr int kCoopMinTiles = 4096;    // levels with at least this many tiles are shared
 struct CoopLevel {
     int t_ready, nslices, pad[2];
     int assign[kCoopMaxGroup];         // slice number of helper g at this level, -1: not taking part
@@ -248,19 +242,15 @@ struct FusedLevels {
 // The per-pair kernels are compiled for two workgroup sizes (vs_align_kernels.inc).  512 threads is the faster shape in
 // every configuration measured (fewer waves behind every block barrier: 239 1080p pairs 0.70 -> 0.62 ms, one pair alone
 // 0.445 -> 0.40 ms, 952 pairs 2.50 -> 2.09 ms, 119 4K pairs 1.34 -> 1.29 ms although the 20736-tile selection itself is
-// slower with half the threads) and is the default for every level size; VS_SMALL_WG_TILES (build time) sends larger levels
-// to the 1024-thread build.
+// slower with half the threads) and takes every level up to kSmallWgTiles tiles; larger levels go to the 1024-thread build.
 namespace nt1024 {
 constexpr int kGnThreads = 1024, kGnVirt = 1024;
 #define VS_GN_FUSED_BOUNDS __launch_bounds__(kGnThreads)
 #include "vs_align_kernels.inc"
 #undef VS_GN_FUSED_BOUNDS
 }  // namespace nt1024
-#ifndef VS_NT_SMALL
-#define VS_NT_SMALL 512
-#endif
 namespace nt512 {
-constexpr int kGnThreads = VS_NT_SMALL, kGnVirt = VS_NT_SMALL;
+constexpr int kGnThreads = 512, kGnVirt = 512;
 #define VS_GN_FUSED_BOUNDS __launch_bounds__(kGnThreads)
 #include "vs_align_kernels.inc"
 #undef VS_GN_FUSED_BOUNDS
@@ -271,35 +261,17 @@ constexpr int kGnThreads = VS_NT_SMALL, kGnVirt = VS_NT_SMALL;
 // soon as one warp workgroup leaves it and the alignment of clip k+1 runs under the warp launch of clip k instead of waiting
 // for whole CUs to drain.  Levels whose selection arrays (6 B per tile) exceed 32 KB -- a 4K level 0: 20736 tiles -- select on a
 // per-pair global scratch (introselect_block_g), up to 128 * 256 tiles.
-#if VS_NT_SMALL == 512
 namespace nt256v {
-// (experiment, -DVS_SHARED_THREADS=512: the co-resident build with all 512 hardware threads at the same 128-VGPR cap -- two waves per SIMD of 128
-// registers each instead of one; profiles/r06_shared_solver_512.txt)
-#ifndef VS_SHARED_THREADS
-#define VS_SHARED_THREADS 256
-#endif
-constexpr int kGnThreads = VS_SHARED_THREADS, kGnVirt = 512;
-#ifndef VS_NT256_MINWAVES
-#define VS_NT256_MINWAVES 4
-#endif
-#ifdef VS_NT256_NUM_VGPR
-#define VS_GN_FUSED_BOUNDS __launch_bounds__(VS_SHARED_THREADS) __attribute__((amdgpu_num_vgpr(VS_NT256_NUM_VGPR)))
-#else
-#define VS_GN_FUSED_BOUNDS __launch_bounds__(VS_SHARED_THREADS, VS_NT256_MINWAVES)
-#endif
+constexpr int kGnThreads = 256, kGnVirt = 512;
+#define VS_GN_FUSED_BOUNDS __launch_bounds__(kGnThreads, 4)
 #include "vs_align_kernels.inc"
 #undef VS_GN_FUSED_BOUNDS
 }  // namespace nt256v
-#define VS_HAVE_NT256V 1
-#endif
 constexpr int kCoResidentMaxTiles = 128 * 256;          // introselect_block_g: 128 elements per thread (and <= kSelectCap)
 constexpr int kSharedMinPairs = 32;                    // VS_BATCH_SHARED: launches of at least this many pairs take the small-footprint build
 constexpr size_t kCoResidentDynMax = 32 * 1024;        // dynamic LDS of the small-footprint build; larger levels select on global scratch
-#ifndef VS_SMALL_WG_TILES
-#define VS_SMALL_WG_TILES 26000
-#endif
-constexpr int kSmallWgTiles = VS_SMALL_WG_TILES;
-constexpr int kPipelineMaxPairs = 128;   // half the CUs   // largest level handled by the 512-thread kernels (<= kSelectCap <= 64 * 512)
+constexpr int kSmallWgTiles = 26000;     // largest level handled by the 512-thread kernels (<= kSelectCap <= 64 * 512)
+constexpr int kPipelineMaxPairs = 128;   // half the CUs
 
 }  // namespace
 
@@ -686,10 +658,6 @@ int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int 
         // BGR -> gray level 0 and level 1 in one pass (levels >= 3 always, so level 1 exists)
         VS_HIP(vsk::ingest_pyr(dframes, W, H, stride, fbits > 8 ? 16 : 8, fbits - 8, slot1,
                                slot1 + L[1].img_off, n, frame_stride, pyr_frame, s));
-#ifdef VS_EXP_REPEAT
-        // analysis builds: a stage launched twice (idempotent) -- the step's growth is what the stage costs beside the warp
-        if (VS_EXP_REPEAT & 1) VS_HIP(vsk::ingest_pyr(dframes, W, H, stride, fbits > 8 ? 16 : 8, fbits - 8, slot1, slot1 + L[1].img_off, n, frame_stride, pyr_frame, s));
-#endif
     }
     t_end(1);
     t_begin(VS_STAGE_PYR_DOWN);
@@ -733,9 +701,6 @@ int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int 
                 // one launch for every level of every keyframe of the run
                 VS_HIP(vsk::keyframe_levels(pyr + so * pyr_frame, lm + so * lm_frame, jac + so * jac_frame, KL, n_odd, 2 * pyr_frame,
                                             2 * lm_frame, 2 * jac_frame, s));
-#ifdef VS_EXP_REPEAT
-                if (VS_EXP_REPEAT & 4) VS_HIP(vsk::keyframe_levels(pyr + so * pyr_frame, lm + so * lm_frame, jac + so * jac_frame, KL, n_odd, 2 * pyr_frame, 2 * lm_frame, 2 * jac_frame, s));
-#endif
                 kf_launches += 1;
             } else {
                 for (int l = 0; l < levels; l++) {
@@ -856,10 +821,8 @@ int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int 
                 group = coop_env >= 0 ? std::max(1, std::min(coop_env, kCoopMaxGroup)) : std::max(1, std::min(kCoopGroup, cu_count / n_pairs));
             // full batches of a handle in VS_BATCH_SHARED mode: the small-footprint build (shares CUs with whatever else is
             // running, e.g. the previous clip's warp launch); VS_GN_CORESIDENT=0 / 1 overrides the rule (1: every launch, helpers off)
-            bool cores = false;
-#ifdef VS_HAVE_NT256V
             static const int cores_env = []() { const char* e = getenv("VS_GN_CORESIDENT"); return e ? atoi(e) : -1; }();
-            cores = small_wg && nt_max <= kCoResidentMaxTiles &&
+            const bool cores = small_wg && nt_max <= kCoResidentMaxTiles &&
                     (cores_env >= 0 ? cores_env != 0 : (batch_mode == VS_BATCH_SHARED && n_pairs >= kSharedMinPairs));
             const size_t selbuf_pair = (((size_t)nt_max * 6 + 255) & ~(size_t)255);
             if (cores) {
@@ -882,14 +845,7 @@ int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int 
                 }
             }
             const auto kernel = cores ? nt256v::vs_k_align_pairs : (small_wg ? nt512::vs_k_align_pairs : nt1024::vs_k_align_pairs);
-#else
-            const auto kernel = small_wg ? nt512::vs_k_align_pairs : nt1024::vs_k_align_pairs;
-#endif
-#ifdef VS_HAVE_NT256V
             const int kthreads = cores ? nt256v::kGnThreads : (small_wg ? nt512::kGnThreads : nt1024::kGnThreads);
-#else
-            const int kthreads = small_wg ? nt512::kGnThreads : nt1024::kGnThreads;
-#endif
             {   // The limit belongs to (kernel, device) and is shared by every handle of the process: it is only ever raised,
                 // and only when a launch needs more than was granted before (the call costs microseconds of host time).
                 static std::mutex dyn_mu;
@@ -1014,13 +970,6 @@ int vs_aligner::chunk_end() {
             VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
             VS_HIP(hipStreamSynchronize(s));
         }
-#ifdef VS_PROFILE_STAMPS
-        for (int l = levels - 1; l >= 0; l--) {
-            const unsigned long long* t = h_states[0].stamps[l];
-            fprintf(stderr, "[stamps] level %d: warpdiff %llu select %llu gather %llu gn(hessian+%d iters) %llu ticks\n", l, t[1] - t[0],
-                    t[2] - t[1], t[3] - t[2], h_states[0].iterations[l], t[4] - t[3]);
-        }
-#endif
         for (int q = 0; q < n_pairs; q++) {
             const int i = pair_frame[q];
             const PairState& st = h_states[q];
@@ -1126,14 +1075,7 @@ vs_aligner* vs_aligner_create(const vs_aligner_params* params, int device) try {
         }();
         if (env_mode >= 0) a->select_mode = env_mode;
     }
-    // VS_ALIGNER_STREAM_PRIORITY=low|high (read once; experiments): the handle's stream at the device's least / greatest priority
-    static const int prio_env = []() { const char* e = getenv("VS_ALIGNER_STREAM_PRIORITY"); return !e ? 0 : (e[0] == 'l' ? -1 : (e[0] == 'h' ? 1 : 0)); }();
-    hipError_t se;
-    if (prio_env != 0) {
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        se = hipStreamCreateWithPriority(&a->stream, hipStreamNonBlocking, prio_env < 0 ? least : greatest);
-    } else se = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
+    const hipError_t se = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
     if (se != hipSuccess) {
         set_error(VS_ERR_HIP, "hipStreamCreate failed");
         delete a;

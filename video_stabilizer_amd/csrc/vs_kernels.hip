@@ -86,10 +86,7 @@ __device__ __forceinline__ void pyr_passes(const uint8_t (*tile)[PD_IWP], uint32
 // (which the fused ingest kernel still runs on its LDS tile).
 // ------------------------------------------------------------------------------------------------
 namespace {
-#ifndef VS_PR_OUT
-#define VS_PR_OUT 16
-#endif
-constexpr int PR_OUT = VS_PR_OUT;           // output rows per wave (batches); a single frame is cut into bands of 4 rows: 4x the waves, a quarter of the walk
+constexpr int PR_OUT = 16;           // output rows per wave (batches); a single frame is cut into bands of 4 rows: 4x the waves, a quarter of the walk
 constexpr int PR_LIVE = 62;                 // lanes of a wave that produce outputs (two each)
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 }

@@ -36,58 +36,22 @@
 #include "vs_kernels.hpp"
 #include <algorithm>
 #include <cmath>
-#include <vector>
 #include "vs_device.hpp"
 
 using namespace vsd;
 
 namespace {
 
-// tuning knobs (tools/build_variant.sh builds the library with other values to compare them on the GPU)
-#ifndef VS_WARP_WS_EXTRA
-#define VS_WARP_WS_EXTRA 8               // staged rows beyond the tile's own in the float-tile (Lanczos2) kernels: 8 -> 24 rows, 31 KB of LDS, 5 workgroups per CU (experiment: 4 ->
-                                         // 20 rows, 25.9 KB, 6 workgroups with VS_WARP_FAST_MINWAVES=6; rotations beyond ~0.9 degrees then leave the window: profiles/r06_warp_sep_occupancy.txt)
-#endif
-#ifndef VS_WARP_FAST_MINWAVES
-#define VS_WARP_FAST_MINWAVES 4          // __launch_bounds__ waves per SIMD of the fast Lanczos2 kernels
-#endif
-#ifndef VS_WARP_FAST_SCHED
-#define VS_WARP_FAST_SCHED 1             // scheduling fences in the fast kernels: 0 none, 1 per row pair, 2 per source row
-#endif
-#ifndef VS_WARP_EXACT_MINWAVES
-#define VS_WARP_EXACT_MINWAVES 4
-#endif
-#ifndef VS_WARP_COORDS_FIRST
-#define VS_WARP_COORDS_FIRST 0           // 1: a scheduling fence between the rows' position arithmetic and the sampler blocks
-#endif
-#ifndef VS_WARP_TILE_H
-#define VS_WARP_TILE_H 16                // output rows per workgroup (4 waves: VS_WARP_TILE_H / 4 rows per wave)
-#endif
-
-#ifndef VS_WARP_WHATIF
-#define VS_WARP_WHATIF 0                 // analysis builds only (wrong results): 1 one LDS read per pixel instead of 16, 2 no fill, 4 no division, 8 no store, 16 no weight chains, 32 loads hit the same lines, 256 every tile takes the rim fill (right results)
-#endif
-#ifndef VS_WARP_TILES_PER_WG
-#define VS_WARP_TILES_PER_WG 1           // consecutive tiles of its XCD's run a workgroup walks; > 1: the next tile's source loads are in flight during the current tile's sampler blocks
-#endif
-#ifndef VS_WARP_TILES_PER_WG_BILINEAR
-#define VS_WARP_TILES_PER_WG_BILINEAR VS_WARP_TILES_PER_WG     // the same for the bilinear mode (measured twice, float tile and raw tile: equal or slower, profiles/r04_ab_warp_bilinear.md)
-#endif
-#ifndef VS_WARP_ROW_BLOCK
-#define VS_WARP_ROW_BLOCK 4              // rows a wave computes in one straight-line block (even); a wave's rows are walked in such blocks
-#endif
-#ifndef VS_WARP_FAST_PIPE
-#define VS_WARP_FAST_PIPE 1              // contracted mode: 1 = the software-pipelined sampler (fast_rows_pipelined), 0 = row pairs (fast_pair); bit-identical
-#endif
-#ifndef VS_WARP_PIPE_AHEAD
-#define VS_WARP_PIPE_AHEAD 6             // ... tap reads in flight ahead of the tap being consumed (< 8: the ring has eight slots)
-#endif
-#ifndef VS_WARP_PIPE_AHEAD_COMPACT
-#define VS_WARP_PIPE_AHEAD_COMPACT 2     // ... in the COMPACT instantiation (six waves per SIMD: 2 -> 72 VGPRs, 3 -> 75, 4 and more spill at the 85-register cap)
-#endif
-constexpr int WT_W = 64, WT_H = VS_WARP_TILE_H;      // output tile
+// Tuned constants.  The float-tile (Lanczos2) kernels stage 8 rows beyond the tile's own: 24 rows, 31 KB of LDS, 5 workgroups per CU
+// (4 extra rows -- 25.9 KB, 6 workgroups -- lose the window for rotations beyond ~0.9 degrees: profiles/r06_warp_sep_occupancy.txt).
+constexpr int WS_EXTRA = 8;
+constexpr int FAST_MINWAVES = 4, EXACT_MINWAVES = 4;  // __launch_bounds__ waves per SIMD of the float-tile Lanczos2 kernels
+// tap reads in flight ahead of the tap being consumed in the pipelined samplers (< 8: the ring has eight slots); the COMPACT
+// instantiation (six waves per SIMD) keeps 2: 72 VGPRs, 3 -> 75, 4 and more spill at the 85-register cap
+constexpr int PIPE_AHEAD = 6, PIPE_AHEAD_COMPACT = 2;
+constexpr int WT_W = 64, WT_H = 16;      // output tile
 constexpr int RPW = WT_H / 4;            // output rows per wave
-constexpr int RB = VS_WARP_ROW_BLOCK < RPW ? VS_WARP_ROW_BLOCK : RPW;
+constexpr int RB = 4;                    // rows a wave computes in one straight-line block (even); a wave's rows are walked in such blocks
 static_assert(RPW % RB == 0 && RB % 2 == 0, "rows per wave: a whole number of row blocks, rows in pairs");
 constexpr int WS_W = 80;                 // staged source pixels per row (multiple of 4)
 // (staged source rows: the tile height + 8, per kernel -- WS_H inside vs_k_bgr_warp_c3, CV_WS_H / CV16_WS_H for the fixed-point bilinear kernels)
@@ -100,59 +64,20 @@ constexpr int WS_RS = WS_W + 1;
 // 4K frame; with the byte tile the kernel is VALU-bound by count like its Lanczos siblings (88 vector instructions per pixel, ~70 of them
 // the sampler: counters and time stamps in profiles/r04_ab_warp_bilinear.md).
 // Row pitch 88 dwords = 24 (mod 64): the fill's 8-lane ds_write_b128 groups (4 rows x 2 column groups) touch every bank once.
-#ifndef VS_WARP_BILINEAR_U8_TILE
-#define VS_WARP_BILINEAR_U8_TILE 1
-#endif
 constexpr int WS_RS8 = WS_W + 8;
 // ... and its output tile is taller: the per-workgroup prologue (tile geometry, fill set-up, ~200 instructions) is paid once per tile, and
 // with a 14 KB tile 32 rows still leave 8 workgroups per CU.  4K: 17.3 -> 15.6 us per frame (64 rows: 15.1, but a 1080p frame is then only
 // 510 tiles); the float-tile kernels lose occupancy instead (contracted Lanczos2 38.2 -> 40.3 us).  profiles/r04_ab_warp_bilinear.md.
-#ifndef VS_WARP_TILE_H_BILINEAR_U8
-#define VS_WARP_TILE_H_BILINEAR_U8 32
-#endif
+constexpr int WT_H_BILINEAR_U8 = 32;
 // Bilinear on 16-bit containers (10 / 12 / 16-bit frames) the same way: the tile holds the source words, 8 bytes {B | G << 16, R} per
 // pixel (17 KB for a 64 x 16 output tile instead of 31 KB of float4), two pixels per ds_write_b128 in the fill, one ds_read2_b64 per window
 // row in the sampler, conversions by SDWA word select.  Same 88-pixel pitch: 176 dwords = 48 (mod 64), conflict-free like the byte tile.
-#ifndef VS_WARP_BILINEAR_U16_TILE
-#define VS_WARP_BILINEAR_U16_TILE 1
-#endif
-#ifndef VS_WARP_CV_ROW_FILL
-#define VS_WARP_CV_ROW_FILL 1            // interior fill of every byte / word tile: a wave slot = three staged rows x twenty column groups, the slots twelve rows apart (see vs_k_bgr_warp_cv_c3)
-#endif
-#ifndef VS_WARP_TILE_H_BILINEAR_U16
-#define VS_WARP_TILE_H_BILINEAR_U16 16
-#endif
-constexpr bool raw_tile_of(int bits, int mode) { return mode == 1 && (bits == 8 ? VS_WARP_BILINEAR_U8_TILE : VS_WARP_BILINEAR_U16_TILE) != 0; }
+constexpr int WT_H_BILINEAR_U16 = 16;
 constexpr int tile_h_of(int bits, int mode) {
-    return !raw_tile_of(bits, mode) ? VS_WARP_TILE_H : (bits == 8 ? VS_WARP_TILE_H_BILINEAR_U8 : VS_WARP_TILE_H_BILINEAR_U16);
+    return mode != 1 ? WT_H : (bits == 8 ? WT_H_BILINEAR_U8 : WT_H_BILINEAR_U16);
 }
-static_assert(VS_WARP_TILE_H_BILINEAR_U16 % 8 == 0, "rows per wave in pairs");
-static_assert(VS_WARP_TILE_H_BILINEAR_U8 % 8 == 0 && (VS_WARP_TILE_H_BILINEAR_U8 + 8) / 4 * (WS_W / 4) < 1024, "fill_item's p / 20 is exact below 1024");
-
-// analysis build (tools/warp_stamps.py): every wave of the first STAMP_WGS workgroups of a launch leaves eight s_memtime stamps
-// (entry, geometry done, loads issued, loads landed, tile written, barrier passed, rows stored, stores drained) and its HW_ID / XCC_ID
-#ifndef VS_WARP_STAMPS
-#define VS_WARP_STAMPS 0
-#endif
-#if VS_WARP_STAMPS
-constexpr int STAMP_WGS = 8192, STAMP_N = 10;
-__device__ unsigned long long g_warp_stamps[STAMP_WGS * 4 * STAMP_N];
-#define VS_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); stamp[i] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define VS_STAMP_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define VS_STAMP(i) ((void)0)
-#define VS_STAMP_DRAIN() ((void)0)
-#endif
-
-// the aligned output stores: plain, or (experiment) non-temporal -- the output is written once and not read by this kernel
-#ifndef VS_WARP_NT_STORE
-#define VS_WARP_NT_STORE 0
-#endif
-#if VS_WARP_NT_STORE
-#define VS_STORE32(p, v) __builtin_nontemporal_store((uint32_t)(v), (uint32_t*)(p))
-#else
-#define VS_STORE32(p, v) (*(uint32_t*)(p) = (v))
-#endif
+static_assert(WT_H_BILINEAR_U16 % 8 == 0, "rows per wave in pairs");
+static_assert(WT_H_BILINEAR_U8 % 8 == 0 && (WT_H_BILINEAR_U8 + 8) / 4 * (WS_W / 4) < 1024, "fill_item's p / 20 is exact below 1024");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -205,7 +130,7 @@ __device__ __forceinline__ void exact_pair(const lds_f4 t[2], const f2 fr[2], fl
         for (int j = 0; j < 2; j++) { x2[j][c] = x[j][c] * x[j][c]; v[j][c] = f2{0.000858519f, 0.000858519f}; }
     const float C[6] = {-0.0158853f, 0.128693f, -0.583468f, 1.52229f, -2.05238f, 0.999861f};
 #pragma unroll
-    for (int s = 0; s < ((VS_WARP_WHATIF & 16) ? 1 : 6); s++) {
+    for (int s = 0; s < 6; s++) {
 #pragma unroll
         for (int c = 0; c < 4; c++)
 #pragma unroll
@@ -224,7 +149,6 @@ __device__ __forceinline__ void exact_pair(const lds_f4 t[2], const f2 fr[2], fl
         v[j][3].y = fabsf(x[j][3].y) >= 2.0f ? 0.0f : v[j][3].y;
     }
     f2 nbg[2] = {f2{0.f, 0.f}, f2{0.f, 0.f}}, nrd[2] = {f2{0.f, 0.f}, f2{0.f, 0.f}};
-    const f4 one_tap[2] = {t[0][0], t[1][0]};
 #pragma unroll
     for (int ry = 0; ry < 4; ry++) {
         f2 p01[2], p23[2];
@@ -239,7 +163,7 @@ __device__ __forceinline__ void exact_pair(const lds_f4 t[2], const f2 fr[2], fl
             f2 mbg[2], mrd[2];
 #pragma unroll
             for (int j = 0; j < 2; j++) {
-                const f4 val = (VS_WARP_WHATIF & 1) ? one_tap[j] : t[j][ry * WS_RS + rx];
+                const f4 val = t[j][ry * WS_RS + rx];
                 const f2 pp = rx < 2 ? p01[j] : p23[j];
                 const float w2d = (rx & 1) ? pp.y : pp.x;
                 const f2 ww = {w2d, w2d};
@@ -257,68 +181,18 @@ __device__ __forceinline__ void exact_pair(const lds_f4 t[2], const f2 fr[2], fl
     for (int j = 0; j < 2; j++) { num[j][0] = nbg[j].x; num[j][1] = nbg[j].y; num[j][2] = nrd[j].x; num[j][3] = nrd[j].y; }
 }
 
-// VS_WARP_LANCZOS2_FAST of two output pixels: the contracted sampler of vs_device.hpp (oracle twin VSO_WARP_LANCZOS2_CONTRACTED)
-// written out for the LDS tile -- Horner steps as single fmas, w2d = wx * wy a rounded product, num = fma(w2d, val, num) per
-// channel and den = den + w2d in the reference's tap order (rx inner, ry outer).  Everything is scalar fp32: a packed fp32
-// instruction next to scalar ones costs more than either pure stream (profiles/r04_ubench_issue.txt: fma 2.8 cycles, pk_fma 4.8,
-// a 3:1 mix 4.6 per instruction).  num[j] = {numB, numG, numR, den}; the caller divides.  (Kept for VS_WARP_FAST_PIPE=0 and the
-// what-if builds; the shipped contracted kernel runs fast_rows_pipelined below.)
-__device__ __forceinline__ void fast_pair(const lds_f4 t[2], const f2 fr[2], float num[2][4]) {
-    // weight chain c of pixel j: 0..3 = x taps 1..4, 4..7 = y taps 1..4
-    float x[2][8], x2[2][8], v[2][8];
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        x[j][0] = -1.0f - fr[j].x; x[j][1] = 0.0f - fr[j].x; x[j][2] = 1.0f - fr[j].x; x[j][3] = 2.0f - fr[j].x;
-        x[j][4] = -1.0f - fr[j].y; x[j][5] = 0.0f - fr[j].y; x[j][6] = 1.0f - fr[j].y; x[j][7] = 2.0f - fr[j].y;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; c++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) { x2[j][c] = x[j][c] * x[j][c]; v[j][c] = 0.000858519f; }
-    const float C[6] = {-0.0158853f, 0.128693f, -0.583468f, 1.52229f, -2.05238f, 0.999861f};
-#pragma unroll
-    for (int s = 0; s < ((VS_WARP_WHATIF & 16) ? 1 : 6); s++)
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) v[j][c] = __builtin_fmaf(v[j][c], x2[j][c], C[s]);
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        // |x| >= 2 can only happen for taps 1 (-1-frac) and 4 (2-frac)
-        v[j][0] = fabsf(x[j][0]) >= 2.0f ? 0.0f : v[j][0];
-        v[j][3] = fabsf(x[j][3]) >= 2.0f ? 0.0f : v[j][3];
-        v[j][4] = fabsf(x[j][4]) >= 2.0f ? 0.0f : v[j][4];
-        v[j][7] = fabsf(x[j][7]) >= 2.0f ? 0.0f : v[j][7];
-        num[j][0] = 0.0f; num[j][1] = 0.0f; num[j][2] = 0.0f; num[j][3] = 0.0f;
-    }
-    const f4 one_tap[2] = {t[0][0], t[1][0]};
-#pragma unroll
-    for (int ry = 0; ry < 4; ry++) {
-#pragma unroll
-        for (int rx = 0; rx < 4; rx++) {
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const f4 val = (VS_WARP_WHATIF & 1) ? one_tap[j] : t[j][ry * WS_RS + rx];
-                const float w2d = v[j][rx] * v[j][4 + ry];
-                num[j][0] = __builtin_fmaf(w2d, val.x, num[j][0]);
-                num[j][1] = __builtin_fmaf(w2d, val.y, num[j][1]);
-                num[j][2] = __builtin_fmaf(w2d, val.z, num[j][2]);
-                num[j][3] = num[j][3] + w2d;
-            }
-        }
-        if (VS_WARP_FAST_SCHED >= 2) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// VS_WARP_FAST_PIPE: the same contracted arithmetic for the RB = 4 pixels of a lane (rows k = 0..3), software-pipelined so that a wave's
-// LDS reads are spread evenly over ALL of its vector work instead of arriving in bursts.  In fast_pair a pixel pair is 150 vector
+// VS_WARP_LANCZOS2_FAST for the RB = 4 pixels of a lane (rows k = 0..3): the contracted sampler of vs_device.hpp (oracle twin
+// VSO_WARP_LANCZOS2_CONTRACTED) -- Horner steps as single fmas, w2d = wx * wy a rounded product, num = fma(w2d, val, num) per channel and
+// den = den + w2d in the reference's tap order (rx inner, ry outer), all scalar fp32 (a packed fp32 instruction next to scalar ones costs
+// more than either pure stream, profiles/r04_ubench_issue.txt) -- software-pipelined so that a wave's LDS reads are spread evenly over
+// ALL of its vector work instead of arriving in bursts.  Computed a pixel pair at a time, straight-line, that is 150 vector
 // instructions of weight chains with no LDS traffic followed by 32 ds_read_b128 inside 160 instructions of tap arithmetic; the four
 // waves of a workgroup leave the fill barrier together, so their tap phases coincide and one workgroup alone asks for ~80 % of the
 // CU's LDS read rate during them (profiles/r04_ubench_issue.txt: a ds_read_b128 per 4 fmas is LDS-bound, 81 cycles per 4 taps
 // against 44 for the fmas).  Here stage k runs three things interleaved, slice by slice (16 slices, one tap each): the taps of pixel k,
 // the weight chains of pixel k + 1 and the division / store conversion of pixel k - 1 -- one ds_read_b128 per ~11 vector
-// instructions throughout, issued VS_WARP_PIPE_AHEAD taps ahead of their use through a ring of eight float4 registers.  Per pixel the
-// operations and their order are fast_pair's (weights: Horner fmas per chain; taps rx inner, ry outer; num = fma(w2d, val, num),
+// instructions throughout, issued AHEAD taps ahead of their use through a ring of eight float4 registers.  Per pixel the operations and
+// their order are the contracted sampler's (weights: Horner fmas per chain; taps rx inner, ry outer; num = fma(w2d, val, num),
 // den = den + w2d; div3_core; store_u), so the result is bit-identical: the pipelining only decides WHEN an instruction issues.
 // Scheduling fences between the slices keep the compiler from undoing the interleave.
 // (Round 5 tried to leave out the four |x| >= 2 selects per pixel in blocks whose fractions cannot reach them -- one min3 / max3 chain over
@@ -326,7 +200,7 @@ __device__ __forceinline__ void fast_pair(const lds_f4 t[2], const f2 fr[2], flo
 // to do it lost: two copies of this function behind a wave-uniform branch took the kernel from 78 to 128 VGPRs with 9 spilled (42.1 us per
 // 4K frame instead of 38.3), scalar branches over the select slices cut the straight-line block into pieces the register allocator
 // handles far worse (135 spilled VGPRs).  profiles/r05_warp_sep.md.)
-template <int NPX, int AHEAD = VS_WARP_PIPE_AHEAD, int RS = WS_RS>
+template <int NPX, int AHEAD, int RS>
 __device__ __forceinline__ void fast_rows_pipelined(const lds_f4 (&t)[NPX], const f2 (&fr)[NPX], float maxv, float (&num)[NPX][4],
                                                     uint32_t (&o)[NPX][3], bool& all_ok) {
     constexpr int NV = 8;
@@ -408,48 +282,14 @@ __device__ __forceinline__ void fast_rows_pipelined(const lds_f4 (&t)[NPX], cons
     }
 }
 
-// RN(1 / den) for den in [0.5, 2): v_rcp, one Newton step, one residual correction.  Equal to the IEEE quotient 1.0f / den for EVERY
-// float of the range (exhaustive: tools/check_rcp.hip, profiles/r05_check_rcp.txt; the compiler's own expansion makes a second
-// correction and scales / fixes up for the operands outside it).  The separable sampler's den = (sum wx)(sum wy) lies in [0.9995, 1.039]
-// for every fraction in [0, 1] (the same tool walks all 2^30 + 1 of them), so no range test guards the call.
-__device__ __forceinline__ float rcp_rn(float den) {
-    float r = __builtin_amdgcn_rcpf(den);
-    const float e = __builtin_fmaf(-den, r, 1.0f);
-    r = __builtin_fmaf(e, r, r);
-    const float tt = __builtin_fmaf(-den, r, 1.0f);
-    return __builtin_fmaf(tt, r, r);
-}
-
-// VS_WARP_LANCZOS2_SEP of one output pixel, straight-line (the what-if builds and VS_WARP_FAST_PIPE=0): num = {numB, numG, numR, den}
-__device__ __forceinline__ void sep_pixel(const lds_f4 t, const f2 fr, float num[4]) {
-    float wx[4], wy[4];
-    lanczos_weights4_fma(fr.x, wx);
-    lanczos_weights4_fma(fr.y, wy);
-    float h[4][3];
-#pragma unroll
-    for (int ry = 0; ry < 4; ry++) {
-#pragma unroll
-        for (int rx = 0; rx < 4; rx++) {
-            const f4 val = t[ry * WS_RS + rx];
-            const float vc[3] = {val.x, val.y, val.z};
-#pragma unroll
-            for (int c = 0; c < 3; c++) h[ry][c] = rx == 0 ? wx[0] * vc[c] : __builtin_fmaf(wx[rx], vc[c], h[ry][c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        num[c] = __builtin_fmaf(wy[3], h[3][c], __builtin_fmaf(wy[2], h[2][c], __builtin_fmaf(wy[1], h[1][c], wy[0] * h[0][c])));
-    num[3] = lanczos_separable_den(wx, wy);
-}
-
 // VS_WARP_LANCZOS2_SEP for the RB = 4 pixels of a lane, software-pipelined like fast_rows_pipelined: stage k interleaves, slice by slice
 // (16 slices, one tap each), the taps of pixel k (3 fmas per tap into the row sums h, 3 more after a row's fourth tap into num), the
 // weight chains of pixel k + 1, the denominator and its reciprocal of pixel k, and the scaling / store conversion of pixel k - 1.  Per
 // pixel: 72 weight-chain operations, 7 for den, 5 for RN(1 / den), 48 + 12 tap fmas, 3 products, 9 store conversions = 156 against the
 // contracted form's 179 -- bit-identical to lanczos_separable_combine / the oracle's
 // VSO_WARP_LANCZOS2_SEPARABLE (the pipelining only decides WHEN an instruction issues).  num[k] = {numB, numG, numR, den}; all_ok is
-// not touched (rcp_rn: den cannot leave its range).
-template <int NPX, int AHEAD = VS_WARP_PIPE_AHEAD, int RS = WS_RS>
+// not touched (den cannot leave its range, see r_slice).
+template <int NPX, int AHEAD, int RS>
 __device__ __forceinline__ void sep_rows_pipelined(const lds_f4 (&t)[NPX], const f2 (&fr)[NPX], float maxv, float (&num)[NPX][4],
                                                    uint32_t (&o)[NPX][3], bool& all_ok) {
     constexpr int NV = 8;
@@ -479,7 +319,11 @@ __device__ __forceinline__ void sep_rows_pipelined(const lds_f4 (&t)[NPX], const
             v[b + 3] = fabsf(wx_[b + 3]) >= 2.0f ? 0.0f : v[b + 3];
         }
     };
-    // den = (sum wx)(sum wy) of pixel kk and its correctly rounded reciprocal (rcp_rn), 12 instructions in 5 slices
+    // den = (sum wx)(sum wy) of pixel kk and its correctly rounded reciprocal, 12 instructions in 5 slices.  RN(1 / den) for den in
+    // [0.5, 2): v_rcp, one Newton step, one residual correction -- equal to the IEEE quotient 1.0f / den for EVERY float of the range
+    // (exhaustive: tools/check_rcp.hip, profiles/r05_check_rcp.txt; the compiler's own expansion makes a second correction and scales /
+    // fixes up for the operands outside it).  den lies in [0.9995, 1.039] for every fraction in [0, 1] (the same tool walks all
+    // 2^30 + 1 of them), so no range test guards it.
     auto r_slice = [&](int j, int kk) {
         const float (&v)[8] = wgt[kk & 1];
         const float den = num[kk][3];
@@ -541,23 +385,10 @@ __device__ __forceinline__ void sep_rows_pipelined(const lds_f4 (&t)[NPX], const
     }
 }
 
-// image_warp's bilinear (generators.cpp:148-163) per channel; t = staged pixel (iy, ix)
-__device__ __forceinline__ void sample_bilinear(lds_f4 t, f2 fr, float q[3]) {
-    const f4 a0 = t[0], a1 = t[1], b0 = t[WS_RS], b1 = t[WS_RS + 1];
-    // lerp(a,b,t) = a*(1-t) + b*t (generators.cpp:161-163) per channel, all scalar: three channels fill one and a half packed
-    // instructions, and a packed fp32 instruction costs the issue time of two scalar ones (40 issue slots packed, 29 scalar)
-    const float tx = fr.x, ty = fr.y, otx = 1.0f - tx, oty = 1.0f - ty;
-    const float a0c[3] = {a0.x, a0.y, a0.z}, a1c[3] = {a1.x, a1.y, a1.z}, b0c[3] = {b0.x, b0.y, b0.z}, b1c[3] = {b1.x, b1.y, b1.z};
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float top = a0c[c] * otx + a1c[c] * tx;
-        const float bot = b0c[c] * otx + b1c[c] * tx;
-        q[c] = top * oty + bot * ty;
-    }
-}
-
-// The same on the byte tile: t = dword of staged pixel (iy, ix) = B | G << 8 | R << 16.  Two ds_read2_b32 fetch the 2 x 2 window; the
-// twelve conversions are exact, so every float below is the float-tile path's value: bit-identical.
+// image_warp's bilinear (generators.cpp:148-163) per channel on the byte tile: t = dword of staged pixel (iy, ix) = B | G << 8 | R << 16.
+// Two ds_read2_b32 fetch the 2 x 2 window; the twelve conversions are exact, so every float below is the reference's value: bit-identical.
+// lerp(a,b,t) = a*(1-t) + b*t (generators.cpp:161-163) per channel, all scalar: three channels fill one and a half packed instructions, and
+// a packed fp32 instruction costs the issue time of two scalar ones (40 issue slots packed, 29 scalar)
 __device__ __forceinline__ void sample_bilinear_u8(const __attribute__((address_space(3))) uint32_t* t, f2 fr, float q[3]) {
     const uint32_t a0 = t[0], a1 = t[1], b0 = t[WS_RS8], b1 = t[WS_RS8 + 1];
     const float tx = fr.x, ty = fr.y, otx = 1.0f - tx, oty = 1.0f - ty;
@@ -674,38 +505,28 @@ __device__ __forceinline__ FillItem fill_item_g(int lane, int slot) {      // th
 // takes them when every frame's rows (and, for shape 2, columns) fit (the host-side extents say the tile's footprint spans under 16 source rows: rotations up to ~0.9 degrees at unit scale); a tile that
 // does not fit its window takes the per-pixel path in either instantiation, so the choice is about speed only -- same arithmetic, same bits.
 template <typename T, int MODE, int BORDER, int SHAPE = 0>
-__global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : SHAPE == 1 ? 6 : VS_WARP_FAST_MINWAVES) : (raw_tile_of((int)sizeof(T) * 8, MODE) ? 8 : VS_WARP_EXACT_MINWAVES)) void vs_k_bgr_warp_c3(
+__global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : SHAPE == 1 ? 6 : FAST_MINWAVES) : (MODE == 1 ? 8 : EXACT_MINWAVES)) void vs_k_bgr_warp_c3(
     const T* __restrict__ src, int w, int h, int src_stride, const float4* __restrict__ params, T* __restrict__ dst,
     int dst_stride, size_t src_fs, size_t dst_fs, int tiles_x, uint32_t tiles_x_magic, int tiles_per_frame, int chunk,
     float maxv, vsk::Roi roi, const float4* __restrict__ extents) {
-    constexpr bool RAWTILE = raw_tile_of((int)sizeof(T) * 8, MODE);       // the tile holds source bytes / words, not floats (both depths)
+    constexpr bool RAWTILE = MODE == 1;                                  // bilinear: the tile holds source bytes / words, not floats (both depths)
     constexpr int PXD = sizeof(T) == 1 ? 1 : 2;                          // ... dwords per staged pixel
     // this kernel's tile height and what follows from it (the namespace-scope values are those of the 16-row kernels)
-    constexpr int WT_H = tile_h_of((int)sizeof(T) * 8, MODE), RPW = WT_H / 4, RB = VS_WARP_ROW_BLOCK < RPW ? VS_WARP_ROW_BLOCK : RPW, WS_H = WT_H + (RAWTILE ? 8 : (SHAPE ? 4 : VS_WARP_WS_EXTRA));
+    constexpr int WT_H = tile_h_of((int)sizeof(T) * 8, MODE), RPW = WT_H / 4, WS_H = WT_H + (RAWTILE ? 8 : (SHAPE ? 4 : WS_EXTRA));
     constexpr bool COMPACT = SHAPE != 0;
     constexpr int KG = SHAPE == 2 ? 18 : WS_W / 4, KRS = SHAPE == 2 ? 4 * KG + 1 : WS_RS;      // column groups per staged row, float-tile row pitch (73 slots = 1168 bytes = 16 (mod 128), like 81)
     static_assert(!COMPACT || (!RAWTILE && (MODE == 2 || MODE == 3)), "the compact windows belong to the float-tile Lanczos2 forms");
     static_assert(SHAPE != 2 || MODE == 3, "seven waves per SIMD: the separable form only (the contracted one needs 77 registers)");
-    static_assert(SHAPE != 2 || (VS_WARP_FAST_PIPE && RB == 4 && !VS_WARP_WHATIF), "the 73-slot pitch is known to the pipelined sampler only");
+    static_assert((MODE != 2 && MODE != 3) || RB == 4, "the pipelined samplers take four rows per block (and know the 73-slot pitch)");
     constexpr int FILL_SLOTS = (WS_H / 4 * KG + 63) / 64;
     static_assert(RPW % RB == 0 && RB % 2 == 0, "rows per wave: a whole number of row blocks, rows in pairs");
     __shared__ f4 tile[RAWTILE ? 1 : WS_H * KRS];         // {B,G,R,1} per staged source pixel
     __shared__ __attribute__((aligned(16))) uint32_t tile_raw[RAWTILE ? WS_H * WS_RS8 * PXD : 4];    // bilinear: B | G << 8 | R << 16 (8-bit frames), {B | G << 16, R} (16-bit containers)
-#ifdef VS_WARP_LDS_PAD
-    __shared__ uint32_t lds_pad[VS_WARP_LDS_PAD / 4];       // occupancy experiments only: fewer workgroups per CU
-    if (w < 0) lds_pad[threadIdx.x] = 0;
-#endif
     // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2) in linear id order and
     // gridDim.x is a multiple of 8, so workgroup b of a frame works on its tile (b % 8) * chunk + b / 8: every XCD walks
     // one contiguous run of tiles in raster order and the halo rows / columns shared by neighbouring tiles hit in its L2.
-    constexpr int NT = MODE == 1 ? VS_WARP_TILES_PER_WG_BILINEAR : VS_WARP_TILES_PER_WG;
-#if VS_WARP_STAMPS
-    unsigned long long stamp[STAMP_N] = {};
-    VS_STAMP(0);
-#endif
-    const int tl0 = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3) * NT;         // this workgroup's first tile
-    const int tl_end = min(tiles_per_frame, (int)((blockIdx.x & 7) + 1) * chunk);        // end of its XCD's run
-    if (tl0 >= tl_end) return;
+    const int tl = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+    if (tl >= min(tiles_per_frame, (int)((blockIdx.x & 7) + 1) * chunk)) return;
     const int frame = blockIdx.y;
     const float4 P = params[frame];
     src += (size_t)frame * src_fs;
@@ -758,54 +579,48 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     }
     // interior tiles (the whole staged window lies inside an aligned frame: all but the frame's rim): no clamps and no border
     // tests per item, one offset from a uniform base
-    const bool interior = !(VS_WARP_WHATIF & 256) && fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h;   // uniform (analysis bit 256: every tile fills like a rim tile)
+    const bool interior = fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h;   // uniform
     return Geom{x0, y0, sx_lo, sy_lo, rows, groups, fits, interior};
     };
 
     // 4 source pixels (12 bytes, one aligned load) per work item, converted once, written as 4 float4.
     // (16 + 8) rows x 20 groups = 480 items = 2 per thread; all loads are issued before the first conversion.
     u32x3 q0[FILL_SLOTS], q1[FILL_SLOTS];
-    // Interior tiles of the raw-tile (bilinear) kernels take the fixed-point bilinear kernels' row-triplet item map (VS_WARP_CV_ROW_FILL): lane ->
+    // Interior tiles of the raw-tile (bilinear) kernels take the fixed-point bilinear kernels' row-triplet item map: lane ->
     // (row lane / 20 of a row triplet, column group lane % 20), once per workgroup; slot s of wave wv stages rows 3 (wv + 4 s) + r3, twelve rows
     // further per slot, so the source offset advances by a uniform and the tile address by a constant.  (Not the float tiles: 64 bytes per
     // item there, and consecutive lanes 64 bytes apart put four lanes of every 16 on the same banks.)
-    constexpr bool ROWFILL = RAWTILE && VS_WARP_CV_ROW_FILL != 0;
-    static_assert(!ROWFILL || (WS_W / 4 == 20 && FILL_SLOTS == (WS_H + 11) / 12), "row-triplet item map");
+    static_assert(!RAWTILE || (WS_W / 4 == 20 && FILL_SLOTS == (WS_H + 11) / 12), "row-triplet item map");
     const int rf_r3 = (int)(((uint32_t)lane * 13u) >> 8), rf_g = lane - 20 * rf_r3, rf_row0 = 3 * wv + rf_r3;      // lane / 20, lane % 20
-    auto item_of = [&](int s, bool interior) -> FillItem {
-        if (ROWFILL && interior) return FillItem{rf_r3 < 3 ? rf_row0 + 12 * s : WS_H, rf_g};                // (lanes 60..63 carry no item: a row beyond every tile)
+    auto interior_item = [&](int s) -> FillItem {
+        if (RAWTILE) return FillItem{rf_r3 < 3 ? rf_row0 + 12 * s : WS_H, rf_g};                // (lanes 60..63 carry no item: a row beyond every tile)
         return fill_item_g<KG>(lane, wv + 4 * s);
     };
-    // the loads of an interior tile: into q0 / q1, which the fill converts -- right away, or (VS_WARP_TILES_PER_WG > 1) after the
-    // previous tile's sampler blocks, so that a tile's memory latency lies under the tile before it
+    // the loads of an interior tile: into q0 / q1, which the fill converts
     auto issue = [&](const Geom& g) {
-        const T* base = (VS_WARP_WHATIF & 32) ? src : src + ((size_t)g.sy_lo * src_stride + (size_t)g.sx_lo * 3);
+        const T* base = src + ((size_t)g.sy_lo * src_stride + (size_t)g.sx_lo * 3);
         const uint32_t rf_off0 = (uint32_t)rf_row0 * (uint32_t)src_stride + 12u * (uint32_t)rf_g;
 #pragma unroll
         for (int s = 0; s < FILL_SLOTS; s++) {
-            const FillItem it = item_of(s, true);
-            uint32_t off = ROWFILL ? rf_off0 + (uint32_t)(12 * s) * (uint32_t)src_stride
-                                   : (uint32_t)it.row * (uint32_t)src_stride + 12u * (uint32_t)it.g;      // elements
-            if (VS_WARP_WHATIF & 32) off &= 0xffcu;                  // (analysis: every load hits the same few cache lines)
+            const FillItem it = interior_item(s);
+            const uint32_t off = RAWTILE ? rf_off0 + (uint32_t)(12 * s) * (uint32_t)src_stride
+                                         : (uint32_t)it.row * (uint32_t)src_stride + 12u * (uint32_t)it.g;      // elements
             if (it.row < g.rows && it.g < g.groups) {
                 q0[s] = *(const u32x3*)(base + off);
                 if (sizeof(T) == 2) q1[s] = *(const u32x3*)(base + off + 6);
             }
         }
     };
-    auto fill = [&](const Geom& g, bool loaded) {
+    auto fill = [&](const Geom& g) {
         const int sx_lo = g.sx_lo, sy_lo = g.sy_lo, rows = g.rows, groups = g.groups;
         FillItem it[FILL_SLOTS];
         bool live[FILL_SLOTS], direct[FILL_SLOTS];
         const T* rowp[FILL_SLOTS];
         if (g.interior) {
-            if (!loaded) issue(g);
-            VS_STAMP(2);
-            VS_STAMP_DRAIN();
-            VS_STAMP(3);
+            issue(g);
 #pragma unroll
             for (int s = 0; s < FILL_SLOTS; s++) {
-                it[s] = item_of(s, true);
+                it[s] = interior_item(s);
                 live[s] = it[s].row < rows && it[s].g < groups;
                 direct[s] = live[s];
                 rowp[s] = src;
@@ -974,8 +789,6 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     bool all_ok = true;
     // rows are processed two at a time, the two rows' instructions alternating in source order: a packed-fp32 result
     // cannot feed the very next VALU instruction without a wait state on gfx950, and the other row's operation fills it
-    // (VS_WARP_COORDS_FIRST: the positions of all RB rows before the first sampler block -- scalar fp32 instructions cost more
-    // between packed ones than among themselves, tools/ubench_mix.hip)
     f2 fr_all[RB];
     lds_f4 t_all[RB];
 #pragma unroll
@@ -993,13 +806,10 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
         t_all[k] = RAWTILE ? (lds_f4)((const __attribute__((address_space(3))) char*)tile_raw + boff)
                           : (lds_f4)((const __attribute__((address_space(3))) char*)tile + boff);
     }
-#if VS_WARP_COORDS_FIRST
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    if (MODE == 2 && VS_WARP_FAST_PIPE && RB == 4 && !VS_WARP_WHATIF) {
-        fast_rows_pipelined<RB, COMPACT ? VS_WARP_PIPE_AHEAD_COMPACT : VS_WARP_PIPE_AHEAD, KRS>(t_all, fr_all, maxv, num, o, all_ok);
-    } else if (MODE == 3 && VS_WARP_FAST_PIPE && RB == 4 && !VS_WARP_WHATIF) {
-        sep_rows_pipelined<RB, COMPACT ? VS_WARP_PIPE_AHEAD_COMPACT : VS_WARP_PIPE_AHEAD, KRS>(t_all, fr_all, maxv, num, o, all_ok);
+    if (MODE == 2) {
+        fast_rows_pipelined<RB, COMPACT ? PIPE_AHEAD_COMPACT : PIPE_AHEAD, KRS>(t_all, fr_all, maxv, num, o, all_ok);
+    } else if (MODE == 3) {
+        sep_rows_pipelined<RB, COMPACT ? PIPE_AHEAD_COMPACT : PIPE_AHEAD, KRS>(t_all, fr_all, maxv, num, o, all_ok);
     } else
 #pragma unroll
     for (int kp = 0; kp < RB; kp += 2) {
@@ -1011,35 +821,14 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 all_ok = all_ok && (num[kp + j][3] > 0.5f && num[kp + j][3] < 2.0f);
-                if (VS_WARP_WHATIF & 4) { q[j][0] = num[kp + j][0]; q[j][1] = num[kp + j][1]; q[j][2] = num[kp + j][2] + num[kp + j][3]; }
-                else div3_core(num[kp + j][0], num[kp + j][1], num[kp + j][2], num[kp + j][3], q[j]);
+                div3_core(num[kp + j][0], num[kp + j][1], num[kp + j][2], num[kp + j][3], q[j]);
             }
-        } else if (MODE == 3) {
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                sep_pixel(t[j], fr[j], num[kp + j]);
-                const float r = rcp_rn(num[kp + j][3]);
-                q[j][0] = num[kp + j][0] * r; q[j][1] = num[kp + j][1] * r; q[j][2] = num[kp + j][2] * r;
-            }
-        } else if (MODE == 2) {
-            fast_pair(t, fr, &num[kp]);
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                all_ok = all_ok && (num[kp + j][3] > 0.5f && num[kp + j][3] < 2.0f);
-                if (VS_WARP_WHATIF & 4) { q[j][0] = num[kp + j][0]; q[j][1] = num[kp + j][1]; q[j][2] = num[kp + j][2] + num[kp + j][3]; }
-                else div3_core(num[kp + j][0], num[kp + j][1], num[kp + j][2], num[kp + j][3], q[j]);
-            }
+        } else if (sizeof(T) == 2) {
+            sample_bilinear_u16((const __attribute__((address_space(3))) u32x2_t*)t[0], fr[0], q[0]);
+            sample_bilinear_u16((const __attribute__((address_space(3))) u32x2_t*)t[1], fr[1], q[1]);
         } else {
-            if (RAWTILE && sizeof(T) == 2) {
-                sample_bilinear_u16((const __attribute__((address_space(3))) u32x2_t*)t[0], fr[0], q[0]);
-                sample_bilinear_u16((const __attribute__((address_space(3))) u32x2_t*)t[1], fr[1], q[1]);
-            } else if (RAWTILE) {
-                sample_bilinear_u8((const __attribute__((address_space(3))) uint32_t*)t[0], fr[0], q[0]);
-                sample_bilinear_u8((const __attribute__((address_space(3))) uint32_t*)t[1], fr[1], q[1]);
-            } else {
-                sample_bilinear(t[0], fr[0], q[0]);
-                sample_bilinear(t[1], fr[1], q[1]);
-            }
+            sample_bilinear_u8((const __attribute__((address_space(3))) uint32_t*)t[0], fr[0], q[0]);
+            sample_bilinear_u8((const __attribute__((address_space(3))) uint32_t*)t[1], fr[1], q[1]);
         }
 #pragma unroll
         for (int j = 0; j < 2; j++) {
@@ -1047,9 +836,8 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
             o[kp + j][1] = store_u(q[j][1], maxv);
             o[kp + j][2] = store_u(q[j][2], maxv);
         }
-        if (MODE == 2 && VS_WARP_FAST_SCHED >= 1) __builtin_amdgcn_sched_barrier(0);   // keeps the second pair's 32 LDS reads (128 VGPRs) behind the first pair
     }
-    if (MODE != 1 && MODE != 3 && !VS_WARP_WHATIF && __any(!all_ok)) {
+    if (MODE != 1 && MODE != 3 && __any(!all_ok)) {
         // a weight sum outside (0.5, 2): cannot happen for frac in [0,1]; kept so that the result is operator/ whatever the input
 #pragma unroll
         for (int k = 0; k < RB; k++) {
@@ -1077,7 +865,7 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
             if (y < roi.h) {                                 // wave-uniform
                 uint8_t* orow = (uint8_t*)dst + (size_t)y * dst_stride;
                 if (rows_aligned && quad_in) {
-                    if (m < 3 && (!(VS_WARP_WHATIF & 8) || d == 0x12345678u)) VS_STORE32((uint32_t*)(orow + loff), d);
+                    if (m < 3) *(uint32_t*)(orow + loff) = d;
                 } else if (lane_in) {
                     orow[(size_t)x * 3] = (uint8_t)o[k][0];
                     orow[(size_t)x * 3 + 1] = (uint8_t)o[k][1];
@@ -1096,8 +884,8 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
                 T* orow = dst + (size_t)y * dst_stride;
                 if (rows_aligned && pair_in) {
                     uint32_t* q = (uint32_t*)(orow + (size_t)(x & ~1) * 3);   // 12 bytes per pixel pair
-                    if (x & 1) VS_STORE32(q + 2, d0);
-                    else { VS_STORE32(q, d0); VS_STORE32(q + 1, d1); }
+                    if (x & 1) q[2] = d0;
+                    else { q[0] = d0; q[1] = d1; }
                 } else if (lane_in) {
                     orow[(size_t)x * 3] = (T)o[k][0];
                     orow[(size_t)x * 3 + 1] = (T)o[k][1];
@@ -1109,40 +897,11 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     }   // row blocks
     };
 
-    Geom g = geom(tl0);
-    VS_STAMP(1);
-    bool loaded = false;
-    if (NT > 1 && g.interior) { issue(g); loaded = true; }
-#pragma unroll 1
-    for (int i = 0; i < NT; i++) {
-        const bool more = i + 1 < NT && tl0 + i + 1 < tl_end;        // (uniform)
-        if (g.fits && !(VS_WARP_WHATIF & 2)) fill(g, loaded);
-        VS_STAMP(4);
-        __syncthreads();
-        VS_STAMP(5);
-        Geom gn = g;
-        bool loaded_n = false;
-        if (more) {
-            gn = geom(tl0 + i + 1);
-            if (gn.interior) { issue(gn); loaded_n = true; }          // in flight during this tile's sampler blocks
-        }
-        sample_tile(g);
-        VS_STAMP(6);
-        VS_STAMP_DRAIN();
-        VS_STAMP(7);
-#if VS_WARP_STAMPS
-        {
-            const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-            stamp[8] = __builtin_amdgcn_s_getreg(4 | (31 << 11));              // HW_REG_HW_ID
-            stamp[9] = __builtin_amdgcn_s_getreg(20 | (31 << 11));             // HW_REG_XCC_ID
-            if (lane == 0 && wg < (unsigned)STAMP_WGS && g.interior)
-                for (int i = 0; i < STAMP_N; i++) g_warp_stamps[((size_t)wg * 4 + wv) * STAMP_N + i] = stamp[i];
-        }
-#endif
-        if (!more) break;
-        __syncthreads();                                               // every wave has read its taps: the tile buffer is free
-        g = gn; loaded = loaded_n;
-    }
+    // (one tile per workgroup; geom / fill / sample_tile stay lambdas: written out inline, the same code compiles to different machine code)
+    const Geom g = geom(tl);
+    if (g.fits) fill(g);
+    __syncthreads();
+    sample_tile(g);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -1161,26 +920,19 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
 // instructions -- three-operand integer instructions issue at half the fma's rate -- not by memory latency or occupancy (profiles/r05_warp_cv.md).
 // Tiles whose footprint does not fit the window (large rotation / zoom) take a per-pixel global path in the same kernel.
 // ------------------------------------------------------------------------------------------------------------------------------------
-#ifndef VS_WARP_CV_W16
-#define VS_WARP_CV_W16 1                 // sampler: 16-bit weights 64 a b (the top-left one saturated to 65535): the sample lands on a byte boundary
-#endif
 // (Measured and dropped, round 6 -- commit 2 of the round, profiles/r06_warp_cv.md: interior tiles filled by LDS-DMA, one `global_load_lds_dword` per 64
 // staged pixels with each lane reading the four bytes at its pixel's byte-aligned address, which lands the sampler's own tile format with no registers and no
 // formatting instructions.  Bit-identical (tools/ubench_glds3.hip: right for every byte offset and pitch), 13.5 us per 4K frame against 10.8: 144 four-byte
 // gathers per tile cost the texture path more than 21 twelve-byte loads and their formatting cost the vector unit.)
-#ifndef VS_WARP_CV_TILE_H
-#define VS_WARP_CV_TILE_H 64             // output rows per workgroup: 32, or a multiple of 64 (the row-origin table is filled 32 rows per wave pass).
-                                         // Measured (profiles/r05_warp_cv.md): 32 rows 12.3 us per 4K frame, 64 rows 11.1, 128 rows 12.9 -- the taller tile halves the
-                                         // prologue and halo shares but leaves 3 workgroups per CU (48 KB of LDS) and the fill of one is no longer covered by the others' sampling
-#endif
-constexpr int CV_TH = VS_WARP_CV_TILE_H, CV_RPW = CV_TH / 4, CV_WS_H = CV_TH + 8;
-#ifndef VS_WARP_CV_RS
-#define VS_WARP_CV_RS WS_W               // row pitch of the 8-bit kernel's byte tile in dwords (>= WS_W, a multiple of 4).  80: 23.0 KB of LDS, SEVEN workgroups per CU (round 6);
-                                         // 88 (the pitch of the float-bilinear byte tile, the 8-bit kernel's until round 6): 25.3 KB, six -- 10.7 us per 4K frame against 10.4.
-                                         // A compact window (72-dword pitch, 68 rows: 19.6 KB, eight workgroups per CU) for stabilisation-sized transforms was built too:
-                                         // equal to seven (profiles/r06_warp_cv.md section 5), not kept.
-#endif
-constexpr int CV_RS = VS_WARP_CV_RS;
+// Output rows per workgroup: 32, or a multiple of 64 (the row-origin table is filled 32 rows per wave pass).  Measured (profiles/r05_warp_cv.md):
+// 32 rows 12.3 us per 4K frame, 64 rows 11.1, 128 rows 12.9 -- the taller tile halves the prologue and halo shares but leaves 3 workgroups per
+// CU (48 KB of LDS) and the fill of one is no longer covered by the others' sampling.
+constexpr int CV_TH = 64, CV_RPW = CV_TH / 4, CV_WS_H = CV_TH + 8;
+// Row pitch of the byte tile in dwords (>= WS_W, a multiple of 4).  80: 23.0 KB of LDS, SEVEN workgroups per CU (round 6); 88 (the pitch of the
+// float-bilinear byte tile, this kernel's until round 6): 25.3 KB, six -- 10.7 us per 4K frame against 10.4.  A compact window (72-dword pitch,
+// 68 rows: 19.6 KB, eight workgroups per CU) for stabilisation-sized transforms was built too: equal to seven (profiles/r06_warp_cv.md
+// section 5), not kept.
+constexpr int CV_RS = WS_W;
 static_assert(CV_RS >= WS_W && CV_RS % 4 == 0, "tile pitch");
 static_assert(CV_TH % 64 == 0 || CV_TH == 32, "row-origin table: waves 2 and 3 fill it 32 rows per pass each (X0 in lanes 0..31, Y0 in lanes 32..63)");
 constexpr int CV_RBK = CV_RPW < 16 ? CV_RPW : 16;          // rows of a wave sampled in one basic block
@@ -1263,17 +1015,9 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
     // 2 x 64 entries in fp64 and shared them through LDS behind a barrier: 29 % of a wave's life, profiles/r05_cv_stamps_final.json).  A tile
     // reads its footprint corners and its rows' origins with SCALAR loads (uniform addresses) and its lane's two column deltas with one
     // vector load each: no fp64, no table barrier, no LDS reads of the tables in the sampler.
-#ifdef VS_WARP_LDS_PAD
-    __shared__ uint32_t lds_pad[VS_WARP_LDS_PAD / 4];       // occupancy experiments only: fewer workgroups per CU
-    if (w < 0) lds_pad[threadIdx.x] = 0;
-#endif
     // XCD-aware tile order, as in vs_k_bgr_warp_c3: every XCD walks one contiguous run of tiles in raster order
     const int tl = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
     if (tl >= min(tiles_per_frame, (int)((blockIdx.x & 7) + 1) * chunk)) return;
-#if VS_WARP_STAMPS
-    unsigned long long stamp[STAMP_N] = {};
-    VS_STAMP(0);
-#endif
     const int frame = blockIdx.y;
     src += (size_t)frame * src_fs;
     dst += (size_t)frame * dst_fs;
@@ -1317,16 +1061,14 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
     }
     const bool src_aligned = ((((uintptr_t)src) | (uintptr_t)src_stride) & 3) == 0;                      // uniform
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    VS_STAMP(1);
     // (row offsets are 24-bit multiplies: a pitch of 2^24 bytes or more takes the rim path, whatever the frame's height)
     const bool interior = fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h &&
                           (size_t)h * (size_t)src_stride < (1ull << 32) && src_stride < (1 << 24);            // uniform
-    if (interior && !(VS_WARP_WHATIF & 2)) {
+    if (interior) {
         // Interior tiles (the whole staged window inside an aligned frame: all but the frame's rim): every address is one 24-bit multiply-add
         // from a uniform base, no border tests.  (Clamping the items beyond the tile's own rows / column groups onto its last row / group
         // instead of predicating them was measured: the ~28 % redundant loads cost more than the branches, 12.1 us per 4K frame against 11.1.)
         const uint8_t* base = src + ((size_t)sy_lo * src_stride + (size_t)sx_lo * 3);
-#if VS_WARP_CV_ROW_FILL
         // Item map of this path: lane -> (row r3 = lane / 20 of a row triplet, column group g = lane % 20), once per tile; slot s of wave wv
         // stages rows 3 (wv + 4 s) + r3 -- twelve rows further per slot: the source address advances by a UNIFORM 12 row pitches and the tile
         // address by a constant (an immediate of the ds_write), so a slot costs one compare beside its load and its four formatting
@@ -1344,9 +1086,6 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
             live[s] = col_live && (int)row0 < rows - 12 * s;
             if (live[s]) q[s] = *(const u32x3*)(base + (size_t)(12 * s) * (size_t)src_stride + goff);
         }
-        VS_STAMP(2);
-        VS_STAMP_DRAIN();
-        VS_STAMP(3);
 #pragma unroll
         for (int s = 0; s < CV_FILL_SLOTS; s++) {
             if (!live[s]) continue;
@@ -1358,33 +1097,7 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
             VS_BOUNDS_CHECK((int)((row0 + 12u * s) * CV_RS + 4u * g) + 3, CV_WS_H * CV_RS, 217);
             *(u32x4*)(tp + 12 * s * CV_RS) = px;
         }
-#else
-        u32x3 q[CV_FILL_SLOTS];
-        uint32_t toff[CV_FILL_SLOTS];
-        bool live[CV_FILL_SLOTS];
-#pragma unroll
-        for (int s = 0; s < CV_FILL_SLOTS; s++) {              // every load is issued before the first tile write
-            const FillItem it = fill_item(lane, wv + 4 * s);
-            live[s] = it.row < rows && it.g < groups;
-            if (live[s]) q[s] = *(const u32x3*)(base + (__umul24((uint32_t)it.row, (uint32_t)src_stride) + 12u * (uint32_t)it.g));
-            toff[s] = (uint32_t)it.row * (uint32_t)CV_RS + 4u * (uint32_t)it.g;
-        }
-        VS_STAMP(2);
-        VS_STAMP_DRAIN();
-        VS_STAMP(3);
-#pragma unroll
-        for (int s = 0; s < CV_FILL_SLOTS; s++) {
-            if (!live[s]) continue;
-            u32x4 px;                                           // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  ->  four dwords B G R 0
-            px.x = q[s].x & 0x00ffffffu;
-            px.y = __builtin_amdgcn_perm(q[s].y, q[s].x, 0x0c050403u);
-            px.z = __builtin_amdgcn_perm(q[s].z, q[s].y, 0x0c040302u);
-            px.w = q[s].z >> 8;
-            VS_BOUNDS_CHECK((int)toff[s] + 3, CV_WS_H * CV_RS, 217);
-            *(u32x4*)(tile_raw + VS_DEBUG_CLAMP((int)toff[s], CV_WS_H * CV_RS - 3)) = px;
-        }
-#endif
-    } else if (fits && !(VS_WARP_WHATIF & 2)) {
+    } else if (fits) {
         u32x3 q[CV_FILL_SLOTS];
         FillItem it[CV_FILL_SLOTS];
         bool live[CV_FILL_SLOTS], direct[CV_FILL_SLOTS];
@@ -1423,13 +1136,10 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
             *(u32x4*)(tile_raw + VS_DEBUG_CLAMP(it[s].row * CV_RS + 4 * it[s].g, CV_WS_H * CV_RS - 3)) = px;
         }
     }
-    VS_STAMP(4);
     __syncthreads();
-    VS_STAMP(5);
 
     const int yw = y0 + wv * CV_RPW;                         // first row of this wave
     if (yw >= roi.h) return;                                 // wave-uniform
-    if (VS_WARP_WHATIF & 128) { if (tile_raw[threadIdx.x] == 0x12345678u) dst[threadIdx.x] = 1; return; }   // (analysis: loads + fill only)
     const int m = lane & 3;
     const bool rows_aligned = ((((uintptr_t)dst) | (uintptr_t)dst_stride) & 3) == 0;                      // uniform
     const bool lane_in = x < roi.w, quad_in = (x | 3) < roi.w;
@@ -1448,20 +1158,13 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
         const uint32_t fx = (Xs >> 5) & 31u, fy32 = Ys & 0x3e0u;
         const int off = VS_DEBUG_CLAMP_BYTES(((int)Ys >> 10) * (4 * CV_RS) + (((int)Xs >> 8) & ~3), 4 * (CV_WS_H * CV_RS - (CV_RS + 2)), 212);
         const __attribute__((address_space(3))) uint32_t* t = (const __attribute__((address_space(3))) uint32_t*)((const __attribute__((address_space(3))) char*)tile_raw + off);
-        if (VS_WARP_WHATIF & 1) return t[0] + fx + fy32;                    // (analysis: one LDS read, no arithmetic)
         const uint32_t p00 = t[0], p01 = t[1], p10 = t[CV_RS], p11 = t[CV_RS + 1];
-#if VS_WARP_CV_W16
         // 16-bit weights 64 a b = twice OpenCV's: (2 S + 2^15) >> 16 is (S + 2^14) >> 15, and the sample is byte 2 of the sum -- no shifts in front
         // of the pack.  Only the top-left weight can reach 2^16 (fx = fy = 0: the other three are 0); the packed multiply saturates it to 65535, and
         // (65535 v + 2^15) >> 16 = v for v <= 255.
         const uint32_t apair = fx * 0x1fffeu + 64u;                         // 2 (32 - fx) | 2 fx << 16
         const uint32_t wb = pk_mul_lo_u16_lo(apair, fy32), wt = pk_mul_lo_u16_lo_sat(apair, 1024u - fy32);
         constexpr uint32_t kHalf = 1u << 15;
-#else
-        const uint32_t apair = fx * 0xffffu + 32u;                          // (32 - fx) | fx << 16
-        const uint32_t wb = apair * fy32, wt = (apair << 10) - wb;          // {32 a0 b1 | 32 a1 b1 << 16}, {32 a0 b0 | 32 a1 b0 << 16}: each <= 32768, no borrow between the halves
-        constexpr uint32_t kHalf = 1u << 14;
-#endif
         uint32_t o[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -1469,12 +1172,7 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
             const uint32_t top = __builtin_amdgcn_perm(p01, p00, selc), bot = __builtin_amdgcn_perm(p11, p10, selc);
             o[c] = udot2(bot, wb, udot2(top, wt, kHalf));                   // bits 15..22 (16..23 with the doubled weights) = the sample
         }
-#if VS_WARP_CV_W16
         return __builtin_amdgcn_perm(o[2], __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0602u), 0x0c060100u);     // {B, G, R, 0}
-#endif
-        // {B, G, R, 0}: shifts put each sample on a byte boundary (B: byte 0 of o0 >> 15, G: byte 1 of o1 >> 7, R: byte 2 of o2 << 1), two v_perm pick them
-        const uint32_t bg = __builtin_amdgcn_perm(o[1] >> 7, o[0] >> 15, 0x0c0c0500u);
-        return __builtin_amdgcn_perm(o[2] << 1, bg, 0x0c060100u);
     };
     if (fits && rows_aligned && nx == WT_W && yw + CV_RPW <= roi.h && (size_t)roi.h * (size_t)dst_stride < (1ull << 32)) {
         // the common case -- the tile fits its window, whole quads, whole rows: all rows are sampled in ONE basic block (the stores sit behind
@@ -1486,23 +1184,11 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
 #pragma unroll
             for (int k = 0; k < CV_RBK; k++)
                 d[k] = quad_pack_bgr(sample((uint32_t)X0p[wv * CV_RPW + k0 + k] + adw, (uint32_t)Y0p[wv * CV_RPW + k0 + k] + (uint32_t)bd), sel);
-            if (m < 3 && (!(VS_WARP_WHATIF & 8) || d[0] == 0x12345678u)) {
+            if (m < 3) {
 #pragma unroll
-                for (int k = 0; k < CV_RBK; k++, roff += (uint32_t)dst_stride) VS_STORE32((uint32_t*)(dst + roff), d[k]);
+                for (int k = 0; k < CV_RBK; k++, roff += (uint32_t)dst_stride) *(uint32_t*)(dst + roff) = d[k];
             } else roff += (uint32_t)CV_RBK * (uint32_t)dst_stride;
         }
-#if VS_WARP_STAMPS
-        VS_STAMP(6);
-        VS_STAMP_DRAIN();
-        VS_STAMP(7);
-        {
-            const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-            stamp[8] = __builtin_amdgcn_s_getreg(4 | (31 << 11));              // HW_REG_HW_ID
-            stamp[9] = __builtin_amdgcn_s_getreg(20 | (31 << 11));             // HW_REG_XCC_ID
-            if (lane == 0 && wg < (unsigned)STAMP_WGS && interior)
-                for (int i = 0; i < STAMP_N; i++) g_warp_stamps[((size_t)wg * 4 + wv) * STAMP_N + i] = stamp[i];
-        }
-#endif
         return;
     }
 #pragma unroll 1
@@ -1519,7 +1205,7 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
         const uint32_t d = quad_pack_bgr(p, sel);            // every lane of the wave takes part in the shuffle
         uint8_t* orow = dst + (size_t)y * dst_stride;
         if (rows_aligned && quad_in) {
-            if (m < 3) VS_STORE32((uint32_t*)(orow + loff), d);
+            if (m < 3) *(uint32_t*)(orow + loff) = d;
         } else if (lane_in) {
             orow[(size_t)x * 3] = (uint8_t)p;
             orow[(size_t)x * 3 + 1] = (uint8_t)(p >> 8);
@@ -1541,22 +1227,13 @@ __global__ __launch_bounds__(256, 7) void vs_k_bgr_warp_cv_c3(const uint8_t* __r
 // {B | G << 16, R} per staged pixel: the float bilinear kernel's).  A tile that holds a sample >= 2^14 (full 16-bit content) evaluates the
 // float expression as written.  Tile 64 x 32 (28 KB of LDS); tables, footprint, stores as in the 8-bit kernel.
 // ------------------------------------------------------------------------------------------------------------------------------------
-#ifndef VS_WARP_CV16_TILE_H
-#define VS_WARP_CV16_TILE_H 32           // output rows per workgroup of the 16-bit kernel (a multiple of 4)
-#endif
-#ifndef VS_WARP_CV16_MINWAVES
-#define VS_WARP_CV16_MINWAVES 6
-#endif
-#ifndef VS_WARP_CV16_WS_EXTRA
-#define VS_WARP_CV16_WS_EXTRA 8          // staged rows beyond the tile's own (a multiple of 4)
-#endif
-constexpr int CV16_TH = VS_WARP_CV16_TILE_H, CV16_RPW = CV16_TH / 4, CV16_WS_H = CV16_TH + VS_WARP_CV16_WS_EXTRA;
-#ifndef VS_WARP_CV16_RS
-#define VS_WARP_CV16_RS WS_W             // row pitch of the word tile in staged pixels (8 bytes each; >= WS_W, a multiple of 4).  80: 25.6 KB of LDS, SIX workgroups per CU (round 6);
-                                         // 88 (until round 6): 28.2 KB, five -- 20.27 us per 4K 10-bit frame against 19.89 (four alternating passes, profiles/r06_ab_cv16_pitch.txt);
-                                         // seven (36 staged rows) 20.03: not kept
-#endif
-constexpr int CV16_RS = VS_WARP_CV16_RS;
+// Output rows per workgroup (a multiple of 4) and staged rows beyond the tile's own (a multiple of 4).
+constexpr int CV16_TH = 32, CV16_RPW = CV16_TH / 4, CV16_WS_H = CV16_TH + 8;
+constexpr int CV16_MINWAVES = 6;
+// Row pitch of the word tile in staged pixels (8 bytes each; >= WS_W, a multiple of 4).  80: 25.6 KB of LDS, SIX workgroups per CU (round 6);
+// 88 (until round 6): 28.2 KB, five -- 20.27 us per 4K 10-bit frame against 19.89 (four alternating passes, profiles/r06_ab_cv16_pitch.txt);
+// seven (36 staged rows) 20.03: not kept.
+constexpr int CV16_RS = WS_W;
 static_assert(CV16_RS >= WS_W && CV16_RS % 4 == 0, "tile pitch");
 static_assert(CV16_TH % 4 == 0 && CV16_TH >= 16, "four waves share a tile's rows");
 constexpr int CV16_FILL_SLOTS = (CV16_WS_H / 4 * (WS_W / 4) + 63) / 64;
@@ -1580,7 +1257,7 @@ __device__ __forceinline__ void cv_pixel_global_u16(const uint16_t* __restrict__
 }
 
 template <int BORDER>
-__global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c3_u16(const uint16_t* __restrict__ src, int w, int h, int src_stride,
+__global__ __launch_bounds__(256, CV16_MINWAVES) void vs_k_bgr_warp_cv_c3_u16(const uint16_t* __restrict__ src, int w, int h, int src_stride,
                                                                  const int* __restrict__ tab, int tab_w, int tab_h, uint16_t* __restrict__ dst, int dst_stride,
                                                                  size_t src_fs, size_t dst_fs, int tiles_x, uint32_t tiles_x_magic, int tiles_per_frame,
                                                                  int chunk, int maxv, vsk::Roi roi) {
@@ -1627,7 +1304,6 @@ __global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c
                           (size_t)h * (size_t)src_stride * 2 < (1ull << 32) && src_stride < (1 << 23);       // uniform (24-bit row-offset multiplies)
     if (interior) {                                          // (as in the 8-bit kernel: one 24-bit multiply-add per address from a uniform base, no border tests)
         const uint8_t* base = (const uint8_t*)(src + ((size_t)sy_lo * src_stride + (size_t)sx_lo * 3));
-#if VS_WARP_CV_ROW_FILL
         // (the 8-bit kernel's row-triplet item map: lane -> (row lane / 20 of a triplet, column group lane % 20), slots twelve rows apart)
         static_assert(WS_W / 4 == 20 && CV16_FILL_SLOTS == (CV16_WS_H + 11) / 12, "row-triplet item map");
         const uint32_t r3 = ((uint32_t)lane * 13u) >> 8, g = (uint32_t)lane - 20u * r3;
@@ -1656,32 +1332,6 @@ __global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c
             dstp[0] = u32x4{a.x, a.y & 0xffffu, __builtin_amdgcn_alignbyte(a.z, a.y, 2), a.z >> 16};
             dstp[1] = u32x4{b.x, b.y & 0xffffu, __builtin_amdgcn_alignbyte(b.z, b.y, 2), b.z >> 16};
         }
-#else
-        u32x3 qa[CV16_FILL_SLOTS], qb[CV16_FILL_SLOTS];
-        uint32_t toff[CV16_FILL_SLOTS];
-        bool live[CV16_FILL_SLOTS];
-#pragma unroll
-        for (int s = 0; s < CV16_FILL_SLOTS; s++) {
-            const FillItem it = fill_item(lane, wv + 4 * s);
-            live[s] = it.row < rows && it.g < groups;
-            if (live[s]) {
-                const uint8_t* gp = base + (__umul24((uint32_t)it.row, 2u * (uint32_t)src_stride) + 24u * (uint32_t)it.g);
-                qa[s] = *(const u32x3*)gp;
-                qb[s] = *(const u32x3*)(gp + 12);
-            }
-            toff[s] = 2u * ((uint32_t)it.row * (uint32_t)CV16_RS + 4u * (uint32_t)it.g);
-        }
-#pragma unroll
-        for (int s = 0; s < CV16_FILL_SLOTS; s++) {
-            if (!live[s]) continue;
-            const u32x3 a = qa[s], b = qb[s];                   // a = B0G0 R0B1 G1R1 ; b = B2G2 R2B3 G3R3
-            seen |= a.x | a.y | a.z | b.x | b.y | b.z;
-            VS_BOUNDS_CHECK((int)toff[s] + 7, CV16_WS_H * CV16_RS * 2, 218);
-            u32x4* dstp = (u32x4*)(tile_raw + VS_DEBUG_CLAMP((int)toff[s], CV16_WS_H * CV16_RS * 2 - 7));
-            dstp[0] = u32x4{a.x, a.y & 0xffffu, __builtin_amdgcn_alignbyte(a.z, a.y, 2), a.z >> 16};
-            dstp[1] = u32x4{b.x, b.y & 0xffffu, __builtin_amdgcn_alignbyte(b.z, b.y, 2), b.z >> 16};
-        }
-#endif
     } else if (fits) {
         u32x3 qa[CV16_FILL_SLOTS], qb[CV16_FILL_SLOTS];
         FillItem it[CV16_FILL_SLOTS];
@@ -1781,12 +1431,12 @@ __global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c
         uint32_t roff = (uint32_t)yw * (2u * (uint32_t)dst_stride) + (uint32_t)(x & ~1) * 6u;      // 12 bytes per pixel pair
         if (x & 1) {
 #pragma unroll
-            for (int k = 0; k < CV16_RPW; k++) VS_STORE32((uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride) + 8u), d0[k]);
+            for (int k = 0; k < CV16_RPW; k++) *(uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride) + 8u) = d0[k];
         } else {
 #pragma unroll
             for (int k = 0; k < CV16_RPW; k++) {
-                VS_STORE32((uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride)), d0[k]);
-                VS_STORE32((uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride) + 4u), d1[k]);
+                *(uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride)) = d0[k];
+                *(uint32_t*)((uint8_t*)dst + roff + (uint32_t)k * (2u * (uint32_t)dst_stride) + 4u) = d1[k];
             }
         }
         return;
@@ -1805,8 +1455,8 @@ __global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c
         uint16_t* orow = dst + (size_t)y * dst_stride;
         if (rows_aligned && pair_in) {
             uint32_t* q = (uint32_t*)(orow + (size_t)(x & ~1) * 3);   // 12 bytes per pixel pair
-            if (x & 1) VS_STORE32(q + 2, d0);
-            else { VS_STORE32(q, d0); VS_STORE32(q + 1, d1); }
+            if (x & 1) q[2] = d0;
+            else { q[0] = d0; q[1] = d1; }
         } else if (lane_in) {
             orow[(size_t)x * 3] = (uint16_t)o[0];
             orow[(size_t)x * 3 + 1] = (uint16_t)o[1];
@@ -1819,18 +1469,6 @@ __global__ __launch_bounds__(256, VS_WARP_CV16_MINWAVES) void vs_k_bgr_warp_cv_c
 
 VS_BOUNDS_TU(vs_bounds_fetch_warp)
 
-#if VS_WARP_STAMPS
-// (analysis build only) copies the stamps of the last launches out and clears them; n = capacity in 64-bit words
-extern "C" __attribute__((visibility("default"))) int vs_debug_warp_stamps(unsigned long long* out, size_t n) {
-    const size_t total = (size_t)STAMP_WGS * 4 * STAMP_N;
-    if (n < total) return -1;
-    if (hipDeviceSynchronize() != hipSuccess) return -2;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_warp_stamps), total * sizeof(unsigned long long)) != hipSuccess) return -3;
-    static std::vector<unsigned long long> zero(total, 0ULL);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_warp_stamps), zero.data(), total * sizeof(unsigned long long)) != hipSuccess) return -4;
-    return STAMP_WGS;
-}
-#endif
 
 namespace vsk {
 
@@ -1851,8 +1489,7 @@ static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const fl
         T* dp = dst + (size_t)f0 * dst_fs;
         const float4* pp = params_dev + f0;
         const float4* ep = extents_dev ? extents_dev + f0 : nullptr;
-        const int nt_wg = mode == 1 ? VS_WARP_TILES_PER_WG_BILINEAR : VS_WARP_TILES_PER_WG;     // tiles a workgroup walks (the kernel's NT)
-        dim3 grid((unsigned)((chunk + nt_wg - 1) / nt_wg * 8), (unsigned)nf), block(256);
+        dim3 grid((unsigned)(chunk * 8), (unsigned)nf), block(256);
 #define VS_LAUNCH(M, Bd) \
         hipLaunchKernelGGL((vs_k_bgr_warp_c3<T, M, Bd>), grid, block, 0, s, sp, w, h, src_stride, pp, dp, dst_stride, src_fs, dst_fs, \
                            tiles_x, magic, (int)tpf, chunk, maxv, roi, ep)
@@ -1904,23 +1541,22 @@ int bgr_warp_c3_compact_shape(const float* E4, int n_frames) {
 }
 
 // ints of table per frame for (bits, window): what bgr_warp_cv_c3's caller reserves (n_frames times) for `tab_dev`
-static inline int cv_tile_w(int) { return WT_W; }           // (output tile width; the 128-wide experiment of round 6 varied it)
 size_t bgr_warp_cv_table_ints(int bits, Roi roi) {
-    const int th = bits == 16 ? CV16_TH : CV_TH, twid = cv_tile_w(bits);
-    const size_t tw = (size_t)((roi.w + twid - 1) / twid) * twid, tt = (size_t)((roi.h + th - 1) / th) * th;
+    const int th = bits == 16 ? CV16_TH : CV_TH;
+    const size_t tw = (size_t)((roi.w + WT_W - 1) / WT_W) * WT_W, tt = (size_t)((roi.h + th - 1) / th) * th;
     return 2 * (tw + tt);
 }
 
 hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bits, const double* minv_dev, const double* minv_host, int* tab_dev, int border, int max_value,
                           void* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, Roi roi, hipStream_t s) {
     if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;   // (8-bit results never exceed 255: the weights sum to 1024)
-    const int th = bits == 16 ? CV16_TH : CV_TH, twid = cv_tile_w(bits);
-    const int tiles_x = (roi.w + twid - 1) / twid, tiles_y = (roi.h + th - 1) / th;
+    const int th = bits == 16 ? CV16_TH : CV_TH;
+    const int tiles_x = (roi.w + WT_W - 1) / WT_W, tiles_y = (roi.h + th - 1) / th;
     const long long tpf = (long long)tiles_x * tiles_y;
     if (tpf > 0x3fffffLL || tpf * tiles_x >= (1LL << 32)) return hipErrorNotSupported;
     const int chunk = (int)((tpf + 7) / 8);
     const uint32_t magic = (uint32_t)(0x100000000ULL / (uint32_t)tiles_x) + 1u;
-    const int tab_w = tiles_x * twid, tab_h = tiles_y * th;
+    const int tab_w = tiles_x * WT_W, tab_h = tiles_y * th;
     const size_t per = 2 * ((size_t)tab_w + (size_t)tab_h), esz = (size_t)bits / 8;
     for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
         const int nf = n_frames - f0 < 65535 ? n_frames - f0 : 65535;
