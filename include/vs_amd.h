@@ -236,6 +236,25 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_frame_stride, int n_
                                 int channels, int bits, const vs_transform* t, int mode, int border, int max_value,
                                 int roi_x, int roi_y, int roi_w, int roi_h,
                                 void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* VS_WARP_BILINEAR_CV with BORDER FILL: what an output frame's own source does not cover is taken from other source frames.
+ * 3 channels, 8- or 16-bit containers, both borders, frames up to 32767 x 32767 (VS_ERR_UNSUPPORTED beyond: cv::warpAffine
+ * saturates source coordinates to short there).  Output frame o (n_out of them) has n_cand (1 .. 16) candidates c, each a
+ * (source frame, forward transform) pair in VS_WARP_BILINEAR_CV's convention: frame cand_frame[o*n_cand + c] of the batch at
+ * `src` (0 <= index < n_src; a negative index ends the list) and cand_t[o*n_cand + c].  Candidate 0 is the frame itself.
+ *   - For a candidate with sampling matrix M (vs_cv_inverse_matrix of its transform) output pixel (x, y) -- full-frame
+ *     coordinates, also under a ROI -- has the integer source position of the warp itself: X = (X0[y] + adelta[x]) >> 5,
+ *     sx = X >> 5, X0[y] = cvRound((M[1] y + M[2]) 1024) + 16, adelta[x] = cvRound(M[0] x 1024); sy likewise from M[3 .. 5].
+ *     The candidate COVERS the pixel iff all four taps lie in the frame: 0 <= sx, sx + 1 <= w - 1, 0 <= sy, sy + 1 <= h - 1.
+ *   - The pixel's value is the value VS_WARP_BILINEAR_CV gives for the FIRST candidate that covers it, bit for bit.  If no
+ *     candidate covers it, it keeps candidate 0's ordinary result under `border`.
+ *   - Hence pixels candidate 0 covers are exactly the plain warp's, and n_cand == 1 is the roi_batch call above, bit for
+ *     bit.  No blending, feathering or photometric matching.
+ * ROI, strides, mem, stream: as in the roi_batch call; cand_frame and cand_t are host arrays of n_out * n_cand entries. */
+int vs_bgr_image_warp_fill_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride,
+                                 int channels, int bits, int n_out, int n_cand, const int32_t* cand_frame,
+                                 const vs_transform* cand_t, int border, int max_value,
+                                 int roi_x, int roi_y, int roi_w, int roi_h,
+                                 void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* same sampling, float output (typed like image_warp); dst interleaved f32 */
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits,
                           const vs_transform* t, int mode, int border,
@@ -444,6 +463,14 @@ int   vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream);
 /* the selection rule of the stabilizer's aligner (VS_SELECT_*, see vs_aligner_set_select_mode); takes effect with the next frame */
 int   vs_stabilizer_set_select_mode(vs_stabilizer* s, int mode);
 int   vs_stabilizer_get_select_mode(const vs_stabilizer* s);
+/* Border fill (the rule: see the fill_batch warp call).  0 (default): off.  1 .. lag: the pixels of every output frame that
+ * the corrected frame does not cover are filled from the next `ahead` input frames -- they are already held in device memory
+ * and their measured motions are known, so the fill costs no latency and no second alignment.  A frame whose alignment failed
+ * ends the list at that frame; frames beyond a reset, a clip boundary or a size change are never candidates.  Takes effect
+ * with the next output frame.  VS_ERR_ARG beyond the handle's lag; a handle whose warp_mode is not VS_WARP_BILINEAR_CV
+ * returns VS_ERR_UNSUPPORTED.  With the fill on, crop_pixels may go to 0. */
+int   vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead);
+int   vs_stabilizer_get_border_fill(const vs_stabilizer* s);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

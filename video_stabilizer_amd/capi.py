@@ -135,6 +135,8 @@ SIGNATURES = {
     "vs_bgr_image_warp_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_roi_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _i32,
                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_image_warp_fill_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32,
+                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
@@ -148,6 +150,8 @@ SIGNATURES = {
     "vs_stabilizer_set_select_mode": (_i32, [_vp, _i32]),
     "vs_aligner_get_select_mode": (_i32, [_vp]),
     "vs_stabilizer_get_select_mode": (_i32, [_vp]),
+    "vs_stabilizer_set_border_fill": (_i32, [_vp, _i32]),
+    "vs_stabilizer_get_border_fill": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
     "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
@@ -519,6 +523,33 @@ def bgr_image_warp_roi_batch(src, ts, roi, mode=WARP_LANCZOS2, border=BORDER_CLA
     return out
 
 
+def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_CONSTANT, max_value=None, src_stride=None, dst_stride=None):
+    """VS_WARP_BILINEAR_CV with border fill (include/vs_amd.h: vs_bgr_image_warp_fill_batch).  src (n_src,h,w,3) numpy; cand_frame
+    (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w, 3).
+    src_stride / dst_stride (elements): the call is made on pitched copies of the frames (the padding is not part of the result)"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    bits = 8 if src.dtype == np.uint8 else 16
+    if max_value is None:
+        max_value = 255 if bits == 8 else 65535
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    arr = (Transform * max(len(flat), 1))(*flat)
+    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
+    ss = w * c if src_stride is None else src_stride
+    ds = rw * c if dst_stride is None else dst_stride
+    if ss != w * c:
+        wide = np.zeros((n_src, h, ss), src.dtype)
+        wide[:, :, :w * c] = src.reshape(n_src, h, w * c)
+        src = wide
+    out = np.zeros((max(n_out, 1), rh, ds), src.dtype)
+    _check(lib().vs_bgr_image_warp_fill_batch(_p(src), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              arr, border, max_value, rx, ry, rw, rh, _p(out), rh * ds, ds, MEM_HOST, None))
+    return np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
+
+
 def bgr_image_warp_batch_device(src_ptr, n, w, h, c, bits, ts, dst_ptr, mode=WARP_LANCZOS2, border=BORDER_CLAMP,
                                 max_value=None, stream=None):
     """device-resident form: dense frames, enqueue only"""
@@ -755,13 +786,22 @@ class Aligner:
 class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
-    def __init__(self, device=0, select_mode=None, **params):
+    def __init__(self, device=0, select_mode=None, border_fill=0, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
             raise VsError("vs_stabilizer_create failed: %s" % lib().vs_last_error().decode())
         if select_mode is not None:
             self.set_select_mode(select_mode)
+        if border_fill:
+            self.set_border_fill(border_fill)
+
+    def set_border_fill(self, ahead):
+        """0: off; 1 .. lag: what the corrected frame does not cover is filled from the next `ahead` input frames (VS_WARP_BILINEAR_CV handles)"""
+        _check(lib().vs_stabilizer_set_border_fill(self.h, int(ahead)))
+
+    def border_fill(self):
+        return _check(lib().vs_stabilizer_get_border_fill(self.h))
 
     def set_select_mode(self, mode):
         """the selection rule of the stabilizer's aligner (SELECT_DEVICE by default, SELECT_STABLE, SELECT_STL_HOST)"""

@@ -728,10 +728,16 @@ int vs_image_warp(const uint8_t* in, int w, int h, int stride, float A, float B,
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
+// Border fill behind the VS_WARP_BILINEAR_CV warp (vs_fill.hip): per output frame n_cand candidates, host arrays of n_frames * n_cand entries.
+// src[o * n_cand + c], c >= 1: the candidate's frame in device memory (w x h, rows of src_stride elements; null ends the list); entry c == 0 is
+// the frame itself and is not read.  t[o * n_cand + c]: its forward transform (entry 0 is what the frame is warped with).
+struct FillSpec { int n_cand; const void* const* src; const vs_transform* t; };
+
 // roi = NULL: the whole w x h output.  Otherwise dst holds only the window (roi->w x roi->h pixels per frame).
 static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int channels,
                            int bits, const vs_transform* t, int mode, int border, int max_value, void* dst,
-                           size_t dst_fs, int dst_stride, bool f32out, int mem, hipStream_t s, const vsk::Roi* roi_in = nullptr) {
+                           size_t dst_fs, int dst_stride, bool f32out, int mem, hipStream_t s, const vsk::Roi* roi_in = nullptr,
+                           const FillSpec* fill = nullptr) {
     VS_DIMS(w, h);
     VS_ARG(src && dst && t && n_frames >= 1 && w > 0 && h > 0 && channels >= 1 && channels <= 4);
     VS_ARG(bits == 8 || bits == 16);
@@ -759,6 +765,8 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
         TableRing* tring = channels == 3 ? table_ring() : nullptr;
         const size_t tab_per = channels == 3 ? vsk::bgr_warp_cv_table_ints(bits, roi) : 0;
         int per_call = (int)(ParamRing::kSlots / 2 / 3);
+        if (fill) per_call = std::min(per_call, (int)(ParamRing::kSlots / 2 / 4) / fill->n_cand);       // (a candidate entry is four slots)
+        std::vector<vsk::FillCand> fc;
         if (tab_per) per_call = (int)std::min<size_t>((size_t)per_call, std::max<size_t>(1, TableRing::kInts / 2 / tab_per));
         std::vector<double> Mv((size_t)std::min(n_frames, per_call) * 6 + 2);   // (+2: an upload is counted in 16-byte slots)
         for (int f0 = 0; f0 < n_frames; f0 += per_call) {
@@ -784,6 +792,37 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
             VS_HIP(e);
             if (mdev) VS_TRY(ring->fence(mdev, s));
             if (tdev) VS_TRY(tring->fence(tdev, s));
+            if (fill && fill->n_cand > 1) {
+                // pass 2 on the same stream: the candidates' matrices and frame pointers travel like the other per-frame parameters (small groups as
+                // kernel arguments of vs_k_param_block, larger ones as one upload of the ring); a group without a single candidate launches nothing
+                const int nc = fill->n_cand;
+                fc.assign((size_t)nf * nc, vsk::FillCand{});
+                bool any = false;
+                for (int i = 0; i < nf; i++) {
+                    vsk::FillCand* row = &fc[(size_t)i * nc];
+                    memcpy(row[0].m, &Mv[(size_t)i * 6], 6 * sizeof(double));
+                    for (int c = 1; c < nc && fill->src[(size_t)(f0 + i) * nc + c]; c++) {
+                        vs_cv_inverse_matrix(&fill->t[(size_t)(f0 + i) * nc + c], w, h, row[c].m);
+                        row[c].src = fill->src[(size_t)(f0 + i) * nc + c];
+                        any = true;
+                    }
+                }
+                if (any) {
+                    static_assert(sizeof(vsk::FillCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
+                    const size_t slots = fc.size() * 4;
+                    float4* fdev = nullptr;
+                    if (slots <= (size_t)kParamBlockSlots) {
+                        ParamBlock blk{};
+                        memcpy(blk.v, fc.data(), slots * sizeof(float4));
+                        VS_TRY(ring->take(slots, s, &fdev));
+                        hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, fdev, (int)slots);
+                        VS_HIP(hipGetLastError());
+                    } else
+                        VS_TRY(ring->upload((const float*)fc.data(), slots, s, &fdev));
+                    VS_HIP(vsk::bgr_warp_cv_fill_c3((const vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, dp, dst_stride, nf, dst_fs, roi, s));
+                    VS_TRY(ring->fence(fdev, s));
+                }
+            }
         }
         return vsi::finish_outputs(mem, s, {&o});
     }
@@ -844,6 +883,64 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_fs, int n_frames, in
                            dst_fs, dst_stride, false, mem, (hipStream_t)stream, &roi);
 } VS_CATCH_ALL
 
+// the checks the fill adds to bgr_warp_common's own
+static int fill_args_ok(int w, int h, int channels, int n_cand) {
+    VS_ARG(channels == 3 && n_cand >= 1 && n_cand <= 16);
+    if (w > 32767 || h > 32767)
+        return set_error(VS_ERR_UNSUPPORTED, "border fill: frames up to 32767 x 32767 (cv::warpAffine saturates source coordinates to short beyond)");
+    return VS_OK;
+}
+
+static int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
+                              const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
+                              int dst_stride, hipStream_t s) {
+    VS_ARG(cand_src && cand_t && n_out >= 1);
+    VS_TRY(fill_args_ok(w, h, 3, n_cand));
+    std::vector<vs_transform> t0((size_t)n_out);
+    for (int o = 0; o < n_out; o++) t0[o] = cand_t[(size_t)o * n_cand];
+    const vsk::Roi roi{roi_x, roi_y, roi_w, roi_h};
+    const FillSpec fill{n_cand, cand_src, cand_t};
+    return bgr_warp_common(src, src_fs, n_out, w, h, src_stride, 3, bits, t0.data(), VS_WARP_BILINEAR_CV, border, max_value, dst, dst_fs, dst_stride, false,
+                           VS_MEM_DEVICE, s, &roi, &fill);
+}
+
+int vs_bgr_image_warp_fill_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int channels, int bits, int n_out, int n_cand,
+                                 const int32_t* cand_frame, const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w,
+                                 int roi_h, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    VS_ARG(src && dst && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && (bits == 8 || bits == 16));
+    VS_TRY(fill_args_ok(w, h, channels, n_cand));
+    VS_ARG(roi_x >= 0 && roi_y >= 0 && roi_w >= 1 && roi_h >= 1 && roi_w <= w && roi_h <= h && roi_x <= w - roi_w && roi_y <= h - roi_h);
+    VS_ARG(src_stride >= w * 3 && dst_stride >= roi_w * 3);
+    VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
+    VS_ARG(n_out == 1 || dst_fs >= img_span(roi_w, roi_h, dst_stride, 3));
+    for (int o = 0; o < n_out; o++) {
+        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
+        for (int c = 0; c < n_cand; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
+    }
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = (size_t)bits / 8;
+    Staged a, o;
+    VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(o.out_image(dst, (size_t)roi_w * 3 * esz, (size_t)roi_h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
+    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
+    for (int i = 0; i < n_out; i++)
+        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
+            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
+    // pass 1 warps runs of outputs whose own frames are consecutive in the batch as one launch each (n_cand == 1 with frames 0 .. n-1 is
+    // vs_bgr_image_warp_roi_batch, launch for launch)
+    for (int j = 0; j < n_out;) {
+        int e = j + 1;
+        while (e < n_out && cand_frame[(size_t)e * n_cand] == cand_frame[(size_t)(e - 1) * n_cand] + 1) e++;
+        VS_TRY(bgr_warp_fill_ptrs(ptrs[(size_t)j * n_cand], src_fs, e - j, w, h, src_stride, bits, n_cand, &ptrs[(size_t)j * n_cand],
+                                  &cand_t[(size_t)j * n_cand], border, max_value, roi_x, roi_y, roi_w, roi_h, (char*)o.dev + (size_t)j * dst_fs * esz,
+                                  dst_fs, dst_stride, s));
+        j = e;
+    }
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits, const vs_transform* t,
                           int mode, int border, float* dst, int dst_stride, int mem, void* stream) try {
     return bgr_warp_common(src, 0, 1, w, h, src_stride, channels, bits, t, mode, border, 0, dst, 0, dst_stride, true, mem,
@@ -865,3 +962,10 @@ int vs_bgr_to_gray(const void* src, int w, int h, int src_stride, int bits, int 
 } VS_CATCH_ALL
 
 }  // extern "C"
+
+int vsi::bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
+                            const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
+                            int dst_stride, hipStream_t s) {
+    return ::bgr_warp_fill_ptrs(src, src_fs, n_out, w, h, src_stride, bits, n_cand, cand_src, cand_t, border, max_value, roi_x, roi_y, roi_w, roi_h, dst,
+                                dst_fs, dst_stride, s);
+}

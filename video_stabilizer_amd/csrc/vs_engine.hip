@@ -1359,6 +1359,8 @@ struct vs_stabilizer {
     vs_smoother* smoother = nullptr;
     int frame_index = 0;
     std::deque<vs_transform> measurements;
+    std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
+    int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
     struct Held { void* ptr; bool owned; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
     std::vector<void*> pool;       // recycled frame buffers
@@ -1746,6 +1748,10 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
 
     struct Job { const void* src; vs_transform sampling; int i; void* release; };
     std::vector<Job> jobs;
+    // border fill (vs_fill.hip): per job 1 + nfill candidates -- the frame itself, then the frames that follow it in the queue
+    const int nfill = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, s->params.lag) : 0;
+    std::vector<const void*> cand_src;
+    std::vector<vs_transform> cand_t;
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
@@ -1759,9 +1765,11 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
         if (s->params.enable_smoother) (void)vs_smoother_update(s->smoother, &meas, &earliest_smoothed);   // :35
         if (!success) s->accum = vs_transform{0, 0, 0, 0};                                                  // :39-41
         s->measurements.push_back(meas);                                                                   // :44
+        s->meas_ok.push_back(success ? 1 : 0);
         if (s->measurements.size() > (size_t)s->params.lag) {                                              // :48
             vs_transform earliest = s->measurements.front();
             s->measurements.pop_front();
+            s->meas_ok.pop_front();
             vs_transform jitter;
             if (s->params.enable_smoother) {
                 vs_transform inv = vs_transform_inverse(&earliest_smoothed);
@@ -1793,6 +1801,23 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 jobs.push_back(Job{src.ptr, s->params.warp_mode == VS_WARP_BILINEAR_CV ? correction : vs_transform_inverse(&correction), i,
                                    src.owned ? src.ptr : nullptr});
                 has_output[i] = 1;
+                if (nfill > 0) {
+                    // The queue now holds the frames k+1 .. behind this frame k, `measurements` their motions T_{k+1} .. (T_j: frame j-1 to j), entry
+                    // for entry.  Frame j shows this output through F_j = compose(inverse(T_{k+1} o .. o T_j), correction); a frame whose alignment
+                    // failed ends the list.  (The frames are read before their own jobs release them: releases follow all launches, below.)
+                    cand_src.push_back(src.ptr);
+                    cand_t.push_back(correction);
+                    vs_transform chain{0, 0, 0, 0};
+                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
+                    int c = 0;
+                    for (; c < nfill && (size_t)c < avail && s->meas_ok[c]; c++) {
+                        chain = vs_transform_compose(&chain, &s->measurements[c]);
+                        const vs_transform back = vs_transform_inverse(&chain);
+                        cand_src.push_back(s->frames[c].ptr);
+                        cand_t.push_back(vs_transform_compose(&back, &correction));
+                    }
+                    for (; c < nfill; c++) { cand_src.push_back(nullptr); cand_t.push_back(vs_transform{0, 0, 0, 0}); }
+                }
             }
         }
     }
@@ -1829,7 +1854,13 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             hipStream_t ws = (s->overlap_warps && !to_host) ? s->warp_stream : st;
             // (beside the next group's alignment the Lanczos2 warp keeps its standard window: see vsi::warp_keeps_solver_slot)
             struct SlotHint { bool& f; bool old; SlotHint(bool on) : f(vsi::warp_keeps_solver_slot()), old(f) { f = on; } ~SlotHint() { f = old; } } hint(s->overlap_warps);
-            int wr = vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, (int)esz * 8, ts.data(),
+            int wr;
+            if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
+                wr = vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, (int)esz * 8, 1 + nfill, &cand_src[j * (1 + nfill)],
+                                             &cand_t[j * (1 + nfill)], s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh, dst, dst_fs,
+                                             ow * 3, ws);
+            else
+                wr = vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, (int)esz * 8, ts.data(),
                                                  s->params.warp_mode, s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh,
                                                  dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws);
             if (wr < 0) return wr;
@@ -1927,6 +1958,17 @@ int vs_stabilizer_get_select_mode(const vs_stabilizer* s) try {
     VS_ARG(s && s->aligner);
     return s->aligner->select_mode;
 } VS_CATCH_ALL
+int vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead) try {
+    VS_ARG(s && ahead >= 0);
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "border fill: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    VS_ARG(ahead <= s->params.lag);
+    s->border_fill = ahead;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->border_fill;
+} VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);
     return vs_aligner_wait_stream(s->aligner, producer_stream);
@@ -1938,6 +1980,7 @@ int vs_stabilizer_reset(vs_stabilizer* s) try {
     for (auto& f : s->frames) if (f.owned) s->pool.push_back(f.ptr);
     s->frames.clear();
     s->measurements.clear();
+    s->meas_ok.clear();
     // (make the new smoother first: if that fails the handle keeps a valid, if stale, one -- never a null pointer for the next call to walk into)
     vs_smoother* fresh = vs_smoother_create(s->params.lag, s->params.smoother_memory, s->params.lambda);
     if (!fresh) return VS_ERR_NOMEM;

@@ -101,6 +101,14 @@ private:
 // the tail of every kernel-level call: D2H of the staged outputs, (host memory) synchronise, rows into the caller's buffers
 int finish_outputs(int mem, hipStream_t s, std::initializer_list<Staged*> outs);
 
+// VS_WARP_BILINEAR_CV with border fill (the rule: vs_fill.hip) on device-resident frames; vs_bgr_image_warp_fill_batch is the index-based wrapper over
+// it.  Output frame o = frame o of the batch at `src` warped by cand_t[o * n_cand]; its uncovered pixels come from candidates c = 1 .. n_cand-1:
+// the frame at cand_src[o * n_cand + c] (any device pointer, w x h, rows of src_stride elements; null ends the list; entry c == 0 is not read)
+// under cand_t[o * n_cand + c].  Host arrays; enqueue only.
+int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
+                       const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
+                       int dst_stride, hipStream_t s);
+
 bool device_ready();   // true when a HIP device is usable (sets last error otherwise)
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the

@@ -65,6 +65,13 @@ size_t bgr_warp_cv_table_ints(int bits, Roi roi);
 constexpr int kCvInlineFrames = 64;          // 3 KiB of kernel arguments
 hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bits, const double* minv_dev, const double* minv_host, int* tab_dev, int border, int max_value,
                           void* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, Roi roi, hipStream_t s);
+// Border fill behind a VS_WARP_BILINEAR_CV warp (vs_fill.hip: the rule and the kernel): the pixels of output frame o that its own source does not
+// cover are rewritten from the first of its candidates 1 .. n_cand-1 that covers them.  cands_dev: n_frames x n_cand entries in device memory;
+// entry 0 of a frame carries the matrix pass 1 warped it with (its frame pointer is not read), a null frame ends the list.  3 channels,
+// frames up to 32767 a side; hipErrorNotSupported otherwise.  Same stream as the warp, after it.
+struct FillCand { double m[6]; const void* src; unsigned long long reserved; };      // 64 bytes = four float4 slots of the parameter ring
+hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, void* dst, int dst_stride,
+                               int n_frames, size_t dst_fs, Roi roi, hipStream_t s);
 // host side of the tuned kernel's tile prologue: per frame {lo_x, hi_x, lo_y, hi_y} from the kernel parameters {A, B, TX, TY}, for the
 // tile of the kernel that bgr_warp_c3 launches for (bits, mode)
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4);

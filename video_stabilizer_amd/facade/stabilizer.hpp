@@ -16,6 +16,7 @@ struct VideoStabilizerParams {
     double min_decay = 0.9, max_decay = 0.7;
     int warp_mode = VS_WARP_BILINEAR_CV;  // cv::warpAffine(INTER_LINEAR) as the reference calls it (imgproc.cpp:472), fixed point; VS_WARP_LANCZOS2* = bgr_image_warp
     int warp_border = VS_BORDER_CONSTANT;
+    int border_fill = 0;                  // a knob of this build: 1 .. lag = fill what the corrected frame does not cover from that many following frames (vs_stabilizer_set_border_fill)
 };
 
 // stabilizer.hpp:32-56.  processFrame returns an empty vector until `lag` frames have arrived
@@ -34,6 +35,11 @@ public:
         vs::check_abi();
         h_ = vs_stabilizer_create(&p, device);
         if (!h_) throw std::runtime_error(std::string("vs_stabilizer_create: ") + vs_last_error());
+        if (params.border_fill != 0 && vs_stabilizer_set_border_fill(h_, params.border_fill) != VS_OK) {
+            const std::string why = vs_last_error();
+            vs_stabilizer_destroy(h_);
+            throw std::runtime_error("vs_stabilizer_set_border_fill: " + why);
+        }
     }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
     VideoStabilizer(const VideoStabilizer&) = delete;
