@@ -271,7 +271,9 @@ int vs_bgr_to_gray(const void* src, int w, int h, int src_stride, int bits, int 
  * own specification, stated in the header comment of vs_flow.hip and restated in numpy by tests/_flow_ref.py, which the kernels
  * equal bit for bit.  Scores are this build's Farneback, not OpenCV's binary.
  * Fields as OpenCV names them; levels counts the layers ABOVE the frame (levels + 1 layers in all).  flags: 0 only (box window,
- * no initial flow); anything else is VS_ERR_UNSUPPORTED.  Limits: winsize 1..31, poly_n 1..7, levels 0..15. */
+ * no initial flow); anything else is VS_ERR_UNSUPPORTED.  Limits: winsize 1..31, poly_n 1..7, levels 0..15.  The pyramid blur of a
+ * layer has at most 257 taps (pyr_scale ^ k >= 1/86): parameters in range that ask for more make a handle, and vs_flow_compute /
+ * vs_flow_jitter return VS_ERR_UNSUPPORTED before they touch the device or their outputs. */
 typedef struct vs_flow_params {
     double pyr_scale;
     int    levels;

@@ -1,8 +1,8 @@
 """The debug build with bounds-checked LDS / scratch indexing ("bounds asserts in debug kernels"; GPU
-AddressSanitizer is not available on this pool).  tools/build_variant.sh bounds compiles vs_engine / vs_warp / vs_phase / vs_capi
+AddressSanitizer is not available on this pool).  tools/build_variant.sh bounds compiles vs_engine / vs_warp / vs_phase / vs_flow / vs_capi
 with -DVS_DEBUG_BOUNDS: the selection arrays (introselect_*, stable_select), the gather / exchange / staging indices of the fused
-aligner kernel, the warp's tile fill and tap windows and the FFT lines are indexed through vsd::Span / VS_BOUNDS_CHECK
-(vs_device.hpp).  A violation is recorded (site, index, limit, workgroup, thread) and redirected to element 0, never executed.
+aligner kernel, the warp's tile fill and tap windows, the FFT lines and the dense flow's LDS tiles, histograms and per-thread scratch offsets are indexed through
+vsd::Span / VS_BOUNDS_CHECK / VS_IDX (vs_device.hpp).  A violation is recorded (site, index, limit, workgroup, thread) and redirected to element 0, never executed.
 
 This module (a) proves the checker reports (a deliberate violation), and (b) runs the existing selection / stable-selection /
 tiny-table / 4K-global-scratch / warp / phase / config tests AGAINST THAT BUILD in a pytest of its own: every result must still be
@@ -68,7 +68,9 @@ def test_selection_warp_phase_and_config_tests_pass_on_the_bounds_build_with_a_c
     runs = [(["tests/test_select_gpu.py", "tests/test_select_stable_gpu.py", "tests/test_warp_sep_gpu.py", "tests/test_warp_cv_gpu.py", "tests/test_phase_gpu.py",
               "tests/test_warp_sweep_gpu.py", "tests/test_engine_sweep_gpu.py"], "not 4k_frame"),   # (the kernel-chain sweep runs the un-instrumented stage kernels of vs_kernels.hip: not here)   # (the 4K frames' time is the CPU oracle's; the second group has a 4K frame)
             (["tests/test_latency_mode_gpu.py", "tests/test_configs_gpu.py"],
-             "coresident_build_at_4k or sixteen_pairs or c3_4k_bgr_lanczos2_warp or c5_one_gpus_share")]
+             "coresident_build_at_4k or sixteen_pairs or c3_4k_bgr_lanczos2_warp or c5_one_gpus_share"),
+            # the dense flow (sites 401-420): everything but the two-chunk 1080p clips, whose kernels and indices the smaller clips run as well
+            (["tests/test_flow_gpu.py", "tests/test_flow_hostile_gpu.py", "tests/test_flow_routes_gpu.py"], "not chunked_clip and not two_chunks")]
     for mods, expr in runs:
         cmd = [sys.executable, "-m", "pytest", *mods, "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"] + (["-k", expr] if expr else [])
         out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)

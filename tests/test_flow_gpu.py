@@ -10,27 +10,10 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _flow_ref as R  # noqa: E402
 from _diff import same  # noqa: E402
+from _flow_cases import moving_pair, sample  # noqa: E402
 from test_flow_cpu import band_limited, shifted_pair  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def moving_pair(w, h, seed):
-    """two u8 frames of a band-limited texture under a small rotation + shift: a smooth, non-constant flow"""
-    t = band_limited(h + 64, w + 64, seed)
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    cx, cy = w / 2, h / 2
-    ang = 0.01
-    sx = np.cos(ang) * (x - cx) - np.sin(ang) * (y - cy) + cx + 32 + 1.7
-    sy = np.sin(ang) * (x - cx) + np.cos(ang) * (y - cy) + cy + 32 - 2.3
-    return np.clip(t[32:32 + h, 32:32 + w], 0, 255).round().astype(np.uint8), np.clip(sample(t, sx, sy), 0, 255).round().astype(np.uint8)
-
-
-def sample(t, sx, sy):
-    x0 = np.clip(np.floor(sx).astype(np.int64), 0, t.shape[1] - 2)
-    y0 = np.clip(np.floor(sy).astype(np.int64), 0, t.shape[0] - 2)
-    fx, fy = np.clip(sx - x0, 0, 1), np.clip(sy - y0, 0, 1)
-    return (t[y0, x0] * (1 - fx) + t[y0, x0 + 1] * fx) * (1 - fy) + (t[y0 + 1, x0] * (1 - fx) + t[y0 + 1, x0 + 1] * fx) * fy
 
 
 @pytest.mark.parametrize("w,h", [(320, 240), (1920, 1080), (97, 61), (13, 9), (5, 3), (1, 1), (64, 16), (65, 17)])
@@ -75,6 +58,14 @@ def test_unsupported_flags_and_bad_params(gpu_vs):
         gpu_vs.Flow(gpu_vs.flow_params(flags=256))
     with pytest.raises(gpu_vs.VsError, match="out of range"):
         gpu_vs.Flow(gpu_vs.flow_params(winsize=33))
+    # every limit of the parameter check, from both sides
+    for kw in (dict(pyr_scale=0.0), dict(pyr_scale=1.0), dict(pyr_scale=float("nan")), dict(levels=-1), dict(levels=16), dict(winsize=0), dict(winsize=32),
+               dict(iterations=0), dict(iterations=101), dict(poly_n=0), dict(poly_n=8), dict(poly_sigma=0.0), dict(poly_sigma=float("nan"))):
+        with pytest.raises(gpu_vs.VsError, match="out of range"):
+            gpu_vs.Flow(gpu_vs.flow_params(**kw))
+    for kw in (dict(pyr_scale=0.999), dict(levels=0), dict(levels=15), dict(winsize=1), dict(winsize=31), dict(iterations=1), dict(iterations=100),
+               dict(poly_n=1), dict(poly_n=7), dict(poly_sigma=1e-3)):
+        gpu_vs.Flow(gpu_vs.flow_params(**kw))               # the last value inside each limit makes a handle
 
 
 def gray_clip(n, w, h, seed):

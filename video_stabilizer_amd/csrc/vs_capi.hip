@@ -450,6 +450,7 @@ int vs_stream_retire(void* stream) try {
 extern "C" int vs_bounds_fetch_engine(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_warp(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_phase(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_flow(unsigned out[8], int reset);
 namespace {
 // the checker checked: element 11 of an 8-element LDS array through a Span -- reported under site 900, executed on element 0
 __global__ void vs_k_bounds_selftest(int* out) {
@@ -468,11 +469,11 @@ int vs_debug_bounds_check(void) try {
 #ifdef VS_DEBUG_BOUNDS
     if (!vsi::device_ready()) return VS_ERR_HIP;
     VS_HIP(hipDeviceSynchronize());
-    int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_capi};
-    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_capi.hip"};
+    int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_flow, vs_bounds_fetch_capi};
+    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_capi.hip"};
     unsigned total = 0;
     char msg[512] = "";
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < 5; k++) {
         unsigned r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fetch[k](r, 1) != 0) return set_error(VS_ERR_HIP, "bounds record of %s is not readable", names[k]);
         if (r[0] && !total)

@@ -17,7 +17,7 @@
 // a violation is reported, never executed: nothing faults, the kernel finishes, and vs_debug_bounds_check() (include/vs_amd.h)
 // hands the record to the host.  (No trap: on this pool a trapping wave can take the whole node down.)  In the regular build
 // VS_SPAN declares the plain restrict pointer the code had before, so the shipped kernels are unchanged instruction for instruction.
-// Site ids: 1xx vs_align_kernels.inc (selection, gather, exchange, staging), 2xx vs_warp.hip, 3xx vs_phase.hip.
+// Site ids: 1xx vs_align_kernels.inc (selection, gather, exchange, staging), 2xx vs_warp.hip, 3xx vs_phase.hip, 4xx vs_flow.hip.
 #ifdef VS_DEBUG_BOUNDS
 namespace vsd {
 static __device__ unsigned int g_bounds_rec[8];      // [0] violations, [1] site, [2] index (low 32 bits), [3] limit, [4] blockIdx.x, [5] threadIdx.x
@@ -44,6 +44,8 @@ struct Span {
 /* a byte offset that must lie in [0, extent): checked, reported under `site`, clamped */
 #define VS_DEBUG_CLAMP_BYTES(off, extent, site) (vsd::bounds_ok((off), (extent), (site)) ? (off) : 0)
 // the host-side reader of this translation unit's record (defined once per .hip file: the record is per translation unit)
+/* an element index that must lie in [0, extent): checked, reported under `site`, redirected to element 0 (arrays left as they are declared) */
+#define VS_IDX(i, extent, site) (vsd::bounds_ok((long long)(i), (long long)(extent), (site)) ? (i) : 0)
 #define VS_BOUNDS_TU(fn)                                                                                                \
     extern "C" int fn(unsigned out[8], int reset) {                                                                     \
         if (hipMemcpyFromSymbol(out, HIP_SYMBOL(vsd::g_bounds_rec), sizeof(unsigned) * 8) != hipSuccess) return -1;      \
@@ -57,6 +59,7 @@ struct Span {
 #define VS_BOUNDS_CHECK(i, extent, site) ((void)0)
 #define VS_DEBUG_CLAMP(i, extent) (i)
 #define VS_DEBUG_CLAMP_BYTES(off, extent, site) (off)
+#define VS_IDX(i, extent, site) (i)
 #define VS_BOUNDS_TU(fn)
 #endif
 

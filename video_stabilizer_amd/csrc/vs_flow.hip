@@ -38,6 +38,7 @@
 #include <new>
 #include <vector>
 
+#include "vs_device.hpp"
 #include "vs_internal.hpp"
 #include "vs_kernels.hpp"
 
@@ -111,32 +112,33 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_hblur_resize(const float* 
 // One 64 x 16 output tile per workgroup: the tile + halo of the layer in LDS, the three vertical moments of every halo column,
 // then the six horizontal moments per pixel.  coef: 5 planes (b1, b2, a11, a22, a12) of w x h per frame.
 constexpr int kPolyPitch = kTW + 2 * kMaxPolyN;                 // 78 floats: rows of the staged tile
+constexpr int kPolyTile = (kTH + 2 * kMaxPolyN) * kPolyPitch, kPolyVm = kTH * kPolyPitch;
 template <typename T>
 __global__ __launch_bounds__(kThreads) void vs_k_flow_polyexp(const T* __restrict__ src, size_t src_fs, int stride, int w, int h, int n,
                                                               PolyConsts pc, float* __restrict__ coef, size_t coef_fs) {
-    __shared__ float tile[(kTH + 2 * kMaxPolyN) * kPolyPitch];
-    __shared__ float vm[3][kTH * kPolyPitch];
+    __shared__ float tile[kPolyTile];
+    __shared__ float vm[3][kPolyVm];
     src += blockIdx.z * src_fs;
     const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH, tid = threadIdx.x;
     const int cols = kTW + 2 * n, rows = kTH + 2 * n;
     for (int i = tid; i < rows * cols; i += kThreads) {
         const int r = i / cols, c = i - r * cols;
         const int gy = clampi(y0 - n + r, 0, h - 1), gx = clampi(x0 - n + c, 0, w - 1);
-        tile[r * kPolyPitch + c] = (float)src[(size_t)gy * stride + gx];
+        tile[VS_IDX(r * kPolyPitch + c, kPolyTile, 401)] = (float)src[(size_t)gy * stride + gx];
     }
     __syncthreads();
     for (int i = tid; i < kTH * cols; i += kThreads) {
         const int r = i / cols, c = i - r * cols;
         float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
         for (int t = 0; t <= 2 * n; t++) {
-            const float v = tile[(r + t) * kPolyPitch + c];
+            const float v = tile[VS_IDX((r + t) * kPolyPitch + c, kPolyTile, 402)];
             s0 = s0 + pc.g[t] * v;
             s1 = s1 + pc.gt[t] * v;
             s2 = s2 + pc.gtt[t] * v;
         }
-        vm[0][r * kPolyPitch + c] = s0;
-        vm[1][r * kPolyPitch + c] = s1;
-        vm[2][r * kPolyPitch + c] = s2;
+        vm[0][VS_IDX(r * kPolyPitch + c, kPolyVm, 403)] = s0;
+        vm[1][VS_IDX(r * kPolyPitch + c, kPolyVm, 403)] = s1;
+        vm[2][VS_IDX(r * kPolyPitch + c, kPolyVm, 403)] = s2;
     }
     __syncthreads();
     const int c = tid % kTW, x = x0 + c;
@@ -146,7 +148,8 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_polyexp(const T* __restric
         const int r = tid / kTW + j * (kThreads / kTW), y = y0 + r;
         float h0 = 0.0f, hx = 0.0f, hxx = 0.0f, hy = 0.0f, hyy = 0.0f, hxy = 0.0f;
         for (int s = 0; s <= 2 * n; s++) {
-            const float v0 = vm[0][r * kPolyPitch + c + s], v1 = vm[1][r * kPolyPitch + c + s], v2 = vm[2][r * kPolyPitch + c + s];
+            const int vi = VS_IDX(r * kPolyPitch + c + s, kPolyVm, 404);
+            const float v0 = vm[0][vi], v1 = vm[1][vi], v2 = vm[2][vi];
             h0 = h0 + pc.g[s] * v0;
             hx = hx + pc.gt[s] * v0;
             hxx = hxx + pc.gtt[s] * v0;
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_polyexp(const T* __restric
             hxy = hxy + pc.gt[s] * v1;
         }
         if (x < w && y < h) {
-            const size_t o = (size_t)y * w + x;
+            const size_t o = VS_IDX((size_t)y * w + x, plane, 405);     // (+ 4 planes: inside the frame's coef_fs floats)
             out[o] = hx * pc.ig11;
             out[plane + o] = hy * pc.ig11;
             out[2 * plane + o] = (h0 * pc.ig03 + hxx * pc.ig33) + hyy * pc.ig34;
@@ -174,14 +177,15 @@ __device__ __forceinline__ void update_px(const float* __restrict__ R0, const fl
     const int x0 = (int)fx, y0 = (int)fy;
     const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
     const float tx = fx - (float)x0, ty = fy - (float)y0;
-    const size_t i00 = (size_t)y0 * w + x0, i10 = (size_t)y0 * w + x1, i01 = (size_t)y1 * w + x0, i11 = (size_t)y1 * w + x1;
+    const size_t i00 = VS_IDX((size_t)y0 * w + x0, plane, 406), i10 = VS_IDX((size_t)y0 * w + x1, plane, 406);
+    const size_t i01 = VS_IDX((size_t)y1 * w + x0, plane, 406), i11 = VS_IDX((size_t)y1 * w + x1, plane, 406);
     float s[5];
 #pragma unroll
     for (int c = 0; c < 5; c++) {
         const float* P = R1 + c * plane;
         s[c] = bilerp(P[i00], P[i10], P[i01], P[i11], tx, ty);
     }
-    const size_t o = (size_t)y * w + x;
+    const size_t o = VS_IDX((size_t)y * w + x, plane, 407);            // R0's and M's five planes
     const float a11 = (R0[2 * plane + o] + s[2]) * 0.5f;
     const float a22 = (R0[3 * plane + o] + s[3]) * 0.5f;
     const float a12 = (R0[4 * plane + o] + s[4]) * 0.5f;
@@ -207,7 +211,10 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_update_first(const float* 
         float tx, ty;
         src_coord(x, rx, wc, x0, x1, tx);
         src_coord(y, ry, hc, y0, y1, ty);
-        const float2 f00 = F[(size_t)y0 * wc + x0], f10 = F[(size_t)y0 * wc + x1], f01 = F[(size_t)y1 * wc + x0], f11 = F[(size_t)y1 * wc + x1];
+        const size_t nc = (size_t)wc * hc;
+        (void)nc;
+        const float2 f00 = F[VS_IDX((size_t)y0 * wc + x0, nc, 408)], f10 = F[VS_IDX((size_t)y0 * wc + x1, nc, 408)];
+        const float2 f01 = F[VS_IDX((size_t)y1 * wc + x0, nc, 408)], f11 = F[VS_IDX((size_t)y1 * wc + x1, nc, 408)];
         dx = bilerp(f00.x, f10.x, f01.x, f11.x, tx, ty) * inv_scale;
         dy = bilerp(f00.y, f10.y, f01.y, f11.y, tx, ty) * inv_scale;
     }
@@ -219,12 +226,13 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_update_first(const float* 
 // Mn != null: the next update at the solved flow into Mn.  Otherwise the layer's result: flow (float2 at fo + y*fstride/2 + x,
 // fstride in floats) and / or the squared magnitude (mag2, dense per pair).
 constexpr int kBoxPitch = kTW + kMaxWin - 1;                    // 94 floats
+constexpr int kBoxTile = (kTH + kMaxWin - 1) * kBoxPitch, kBoxVs = kTH * kBoxPitch;
 __global__ __launch_bounds__(kThreads) void vs_k_flow_blur_solve(const float* __restrict__ M, size_t m_ps, int w, int h, int win,
                                                                  const float* __restrict__ coef, size_t coef_fs, float* __restrict__ Mn,
                                                                  float* __restrict__ fo, size_t fo_ps, int fstride, float* __restrict__ mag2,
                                                                  size_t mag_ps) {
-    __shared__ float tile[(kTH + kMaxWin - 1) * kBoxPitch];
-    __shared__ float vs[kTH * kBoxPitch];
+    __shared__ float tile[kBoxTile];
+    __shared__ float vs[kBoxVs];
     const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH, tid = threadIdx.x, p = blockIdx.z;
     const int lo = -(win / 2), cols = kTW + win - 1, rows = kTH + win - 1;
     const size_t plane = (size_t)w * h;
@@ -236,21 +244,21 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_blur_solve(const float* __
         const float* P = Mp + q * plane;
         for (int i = tid; i < rows * cols; i += kThreads) {
             const int r = i / cols, cc = i - r * cols;
-            tile[r * kBoxPitch + cc] = P[(size_t)clampi(y0 + lo + r, 0, h - 1) * w + clampi(x0 + lo + cc, 0, w - 1)];
+            tile[VS_IDX(r * kBoxPitch + cc, kBoxTile, 409)] = P[VS_IDX((size_t)clampi(y0 + lo + r, 0, h - 1) * w + clampi(x0 + lo + cc, 0, w - 1), plane, 410)];
         }
         __syncthreads();
         for (int i = tid; i < kTH * cols; i += kThreads) {
             const int r = i / cols, cc = i - r * cols;
             float s = 0.0f;
-            for (int t = 0; t < win; t++) s = s + tile[(r + t) * kBoxPitch + cc];
-            vs[r * kBoxPitch + cc] = s;
+            for (int t = 0; t < win; t++) s = s + tile[VS_IDX((r + t) * kBoxPitch + cc, kBoxTile, 411)];
+            vs[VS_IDX(r * kBoxPitch + cc, kBoxVs, 412)] = s;
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < kPer; j++) {
             const int r = tid / kTW + j * (kThreads / kTW);
             float s = 0.0f;
-            for (int t = 0; t < win; t++) s = s + vs[r * kBoxPitch + c + t];
+            for (int t = 0; t < win; t++) s = s + vs[VS_IDX(r * kBoxPitch + c + t, kBoxVs, 413)];
             m[q][j] = s;
         }
         __syncthreads();
@@ -269,11 +277,11 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_blur_solve(const float* __
             update_px(coef + p * coef_fs, coef + (p + 1) * coef_fs, plane, w, h, x, y, dx, dy, Mn + p * m_ps);
         } else {
             if (fo) {
-                float* f = fo + p * fo_ps + (size_t)y * fstride + 2 * x;
+                float* f = fo + p * fo_ps + VS_IDX((size_t)y * fstride + 2 * x, (size_t)(h - 1) * fstride + 2 * (size_t)w - 1, 420);
                 f[0] = dx;
                 f[1] = dy;
             }
-            if (mag2) mag2[p * mag_ps + (size_t)y * w + x] = dx * dx + dy * dy;
+            if (mag2) mag2[p * mag_ps + VS_IDX((size_t)y * w + x, plane, 414)] = dx * dx + dy * dy;
         }
     }
 }
@@ -298,12 +306,12 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_hist(const uint32_t* __res
     const uint32_t* b = bits + p * ps;
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
         const uint32_t v = b[i];
-        if ((v & mask) == prefix) atomicAdd(&lh[(v >> shift) & (uint32_t)(bins - 1)], 1u);
+        if ((v & mask) == prefix) atomicAdd(&lh[VS_IDX((v >> shift) & (uint32_t)(bins - 1), bins, 415)], 1u);
     }
     __syncthreads();
     uint32_t* g = hist + ((size_t)pass * gridDim.z + p) * kHistBins;
     for (int i = threadIdx.x; i < bins; i += kThreads)
-        if (lh[i]) atomicAdd(&g[i], lh[i]);
+        if (lh[VS_IDX(i, kHistBins, 416)]) atomicAdd(&g[VS_IDX(i, bins, 417)], lh[i]);
 }
 // one workgroup per pair: the bin that holds element k of the candidates; prefix and k move on to it
 __global__ __launch_bounds__(kThreads) void vs_k_flow_pick(const uint32_t* __restrict__ hist, int pass, uint32_t k0, SelState* __restrict__ st) {
@@ -317,8 +325,8 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_pick(const uint32_t* __res
     uint32_t loc[kPerT];
     uint32_t s = 0;
 #pragma unroll
-    for (int i = 0; i < kPerT; i++) { loc[i] = tid * kPerT + i < bins ? g[tid * kPerT + i] : 0u; s += loc[i]; }
-    sums[tid] = s;
+    for (int i = 0; i < kPerT; i++) { loc[i] = tid * kPerT + i < bins ? g[VS_IDX(tid * kPerT + i, bins, 418)] : 0u; s += loc[i]; }
+    sums[VS_IDX(tid, kThreads, 419)] = s;
     const uint32_t k = pass == 0 ? k0 : st[p].k;
     const uint32_t prefix = pass == 0 ? 0u : st[p].prefix;
     __syncthreads();
@@ -327,7 +335,7 @@ __global__ __launch_bounds__(kThreads) void vs_k_flow_pick(const uint32_t* __res
         for (int i = 0; i < kThreads; i++) { const uint32_t v = sums[i]; sums[i] = run; run += v; }
     }
     __syncthreads();
-    uint32_t cum = sums[tid];
+    uint32_t cum = sums[VS_IDX(tid, kThreads, 419)];
     if (cum <= k && k < cum + s) {                               // exactly one thread holds element k
         for (int i = 0; i < kPerT; i++) {
             if (k < cum + loc[i]) {
@@ -363,11 +371,17 @@ std::vector<Layer> layers_of(int w, int h, double pyr_scale, int levels) {
     return L;
 }
 
-bool pyr_taps(double scale, PyrTaps& taps, int& r) {
-    const double sigma = (1.0 / scale - 1.0) * 0.5;
+bool pyr_radius(double scale, double& sigma, int& r) {
+    sigma = (1.0 / scale - 1.0) * 0.5;
     const double rr = std::max(1.0, std::ceil(3.0 * sigma));
     if (!(rr <= kMaxPyrR)) return false;
     r = (int)rr;
+    return true;
+}
+
+bool pyr_taps(double scale, PyrTaps& taps, int& r) {
+    double sigma;
+    if (!pyr_radius(scale, sigma, r)) return false;
     const std::vector<double> g = gauss_double(sigma, r);
     memset(&taps, 0, sizeof taps);
     for (int i = 0; i <= 2 * r; i++) taps.v[i] = (float)g[(size_t)i];
@@ -472,6 +486,19 @@ int check_params(const vs_flow_params& p) {
     return VS_OK;
 }
 
+// Parameters in range can still ask for a pyramid blur the kernels do not have (sigma grows as 1/scale): refused per call, on the
+// host, before anything of the call is allocated, copied or launched.
+int check_layers(const vs_flow_params& p, int w, int h) {
+    const std::vector<Layer> lay = layers_of(w, h, p.pyr_scale, p.levels);
+    for (int k = 1; k <= p.levels; k++) {
+        double sigma;
+        int r = 0;
+        if (!pyr_radius(lay[(size_t)k].scale, sigma, r))
+            return set_error(VS_ERR_UNSUPPORTED, "vs_flow: layer %d needs a pyramid blur wider than %d taps", k, 2 * kMaxPyrR + 1);
+    }
+    return VS_OK;
+}
+
 // The flow of the C - 1 pairs of a chunk whose gray frames are in the layout's `gray` slots (dense, stride w).  Layer 0's result
 // goes to `flow_out` (per pair fo_ps floats apart, row stride fstride floats) and / or the squared magnitudes to the `mag` slots.
 int run_chunk(vs_flow* f, const ChunkLayout& Lo, int C, int w, int h, float* flow_out, size_t fo_ps, int fstride, bool want_mag) {
@@ -499,8 +526,7 @@ int run_chunk(vs_flow* f, const ChunkLayout& Lo, int C, int w, int h, float* flo
         } else {
             PyrTaps taps;
             int r = 0;
-            if (!pyr_taps(lay[(size_t)k].scale, taps, r))
-                return set_error(VS_ERR_UNSUPPORTED, "vs_flow: layer %d needs a pyramid blur wider than %d taps", k, 2 * kMaxPyrR + 1);
+            if (!pyr_taps(lay[(size_t)k].scale, taps, r)) return set_error(VS_ERR_STATE, "vs_flow: layer %d was not checked", k);      // (check_layers)
             vs_k_flow_vblur<<<dim3(cdiv(w, kThreads), h, C), kThreads, 0, s>>>(gray, gfs, w, w, h, taps, r, V, ffs);
             vs_k_flow_hblur_resize<<<dim3(cdiv(wk, kThreads), hk, C), kThreads, 0, s>>>(V, ffs, w, h, taps, r, (float)((double)w / wk),
                                                                                       (float)((double)h / hk), Lk, ffs, wk, hk);
@@ -623,6 +649,7 @@ int vs_flow_compute(vs_flow* f, const uint8_t* prev, const uint8_t* next, int w,
                     int flow_stride) try {
     VSF_ARG(f && prev && next && flow && w > 0 && h > 0 && w <= 65535 && h <= 65535 && stride >= w && flow_stride >= 2 * w);
     VSF_ARG(mem == VS_MEM_HOST || mem == VS_MEM_DEVICE);
+    VSF_TRY(check_layers(f->p, w, h));
     VSF_TRY(enter(f));
     hipStream_t s = f->stream;
     ChunkLayout Lo;
@@ -653,6 +680,7 @@ int vs_flow_jitter(vs_flow* f, const void* frames, size_t frame_stride, int n, i
     const int ch = format == VS_FMT_GRAY8 ? 1 : 3;
     const size_t esz = bits > 8 ? 2 : 1;
     VSF_ARG(stride >= w * ch && frame_stride >= (size_t)(h - 1) * stride + (size_t)w * ch);
+    VSF_TRY(check_layers(f->p, w, h));
     VSF_TRY(enter(f));
     hipStream_t s = f->stream;
     const size_t N = (size_t)w * h;
@@ -684,3 +712,5 @@ int vs_flow_jitter(vs_flow* f, const void* frames, size_t frame_stride, int n, i
 } VS_CATCH_ALL
 
 }  // extern "C"
+
+VS_BOUNDS_TU(vs_bounds_fetch_flow)
