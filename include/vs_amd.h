@@ -255,6 +255,35 @@ int vs_bgr_image_warp_fill_batch(const void* src, size_t src_frame_stride, int n
                                  const vs_transform* cand_t, int border, int max_value,
                                  int roi_x, int roi_y, int roi_w, int roi_h,
                                  void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* DEBLUR BY TRANSFER: a frame that shake has blurred is blended with what its SHARPER neighbours show at the same scene point
+ * (Matsushita et al. 2006; the role of OpenCV videostab's WeightingDeblurer).  Interleaved BGR, every VS_FMT_BGR*.  The rule:
+ *   - Gray g = min(((B*3735 + G*19235 + R*9798 + 16384) >> 15) >> (bits - 8), 255): vs_bgr_to_gray's rule shifted to 8 bits.
+ *   - Sharpness of a frame: S = sum over 1 <= x <= w-2, 1 <= y <= h-2 of (g(x+1,y) - g(x-1,y))^2 + (g(x,y+1) - g(x,y-1))^2 as
+ *     uint64_t (integer sums: exact; S <= 130050 w h < 2^53, so (double)S is exact).
+ *   - Output frame o has n_cand (1 .. 16) candidates c: frame cand_frame[o*n_cand + c] of the batch at `src` (a negative index
+ *     ends the list) and cand_t[o*n_cand + c], exactly as in vs_bgr_image_warp_fill_batch.  Candidate 0 is the target frame k
+ *     itself; its transform is ignored.  Candidate j takes part iff S_j > S_k, strictly, with
+ *     r_j = (float)min((double)S_j / (double)max(S_k, 1), (double)max_ratio).  If no candidate takes part the frame is copied.
+ *   - With M = vs_cv_inverse_matrix(cand_t) target pixel (x, y) lies in candidate j at qx = rint((M0 x + M1 y) + M2),
+ *     qy = rint((M3 x + M4 y) + M5) (double, that order, no fma, ties to even): VS_WARP_BILINEAR_CV's convention and centre.
+ *     Nearest sample.  Outside the frame the candidate contributes nothing at that pixel; otherwise, with
+ *     d = |g_k(x,y) - g_j(qx,qy)| as float, w = (r_j * r_j) / (d + sensitivity) in fp32 with a correctly rounded division.  Per
+ *     channel acc_c = p_c + sum_j w q_c and W = 1 + sum_j w, in candidate order, fp32, no fma; the output is
+ *     floor(acc_c / W + 0.5) saturated to the format's maximum.
+ *   - Hence a frame with no sharper candidate, identical frames (ties on S) and n_cand == 1 come back bit for bit.
+ * sensitivity: gray levels (> 0); max_ratio (> 0) bounds r_j, so that a dark or flat frame (a fade) is not replaced by its
+ * neighbour. */
+typedef struct vs_deblur_params { float sensitivity; float max_ratio; } vs_deblur_params;
+void vs_deblur_params_default(vs_deblur_params* p);   /* 2, 4 */
+/* sharpness[i] = S of frame i (n frames, frame i at src + i*src_frame_stride elements); `sharpness` lives in `mem` */
+int vs_bgr_sharpness_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
+                           uint64_t* sharpness, int mem, void* stream);
+/* sharpness: the S of the n_src frames at `src` (in `mem`, as vs_bgr_sharpness_batch leaves them); cand_frame and cand_t are
+ * host arrays of n_out * n_cand entries; dst holds full w x h frames.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_deblur_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride, int format,
+                        const uint64_t* sharpness, int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
+                        const vs_deblur_params* params /* NULL = defaults */,
+                        void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* same sampling, float output (typed like image_warp); dst interleaved f32 */
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits,
                           const vs_transform* t, int mode, int border,
@@ -473,6 +502,16 @@ int   vs_stabilizer_get_select_mode(const vs_stabilizer* s);
  * returns VS_ERR_UNSUPPORTED.  With the fill on, crop_pixels may go to 0. */
 int   vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead);
 int   vs_stabilizer_get_border_fill(const vs_stabilizer* s);
+/* Deblur (the rule: see vs_bgr_deblur_batch).  0 (default): off.  1 .. lag: every frame is deblurred from the next `ahead` input
+ * frames before it is warped -- they are already held in device memory with their measured motions, and their sharpness was
+ * computed on the device when they arrived, so the pass costs no latency, no second alignment and no host synchronisation.
+ * Candidate j's transform is inverse(T_{k+1} o .. o T_j); a frame whose alignment failed ends the list, frames beyond a reset,
+ * a clip boundary or a size change are never candidates.  Every warp_mode: the pass only replaces the warp's source (with
+ * the border fill on too, the fill's candidate 0 is the deblurred frame, its other candidates the original frames).  The aligner
+ * always sees the original frames: transforms, vs_stabilizer_state and has_output do not depend on this setting.  params: NULL =
+ * defaults.  Takes effect with the next output frame.  VS_ERR_ARG beyond the handle's lag.  get returns `ahead`. */
+int   vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params);
+int   vs_stabilizer_get_deblur(const vs_stabilizer* s);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -76,6 +76,11 @@ class FlowParams(C.Structure):
         return (self.pyr_scale, self.levels, self.winsize, self.iterations, self.poly_n, self.poly_sigma, self.flags)
 
 
+class DeblurParams(C.Structure):
+    """vs_deblur_params: sensitivity in gray levels, max_ratio bounds a candidate's sharpness ratio"""
+    _fields_ = [("sensitivity", C.c_float), ("max_ratio", C.c_float)]
+
+
 class VsError(RuntimeError):
     pass
 
@@ -137,6 +142,10 @@ SIGNATURES = {
                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_fill_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32,
                                             _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_deblur_params_default": (None, [C.POINTER(DeblurParams)]),
+    "vs_bgr_sharpness_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "vs_bgr_deblur_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeblurParams),
+                                   _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
@@ -152,6 +161,8 @@ SIGNATURES = {
     "vs_stabilizer_get_select_mode": (_i32, [_vp]),
     "vs_stabilizer_set_border_fill": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_border_fill": (_i32, [_vp]),
+    "vs_stabilizer_set_deblur": (_i32, [_vp, _i32, C.POINTER(DeblurParams)]),
+    "vs_stabilizer_get_deblur": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
     "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
@@ -550,6 +561,76 @@ def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_C
     return np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
 
 
+def deblur_params(**kw):
+    p = DeblurParams()
+    lib().vs_deblur_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _pitched(src, stride):
+    """(n,h,w,c) -> (n,h,stride) with the rows' own elements in front (the padding is zero)"""
+    n, h, w, c = src.shape
+    if stride == w * c:
+        return src.reshape(n, h, w * c)
+    wide = np.zeros((n, h, stride), src.dtype)
+    wide[:, :, :w * c] = src.reshape(n, h, w * c)
+    return wide
+
+
+def sharpness_batch(src, fmt=None, src_stride=None):
+    """the gradient energy S of every frame (include/vs_amd.h: vs_bgr_sharpness_batch).  src (n,h,w,3) numpy -> (n,) uint64.
+    src_stride (elements): the call is made on pitched copies of the frames"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    buf = _pitched(src, ss)
+    out = np.zeros(n, np.uint64)
+    _check(lib().vs_bgr_sharpness_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(out), MEM_HOST, None))
+    return out
+
+
+def bgr_deblur_batch(src, sharpness, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """deblur by transfer (include/vs_amd.h: vs_bgr_deblur_batch).  src (n_src,h,w,3) numpy; sharpness (n_src,) uint64; cand_frame
+    (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).
+    src_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with
+    first; the padded buffer is returned as well, so that the caller can see that the padding was left alone"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    arr = (Transform * max(len(flat), 1))(*flat)
+    ss = w * c if src_stride is None else src_stride
+    ds = w * c if dst_stride is None else dst_stride
+    buf = _pitched(src, ss)
+    sh = _c(sharpness, np.uint64)
+    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_deblur_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, _p(sh), n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                     C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
+    return (res, out) if guard is not None else res
+
+
+def bgr_deblur_batch_device(src_ptr, n_src, w, h, fmt, sharp_ptr, cand_frame, cand_t, dst_ptr, params=None, stream=None):
+    """device-resident form: dense frames, sharpness in device memory, enqueue only"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape
+    flat = [t for row in cand_t for t in row]
+    arr = (Transform * len(flat))(*flat)
+    _check(lib().vs_bgr_deblur_batch(_p(src_ptr), h * w * 3, n_src, w, h, w * 3, fmt, _p(sharp_ptr), n_out, n_cand,
+                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, C.byref(params) if params is not None else None,
+                                     _p(dst_ptr), h * w * 3, w * 3, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
+def sharpness_batch_device(src_ptr, n, w, h, fmt, sharp_ptr, stream=None):
+    _check(lib().vs_bgr_sharpness_batch(_p(src_ptr), h * w * 3, n, w, h, w * 3, fmt, _p(sharp_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
 def bgr_image_warp_batch_device(src_ptr, n, w, h, c, bits, ts, dst_ptr, mode=WARP_LANCZOS2, border=BORDER_CLAMP,
                                 max_value=None, stream=None):
     """device-resident form: dense frames, enqueue only"""
@@ -786,7 +867,7 @@ class Aligner:
 class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
-    def __init__(self, device=0, select_mode=None, border_fill=0, **params):
+    def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -795,6 +876,15 @@ class Stabilizer:
             self.set_select_mode(select_mode)
         if border_fill:
             self.set_border_fill(border_fill)
+        if deblur:
+            self.set_deblur(deblur, deblur_params)
+
+    def set_deblur(self, ahead, params=None):
+        """0: off; 1 .. lag: every frame is deblurred from the next `ahead` input frames before it is warped (params: DeblurParams, None = defaults)"""
+        _check(lib().vs_stabilizer_set_deblur(self.h, int(ahead), C.byref(params) if params is not None else None))
+
+    def deblur(self):
+        return _check(lib().vs_stabilizer_get_deblur(self.h))
 
     def set_border_fill(self, ahead):
         """0: off; 1 .. lag: what the corrected frame does not cover is filled from the next `ahead` input frames (VS_WARP_BILINEAR_CV handles)"""

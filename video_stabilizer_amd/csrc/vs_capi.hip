@@ -962,7 +962,131 @@ int vs_bgr_to_gray(const void* src, int w, int h, int src_stride, int bits, int 
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
+// ---- deblur by transfer (vs_deblur.hip) ----
+static int deblur_format_ok(int format, int* bits) {
+    *bits = vs_format_bits(format);
+    VS_ARG(format != VS_FMT_GRAY8 && *bits != 0);
+    return VS_OK;
+}
+
+int vs_bgr_sharpness_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, uint64_t* sharpness, int mem,
+                           void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deblur_format_ok(format, &bits));
+    VS_ARG(src && sharpness && n >= 1 && src_stride >= w * 3);
+    VS_ARG(n == 1 || src_fs >= img_span(w, h, src_stride, 3));
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    Staged a, o;
+    VS_TRY(a.in(src, ((size_t)(n - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(o.out(sharpness, (size_t)n * sizeof(uint64_t), mem));
+    VS_HIP(vsk::bgr_sharpness(a.dev, w, h, src_stride, (int)esz * 8, bits - 8, o.as<unsigned long long>(), n, src_fs, s));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+static int deblur_params_ok(const vs_deblur_params* params, vs_deblur_params* p) {
+    if (params) *p = *params; else vs_deblur_params_default(p);
+    VS_ARG(p->sensitivity > 0.0f && p->sensitivity <= 3.0e38f && p->max_ratio > 0.0f && p->max_ratio <= 1.0e18f);
+    return VS_OK;
+}
+
+// The deblur pass on device-resident frames: output frame o is the frame at cand_src[o * n_cand] deblurred from candidates c = 1 .. n_cand-1 (the
+// frame at cand_src[o * n_cand + c], null ends the list, under cand_t[o * n_cand + c]); cand_sharp[..]: where each frame's S lies in device
+// memory.  Host arrays; enqueue only.  Frame pointers, sharpness pointers and matrices travel like the fill's per-candidate entries (small groups
+// as kernel arguments of vs_k_param_block, larger ones as one upload of the ring); the ratios take a span of the same ring.
+static int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
+                           const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deblur_format_ok(format, &bits));
+    VS_ARG(cand_src && cand_sharp && cand_t && dst && n_out >= 1 && n_cand >= 1 && n_cand <= 16 && src_stride >= w * 3 && dst_stride >= w * 3);
+    VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
+    vs_deblur_params p;
+    VS_TRY(deblur_params_ok(params, &p));
+    ParamRing* ring = param_ring();
+    if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
+    const size_t esz = bits > 8 ? 2 : 1;
+    static_assert(sizeof(vsk::DeblurCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
+    const int per_call = std::max(1, (int)(ParamRing::kSlots / 2 / 5) / n_cand);      // (entries and ratios together stay inside half the ring)
+    std::vector<vsk::DeblurCand> dc;
+    for (int f0 = 0; f0 < n_out; f0 += per_call) {
+        const int nf = std::min(per_call, n_out - f0);
+        dc.assign((size_t)nf * n_cand, vsk::DeblurCand{});
+        bool aligned = true;                                             // every target of the group starts on a dword
+        for (int i = 0; i < nf; i++) {
+            vsk::DeblurCand* row = &dc[(size_t)i * n_cand];
+            const size_t base = (size_t)(f0 + i) * n_cand;
+            VS_ARG(cand_src[base] && cand_sharp[base]);
+            row[0].src = cand_src[base];
+            aligned = aligned && ((uintptr_t)cand_src[base] & 3) == 0;
+            row[0].sharp = (const unsigned long long*)cand_sharp[base];
+            for (int c = 1; c < n_cand && cand_src[base + c] && cand_sharp[base + c]; c++) {
+                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
+                row[c].src = cand_src[base + c];
+                row[c].sharp = (const unsigned long long*)cand_sharp[base + c];
+            }
+        }
+        const size_t slots = dc.size() * 4, rslots = (dc.size() + 3) / 4;
+        float4 *cdev = nullptr, *rdev = nullptr;
+        if (slots <= (size_t)kParamBlockSlots) {
+            ParamBlock blk{};
+            memcpy(blk.v, dc.data(), slots * sizeof(float4));
+            VS_TRY(ring->take(slots, s, &cdev));
+            hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, cdev, (int)slots);
+            VS_HIP(hipGetLastError());
+        } else
+            VS_TRY(ring->upload((const float*)dc.data(), slots, s, &cdev));
+        VS_TRY(ring->take(rslots, s, &rdev));
+        VS_HIP(vsk::bgr_deblur((const vsk::DeblurCand*)cdev, (float*)rdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format),
+                               p.sensitivity, p.max_ratio, (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, aligned, s));
+        VS_TRY(ring->fence(cdev, s));
+        VS_TRY(ring->fence(rdev, s));
+    }
+    return VS_OK;
+}
+
+int vs_bgr_deblur_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, const uint64_t* sharpness, int n_out,
+                        int n_cand, const int32_t* cand_frame, const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs,
+                        int dst_stride, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deblur_format_ok(format, &bits));
+    VS_ARG(src && dst && sharpness && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && n_cand >= 1 && n_cand <= 16);
+    VS_ARG(src_stride >= w * 3 && dst_stride >= w * 3);
+    VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
+    VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
+    for (int o = 0; o < n_out; o++) {
+        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
+        for (int c = 0; c < n_cand; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
+    }
+    vs_deblur_params p;
+    VS_TRY(deblur_params_ok(params, &p));
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    Staged a, sh, o;
+    VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(sh.in(sharpness, (size_t)n_src * sizeof(uint64_t), mem, s));
+    VS_TRY(o.out_image(dst, (size_t)w * 3 * esz, (size_t)h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
+    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
+    std::vector<const uint64_t*> sharp((size_t)n_out * n_cand, nullptr);
+    for (int i = 0; i < n_out; i++)
+        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++) {
+            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
+            sharp[(size_t)i * n_cand + c] = (const uint64_t*)sh.dev + cand_frame[(size_t)i * n_cand + c];
+        }
+    VS_TRY(bgr_deblur_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), sharp.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
 }  // extern "C"
+
+int vsi::bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
+                         const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+    return ::bgr_deblur_ptrs(n_out, w, h, src_stride, format, n_cand, cand_src, cand_sharp, cand_t, params, dst, dst_fs, dst_stride, s);
+}
 
 int vsi::bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
                             const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,

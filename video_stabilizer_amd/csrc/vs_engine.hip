@@ -1361,7 +1361,15 @@ struct vs_stabilizer {
     std::deque<vs_transform> measurements;
     std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
     int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
-    struct Held { void* ptr; bool owned; };   // owned: a buffer of ours; else a frame of the batch being processed
+    // deblur (vs_deblur.hip): the sharpness of every queued frame lies in device memory, one value per frame in a block taken per call; a block is
+    // free again when no queued frame and no launch in flight refers to it (refs; sharp_pending: references given up, counted down at the next point
+    // where every reader has been ordered before whatever may refill the block)
+    struct SharpBlock { unsigned long long* dev; size_t cap; int refs; };
+    std::vector<SharpBlock*> sharp_blocks, sharp_pending;
+    int deblur = 0;                // vs_stabilizer_set_deblur: following frames a frame is deblurred from (0: off)
+    vs_deblur_params deblur_params{2.0f, 4.0f};
+    void* deblur_buf = nullptr; size_t deblur_bytes = 0;     // the deblurred frames of the current call: the source of its warps
+    struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
     std::vector<void*> pool;       // recycled frame buffers
     size_t frame_bytes = 0;
@@ -1394,8 +1402,16 @@ struct vs_stabilizer {
     int w = 0, h = 0, fmt = -1;
 };
 
+static void sharp_unhold(vs_stabilizer* s, vs_stabilizer::Held& f) {
+    if (f.sb) s->sharp_pending.push_back(f.sb);
+    f.sb = nullptr; f.sharp = nullptr;
+}
+static void sharp_settle(vs_stabilizer* s) {
+    for (auto* b : s->sharp_pending) --b->refs;
+    s->sharp_pending.clear();
+}
 static void stab_drop_frames(vs_stabilizer* s) {
-    for (auto& f : s->frames) if (f.owned) (void)hipFree(f.ptr);
+    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) (void)hipFree(f.ptr); }
     for (void* p : s->pool) (void)hipFree(p);
     s->frames.clear();
     s->pool.clear();
@@ -1424,6 +1440,8 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     (void)hipSetDevice(s->aligner->device);
     stab_drop_frames(s);
     for (auto& f : s->down) if (f.valid()) (void)f.get();
+    for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
+    if (s->deblur_buf) (void)hipFree(s->deblur_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
@@ -1534,6 +1552,7 @@ static int stab_run(vs_stabilizer* s, const void* frames, size_t frame_stride, i
         if (we != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "stabilizer warps: %s", hipGetErrorString(we));
         for (void* b : s->held_release) s->pool.push_back(b);
         s->held_release.clear();
+        sharp_settle(s);
     } else if (time_chunk > 0) {
         // ONE long device-resident clip: cut in time.  The batched form is n successive process calls, so the chunks are the same
         // calls in the same order; the warps of chunk c (on warp_stream) run under the alignment of chunk c + 1.  Frames still
@@ -1569,6 +1588,7 @@ static int stab_run(vs_stabilizer* s, const void* frames, size_t frame_stride, i
         if (we != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "stabilizer warps: %s", hipGetErrorString(we));
         for (void* b : s->held_release) s->pool.push_back(b);
         s->held_release.clear();
+        sharp_settle(s);
     } else
         r = stab_run_impl(s, frames, frame_stride, n, clip_len, w, h, stride, format, mem, mem, -1, out, out_frame_stride, has_output,
                           out_w, out_h);
@@ -1583,6 +1603,10 @@ static int stab_run(vs_stabilizer* s, const void* frames, size_t frame_stride, i
         (void)hipStreamSynchronize(s->aligner->stream);
         for (auto it = s->frames.begin(); it != s->frames.end();) it = it->owned ? it + 1 : s->frames.erase(it);
         (void)vs_stabilizer_reset(s);
+        // (everything is quiet now: the sharpness blocks are referred to by what is still queued, if anything, and by nothing else)
+        s->sharp_pending.clear();
+        for (auto* b : s->sharp_blocks) b->refs = 0;
+        for (auto& f : s->frames) if (f.sb) ++f.sb->refs;
         set_error(r, "%s", why.c_str());
     }
     return r;
@@ -1719,6 +1743,38 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
         dense = (const uint8_t*)s->batch_in;
     }
 
+    // deblur (vs_deblur.hip): the sharpness of the call's frames, one launch over all of them, into a block of its own; the values stay on the
+    // device.  (Queued frames that arrived while deblur was off are measured here too, once.)
+    const int ndb = std::min(s->deblur, s->params.lag);
+    const bool warps_apart = s->overlap_warps && out_mem != VS_MEM_HOST;      // the warps of this call go to warp_stream
+    if (!s->overlap_warps) sharp_settle(s);
+    vs_stabilizer::SharpBlock* sblk = nullptr;
+    if (ndb > 0) {
+        size_t need = (size_t)n;
+        for (auto& f : s->frames) if (!f.sb) need++;
+        for (auto* b : s->sharp_blocks) if (b->refs == 0 && b->cap >= need) { sblk = b; break; }
+        if (!sblk) {
+            for (auto it = s->sharp_blocks.begin(); it != s->sharp_blocks.end();)           // idle blocks that are too small make room
+                if ((*it)->refs == 0) { (void)hipFree((*it)->dev); delete *it; it = s->sharp_blocks.erase(it); } else ++it;
+            void* q = nullptr;
+            VS_HIP(vsi::dev_alloc(&q, need * sizeof(unsigned long long)));
+            s->sharp_blocks.reserve(s->sharp_blocks.size() + 1);
+            sblk = new vs_stabilizer::SharpBlock{(unsigned long long*)q, need, 0};
+            s->sharp_blocks.push_back(sblk);
+        }
+        VS_HIP(vsk::bgr_sharpness(dense, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev, n, (size_t)w * h * 3, st));
+        size_t k = (size_t)n;
+        for (auto& f : s->frames) {
+            if (f.sb) continue;
+            VS_HIP(vsk::bgr_sharpness(f.ptr, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev + k, 1, 0, st));
+            f.sb = sblk; f.sharp = sblk->dev + k; ++sblk->refs; k++;
+        }
+        if (warps_apart) {                                  // the deblur pass reads the values on warp_stream
+            VS_HIP(hipEventRecord(s->warp_ev, st));
+            VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
+        }
+    }
+
     // stabilizer.cpp:18-19 for all n frames.  In a chunked device-resident batch (stab_run) the alignment of the NEXT chunk is
     // started as soon as this one's results are in, so that it runs under this chunk's host work (smoother, correction chain, warp
     // launches) as well as under its warps.
@@ -1752,10 +1808,15 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     const int nfill = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, s->params.lag) : 0;
     std::vector<const void*> cand_src;
     std::vector<vs_transform> cand_t;
+    // deblur: per job 1 + ndb candidates likewise, with where each frame's sharpness lies
+    std::vector<const void*> db_src;
+    std::vector<const uint64_t*> db_sharp;
+    std::vector<vs_transform> db_t;
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
-        s->frames.push_back(vs_stabilizer::Held{(void*)(dense + (size_t)i * fbytes), false});
+        s->frames.push_back(vs_stabilizer::Held{(void*)(dense + (size_t)i * fbytes), false, sblk, sblk ? sblk->dev + i : nullptr});
+        if (sblk) ++sblk->refs;
         const vs_transform meas = t_buf[i];
         const bool success = st_buf[i] == 1;
         s->last_meas = meas; s->last_success = success ? 1 : 0;
@@ -1794,6 +1855,7 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             if (!s->frames.empty()) {
                 vs_stabilizer::Held src = s->frames.front();
                 s->frames.pop_front();
+                if (src.sb) s->sharp_pending.push_back(src.sb);   // (the jobs' launches below still read it: counted down after them)
                 // :97-99: warpBySimilarityTransform(frame, accum^-1); cv::warpAffine without WARP_INVERSE_MAP
                 // inverts the matrix it is given (imgproc.cpp:472), so the sampling map is (accum^-1)^-1.
                 // (VS_WARP_BILINEAR_CV is cv::warpAffine itself, inversion included: it takes the correction as the reference hands it over)
@@ -1818,6 +1880,19 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                     }
                     for (; c < nfill; c++) { cand_src.push_back(nullptr); cand_t.push_back(vs_transform{0, 0, 0, 0}); }
                 }
+                if (ndb > 0) {
+                    // the same chain without the correction: frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j)
+                    db_src.push_back(src.ptr); db_sharp.push_back((const uint64_t*)src.sharp); db_t.push_back(vs_transform{0, 0, 0, 0});
+                    vs_transform chain{0, 0, 0, 0};
+                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
+                    int c = 0;
+                    for (; c < ndb && (size_t)c < avail && s->meas_ok[c] && s->frames[c].sharp; c++) {
+                        chain = vs_transform_compose(&chain, &s->measurements[c]);
+                        db_src.push_back(s->frames[c].ptr); db_sharp.push_back((const uint64_t*)s->frames[c].sharp);
+                        db_t.push_back(vs_transform_inverse(&chain));
+                    }
+                    for (; c < ndb; c++) { db_src.push_back(nullptr); db_sharp.push_back(nullptr); db_t.push_back(vs_transform{0, 0, 0, 0}); }
+                }
             }
         }
     }
@@ -1838,6 +1913,25 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 s->batch_out[slot] = nullptr; s->batch_out_bytes[slot] = 0;
                 VS_HIP(vsi::dev_alloc(&s->batch_out[slot], obytes * jobs.size()));
                 s->batch_out_bytes[slot] = obytes * jobs.size();
+            }
+        }
+        if (ndb > 0) {
+            // every due frame is deblurred into a scratch frame of its own, one launch, in front of the warps on their stream; the warps (and the
+            // fill's candidate 0) then read the scratch frames.  The candidates are read before their own jobs release them: releases follow below.
+            hipStream_t ws = warps_apart ? s->warp_stream : st;
+            if (s->deblur_bytes < fbytes * jobs.size()) {
+                VS_HIP(hipStreamSynchronize(ws));           // (warps of an earlier chunk may still read the area)
+                if (s->deblur_buf) (void)hipFree(s->deblur_buf);
+                s->deblur_buf = nullptr; s->deblur_bytes = 0;
+                VS_HIP(vsi::dev_alloc(&s->deblur_buf, fbytes * jobs.size()));
+                s->deblur_bytes = fbytes * jobs.size();
+            }
+            const int dr = vsi::bgr_deblur_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndb, db_src.data(), db_sharp.data(), db_t.data(), &s->deblur_params,
+                                                s->deblur_buf, (size_t)w * h * 3, w * 3, ws);
+            if (dr < 0) return dr;
+            for (size_t j = 0; j < jobs.size(); j++) {
+                jobs[j].src = (const uint8_t*)s->deblur_buf + j * fbytes;
+                if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
             }
         }
         std::vector<vs_transform> ts;
@@ -1911,6 +2005,7 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             }
         }
     }
+    if (!warps_apart) sharp_settle(s);                  // (readers and the next writer share this stream)
     if (clip_len > 0) VS_TRY(vs_stabilizer_reset(s));   // nothing carries over from the last clip
     // frames of this batch that are still queued move into buffers of our own
     for (auto& f : s->frames) {
@@ -1969,6 +2064,19 @@ int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
     VS_ARG(s);
     return s->border_fill;
 } VS_CATCH_ALL
+int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_deblur_params p;
+    if (params) p = *params; else vs_deblur_params_default(&p);
+    VS_ARG(p.sensitivity > 0.0f && p.sensitivity <= 3.0e38f && p.max_ratio > 0.0f && p.max_ratio <= 1.0e18f);
+    s->deblur = ahead;
+    s->deblur_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_deblur(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->deblur;
+} VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);
     return vs_aligner_wait_stream(s->aligner, producer_stream);
@@ -1977,7 +2085,7 @@ int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
 int vs_stabilizer_reset(vs_stabilizer* s) try {
     VS_ARG(s);
     VS_HIP(hipSetDevice(s->aligner->device));
-    for (auto& f : s->frames) if (f.owned) s->pool.push_back(f.ptr);
+    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) s->pool.push_back(f.ptr); }
     s->frames.clear();
     s->measurements.clear();
     s->meas_ok.clear();

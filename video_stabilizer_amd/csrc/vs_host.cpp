@@ -77,6 +77,11 @@ void vs_stabilizer_params_default(vs_stabilizer_params* p) {
     p->warp_mode = VS_WARP_BILINEAR_CV;
     p->warp_border = VS_BORDER_CONSTANT;
 }
+// vs_deblur.hip (DESIGN.md "Deblur": 0.5 and 2 gray levels restore equally well, 8 is worse; max_ratio keeps a fade from being replaced)
+void vs_deblur_params_default(vs_deblur_params* p) {
+    p->sensitivity = 2.0f;
+    p->max_ratio = 4.0f;
+}
 
 // imgproc.cpp:333-359
 vs_transform vs_transform_inverse(const vs_transform* t) {

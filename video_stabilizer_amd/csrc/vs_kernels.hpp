@@ -72,6 +72,16 @@ hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bit
 struct FillCand { double m[6]; const void* src; unsigned long long reserved; };      // 64 bytes = four float4 slots of the parameter ring
 hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, void* dst, int dst_stride,
                                int n_frames, size_t dst_fs, Roi roi, hipStream_t s);
+// Deblur by transfer from sharper frames (vs_deblur.hip: the rule and the kernels).
+// bgr_sharpness: out[i] (device, n_frames x uint64) = the gradient energy S of frame i; zeroes `out` on `s` first.
+// bgr_deblur: cands_dev = n_frames x n_cand entries in device memory; entry 0 of a frame is the target (frame and sharpness; matrix not read), a
+// null frame ends the list; `sharp` points at the frame's S in device memory.  r2_dev: n_frames x n_cand floats of device scratch (the ratios,
+// made by a small kernel in front of the deblur launch).  dst: full w x h frames.  targets_aligned: every target frame starts on a dword.
+struct DeblurCand { double m[6]; const void* src; const unsigned long long* sharp; };  // 64 bytes = four float4 slots of the parameter ring
+hipError_t bgr_sharpness(const void* src, int w, int h, int src_stride, int bits, int shift_to_8, unsigned long long* out, int n_frames, size_t src_fs,
+                         hipStream_t s);
+hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value,
+                      float sensitivity, float max_ratio, void* dst, int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s);
 // host side of the tuned kernel's tile prologue: per frame {lo_x, hi_x, lo_y, hi_y} from the kernel parameters {A, B, TX, TY}, for the
 // tile of the kernel that bgr_warp_c3 launches for (bits, mode)
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4);

@@ -17,6 +17,7 @@ struct VideoStabilizerParams {
     int warp_mode = VS_WARP_BILINEAR_CV;  // cv::warpAffine(INTER_LINEAR) as the reference calls it (imgproc.cpp:472), fixed point; VS_WARP_LANCZOS2* = bgr_image_warp
     int warp_border = VS_BORDER_CONSTANT;
     int border_fill = 0;                  // a knob of this build: 1 .. lag = fill what the corrected frame does not cover from that many following frames (vs_stabilizer_set_border_fill)
+    int deblur = 0;                       // a knob of this build: 1 .. lag = deblur every frame from the sharper ones among that many following frames (vs_stabilizer_set_deblur, default parameters)
 };
 
 // stabilizer.hpp:32-56.  processFrame returns an empty vector until `lag` frames have arrived
@@ -39,6 +40,11 @@ public:
             const std::string why = vs_last_error();
             vs_stabilizer_destroy(h_);
             throw std::runtime_error("vs_stabilizer_set_border_fill: " + why);
+        }
+        if (params.deblur != 0 && vs_stabilizer_set_deblur(h_, params.deblur, nullptr) != VS_OK) {
+            const std::string why = vs_last_error();
+            vs_stabilizer_destroy(h_);
+            throw std::runtime_error("vs_stabilizer_set_deblur: " + why);
         }
     }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
