@@ -244,6 +244,9 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_frame_stride, int n_
  *   - For a candidate with sampling matrix M (vs_cv_inverse_matrix of its transform) output pixel (x, y) -- full-frame
  *     coordinates, also under a ROI -- has the integer source position of the warp itself: X = (X0[y] + adelta[x]) >> 5,
  *     sx = X >> 5, X0[y] = cvRound((M[1] y + M[2]) 1024) + 16, adelta[x] = cvRound(M[0] x 1024); sy likewise from M[3 .. 5].
+ *     int32 throughout, as in cv::warpAffine: cvRound saturates to [INT_MIN, INT_MAX] (NaN gives 0), and the additions (+ 16,
+ *     X0 + adelta) wrap in two's complement before the arithmetic shifts.  An extreme matrix (a near-singular transform, a
+ *     shift beyond 2^21 pixels) is therefore judged on the saturated, wrapped position -- the one the plain warp samples.
  *     The candidate COVERS the pixel iff all four taps lie in the frame: 0 <= sx, sx + 1 <= w - 1, 0 <= sy, sy + 1 <= h - 1.
  *   - The pixel's value is the value VS_WARP_BILINEAR_CV gives for the FIRST candidate that covers it, bit for bit.  If no
  *     candidate covers it, it keeps candidate 0's ordinary result under `border`.
@@ -272,7 +275,10 @@ int vs_bgr_image_warp_fill_batch(const void* src, size_t src_frame_stride, int n
  *     floor(acc_c / W + 0.5) saturated to the format's maximum.
  *   - Hence a frame with no sharper candidate, identical frames (ties on S) and n_cand == 1 come back bit for bit.
  * sensitivity: gray levels (> 0); max_ratio (> 0) bounds r_j, so that a dark or flat frame (a fade) is not replaced by its
- * neighbour. */
+ * neighbour.  Accepted (VS_ERR_ARG otherwise): 0 < sensitivity <= 3e38, 0 < max_ratio <= 1e18 and, evaluated in double,
+ * min(max_ratio, 2^53)^2 <= sensitivity * 2^100.  S < 2^53 bounds r_j by the same minimum, so a weight is at most 2^100 and the
+ * fp32 sums of at most 15 weights times samples <= 65535 stay below 2^121: acc_c and W are finite for every frame, and the rule
+ * defines every output sample.  (Outside it W reaches inf -- a black target, sensitivity 1e-38 -- and acc_c / W is inf / inf.) */
 typedef struct vs_deblur_params { float sensitivity; float max_ratio; } vs_deblur_params;
 void vs_deblur_params_default(vs_deblur_params* p);   /* 2, 4 */
 /* sharpness[i] = S of frame i (n frames, frame i at src + i*src_frame_stride elements); `sharpness` lives in `mem` */

@@ -16,11 +16,15 @@ import numpy as np
 F32 = np.float32
 
 
+def gray_unclamped(img, bits):
+    """the gray before the rule's min(g, 255): above 255 only where a 10- or 12-bit container holds a sample above its format's maximum"""
+    v = img.astype(np.int64)
+    return ((v[..., 0] * 3735 + v[..., 1] * 19235 + v[..., 2] * 9798 + 16384) >> 15) >> (bits - 8)
+
+
 def gray8(img, bits):
     """vs_bgr_to_gray's rule shifted to 8 bits: (..., 3) integers -> (...) int64 in 0 .. 255"""
-    v = img.astype(np.int64)
-    g = ((v[..., 0] * 3735 + v[..., 1] * 19235 + v[..., 2] * 9798 + 16384) >> 15) >> (bits - 8)
-    return np.minimum(g, 255)
+    return np.minimum(gray_unclamped(img, bits), 255)
 
 
 def sharpness(frame, bits):
@@ -37,6 +41,16 @@ def sharpness_batch(src, bits):
     return np.array([sharpness(f, bits) for f in src], np.uint64)
 
 
+def sharpness_many(src, bits):
+    """sharpness_batch vectorised over the batch (the same integer sums): for batches of many small frames"""
+    g = gray8(src, bits)
+    if g.shape[1] < 3 or g.shape[2] < 3:
+        return np.zeros(len(src), np.uint64)
+    dx = g[:, 1:-1, 2:] - g[:, 1:-1, :-2]
+    dy = g[:, 2:, 1:-1] - g[:, :-2, 1:-1]
+    return (dx * dx + dy * dy).sum(axis=(1, 2)).astype(np.uint64)
+
+
 def nearest_map(M, w, h):
     """(qx, qy) float64 (h, w): rint((M0 x + M1 y) + M2), rint((M3 x + M4 y) + M5)"""
     M = np.asarray(M, np.float64).reshape(6)
@@ -45,9 +59,10 @@ def nearest_map(M, w, h):
     return np.rint((M[0] * xs + M[1] * ys) + M[2]), np.rint((M[3] * xs + M[4] * ys) + M[5])
 
 
-def deblur_frame(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensitivity=2.0, max_ratio=4.0, want_weight=False):
+def deblur_frame(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensitivity=2.0, max_ratio=4.0, want_weight=False, want_raw=False):
     """one output frame.  src (n_src, h, w, 3); sharp: the S of every frame of src; cand_frame: indices (a negative one ends the list);
-    cand_t: Transforms; cvinv(t, w, h) -> the six doubles of vs_cv_inverse_matrix.  want_weight: also W (h, w) float32"""
+    cand_t: Transforms; cvinv(t, w, h) -> the six doubles of vs_cv_inverse_matrix.  want_weight: also W (h, w) float32; want_raw: (out, W,
+    floor(acc / W + 0.5) before the saturation, float32 (h, w, 3))"""
     _, h, w, _ = src.shape
     k = int(cand_frame[0])
     assert k >= 0
@@ -64,6 +79,8 @@ def deblur_frame(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensiti
             part.append((f, t, F32(r * r)))
     tgt = src[k]
     if not part:
+        if want_raw:
+            return tgt.copy(), np.ones((h, w), F32), tgt.astype(F32)
         return (tgt.copy(), np.ones((h, w), F32)) if want_weight else tgt.copy()
     gk = gray8(tgt, bits)
     acc = tgt.astype(F32)
@@ -80,8 +97,10 @@ def deblur_frame(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensiti
             prod = (wt * q[..., c].astype(F32)).astype(F32)
             acc[..., c] = np.where(inside, acc[..., c] + prod, acc[..., c])
         W = np.where(inside, W + wt, W).astype(F32)
-    out = np.floor((acc / W[..., None]).astype(F32) + F32(0.5))
-    out = np.clip(out, 0, max_value).astype(src.dtype)
+    raw = np.floor((acc / W[..., None]).astype(F32) + F32(0.5))
+    out = np.clip(raw, 0, max_value).astype(src.dtype)
+    if want_raw:
+        return out, W, raw
     return (out, W) if want_weight else out
 
 

@@ -13,24 +13,69 @@ Test infrastructure only: nothing of the product is used here.
 import numpy as np
 
 
-def cv_source_ints(O, t, w, h):
-    """integer source position (sx, sy) of every output pixel for the FORWARD transform t, full frame"""
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def cv_round_sat(v):
+    """cvRound as the rule has it (vs_device.hpp / the oracle's cv_round_sat): ties to even, saturated to int32, NaN -> 0.  float64 -> int64"""
+    with np.errstate(invalid="ignore"):
+        r = np.rint(np.asarray(v, np.float64))
+        r = np.where(np.isnan(r), 0.0, np.clip(r, float(INT32_MIN), float(INT32_MAX)))
+    return r.astype(np.int64)
+
+
+def wrap32(v):
+    """an int64 sum taken back into int32 the way two's-complement addition leaves it"""
+    return ((np.asarray(v, np.int64) + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+
+
+def _table_terms(O, t, w, h, rnd):
     M = np.asarray(O.cv_inverse_matrix(t, w, h), np.float64).reshape(6)
     xs = np.arange(w, dtype=np.float64)
     ys = np.arange(h, dtype=np.float64)[:, None]
-    ad = np.rint(M[0] * xs * 1024).astype(np.int64)[None, :]
-    bd = np.rint(M[3] * xs * 1024).astype(np.int64)[None, :]
-    X0 = np.rint((M[1] * ys + M[2]) * 1024).astype(np.int64) + 16
-    Y0 = np.rint((M[4] * ys + M[5]) * 1024).astype(np.int64) + 16
-    X = (X0 + ad) >> 5
-    Y = (Y0 + bd) >> 5
+    with np.errstate(invalid="ignore", over="ignore"):
+        ad = rnd(M[0] * xs * 1024)[None, :]
+        bd = rnd(M[3] * xs * 1024)[None, :]
+        X0 = rnd((M[1] * ys + M[2]) * 1024)
+        Y0 = rnd((M[4] * ys + M[5]) * 1024)
+    return X0, Y0, ad, bd
+
+
+def cv_source_ints(O, t, w, h):
+    """integer source position (sx, sy) of every output pixel for the FORWARD transform t, full frame: THE RULE -- cvRound saturated to
+    int32, + 16 and X0 + adelta wrapping in int32, arithmetic shifts (cv_round_sat, cv_row_origin, cv_pos in vs_device.hpp / vs_fill.hip; the
+    oracle's plain warp)"""
+    X0, Y0, ad, bd = _table_terms(O, t, w, h, cv_round_sat)
+    X = wrap32(wrap32(X0 + 16) + ad) >> 5
+    Y = wrap32(wrap32(Y0 + 16) + bd) >> 5
     return X >> 5, Y >> 5
+
+
+def cv_source_ints_int64(O, t, w, h):
+    """the same positions in unbounded (int64) arithmetic: NOT the rule.  Equal to it wherever no term saturates and no sum leaves int32 --
+    every moderate transform; kept for the premise assertions of the hostile cases and for tests/test_fill_cpu.py, which pins where the two
+    part.  (Non-finite terms have no int64 value: they become 0 here.)"""
+    def rnd(v):
+        r = np.rint(v)
+        return np.where(np.isfinite(r), np.clip(r, -2.0 ** 62, 2.0 ** 62), 0.0).astype(np.int64)
+    X0, Y0, ad, bd = _table_terms(O, t, w, h, rnd)
+    X = (X0 + 16 + ad) >> 5
+    Y = (Y0 + 16 + bd) >> 5
+    return X >> 5, Y >> 5
+
+
+def _inside(sx, sy, w, h):
+    return (sx >= 0) & (sx + 1 <= w - 1) & (sy >= 0) & (sy + 1 <= h - 1)
 
 
 def covered(O, t, w, h):
     """(h, w) bool: all four taps of the pixel lie in the frame"""
-    sx, sy = cv_source_ints(O, t, w, h)
-    return (sx >= 0) & (sx + 1 <= w - 1) & (sy >= 0) & (sy + 1 <= h - 1)
+    return _inside(*cv_source_ints(O, t, w, h), w, h)
+
+
+def covered_int64(O, t, w, h):
+    """covered() on the int64 positions: premise assertions only"""
+    return _inside(*cv_source_ints_int64(O, t, w, h), w, h)
 
 
 def fill_frame(O, src, cand_frame, cand_t, border, max_value=None, roi=None, want_masks=False):

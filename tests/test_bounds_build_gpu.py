@@ -1,6 +1,6 @@
 """The debug build with bounds-checked LDS / scratch indexing ("bounds asserts in debug kernels"; GPU
-AddressSanitizer is not available on this pool).  tools/build_variant.sh bounds compiles vs_engine / vs_warp / vs_phase / vs_flow / vs_capi
-with -DVS_DEBUG_BOUNDS: the selection arrays (introselect_*, stable_select), the gather / exchange / staging indices of the fused
+AddressSanitizer is not available on this pool).  tools/build_variant.sh bounds compiles vs_engine / vs_warp / vs_fill / vs_deblur / vs_phase /
+vs_flow / vs_capi with -DVS_DEBUG_BOUNDS: the gathers and stores of the border fill and the deblur (global memory: element offsets within a frame, sites 501-522), the selection arrays (introselect_*, stable_select), the gather / exchange / staging indices of the fused
 aligner kernel, the warp's tile fill and tap windows, the FFT lines and the dense flow's LDS tiles, histograms and per-thread scratch offsets are indexed through
 vsd::Span / VS_BOUNDS_CHECK / VS_IDX (vs_device.hpp).  A violation is recorded (site, index, limit, workgroup, thread) and redirected to element 0, never executed.
 
@@ -69,6 +69,10 @@ def test_selection_warp_phase_and_config_tests_pass_on_the_bounds_build_with_a_c
               "tests/test_warp_sweep_gpu.py", "tests/test_engine_sweep_gpu.py"], "not 4k_frame"),   # (the kernel-chain sweep runs the un-instrumented stage kernels of vs_kernels.hip: not here)   # (the 4K frames' time is the CPU oracle's; the second group has a 4K frame)
             (["tests/test_latency_mode_gpu.py", "tests/test_configs_gpu.py"],
              "coresident_build_at_4k or sixteen_pairs or c3_4k_bgr_lanczos2_warp or c5_one_gpus_share"),
+            # the border fill and the deblur (sites 501-522): the hostile modules first -- NaN, singular and saturating maps are what an unchecked
+            # gather would go wrong on -- then the kernel-level and route tests, without the allocation-failure walks and the app tests
+            (["tests/test_deblur_hostile_gpu.py", "tests/test_fill_hostile_gpu.py", "tests/test_fill_gpu.py", "tests/test_deblur_gpu.py"],
+             "not allocation_failure and not video_test"),
             # the dense flow (sites 401-420): everything but the two-chunk 1080p clips, whose kernels and indices the smaller clips run as well
             (["tests/test_flow_gpu.py", "tests/test_flow_hostile_gpu.py", "tests/test_flow_routes_gpu.py"], "not chunked_clip and not two_chunks")]
     for mods, expr in runs:

@@ -99,7 +99,7 @@ def _cand_lists(vs, rng, n_out, n_cand, n_src, w, h):
 
 @pytest.mark.parametrize("shape", [(203, 149), (260, 75)], ids=["203x149", "260x75"])     # (the per-sample kernel; four pixels per lane)
 @pytest.mark.parametrize("n_cand", [1, 4, 16])
-@pytest.mark.parametrize("fmt", ["bgr8", "bgr10", "bgr16"])
+@pytest.mark.parametrize("fmt", ["bgr8", "bgr10", "bgr12", "bgr16"])
 def test_deblur_batch_equals_the_rule(gpu_vs, fmt, n_cand, shape):
     vs = gpu_vs
     code, dtype, bits = FORMATS[fmt]

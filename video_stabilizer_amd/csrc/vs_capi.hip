@@ -451,6 +451,8 @@ extern "C" int vs_bounds_fetch_engine(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_warp(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_phase(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_flow(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_fill(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_deblur(unsigned out[8], int reset);
 namespace {
 // the checker checked: element 11 of an 8-element LDS array through a Span -- reported under site 900, executed on element 0
 __global__ void vs_k_bounds_selftest(int* out) {
@@ -469,11 +471,12 @@ int vs_debug_bounds_check(void) try {
 #ifdef VS_DEBUG_BOUNDS
     if (!vsi::device_ready()) return VS_ERR_HIP;
     VS_HIP(hipDeviceSynchronize());
-    int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_flow, vs_bounds_fetch_capi};
-    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_capi.hip"};
+    int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_flow, vs_bounds_fetch_fill,
+                                            vs_bounds_fetch_deblur, vs_bounds_fetch_capi};
+    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_fill.hip", "vs_deblur.hip", "vs_capi.hip"};
     unsigned total = 0;
     char msg[512] = "";
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < 7; k++) {
         unsigned r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fetch[k](r, 1) != 0) return set_error(VS_ERR_HIP, "bounds record of %s is not readable", names[k]);
         if (r[0] && !total)
@@ -988,7 +991,7 @@ int vs_bgr_sharpness_batch(const void* src, size_t src_fs, int n, int w, int h, 
 
 static int deblur_params_ok(const vs_deblur_params* params, vs_deblur_params* p) {
     if (params) *p = *params; else vs_deblur_params_default(p);
-    VS_ARG(p->sensitivity > 0.0f && p->sensitivity <= 3.0e38f && p->max_ratio > 0.0f && p->max_ratio <= 1.0e18f);
+    VS_ARG(vsi::deblur_params_finite(p->sensitivity, p->max_ratio));      // (the box and max_ratio^2 / sensitivity <= 2^100: the fp32 sums stay finite)
     return VS_OK;
 }
 

@@ -38,6 +38,11 @@ namespace {
 constexpr int SH_COLS = 62, SH_ROWS = 32, SH_WAVES = 4;   // sharpness: interior columns / rows per wave, waves (stacked) per workgroup
 constexpr int DB_W = 64, DB_ROWS = 16, DB_WAVES = 4;      // deblur: a wave's strip, four strips stacked = a 64 x 64 tile
 
+// The bounds build (-DVS_DEBUG_BOUNDS, vs_device.hpp) checks every gather and every store of this file, sites 501-516: an element offset within
+// a frame, the access's last sample included, lies below (h - 1) * stride + 3 w, source and destination alike (a pixel's address: its row offset
+// at most (h - 1) * stride and its column offset, last sample included, below 3 w).  The extents are written inside
+// the macros' arguments, which the regular build drops: its kernels are instruction for instruction what they were.
+
 template <typename T>
 __device__ __forceinline__ int gray8(const T* __restrict__ p, int shift) {
     const uint32_t g = (((uint32_t)p[0] * 3735u + (uint32_t)p[1] * 19235u + (uint32_t)p[2] * 9798u + 16384u) >> 15) >> shift;
@@ -56,12 +61,13 @@ __global__ __launch_bounds__(64 * SH_WAVES) void vs_k_bgr_sharpness(const T* __r
     const int x = txi * SH_COLS + lane;                                   // lanes 1 .. 62 own interior columns, 0 and 63 are their neighbours
     const bool centre = lane >= 1 && lane <= SH_COLS && x <= w - 2;
     const T* const col = src + (size_t)blockIdx.y * src_fs + (size_t)min(x, w - 1) * 3;
-    int gu = gray8(col + (size_t)(ya - 1) * (size_t)src_stride, shift), gm = gray8(col + (size_t)ya * (size_t)src_stride, shift);
+    int gu = gray8(col + VS_IDX((size_t)(ya - 1) * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * min(x, w - 1) - 2, 501), shift);
+    int gm = gray8(col + VS_IDX((size_t)ya * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * min(x, w - 1) - 2, 501), shift);
     uint32_t acc = 0;                                                     // <= 32 * 130050
 #pragma unroll 8
     for (int r = 0; r < SH_ROWS; r++) {                                   // (a fixed trip count: rows past the last one are read clamped and not counted)
         const int y = ya + r;
-        const int gd = gray8(col + (size_t)min(y + 1, h - 1) * (size_t)src_stride, shift);
+        const int gd = gray8(col + VS_IDX((size_t)min(y + 1, h - 1) * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * min(x, w - 1) - 2, 502), shift);
         const int dx = __shfl_down(gm, 1) - __shfl_up(gm, 1), dy = gd - gu;
         if (centre && y < yb) acc += (uint32_t)(dx * dx + dy * dy);
         gu = gm; gm = gd;
@@ -113,13 +119,14 @@ __global__ __launch_bounds__(64 * SH_WAVES) void vs_k_bgr_sharpness_x4(const T* 
         if (xs < w && pi >= 1 && pi <= SV_COLS && xs + i >= 1 && xs + i <= w - 2) count |= 1u << i;
     }
     const T* const col = src + (size_t)blockIdx.y * src_fs + (size_t)x * 3;
-    uint32_t gu = gray8x4<T>((const uint32_t*)(col + (size_t)(ya - 1) * (size_t)src_stride), shift);
-    uint32_t gm = gray8x4<T>((const uint32_t*)(col + (size_t)ya * (size_t)src_stride), shift);
+    // (twelve samples per read)
+    uint32_t gu = gray8x4<T>((const uint32_t*)(col + VS_IDX((size_t)(ya - 1) * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * x - 11, 503)), shift);
+    uint32_t gm = gray8x4<T>((const uint32_t*)(col + VS_IDX((size_t)ya * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * x - 11, 503)), shift);
     uint32_t acc = 0;                                                     // <= 4 * 32 * 130050
 #pragma unroll 4
     for (int r = 0; r < SH_ROWS; r++) {
         const int y = ya + r;
-        const uint32_t gd = gray8x4<T>((const uint32_t*)(col + (size_t)min(y + 1, h - 1) * (size_t)src_stride), shift);
+        const uint32_t gd = gray8x4<T>((const uint32_t*)(col + VS_IDX((size_t)min(y + 1, h - 1) * (size_t)src_stride, (long long)(h - 1) * src_stride + 3LL * w - 3LL * x - 11, 504)), shift);
         const uint32_t left = __shfl_up(gm, 1) >> 24, right = __shfl_down(gm, 1) & 255u;
         const uint32_t live = y < yb ? count : 0u;
 #pragma unroll
@@ -185,10 +192,12 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur(const vsk::Debl
             size_t done = 0;
             if (wide) {
                 const size_t nd = row_bytes / 4;
-                for (size_t i = lane; i < nd; i += 64) ((uint32_t*)dp)[i] = ((const uint32_t*)sp)[i];
+                for (size_t i = lane; i < nd; i += 64)
+                    ((uint32_t*)dp)[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 505)] = ((const uint32_t*)sp)[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 506)];
                 done = nd * 4;
             }
-            for (size_t i = done + lane; i < row_bytes; i += 64) dp[i] = sp[i];
+            for (size_t i = done + lane; i < row_bytes; i += 64)
+                dp[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T), 507)] = sp[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T), 508)];
         }
         return;
     }
@@ -198,7 +207,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur(const vsk::Debl
 #pragma unroll 1
     for (int y = y0; y < y1; y++) {
         const double dyy = (double)y;
-        const T* const tp = tgt + (size_t)y * (size_t)src_stride + (size_t)x * 3;
+        const T* const tp = tgt + VS_IDX((size_t)y * (size_t)src_stride, (long long)(h - 1) * src_stride + 1, 509) + VS_IDX((size_t)x * 3, 3LL * w - 2, 509);
         const int gk = gray8(tp, shift);
         float a0 = (float)tp[0], a1 = (float)tp[1], a2 = (float)tp[2], W = 1.0f;
 #pragma unroll 1
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur(const vsk::Debl
             const double fx = rint((cands[c].m[0] * dxx + cands[c].m[1] * dyy) + cands[c].m[2]);
             const double fy = rint((cands[c].m[3] * dxx + cands[c].m[4] * dyy) + cands[c].m[5]);
             if (fx >= 0.0 && fx <= (double)(w - 1) && fy >= 0.0 && fy <= (double)(h - 1)) {       // (false for NaN)
-                const T* const qp = cs + (size_t)(int)fy * (size_t)src_stride + (size_t)(int)fx * 3;
+                const T* const qp = cs + VS_IDX((size_t)(int)fy * (size_t)src_stride, (long long)(h - 1) * src_stride + 1, 510) + VS_IDX((size_t)(int)fx * 3, 3LL * w - 2, 510);
                 const float q0 = (float)qp[0], q1 = (float)qp[1], q2 = (float)qp[2];
                 const float d = fabsf((float)(gk - gray8(qp, shift)));
                 const float wt = r2 / (d + sens);
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur(const vsk::Debl
                 W = W + wt;
             }
         }
-        T* const op = dst + (size_t)y * (size_t)dst_stride + (size_t)x * 3;
+        T* const op = dst + VS_IDX((size_t)y * (size_t)dst_stride, (long long)(h - 1) * dst_stride + 1, 511) + VS_IDX((size_t)x * 3, 3LL * w - 2, 511);
         op[0] = (T)min(max((int)floorf(a0 / W + 0.5f), 0), maxv);
         op[1] = (T)min(max((int)floorf(a1 / W + 0.5f), 0), maxv);
         op[2] = (T)min(max((int)floorf(a2 / W + 0.5f), 0), maxv);
@@ -249,7 +258,8 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
         for (int y = y0; y < y1; y++) {
             const uint32_t* const sp = (const uint32_t*)(tgt + (size_t)y * (size_t)src_stride + (size_t)x0 * 3);
             uint32_t* const dp = (uint32_t*)(dst + (size_t)y * (size_t)dst_stride + (size_t)x0 * 3);
-            for (size_t i = lane; i < nd; i += 64) dp[i] = sp[i];
+            for (size_t i = lane; i < nd; i += 64)
+                dp[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 512)] = sp[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 513)];
         }
         return;
     }
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
 #pragma unroll 1
     for (int y = y0; y < y1; y++) {
         const double dyy = (double)y;
-        const uint32_t* const tp = (const uint32_t*)(tgt + (size_t)y * (size_t)src_stride + (size_t)x * 3);
+        const uint32_t* const tp = (const uint32_t*)(tgt + VS_IDX((size_t)y * (size_t)src_stride, (long long)(h - 1) * src_stride + 1, 514) + VS_IDX((size_t)x * 3, 3LL * w - 11, 514));      // (twelve samples)
         uint32_t d[ND];
 #pragma unroll
         for (int k = 0; k < ND; k++) d[k] = tp[k];
@@ -285,7 +295,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
                 const double fx = rint((m0 * dxx + m1 * dyy) + m2);
                 const double fy = rint((m3 * dxx + m4 * dyy) + m5);
                 if (fx >= 0.0 && fx <= (double)(w - 1) && fy >= 0.0 && fy <= (double)(h - 1)) {       // (false for NaN)
-                    const T* const qp = cs + (size_t)(int)fy * (size_t)src_stride + (size_t)(int)fx * 3;
+                    const T* const qp = cs + VS_IDX((size_t)(int)fy * (size_t)src_stride, (long long)(h - 1) * src_stride + 1, 515) + VS_IDX((size_t)(int)fx * 3, 3LL * w - 2, 515);
                     const float q0 = (float)qp[0], q1 = (float)qp[1], q2 = (float)qp[2];
                     const float dg = fabsf((float)(gk[i] - gray8(qp, shift)));
                     const float wt = r2 / (dg + sens);
@@ -302,13 +312,15 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
             const uint32_t v = (uint32_t)min(max((int)floorf(a[k] / W[k / 3] + 0.5f), 0), maxv);
             if (sizeof(T) == 1) o[k / 4] |= v << (8 * (k % 4)); else o[k / 2] |= v << (16 * (k % 2));
         }
-        uint32_t* const op = (uint32_t*)(dst + (size_t)y * (size_t)dst_stride + (size_t)x * 3);
+        uint32_t* const op = (uint32_t*)(dst + VS_IDX((size_t)y * (size_t)dst_stride, (long long)(h - 1) * dst_stride + 1, 516) + VS_IDX((size_t)x * 3, 3LL * w - 11, 516));
 #pragma unroll
         for (int k = 0; k < ND; k++) op[k] = o[k];
     }
 }
 
 }  // namespace
+
+VS_BOUNDS_TU(vs_bounds_fetch_deblur)
 
 namespace vsk {
 

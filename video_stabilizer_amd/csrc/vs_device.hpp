@@ -169,9 +169,11 @@ __device__ __forceinline__ float lanczos_separable_combine(const float v[4][4], 
 
 // ---- VS_WARP_BILINEAR_CV: cv::warpAffine's fixed-point coordinates (OpenCV 4.x imgwarp.cpp, AB_BITS = 10, INTER_BITS = 5) -------------------
 // cvRound = round half to even; a value outside the int range saturates (as the oracle's cv_round_sat; no frame gets near it)
+// (NaN is asked about BEFORE the clamp: fmax / fmin return their other operand for a NaN, so a test behind them never sees one and NaN came out
+// as INT_MIN -- a NaN translation, tests/test_fill_hostile_gpu.py)
 __device__ __forceinline__ int cv_round_sat(double v) {
-    v = fmin(fmax(rint(v), -2147483648.0), 2147483647.0);
-    return (v == v) ? (int)v : 0;
+    if (!(v == v)) return 0;
+    return (int)fmin(fmax(rint(v), -2147483648.0), 2147483647.0);
 }
 // adelta[x] / bdelta[x]: cvRound(m * x * 1024) -- the product m * x rounds to double before the scaling (exact), as in the source
 __device__ __forceinline__ int cv_delta(double m, int x) { return cv_round_sat(m * (double)x * 1024.0); }

@@ -2068,7 +2068,7 @@ int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
     vs_deblur_params p;
     if (params) p = *params; else vs_deblur_params_default(&p);
-    VS_ARG(p.sensitivity > 0.0f && p.sensitivity <= 3.0e38f && p.max_ratio > 0.0f && p.max_ratio <= 1.0e18f);
+    VS_ARG(vsi::deblur_params_finite(p.sensitivity, p.max_ratio));
     s->deblur = ahead;
     s->deblur_params = p;
     return VS_OK;

@@ -8,6 +8,9 @@
 //   * For a candidate, output pixel (x, y) -- full-frame coordinates, also under a ROI -- has the integer source position of the existing warp:
 //       X = (X0[y] + adelta[x]) >> 5,  sx = X >> 5        X0[y] = cvRound((M[1] y + M[2]) 1024) + 16,  adelta[x] = cvRound(M[0] x 1024)
 //       Y = (Y0[y] + bdelta[x]) >> 5,  sy = Y >> 5        Y0[y] = cvRound((M[4] y + M[5]) 1024) + 16,  bdelta[x] = cvRound(M[3] x 1024)
+//     All of it in int32 as in cv::warpAffine: cvRound saturates to [INT_MIN, INT_MAX] (NaN -> 0; cv_round_sat), the additions (+ 16 in
+//     cv_row_origin, X0 + adelta in cv_pos) wrap in two's complement, the shifts are arithmetic.  An extreme matrix is judged on the saturated,
+//     wrapped position: the one pass 1 samples.
 //     The candidate COVERS the pixel iff all four taps lie in the frame: 0 <= sx && sx + 1 <= w - 1 && 0 <= sy && sy + 1 <= h - 1.
 //   * The pixel's value is the value VS_WARP_BILINEAR_CV gives for the FIRST candidate that covers it, bit for bit (8-bit: integer weights,
 //     (sum + 512) >> 10; 16-bit: float weights a b / 1024, cvRound, saturated to max_value).  A candidate without a frame ends the list.  If
@@ -55,7 +58,11 @@ __device__ __forceinline__ bool cv_covers_rect(const double M[6], vsk::Roi roi, 
     const int XA = cv_row_origin(M[1], M[2], fyA), XB = cv_row_origin(M[1], M[2], fyB);
     const int YA = cv_row_origin(M[4], M[5], fyA), YB = cv_row_origin(M[4], M[5], fyB);
     const int lim = 1 << 29;
-    const bool small = max(max(max(abs(adA), abs(adB)), max(abs(bdA), abs(bdB))), max(max(abs(XA), abs(XB)), max(abs(YA), abs(YB)))) < lim;
+    // (-lim < term < lim asked of the terms as they stand: a delta that cvRound saturated to INT_MIN has no absolute value in int, and abs() would
+    // hand it back negative -- "small".  Reached by a near-singular candidate 0 on a one-row window at frame row 0: tests/test_fill_hostile_gpu.py)
+    const int lo = min(min(min(adA, adB), min(bdA, bdB)), min(min(XA, XB), min(YA, YB)));
+    const int hi = max(max(max(adA, adB), max(bdA, bdB)), max(max(XA, XB), max(YA, YB)));
+    const bool small = lo > -lim && hi < lim;
     const int mnX = min(XA, XB) + min(adA, adB), mxX = max(XA, XB) + max(adA, adB);
     const int mnY = min(YA, YB) + min(bdA, bdB), mxY = max(YA, YB) + max(bdA, bdB);
     // ((X0 + adelta) >> 5) >> 5 = (X0 + adelta) >> 10
@@ -124,7 +131,15 @@ __global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_c3(const 
                 const CvPos p = cv_pos(cv_row_origin(C[1], C[2], fy), cv_row_origin(C[4], C[5], fy), cv_delta(C[0], fx), cv_delta(C[3], fx));
                 if (open && cv_covers(p, w, h)) {
                     T o[3];
+#ifdef VS_DEBUG_BOUNDS
+                    // the bounds build (vs_device.hpp), sites 521 / 522: the 2 x 2 taps' last sample, at stride + 5 from the first, lies inside the source
+                    // frame's (h - 1) * stride + 3 w elements -- else pixel (0, 0) is sampled; the store's last sample lies inside the output window
+                    const bool taps_in = vsd::bounds_ok((long long)(p.Y >> 5) * src_stride + 3LL * (p.X >> 5) + src_stride + 5, (long long)(h - 1) * src_stride + 3LL * w, 521);
+                    cv_sample_inside(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, o);
+                    if (!vsd::bounds_ok((long long)y * dst_stride + 3LL * x + 2, (long long)(roi.h - 1) * dst_stride + 3LL * roi.w, 522)) continue;
+#else
                     cv_sample_inside(cs, src_stride, p, maxv, o);
+#endif
                     px[0] = o[0]; px[1] = o[1]; px[2] = o[2];
                     open = false;
                 }
@@ -134,6 +149,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_c3(const 
 }
 
 }  // namespace
+
+VS_BOUNDS_TU(vs_bounds_fetch_fill)
 
 namespace vsk {
 

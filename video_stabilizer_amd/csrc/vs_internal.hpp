@@ -18,6 +18,14 @@ template <typename F>
 inline int guarded(F&& f) noexcept {
     try { return f(); } catch (...) { return caught(); }
 }
+// The vs_deblur_params the library accepts (include/vs_amd.h): with r <= min(max_ratio, 2^53) (S < 2^53) a weight is
+// at most r^2 / sensitivity, so under r^2 / sensitivity <= 2^100 the sums of at most 15 weights times samples <= 65535 stay below
+// 2^4 * 2^100 * 2^16 * (1 + 2^-24)^64 < 2^121: acc and W are finite for every frame.  (fp32 overflows from r^2 / sensitivity of about 2^108.)
+inline bool deblur_params_finite(float sensitivity, float max_ratio) {
+    if (!(sensitivity > 0.0f && sensitivity <= 3.0e38f && max_ratio > 0.0f && max_ratio <= 1.0e18f)) return false;
+    const double r = (double)max_ratio < 9007199254740992.0 ? (double)max_ratio : 9007199254740992.0;
+    return r * r <= (double)sensitivity * 0x1p100;
+}
 }  // namespace vsi
 #define VS_CATCH_ALL catch (...) { return vsi::caught(); }
 #define VS_CATCH_ALL_NULL catch (...) { (void)vsi::caught(); return nullptr; }
