@@ -1,9 +1,10 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--deblur N] [--bilinear | --lanczos2] [--444]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--deblur N] [--denoise N] [--denoise-strength T] [--bilinear | --lanczos2] [--444]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill).  --deblur N: every frame is deblurred from
-// the sharper ones among the next N input frames before it is warped (vs_stabilizer_set_deblur).  Frames go to the GPU in
+// the sharper ones among the next N input frames before it is warped (vs_stabilizer_set_deblur).  --denoise N: every frame is averaged
+// with what the next N input frames show at the same scene point (vs_stabilizer_set_denoise; --denoise-strength T: 1 .. 255, default 24).  Frames go to the GPU in
 // chunks of N (default 64) and through vs_stabilizer_process_batch, which is defined as N successive processFrame calls.
 #include <chrono>
 #include <filesystem>
@@ -13,7 +14,7 @@
 namespace fs = std::filesystem;
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
-                         bool force444, int fill, int deblur) {
+                         bool force444, int fill, int deblur, int denoise, int denoise_strength) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -43,6 +44,16 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
         std::cerr << "Error: vs_stabilizer_set_deblur: " << vs_last_error() << std::endl;
         vs_stabilizer_destroy(stab);
         return false;
+    }
+    if (denoise != 0) {
+        vs_denoise_params dp;
+        vs_denoise_params_default(&dp);
+        if (denoise_strength != 0) dp.strength = denoise_strength;
+        if (vs_stabilizer_set_denoise(stab, denoise, &dp) != VS_OK) {
+            std::cerr << "Error: vs_stabilizer_set_denoise: " << vs_last_error() << std::endl;
+            vs_stabilizer_destroy(stab);
+            return false;
+        }
     }
 
     long frame_count = 0, written = 0, next_report = 100;
@@ -76,7 +87,7 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
 
 int main(int argc, char** argv) {
     std::string input_dir = "../recordings", output_dir = "output";   // video_test.cpp:12-13
-    int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, positional = 0;
+    int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, denoise = 0, denoise_strength = 0, positional = 0;
     bool bilinear = false, lanczos2 = false, force444 = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -85,12 +96,14 @@ int main(int argc, char** argv) {
         else if (a == "--crop" && i + 1 < argc) crop = std::atoi(argv[++i]);
         else if (a == "--fill" && i + 1 < argc) fill = std::atoi(argv[++i]);
         else if (a == "--deblur" && i + 1 < argc) deblur = std::atoi(argv[++i]);
+        else if (a == "--denoise" && i + 1 < argc) denoise = std::atoi(argv[++i]);
+        else if (a == "--denoise-strength" && i + 1 < argc) denoise_strength = std::atoi(argv[++i]);
         else if (a == "--bilinear") bilinear = true;
         else if (a == "--lanczos2") lanczos2 = true;
         else if (a == "--444") force444 = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--deblur N] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--deblur N] [--denoise N] [--denoise-strength T] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -116,7 +129,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, deblur)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, deblur, denoise, denoise_strength)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

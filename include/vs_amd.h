@@ -290,6 +290,35 @@ int vs_bgr_deblur_batch(const void* src, size_t src_frame_stride, int n_src, int
                         const uint64_t* sharpness, int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
                         const vs_deblur_params* params /* NULL = defaults */,
                         void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* TEMPORAL DENOISE, MOTION COMPENSATED: a pixel is averaged with what other frames show at the same scene point, as far as they agree
+ * with it.  Interleaved BGR, every VS_FMT_BGR*, frames up to 32767 x 32767 (VS_ERR_UNSUPPORTED beyond, as in the fill).  The rule:
+ *   - Output frame o has n_cand (1 .. 16) candidates (cand_frame, cand_t), exactly as in vs_bgr_deblur_batch.  Candidate 0 is the target
+ *     frame k itself and its transform is ignored; a negative index ends the list.
+ *   - cand_t is in VS_WARP_BILINEAR_CV's forward convention.  The sample q_c of candidate j at target pixel (x, y) is, bit for bit, what
+ *     vs_bgr_image_warp_roi_batch gives in mode VS_WARP_BILINEAR_CV for that frame and transform with max_value =
+ *     vs_format_max_value(format): cv::warpAffine's fixed-point bilinear on int32 positions (see vs_bgr_image_warp_fill_batch).
+ *     Candidate j takes part at the pixel only if it COVERS it by the fill's rule: all four taps at the warp's own integer source
+ *     position lie in the frame.  No sample ever meets a border rule.
+ *   - All arithmetic in unsigned 32-bit integers.  s = bits - 8; t = strength, 1 .. 255, in 8-bit levels (default 24).
+ *       d_j = max over the three channels of |p_c - q_c| >> s;      w_j = t - d_j if d_j < t, else 0
+ *       acc_c = t p_c + sum_j w_j q_c;      W = t + sum_j w_j
+ *     If sum_j w_j == 0 the pixel is p_c, bit for bit.  Otherwise it is min((2 acc_c + W) / (2 W), max_value), floor division.
+ *   - Bound: 2 acc_c + W <= 2 * 16 * 255 * 65535 + 4080 < 2^30, so every term fits and the rule defines every sample for every input
+ *     the call accepts.
+ *   - Hence (a) n_cand == 1, an all-negative list and candidates that lie wholly outside the frame give the frame back bit for bit;
+ *     (b) identical frames under identity maps come back bit for bit; (c) |out_c - p_c| < t << s at every pixel, whatever the content
+ *     and the maps (the ghost bound); (d) a pixel whose candidates all differ from it by t levels or more in some channel is untouched.
+ * A strength outside 1 .. 255 is VS_ERR_ARG. */
+typedef struct vs_denoise_params { int strength; } vs_denoise_params;
+void vs_denoise_params_default(vs_denoise_params* p);   /* 24 */
+/* cand_frame and cand_t are host arrays of n_out * n_cand entries; dst holds full w x h frames.  VS_MEM_DEVICE only enqueues.  The
+ * candidate entries reach the device in groups of (kSlots / 2 / 4) / n_cand output frames (kSlots = 32768 slots of the parameter ring, an
+ * entry is four slots: 256 frames at 16 candidates, 2048 at 2); a group whose targets or destination do not all start on dwords takes the
+ * per-sample kernel, with the same result. */
+int vs_bgr_denoise_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride, int format,
+                         int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
+                         const vs_denoise_params* params /* NULL = defaults */,
+                         void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* same sampling, float output (typed like image_warp); dst interleaved f32 */
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits,
                           const vs_transform* t, int mode, int border,
@@ -518,6 +547,17 @@ int   vs_stabilizer_get_border_fill(const vs_stabilizer* s);
  * defaults.  Takes effect with the next output frame.  VS_ERR_ARG beyond the handle's lag.  get returns `ahead`. */
 int   vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params);
 int   vs_stabilizer_get_deblur(const vs_stabilizer* s);
+/* Temporal denoise (the rule: see vs_bgr_denoise_batch).  0 (default): off.  1 .. lag: every frame is averaged, pixel by pixel, with what
+ * the next `ahead` input frames show at the same scene point, before it is warped -- they are already held in device memory with their
+ * measured motions, so the pass costs no latency, no second alignment and no host synchronisation.  Candidate j's transform is
+ * inverse(T_{k+1} o .. o T_j); a frame whose alignment failed ends the list, frames beyond a reset, a clip boundary or a size change are
+ * never candidates.  Order: deblur (if on), denoise, warp, border fill (if on).  The target is the deblurred frame when deblur is on; the
+ * candidates are always the original input frames; every warp_mode reads the denoised frame; the fill's candidate 0 is the denoised frame
+ * and its other candidates stay the originals.  The aligner always sees the original frames: transforms, vs_stabilizer_state and
+ * has_output do not depend on this setting.  params: NULL = defaults.  Takes effect with the next output frame.  VS_ERR_ARG beyond the
+ * handle's lag or for a strength outside 1 .. 255.  get returns `ahead`. */
+int   vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params);
+int   vs_stabilizer_get_denoise(const vs_stabilizer* s);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -81,6 +81,11 @@ class DeblurParams(C.Structure):
     _fields_ = [("sensitivity", C.c_float), ("max_ratio", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """vs_denoise_params: strength in 8-bit levels, 1 .. 255"""
+    _fields_ = [("strength", C.c_int)]
+
+
 class VsError(RuntimeError):
     pass
 
@@ -146,6 +151,9 @@ SIGNATURES = {
     "vs_bgr_sharpness_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "vs_bgr_deblur_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeblurParams),
                                    _vp, _sz, _i32, _i32, _vp]),
+    "vs_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "vs_bgr_denoise_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DenoiseParams),
+                                    _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
@@ -163,6 +171,8 @@ SIGNATURES = {
     "vs_stabilizer_get_border_fill": (_i32, [_vp]),
     "vs_stabilizer_set_deblur": (_i32, [_vp, _i32, C.POINTER(DeblurParams)]),
     "vs_stabilizer_get_deblur": (_i32, [_vp]),
+    "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, C.POINTER(DenoiseParams)]),
+    "vs_stabilizer_get_denoise": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
     "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
@@ -627,6 +637,48 @@ def bgr_deblur_batch_device(src_ptr, n_src, w, h, fmt, sharp_ptr, cand_frame, ca
                                      _p(dst_ptr), h * w * 3, w * 3, MEM_DEVICE, C.c_void_p(stream) if stream else None))
 
 
+def denoise_params(**kw):
+    p = DenoiseParams()
+    lib().vs_denoise_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def denoise_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """motion-compensated temporal denoise (include/vs_amd.h: vs_bgr_denoise_batch).  src (n_src,h,w,3) numpy; cand_frame (n_out, n_cand)
+    ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).  src_stride / dst_stride
+    (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer
+    is returned as well, so that the caller can see that the padding was left alone"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    arr = (Transform * max(len(flat), 1))(*flat)
+    ss = w * c if src_stride is None else src_stride
+    ds = w * c if dst_stride is None else dst_stride
+    buf = _pitched(src, ss)
+    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_denoise_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                      C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
+    return (res, out) if guard is not None else res
+
+
+def denoise_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape
+    flat = [t for row in cand_t for t in row]
+    arr = (Transform * len(flat))(*flat)
+    _check(lib().vs_bgr_denoise_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                      C.byref(params) if params is not None else None, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
+                                      C.c_void_p(stream) if stream else None))
+
+
 def sharpness_batch_device(src_ptr, n, w, h, fmt, sharp_ptr, stream=None):
     _check(lib().vs_bgr_sharpness_batch(_p(src_ptr), h * w * 3, n, w, h, w * 3, fmt, _p(sharp_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
 
@@ -867,7 +919,7 @@ class Aligner:
 class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
-    def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, **params):
+    def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -878,6 +930,16 @@ class Stabilizer:
             self.set_border_fill(border_fill)
         if deblur:
             self.set_deblur(deblur, deblur_params)
+        if denoise:
+            self.set_denoise(denoise, denoise_params)
+
+    def set_denoise(self, ahead, params=None):
+        """0: off; 1 .. lag: every frame is averaged with what the next `ahead` input frames show at the same scene point before it is warped
+        (params: DenoiseParams, None = defaults)"""
+        _check(lib().vs_stabilizer_set_denoise(self.h, int(ahead), C.byref(params) if params is not None else None))
+
+    def get_denoise(self):
+        return _check(lib().vs_stabilizer_get_denoise(self.h))
 
     def set_deblur(self, ahead, params=None):
         """0: off; 1 .. lag: every frame is deblurred from the next `ahead` input frames before it is warped (params: DeblurParams, None = defaults)"""

@@ -1369,6 +1369,10 @@ struct vs_stabilizer {
     int deblur = 0;                // vs_stabilizer_set_deblur: following frames a frame is deblurred from (0: off)
     vs_deblur_params deblur_params{2.0f, 4.0f};
     void* deblur_buf = nullptr; size_t deblur_bytes = 0;     // the deblurred frames of the current call: the source of its warps
+    // temporal denoise (vs_denoise.hip)
+    int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
+    vs_denoise_params denoise_params{24};
+    void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
     struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
     std::vector<void*> pool;       // recycled frame buffers
@@ -1442,6 +1446,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     for (auto& f : s->down) if (f.valid()) (void)f.get();
     for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
     if (s->deblur_buf) (void)hipFree(s->deblur_buf);
+    if (s->denoise_buf) (void)hipFree(s->denoise_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
@@ -1812,6 +1817,10 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     std::vector<const void*> db_src;
     std::vector<const uint64_t*> db_sharp;
     std::vector<vs_transform> db_t;
+    // denoise (vs_denoise.hip): per job 1 + ndn candidates likewise
+    const int ndn = std::min(s->denoise, s->params.lag);
+    std::vector<const void*> dn_src;
+    std::vector<vs_transform> dn_t;
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
@@ -1893,6 +1902,19 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                     }
                     for (; c < ndb; c++) { db_src.push_back(nullptr); db_sharp.push_back(nullptr); db_t.push_back(vs_transform{0, 0, 0, 0}); }
                 }
+                if (ndn > 0) {
+                    // the deblur's list: frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j); a failed alignment ends it
+                    dn_src.push_back(src.ptr); dn_t.push_back(vs_transform{0, 0, 0, 0});
+                    vs_transform chain{0, 0, 0, 0};
+                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
+                    int c = 0;
+                    for (; c < ndn && (size_t)c < avail && s->meas_ok[c]; c++) {
+                        chain = vs_transform_compose(&chain, &s->measurements[c]);
+                        dn_src.push_back(s->frames[c].ptr);
+                        dn_t.push_back(vs_transform_inverse(&chain));
+                    }
+                    for (; c < ndn; c++) { dn_src.push_back(nullptr); dn_t.push_back(vs_transform{0, 0, 0, 0}); }
+                }
             }
         }
     }
@@ -1931,6 +1953,27 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             if (dr < 0) return dr;
             for (size_t j = 0; j < jobs.size(); j++) {
                 jobs[j].src = (const uint8_t*)s->deblur_buf + j * fbytes;
+                if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
+            }
+        }
+        if (ndn > 0) {
+            // every due frame (deblurred, if that pass is on) is denoised into a scratch frame of its own, one launch, in front of the warps on
+            // their stream; the warps (and the fill's candidate 0) then read the scratch frames.  The candidates are the original input frames,
+            // read before their own jobs release them: releases follow below.
+            hipStream_t ws = warps_apart ? s->warp_stream : st;
+            if (s->denoise_bytes < fbytes * jobs.size()) {
+                VS_HIP(hipStreamSynchronize(ws));           // (warps of an earlier chunk may still read the area)
+                if (s->denoise_buf) (void)hipFree(s->denoise_buf);
+                s->denoise_buf = nullptr; s->denoise_bytes = 0;
+                VS_HIP(vsi::dev_alloc(&s->denoise_buf, fbytes * jobs.size()));
+                s->denoise_bytes = fbytes * jobs.size();
+            }
+            for (size_t j = 0; j < jobs.size(); j++) dn_src[j * (1 + ndn)] = jobs[j].src;
+            const int dr = vsi::bgr_denoise_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndn, dn_src.data(), dn_t.data(), &s->denoise_params, s->denoise_buf,
+                                                 (size_t)w * h * 3, w * 3, ws);
+            if (dr < 0) return dr;
+            for (size_t j = 0; j < jobs.size(); j++) {
+                jobs[j].src = (const uint8_t*)s->denoise_buf + j * fbytes;
                 if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
             }
         }
@@ -2076,6 +2119,19 @@ int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params
 int vs_stabilizer_get_deblur(const vs_stabilizer* s) try {
     VS_ARG(s);
     return s->deblur;
+} VS_CATCH_ALL
+int vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_denoise_params p;
+    if (params) p = *params; else vs_denoise_params_default(&p);
+    VS_ARG(p.strength >= 1 && p.strength <= 255);
+    s->denoise = ahead;
+    s->denoise_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->denoise;
 } VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);

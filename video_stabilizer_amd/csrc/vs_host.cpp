@@ -82,6 +82,10 @@ void vs_deblur_params_default(vs_deblur_params* p) {
     p->sensitivity = 2.0f;
     p->max_ratio = 4.0f;
 }
+// vs_denoise.hip (DESIGN.md "Temporal denoise": 24 levels is at the ideal of equally weighted samples for 4 LSB of noise, see the table there)
+void vs_denoise_params_default(vs_denoise_params* p) {
+    p->strength = 24;
+}
 
 // imgproc.cpp:333-359
 vs_transform vs_transform_inverse(const vs_transform* t) {

@@ -124,6 +124,12 @@ int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, 
 int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
                     const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
 
+// The denoise pass (the rule: vs_denoise.hip) on device-resident frames; vs_bgr_denoise_batch is the index-based wrapper over it.  Output frame o
+// = the frame at cand_src[o * n_cand] averaged with its candidates c = 1 .. n_cand-1: the frame at cand_src[o * n_cand + c] (any device pointer,
+// w x h, rows of src_stride elements; null ends the list) under cand_t[o * n_cand + c].  dst: full frames.  Host arrays; enqueue only.
+int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                     const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
+
 bool device_ready();   // true when a HIP device is usable (sets last error otherwise)
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the

@@ -82,6 +82,11 @@ hipError_t bgr_sharpness(const void* src, int w, int h, int src_stride, int bits
                          hipStream_t s);
 hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value,
                       float sensitivity, float max_ratio, void* dst, int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s);
+// Motion-compensated temporal denoise (vs_denoise.hip: the rule and the kernels).  cands_dev = n_frames x n_cand entries in device memory; entry 0
+// of a frame is the target (its matrix is not read), a null frame ends the list.  dst: full w x h frames.  strength: 1 .. 255.  targets_aligned:
+// every target frame starts on a dword.
+hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int strength, void* dst,
+                       int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s);
 // host side of the tuned kernel's tile prologue: per frame {lo_x, hi_x, lo_y, hi_y} from the kernel parameters {A, B, TX, TY}, for the
 // tile of the kernel that bgr_warp_c3 launches for (bits, mode)
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4);

@@ -18,6 +18,7 @@ struct VideoStabilizerParams {
     int warp_border = VS_BORDER_CONSTANT;
     int border_fill = 0;                  // a knob of this build: 1 .. lag = fill what the corrected frame does not cover from that many following frames (vs_stabilizer_set_border_fill)
     int deblur = 0;                       // a knob of this build: 1 .. lag = deblur every frame from the sharper ones among that many following frames (vs_stabilizer_set_deblur, default parameters)
+    int denoise = 0;                      // a knob of this build: 1 .. lag = average every frame with what that many following frames show at the same scene point (vs_stabilizer_set_denoise, default parameters)
 };
 
 // stabilizer.hpp:32-56.  processFrame returns an empty vector until `lag` frames have arrived
@@ -45,6 +46,11 @@ public:
             const std::string why = vs_last_error();
             vs_stabilizer_destroy(h_);
             throw std::runtime_error("vs_stabilizer_set_deblur: " + why);
+        }
+        if (params.denoise != 0 && vs_stabilizer_set_denoise(h_, params.denoise, nullptr) != VS_OK) {
+            const std::string why = vs_last_error();
+            vs_stabilizer_destroy(h_);
+            throw std::runtime_error("vs_stabilizer_set_denoise: " + why);
         }
     }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
