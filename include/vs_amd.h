@@ -251,13 +251,45 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_frame_stride, int n_
  *   - The pixel's value is the value VS_WARP_BILINEAR_CV gives for the FIRST candidate that covers it, bit for bit.  If no
  *     candidate covers it, it keeps candidate 0's ordinary result under `border`.
  *   - Hence pixels candidate 0 covers are exactly the plain warp's, and n_cand == 1 is the roi_batch call above, bit for
- *     bit.  No blending, feathering or photometric matching.
+ *     bit.  No blending, feathering or photometric matching in this call: see vs_bgr_image_warp_fill_blend_batch below.
  * ROI, strides, mem, stream: as in the roi_batch call; cand_frame and cand_t are host arrays of n_out * n_cand entries. */
 int vs_bgr_image_warp_fill_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride,
                                  int channels, int bits, int n_out, int n_cand, const int32_t* cand_frame,
                                  const vs_transform* cand_t, int border, int max_value,
                                  int roi_x, int roi_y, int roi_w, int roi_h,
                                  void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* THE FILL WITH ITS SEAMS BLENDED: two independent switches on the fill above, both exact integer rules.  Candidates, coverage, the
+ * int32 positions X, Y (5 fraction bits) and the sample q_c of a covering candidate are vs_bgr_image_warp_fill_batch's.
+ *   - Channel sums: S_i,c = the sum of the raw samples of channel c over all w x h pixels of frame i, as uint64_t; no clamp to the
+ *     format's maximum.  S <= 65535 * 32767^2 < 2^46; integer sums, so the order of the reduction cannot matter.
+ *   - Gain (match == 1) of candidate j >= 1 for output frame k (candidate 0's frame), per channel c, Q15, unsigned 64-bit:
+ *     G = 32768 if S_j,c == 0 or S_k,c == 0; otherwise G = clamp((2 * 32768 * S_k,c + S_j,c) / (2 * S_j,c), 16384, 65536) with
+ *     floor division (every term below 2^63).  With match == 0, G = 32768.
+ *   - Matched fill sample of the FIRST candidate j >= 1 that covers the pixel (q_c <= max_value):
+ *     f_c = min((q_c * G + 16384) >> 15, max_value) in unsigned 32-bit (65535 * 65536 + 16384 < 2^32).
+ *   - A pixel candidate 0 does not cover: out_c = f_c if a later candidate covers it; otherwise candidate 0's result under
+ *     `border`, as in the fill.
+ *   - Band pixel (feather >= 1): K = 32 << feather, Xmax = (w - 1) * 32 - 1, Ymax = (h - 1) * 32 - 1.  A pixel candidate 0 covers
+ *     has 0 <= X <= Xmax and 0 <= Y <= Ymax; d = min(X, Xmax - X, Y, Ymax - Y), k = d + 1.  If k >= K, or no later candidate covers
+ *     the pixel, it is the plain warp's value p_c bit for bit; otherwise
+ *     out_c = (k * p_c + (K - k) * f_c + K / 2) >> (5 + feather)   (the sum is below 2^27: unsigned 32-bit).
+ *   - Hence (a) feather == 0 && match == 0 is vs_bgr_image_warp_fill_batch bit for bit; (b) n_cand == 1, or a list whose later
+ *     entries are all negative, is the plain ROI warp; (c) a band pixel lies between min(p_c, f_c) and max(p_c, f_c);
+ *     (d) identical frames under identity maps come back bit for bit with any setting; (e) a pixel at least 2^feather source
+ *     pixels inside candidate 0's frame is never changed.
+ * feather: 0 (off) or 1 .. 6; match: 0 or 1; anything else is VS_ERR_ARG. */
+typedef struct vs_fill_blend_params { int feather; int match; } vs_fill_blend_params;
+/* sums[3*i + c] = S_i,c of frame i (n frames, frame i at src + i*src_frame_stride elements); every VS_FMT_BGR*, frames up to
+ * 32767 x 32767 (VS_ERR_UNSUPPORTED beyond, as in the fill); `sums` lives in `mem`. */
+int vs_bgr_channel_sums_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
+                              uint64_t* sums, int mem, void* stream);
+/* The fill call's arguments plus sums (3 * n_src values in `mem`, as vs_bgr_channel_sums_batch leaves them; NULL is allowed only
+ * with match == 0) and params (required). */
+int vs_bgr_image_warp_fill_blend_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride,
+                                       int channels, int bits, int n_out, int n_cand, const int32_t* cand_frame,
+                                       const vs_transform* cand_t, const uint64_t* sums, const vs_fill_blend_params* params,
+                                       int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h,
+                                       void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* DEBLUR BY TRANSFER: a frame that shake has blurred is blended with what its SHARPER neighbours show at the same scene point
  * (Matsushita et al. 2006; the role of OpenCV videostab's WeightingDeblurer).  Interleaved BGR, every VS_FMT_BGR*.  The rule:
  *   - Gray g = min(((B*3735 + G*19235 + R*9798 + 16384) >> 15) >> (bits - 8), 255): vs_bgr_to_gray's rule shifted to 8 bits.
@@ -537,6 +569,16 @@ int   vs_stabilizer_get_select_mode(const vs_stabilizer* s);
  * returns VS_ERR_UNSUPPORTED.  With the fill on, crop_pixels may go to 0. */
 int   vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead);
 int   vs_stabilizer_get_border_fill(const vs_stabilizer* s);
+/* The border fill's seam blend (the rule: see vs_bgr_image_warp_fill_blend_batch).  NULL or {0, 0} (default): off -- the fill as
+ * it is without this call, launch for launch.  feather 1 .. 6: the fill is cross-faded into the frame's own pixels over 2^feather
+ * source pixels inside the edge of its coverage.  match 1: every fill candidate is scaled per channel to the output frame's
+ * exposure; the channel sums of every arriving frame are then computed on the device at ingest (always of the ORIGINAL input
+ * frames, also when deblur or denoise replaces candidate 0's pixels) and never reach the host.  Meaningful only while the border
+ * fill is on; takes effect with the next output frame -- switching match on mid-clip gives what a handle that had it from the
+ * first frame gives (the sums of the frames already queued are computed at the next call).  A handle whose warp_mode is not
+ * VS_WARP_BILINEAR_CV returns VS_ERR_UNSUPPORTED. */
+int   vs_stabilizer_set_fill_blend(vs_stabilizer* s, const vs_fill_blend_params* params);
+int   vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* params);
 /* Deblur (the rule: see vs_bgr_deblur_batch).  0 (default): off.  1 .. lag: every frame is deblurred from the next `ahead` input
  * frames before it is warped -- they are already held in device memory with their measured motions, and their sharpness was
  * computed on the device when they arrived, so the pass costs no latency, no second alignment and no host synchronisation.

@@ -86,6 +86,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("strength", C.c_int)]
 
 
+class FillBlendParams(C.Structure):
+    """vs_fill_blend_params: feather 0 (off) or 1 .. 6; match 0 or 1"""
+    _fields_ = [("feather", C.c_int), ("match", C.c_int)]
+
+
 class VsError(RuntimeError):
     pass
 
@@ -147,6 +152,9 @@ SIGNATURES = {
                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_fill_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32,
                                             _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_channel_sums_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "vs_bgr_image_warp_fill_blend_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _vp,
+                                                  C.POINTER(FillBlendParams), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_deblur_params_default": (None, [C.POINTER(DeblurParams)]),
     "vs_bgr_sharpness_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "vs_bgr_deblur_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeblurParams),
@@ -169,6 +177,8 @@ SIGNATURES = {
     "vs_stabilizer_get_select_mode": (_i32, [_vp]),
     "vs_stabilizer_set_border_fill": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_border_fill": (_i32, [_vp]),
+    "vs_stabilizer_set_fill_blend": (_i32, [_vp, C.POINTER(FillBlendParams)]),
+    "vs_stabilizer_get_fill_blend": (_i32, [_vp, C.POINTER(FillBlendParams)]),
     "vs_stabilizer_set_deblur": (_i32, [_vp, _i32, C.POINTER(DeblurParams)]),
     "vs_stabilizer_get_deblur": (_i32, [_vp]),
     "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, C.POINTER(DenoiseParams)]),
@@ -571,6 +581,59 @@ def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_C
     return np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
 
 
+def channel_sums_batch(src, fmt=None, src_stride=None):
+    """the per-channel sample sums of every frame (include/vs_amd.h: vs_bgr_channel_sums_batch).  src (n,h,w,3) numpy -> (n,3) uint64.
+    src_stride (elements): the call is made on pitched copies of the frames"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    buf = src.reshape(n, h, w * c) if ss == w * c else None
+    if buf is None:
+        buf = np.zeros((n, h, ss), src.dtype)
+        buf[:, :, :w * c] = src.reshape(n, h, w * c)
+    out = np.zeros((n, 3), np.uint64)
+    _check(lib().vs_bgr_channel_sums_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(out), MEM_HOST, None))
+    return out
+
+
+def channel_sums_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, sums_ptr, stream=None):
+    """device-resident form (any base address and pitch, in elements): enqueue only"""
+    _check(lib().vs_bgr_channel_sums_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(sums_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
+def bgr_image_warp_fill_blend_batch(src, cand_frame, cand_t, sums=None, feather=0, match=0, roi=None, border=BORDER_CONSTANT, max_value=None,
+                                    src_stride=None, dst_stride=None, guard=None):
+    """the fill with its seams blended (include/vs_amd.h: vs_bgr_image_warp_fill_blend_batch).  Arguments as bgr_image_warp_fill_batch;
+    sums (n_src,3) uint64 (None only with match == 0).  guard: a value the destination's padding is filled with first; the padded buffer
+    is returned as well, so that the caller can see that the padding was left alone"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    bits = 8 if src.dtype == np.uint8 else 16
+    if max_value is None:
+        max_value = 255 if bits == 8 else 65535
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    arr = (Transform * max(len(flat), 1))(*flat)
+    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
+    ss = w * c if src_stride is None else src_stride
+    ds = rw * c if dst_stride is None else dst_stride
+    if ss != w * c:
+        wide = np.zeros((n_src, h, ss), src.dtype)
+        wide[:, :, :w * c] = src.reshape(n_src, h, w * c)
+        src = wide
+    sm = _c(sums, np.uint64) if sums is not None else None
+    p = FillBlendParams(int(feather), int(match))
+    out = np.full((max(n_out, 1), rh, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_image_warp_fill_blend_batch(_p(src), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    arr, _p(sm) if sm is not None else None, C.byref(p), border, max_value, rx, ry, rw, rh, _p(out),
+                                                    rh * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
+    return (res, out) if guard is not None else res
+
+
 def deblur_params(**kw):
     p = DeblurParams()
     lib().vs_deblur_params_default(C.byref(p))
@@ -919,7 +982,8 @@ class Aligner:
 class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
-    def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, **params):
+    def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
+                 **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -928,6 +992,8 @@ class Stabilizer:
             self.set_select_mode(select_mode)
         if border_fill:
             self.set_border_fill(border_fill)
+        if fill_blend:
+            self.set_fill_blend(*fill_blend)
         if deblur:
             self.set_deblur(deblur, deblur_params)
         if denoise:
@@ -954,6 +1020,16 @@ class Stabilizer:
 
     def border_fill(self):
         return _check(lib().vs_stabilizer_get_border_fill(self.h))
+
+    def set_fill_blend(self, feather=0, match=0):
+        """the border fill's seam blend: feather 0 (off) or 1 .. 6, match 0 / 1 (exposure match); (0, 0): off (VS_WARP_BILINEAR_CV handles)"""
+        p = FillBlendParams(int(feather), int(match))
+        _check(lib().vs_stabilizer_set_fill_blend(self.h, C.byref(p)))
+
+    def fill_blend(self):
+        p = FillBlendParams()
+        _check(lib().vs_stabilizer_get_fill_blend(self.h, C.byref(p)))
+        return p.feather, p.match
 
     def set_select_mode(self, mode):
         """the selection rule of the stabilizer's aligner (SELECT_DEVICE by default, SELECT_STABLE, SELECT_STL_HOST)"""

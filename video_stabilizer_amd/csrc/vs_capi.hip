@@ -736,7 +736,9 @@ int vs_image_warp(const uint8_t* in, int w, int h, int stride, float A, float B,
 // Border fill behind the VS_WARP_BILINEAR_CV warp (vs_fill.hip): per output frame n_cand candidates, host arrays of n_frames * n_cand entries.
 // src[o * n_cand + c], c >= 1: the candidate's frame in device memory (w x h, rows of src_stride elements; null ends the list); entry c == 0 is
 // the frame itself and is not read.  t[o * n_cand + c]: its forward transform (entry 0 is what the frame is warped with).
-struct FillSpec { int n_cand; const void* const* src; const vs_transform* t; };
+// The blend (vs_fill.hip, THE BLEND RULE): feather / match as in vs_fill_blend_params; sums[o * n_cand + c] (match only): where the three channel
+// sums of that candidate's ORIGINAL frame lie in device memory (entry 0: the output frame's).  Both switches off: the fill as it always was.
+struct FillSpec { int n_cand; const void* const* src; const vs_transform* t; const uint64_t* const* sums = nullptr; int feather = 0, match = 0; };
 
 // roi = NULL: the whole w x h output.  Otherwise dst holds only the window (roi->w x roi->h pixels per frame).
 static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int channels,
@@ -801,14 +803,18 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
                 // pass 2 on the same stream: the candidates' matrices and frame pointers travel like the other per-frame parameters (small groups as
                 // kernel arguments of vs_k_param_block, larger ones as one upload of the ring); a group without a single candidate launches nothing
                 const int nc = fill->n_cand;
+                const bool blend = fill->feather > 0 || fill->match != 0;
                 fc.assign((size_t)nf * nc, vsk::FillCand{});
                 bool any = false;
                 for (int i = 0; i < nf; i++) {
                     vsk::FillCand* row = &fc[(size_t)i * nc];
                     memcpy(row[0].m, &Mv[(size_t)i * 6], 6 * sizeof(double));
+                    if (fill->match) row[0].reserved = (unsigned long long)(uintptr_t)fill->sums[(size_t)(f0 + i) * nc];
                     for (int c = 1; c < nc && fill->src[(size_t)(f0 + i) * nc + c]; c++) {
                         vs_cv_inverse_matrix(&fill->t[(size_t)(f0 + i) * nc + c], w, h, row[c].m);
                         row[c].src = fill->src[(size_t)(f0 + i) * nc + c];
+                        if (fill->match) row[c].reserved = (unsigned long long)(uintptr_t)fill->sums[(size_t)(f0 + i) * nc + c];
+                        else if (blend) row[c].reserved = vsk::fill_unit_gains();
                         any = true;
                     }
                 }
@@ -824,7 +830,11 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
                         VS_HIP(hipGetLastError());
                     } else
                         VS_TRY(ring->upload((const float*)fc.data(), slots, s, &fdev));
-                    VS_HIP(vsk::bgr_warp_cv_fill_c3((const vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, dp, dst_stride, nf, dst_fs, roi, s));
+                    if (blend)
+                        VS_HIP(vsk::bgr_warp_cv_fill_blend_c3((vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, fill->feather, fill->match != 0, dp, dst_stride,
+                                                              nf, dst_fs, roi, s));
+                    else
+                        VS_HIP(vsk::bgr_warp_cv_fill_c3((const vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, dp, dst_stride, nf, dst_fs, roi, s));
                     VS_TRY(ring->fence(fdev, s));
                 }
             }
@@ -888,6 +898,7 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_fs, int n_frames, in
                            dst_fs, dst_stride, false, mem, (hipStream_t)stream, &roi);
 } VS_CATCH_ALL
 
+static int deblur_format_ok(int format, int* bits);
 // the checks the fill adds to bgr_warp_common's own
 static int fill_args_ok(int w, int h, int channels, int n_cand) {
     VS_ARG(channels == 3 && n_cand >= 1 && n_cand <= 16);
@@ -896,25 +907,44 @@ static int fill_args_ok(int w, int h, int channels, int n_cand) {
     return VS_OK;
 }
 
+static int fill_blend_params_ok(const vs_fill_blend_params* params, vs_fill_blend_params* p) {
+    *p = params ? *params : vs_fill_blend_params{0, 0};
+    VS_ARG(p->feather >= 0 && p->feather <= 6 && (p->match == 0 || p->match == 1));
+    return VS_OK;
+}
+
+// cand_sums / blend: see FillSpec; blend == NULL or {0, 0}: the plain fill, launch for launch
 static int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
                               const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
-                              int dst_stride, hipStream_t s) {
+                              int dst_stride, hipStream_t s, const uint64_t* const* cand_sums = nullptr, const vs_fill_blend_params* blend = nullptr) {
     VS_ARG(cand_src && cand_t && n_out >= 1);
     VS_TRY(fill_args_ok(w, h, 3, n_cand));
+    vs_fill_blend_params bp;
+    VS_TRY(fill_blend_params_ok(blend, &bp));
+    if (bp.match) {                                      // every candidate that has a frame has its sums
+        VS_ARG(cand_sums);
+        for (int o = 0; o < n_out; o++) {
+            VS_ARG(cand_sums[(size_t)o * n_cand]);
+            for (int c = 1; c < n_cand && cand_src[(size_t)o * n_cand + c]; c++) VS_ARG(cand_sums[(size_t)o * n_cand + c]);
+        }
+    }
     std::vector<vs_transform> t0((size_t)n_out);
     for (int o = 0; o < n_out; o++) t0[o] = cand_t[(size_t)o * n_cand];
     const vsk::Roi roi{roi_x, roi_y, roi_w, roi_h};
-    const FillSpec fill{n_cand, cand_src, cand_t};
+    const FillSpec fill{n_cand, cand_src, cand_t, cand_sums, bp.feather, bp.match};
     return bgr_warp_common(src, src_fs, n_out, w, h, src_stride, 3, bits, t0.data(), VS_WARP_BILINEAR_CV, border, max_value, dst, dst_fs, dst_stride, false,
                            VS_MEM_DEVICE, s, &roi, &fill);
 }
 
-int vs_bgr_image_warp_fill_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int channels, int bits, int n_out, int n_cand,
+static int fill_batch_impl(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int channels, int bits, int n_out, int n_cand,
                                  const int32_t* cand_frame, const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w,
-                                 int roi_h, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+                                 int roi_h, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream, const uint64_t* sums, const vs_fill_blend_params* blend) {
     VS_DIMS(w, h);
     VS_ARG(src && dst && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && (bits == 8 || bits == 16));
     VS_TRY(fill_args_ok(w, h, channels, n_cand));
+    vs_fill_blend_params bp;
+    VS_TRY(fill_blend_params_ok(blend, &bp));
+    VS_ARG(sums || !bp.match);
     VS_ARG(roi_x >= 0 && roi_y >= 0 && roi_w >= 1 && roi_h >= 1 && roi_w <= w && roi_h <= h && roi_x <= w - roi_w && roi_y <= h - roi_h);
     VS_ARG(src_stride >= w * 3 && dst_stride >= roi_w * 3);
     VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
@@ -926,13 +956,17 @@ int vs_bgr_image_warp_fill_batch(const void* src, size_t src_fs, int n_src, int 
     if (!vsi::device_ready()) return VS_ERR_HIP;
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = (size_t)bits / 8;
-    Staged a, o;
+    Staged a, sm, o;
     VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    if (bp.match) VS_TRY(sm.in(sums, (size_t)n_src * 3 * sizeof(uint64_t), mem, s));
     VS_TRY(o.out_image(dst, (size_t)roi_w * 3 * esz, (size_t)roi_h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
     std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
+    std::vector<const uint64_t*> sptrs(bp.match ? (size_t)n_out * n_cand : 0, nullptr);
     for (int i = 0; i < n_out; i++)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
+        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++) {
             ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
+            if (bp.match) sptrs[(size_t)i * n_cand + c] = (const uint64_t*)sm.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * 3;
+        }
     // pass 1 warps runs of outputs whose own frames are consecutive in the batch as one launch each (n_cand == 1 with frames 0 .. n-1 is
     // vs_bgr_image_warp_roi_batch, launch for launch)
     for (int j = 0; j < n_out;) {
@@ -940,9 +974,42 @@ int vs_bgr_image_warp_fill_batch(const void* src, size_t src_fs, int n_src, int 
         while (e < n_out && cand_frame[(size_t)e * n_cand] == cand_frame[(size_t)(e - 1) * n_cand] + 1) e++;
         VS_TRY(bgr_warp_fill_ptrs(ptrs[(size_t)j * n_cand], src_fs, e - j, w, h, src_stride, bits, n_cand, &ptrs[(size_t)j * n_cand],
                                   &cand_t[(size_t)j * n_cand], border, max_value, roi_x, roi_y, roi_w, roi_h, (char*)o.dev + (size_t)j * dst_fs * esz,
-                                  dst_fs, dst_stride, s));
+                                  dst_fs, dst_stride, s, bp.match ? &sptrs[(size_t)j * n_cand] : nullptr, &bp));
         j = e;
     }
+    return vsi::finish_outputs(mem, s, {&o});
+}
+
+int vs_bgr_image_warp_fill_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int channels, int bits, int n_out, int n_cand,
+                                 const int32_t* cand_frame, const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w,
+                                 int roi_h, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+    return fill_batch_impl(src, src_fs, n_src, w, h, src_stride, channels, bits, n_out, n_cand, cand_frame, cand_t, border, max_value, roi_x, roi_y, roi_w, roi_h,
+                           dst, dst_fs, dst_stride, mem, stream, nullptr, nullptr);
+} VS_CATCH_ALL
+
+int vs_bgr_image_warp_fill_blend_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int channels, int bits, int n_out, int n_cand,
+                                       const int32_t* cand_frame, const vs_transform* cand_t, const uint64_t* sums, const vs_fill_blend_params* params,
+                                       int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs, int dst_stride,
+                                       int mem, void* stream) try {
+    VS_ARG(params);
+    return fill_batch_impl(src, src_fs, n_src, w, h, src_stride, channels, bits, n_out, n_cand, cand_frame, cand_t, border, max_value, roi_x, roi_y, roi_w, roi_h,
+                           dst, dst_fs, dst_stride, mem, stream, sums, params);
+} VS_CATCH_ALL
+
+int vs_bgr_channel_sums_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, uint64_t* sums, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deblur_format_ok(format, &bits));
+    VS_ARG(src && sums && n >= 1 && w >= 1 && h >= 1 && src_stride >= w * 3);
+    if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "channel sums: frames up to 32767 x 32767, as the border fill");
+    VS_ARG(n == 1 || src_fs >= img_span(w, h, src_stride, 3));
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    Staged a, o;
+    VS_TRY(a.in(src, ((size_t)(n - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(o.out(sums, (size_t)n * 3 * sizeof(uint64_t), mem));
+    VS_HIP(vsk::bgr_channel_sums(a.dev, w, h, src_stride, (int)esz * 8, o.as<unsigned long long>(), n, src_fs, s));
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
@@ -1195,7 +1262,7 @@ int vsi::bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, in
 
 int vsi::bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
                             const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
-                            int dst_stride, hipStream_t s) {
+                            int dst_stride, hipStream_t s, const uint64_t* const* cand_sums, const vs_fill_blend_params* blend) {
     return ::bgr_warp_fill_ptrs(src, src_fs, n_out, w, h, src_stride, bits, n_cand, cand_src, cand_t, border, max_value, roi_x, roi_y, roi_w, roi_h, dst,
-                                dst_fs, dst_stride, s);
+                                dst_fs, dst_stride, s, cand_sums, blend);
 }

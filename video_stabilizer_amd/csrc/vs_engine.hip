@@ -1361,6 +1361,8 @@ struct vs_stabilizer {
     std::deque<vs_transform> measurements;
     std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
     int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
+    vs_fill_blend_params fill_blend{0, 0};   // vs_stabilizer_set_fill_blend.  With match on, the three channel sums of every queued frame lie in device
+                                   // memory like the sharpness below: in blocks of the same pool, under the same reference protocol (Held::mb / sums)
     // deblur (vs_deblur.hip): the sharpness of every queued frame lies in device memory, one value per frame in a block taken per call; a block is
     // free again when no queued frame and no launch in flight refers to it (refs; sharp_pending: references given up, counted down at the next point
     // where every reader has been ordered before whatever may refill the block)
@@ -1373,7 +1375,8 @@ struct vs_stabilizer {
     int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
     vs_denoise_params denoise_params{24};
     void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
-    struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
+    struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
+                  SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
     std::vector<void*> pool;       // recycled frame buffers
     size_t frame_bytes = 0;
@@ -1408,7 +1411,9 @@ struct vs_stabilizer {
 
 static void sharp_unhold(vs_stabilizer* s, vs_stabilizer::Held& f) {
     if (f.sb) s->sharp_pending.push_back(f.sb);
+    if (f.mb) s->sharp_pending.push_back(f.mb);
     f.sb = nullptr; f.sharp = nullptr;
+    f.mb = nullptr; f.sums = nullptr;
 }
 static void sharp_settle(vs_stabilizer* s) {
     for (auto* b : s->sharp_pending) --b->refs;
@@ -1611,7 +1616,7 @@ static int stab_run(vs_stabilizer* s, const void* frames, size_t frame_stride, i
         // (everything is quiet now: the sharpness blocks are referred to by what is still queued, if anything, and by nothing else)
         s->sharp_pending.clear();
         for (auto* b : s->sharp_blocks) b->refs = 0;
-        for (auto& f : s->frames) if (f.sb) ++f.sb->refs;
+        for (auto& f : s->frames) { if (f.sb) ++f.sb->refs; if (f.mb) ++f.mb->refs; }
         set_error(r, "%s", why.c_str());
     }
     return r;
@@ -1754,19 +1759,22 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     const bool warps_apart = s->overlap_warps && out_mem != VS_MEM_HOST;      // the warps of this call go to warp_stream
     if (!s->overlap_warps) sharp_settle(s);
     vs_stabilizer::SharpBlock* sblk = nullptr;
+    // an idle block of at least `need` values, or a new one (`keep`: a block taken earlier in this call, still without references)
+    auto take_block = [&](size_t need, vs_stabilizer::SharpBlock* keep, vs_stabilizer::SharpBlock** out) -> int {
+        for (auto* b : s->sharp_blocks) if (b != keep && b->refs == 0 && b->cap >= need) { *out = b; return VS_OK; }
+        for (auto it = s->sharp_blocks.begin(); it != s->sharp_blocks.end();)           // idle blocks that are too small make room
+            if (*it != keep && (*it)->refs == 0) { (void)hipFree((*it)->dev); delete *it; it = s->sharp_blocks.erase(it); } else ++it;
+        void* q = nullptr;
+        VS_HIP(vsi::dev_alloc(&q, need * sizeof(unsigned long long)));
+        s->sharp_blocks.reserve(s->sharp_blocks.size() + 1);
+        *out = new vs_stabilizer::SharpBlock{(unsigned long long*)q, need, 0};
+        s->sharp_blocks.push_back(*out);
+        return VS_OK;
+    };
     if (ndb > 0) {
         size_t need = (size_t)n;
         for (auto& f : s->frames) if (!f.sb) need++;
-        for (auto* b : s->sharp_blocks) if (b->refs == 0 && b->cap >= need) { sblk = b; break; }
-        if (!sblk) {
-            for (auto it = s->sharp_blocks.begin(); it != s->sharp_blocks.end();)           // idle blocks that are too small make room
-                if ((*it)->refs == 0) { (void)hipFree((*it)->dev); delete *it; it = s->sharp_blocks.erase(it); } else ++it;
-            void* q = nullptr;
-            VS_HIP(vsi::dev_alloc(&q, need * sizeof(unsigned long long)));
-            s->sharp_blocks.reserve(s->sharp_blocks.size() + 1);
-            sblk = new vs_stabilizer::SharpBlock{(unsigned long long*)q, need, 0};
-            s->sharp_blocks.push_back(sblk);
-        }
+        VS_TRY(take_block(need, nullptr, &sblk));
         VS_HIP(vsk::bgr_sharpness(dense, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev, n, (size_t)w * h * 3, st));
         size_t k = (size_t)n;
         for (auto& f : s->frames) {
@@ -1774,10 +1782,29 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             VS_HIP(vsk::bgr_sharpness(f.ptr, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev + k, 1, 0, st));
             f.sb = sblk; f.sharp = sblk->dev + k; ++sblk->refs; k++;
         }
-        if (warps_apart) {                                  // the deblur pass reads the values on warp_stream
-            VS_HIP(hipEventRecord(s->warp_ev, st));
-            VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
+    }
+    // fill blend with exposure match (vs_fill.hip): the three channel sums of the call's frames likewise -- one launch, a block of their own, the
+    // values stay on the device.  (Queued frames that arrived while the match was off are summed here too, once: switching on mid-clip gives
+    // what a handle that had it from the first frame gives.)
+    const int nfill = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, s->params.lag) : 0;
+    const bool blend_on = nfill > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
+    const bool want_sums = nfill > 0 && s->fill_blend.match != 0;
+    vs_stabilizer::SharpBlock* mblk = nullptr;
+    if (want_sums) {
+        size_t need = (size_t)n;
+        for (auto& f : s->frames) if (!f.mb) need++;
+        VS_TRY(take_block(3 * need, sblk, &mblk));
+        VS_HIP(vsk::bgr_channel_sums(dense, w, h, w * 3, (int)esz * 8, mblk->dev, n, (size_t)w * h * 3, st));
+        size_t k = (size_t)n;
+        for (auto& f : s->frames) {
+            if (f.mb) continue;
+            VS_HIP(vsk::bgr_channel_sums(f.ptr, w, h, w * 3, (int)esz * 8, mblk->dev + 3 * k, 1, 0, st));
+            f.mb = mblk; f.sums = mblk->dev + 3 * k; ++mblk->refs; k++;
         }
+    }
+    if ((ndb > 0 || want_sums) && warps_apart) {            // the deblur pass / the fill's gain kernel read the values on warp_stream
+        VS_HIP(hipEventRecord(s->warp_ev, st));
+        VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
     }
 
     // stabilizer.cpp:18-19 for all n frames.  In a chunked device-resident batch (stab_run) the alignment of the NEXT chunk is
@@ -1810,9 +1837,9 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     struct Job { const void* src; vs_transform sampling; int i; void* release; };
     std::vector<Job> jobs;
     // border fill (vs_fill.hip): per job 1 + nfill candidates -- the frame itself, then the frames that follow it in the queue
-    const int nfill = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, s->params.lag) : 0;
     std::vector<const void*> cand_src;
     std::vector<vs_transform> cand_t;
+    std::vector<const uint64_t*> cand_sums;        // (exposure match only) where each candidate's channel sums lie: the ORIGINAL frames' throughout
     // deblur: per job 1 + ndb candidates likewise, with where each frame's sharpness lies
     std::vector<const void*> db_src;
     std::vector<const uint64_t*> db_sharp;
@@ -1824,8 +1851,10 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
-        s->frames.push_back(vs_stabilizer::Held{(void*)(dense + (size_t)i * fbytes), false, sblk, sblk ? sblk->dev + i : nullptr});
+        s->frames.push_back(vs_stabilizer::Held{(void*)(dense + (size_t)i * fbytes), false, sblk, sblk ? sblk->dev + i : nullptr, mblk,
+                                                mblk ? mblk->dev + 3 * (size_t)i : nullptr});
         if (sblk) ++sblk->refs;
+        if (mblk) ++mblk->refs;
         const vs_transform meas = t_buf[i];
         const bool success = st_buf[i] == 1;
         s->last_meas = meas; s->last_success = success ? 1 : 0;
@@ -1865,6 +1894,7 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 vs_stabilizer::Held src = s->frames.front();
                 s->frames.pop_front();
                 if (src.sb) s->sharp_pending.push_back(src.sb);   // (the jobs' launches below still read it: counted down after them)
+                if (src.mb) s->sharp_pending.push_back(src.mb);
                 // :97-99: warpBySimilarityTransform(frame, accum^-1); cv::warpAffine without WARP_INVERSE_MAP
                 // inverts the matrix it is given (imgproc.cpp:472), so the sampling map is (accum^-1)^-1.
                 // (VS_WARP_BILINEAR_CV is cv::warpAffine itself, inversion included: it takes the correction as the reference hands it over)
@@ -1878,6 +1908,7 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                     // failed ends the list.  (The frames are read before their own jobs release them: releases follow all launches, below.)
                     cand_src.push_back(src.ptr);
                     cand_t.push_back(correction);
+                    if (want_sums) cand_sums.push_back((const uint64_t*)src.sums);
                     vs_transform chain{0, 0, 0, 0};
                     const size_t avail = std::min(s->frames.size(), s->measurements.size());
                     int c = 0;
@@ -1886,8 +1917,12 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                         const vs_transform back = vs_transform_inverse(&chain);
                         cand_src.push_back(s->frames[c].ptr);
                         cand_t.push_back(vs_transform_compose(&back, &correction));
+                        if (want_sums) cand_sums.push_back((const uint64_t*)s->frames[c].sums);
                     }
-                    for (; c < nfill; c++) { cand_src.push_back(nullptr); cand_t.push_back(vs_transform{0, 0, 0, 0}); }
+                    for (; c < nfill; c++) {
+                        cand_src.push_back(nullptr); cand_t.push_back(vs_transform{0, 0, 0, 0});
+                        if (want_sums) cand_sums.push_back(nullptr);
+                    }
                 }
                 if (ndb > 0) {
                     // the same chain without the correction: frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j)
@@ -1995,7 +2030,7 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
                 wr = vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, (int)esz * 8, 1 + nfill, &cand_src[j * (1 + nfill)],
                                              &cand_t[j * (1 + nfill)], s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh, dst, dst_fs,
-                                             ow * 3, ws);
+                                             ow * 3, ws, want_sums ? &cand_sums[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr);
             else
                 wr = vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, (int)esz * 8, ts.data(),
                                                  s->params.warp_mode, s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh,
@@ -2106,6 +2141,19 @@ int vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead) try {
 int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
     VS_ARG(s);
     return s->border_fill;
+} VS_CATCH_ALL
+int vs_stabilizer_set_fill_blend(vs_stabilizer* s, const vs_fill_blend_params* params) try {
+    VS_ARG(s);
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "fill blend: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    const vs_fill_blend_params p = params ? *params : vs_fill_blend_params{0, 0};
+    VS_ARG(p.feather >= 0 && p.feather <= 6 && (p.match == 0 || p.match == 1));
+    s->fill_blend = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* params) try {
+    VS_ARG(s && params);
+    *params = s->fill_blend;
+    return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);

@@ -16,7 +16,8 @@
 //     (sum + 512) >> 10; 16-bit: float weights a b / 1024, cvRound, saturated to max_value).  A candidate without a frame ends the list.  If
 //     no candidate covers the pixel it keeps candidate 0's ordinary result under `border`.
 //   * Hence the pixels candidate 0 covers are exactly the plain warp's output, and n_cand == 1 IS the plain warp.  No blending, no
-//     feathering, no photometric matching.
+//     feathering, no photometric matching here: those are the two switches of THE BLEND RULE below (vs_k_bgr_warp_cv_fill_blend_c3), off by
+//     default; with both off this kernel serves the call as it always did.
 //
 // TWO PASSES.  Pass 1 is the existing warp launch for candidate 0 (vs_warp.hip, untouched).  Pass 2 is the kernel below, on the same stream,
 // over the output of all frames of the run.  X(x, y) is a term monotone in x plus a term monotone in y, so a rectangle of output pixels is
@@ -148,6 +149,192 @@ __global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_c3(const 
     }
 }
 
+
+// ---- THE BLEND RULE (also include/vs_amd.h, vs_bgr_image_warp_fill_blend_batch; DESIGN.md "Fill blend") ----------------------------------
+// Two independent switches on the fill, exact integer rules.  Candidates, coverage, the int32 positions X, Y (5 fraction bits) and the sample
+// q_c of a covering candidate are the fill's above.
+//   * CHANNEL SUMS.  S_i,c = the sum of the raw samples of channel c over all w x h pixels of frame i, uint64 (no clamp to the format's
+//     maximum; <= 65535 * 32767^2 < 2^46; integers: the order of the reduction cannot matter).
+//   * GAIN (match == 1) of candidate j >= 1 for output frame k (candidate 0's frame), per channel, Q15, unsigned 64-bit, floor division:
+//       G = 32768                                                        if S_j,c == 0 or S_k,c == 0
+//       G = clamp((2 * 32768 * S_k,c + S_j,c) / (2 * S_j,c), 16384, 65536)   otherwise          (every term < 2^63)
+//     With match == 0, G = 32768.
+//   * MATCHED FILL SAMPLE of the first candidate j >= 1 that covers the pixel: f_c = min((q_c * G + 16384) >> 15, max_value), unsigned 32-bit
+//     (65535 * 65536 + 16384 < 2^32).  G = 32768 passes q_c through unchanged.
+//   * UNCOVERED PIXEL (candidate 0 does not cover it): f_c if a later candidate covers it; else candidate 0's result under `border`, as ever.
+//   * BAND PIXEL (feather >= 1): K = 32 << feather, Xmax = (w - 1) * 32 - 1, Ymax = (h - 1) * 32 - 1.  A pixel candidate 0 covers has
+//     0 <= X <= Xmax, 0 <= Y <= Ymax; d = min(X, Xmax - X, Y, Ymax - Y), k = d + 1.  If k >= K or no later candidate covers the pixel it is the
+//     plain warp's value p_c bit for bit; otherwise out_c = (k * p_c + (K - k) * f_c + K / 2) >> (5 + feather)  (< 2^27: unsigned 32-bit).
+//   * Hence (a) feather == 0 && match == 0 is the fill above bit for bit; (b) n_cand == 1 or a list without a later candidate is the plain ROI
+//     warp; (c) a band pixel lies between min(p_c, f_c) and max(p_c, f_c); (d) identical frames under identity maps come back bit for bit with
+//     any setting; (e) a pixel at least 2^feather source pixels inside candidate 0's frame is never changed.
+//
+// PASSES.  Pass 1 is the warp launch for candidate 0, as in the fill.  With match on, vs_k_fill_gains (one thread per output frame) turns the two
+// sum pointers of every candidate entry into three Q15 gains of 17 bits, packed into the entry's eight reserved bytes: the host never sees a
+// sum.  Pass 2 is vs_k_bgr_warp_cv_fill_blend_c3, one launch over all frames of the run on the same stream: the fill kernel's block / strip walk with
+// the test "candidate 0 covers the rectangle" replaced by "DEEP INSIDE": all four corner positions have d >= K - 1 (X is a term monotone in x plus
+// a term monotone in y, so the corners bound the rectangle; the same 2^29 guard on the table terms).  A band lane reads pass 1's value back from
+// dst (written on this stream before the launch) and blends; the gains are scalar loads, wave-uniform per candidate.  No LDS, no barrier.
+
+constexpr int CS_ROWS = 16, CS_WAVES = 4;                  // channel sums: a wave sums 16 rows of its 64 lanes' pixel groups
+constexpr unsigned long long kUnitGains = 32768ull | (32768ull << 17) | (32768ull << 34);
+
+// out[3 * frame + c] (zeroed by the launcher on the same stream) += this wave's share of S_c.  X4: a lane owns the 12 bytes of four (u8) or two
+// (u16) consecutive pixels and reads them as three dwords (every row starts on a dword); the pixels behind the row's last whole group, and every
+// pixel of the other variant, are read sample by sample.
+template <typename T, bool X4>
+__global__ __launch_bounds__(64 * CS_WAVES) void vs_k_bgr_channel_sums(const T* __restrict__ src, int w, int h, int src_stride, size_t src_fs,
+                                                                       unsigned long long* __restrict__ out, int tiles_x) {
+    constexpr int G = X4 ? 12 / (3 * (int)sizeof(T)) : 1;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int tyi = (int)blockIdx.x / tiles_x, txi = (int)blockIdx.x - tyi * tiles_x;
+    const int y0 = (tyi * CS_WAVES + wv) * CS_ROWS;
+    if (y0 >= h) return;                                                  // wave-uniform
+    const int y1 = min(y0 + CS_ROWS, h);
+    const int x = (txi * 64 + lane) * G;                                  // this lane's first pixel
+    const T* const frame = src + (size_t)blockIdx.y * src_fs;
+    const long long extent = (long long)(h - 1) * src_stride + 3LL * w;   // elements of a frame
+    (void)extent;
+    uint32_t a[3] = {0u, 0u, 0u};                                         // <= 16 rows * 4 * 255 or 16 * 2 * 65535
+    for (int y = y0; y < y1; y++) {
+        const size_t ro = (size_t)y * (size_t)src_stride + (size_t)x * 3;
+        if (X4 && x + G <= w) {
+            const uint32_t* const q = (const uint32_t*)(frame + VS_IDX(ro, extent - (3 * G - 1), 526));
+            const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
+            if (sizeof(T) == 1) {                                          // B G R B | G R B G | R B G R
+                a[0] += (d0 & 255u) + (d0 >> 24) + ((d1 >> 16) & 255u) + ((d2 >> 8) & 255u);
+                a[1] += ((d0 >> 8) & 255u) + (d1 & 255u) + (d1 >> 24) + ((d2 >> 16) & 255u);
+                a[2] += ((d0 >> 16) & 255u) + ((d1 >> 8) & 255u) + (d2 & 255u) + (d2 >> 24);
+            } else {                                                       // B G | R B | G R
+                a[0] += (d0 & 65535u) + (d1 >> 16);
+                a[1] += (d0 >> 16) + (d2 & 65535u);
+                a[2] += (d1 & 65535u) + (d2 >> 16);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < G; i++)
+                if (x + i < w) {
+                    const T* const px = frame + VS_IDX(ro + 3 * i, extent - 2, 527);
+                    a[0] += px[0]; a[1] += px[1]; a[2] += px[2];
+                }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {                                          // a wave's share is below 2^32: 64 lanes * 2^21
+        uint32_t sum = a[c];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+        if (lane == 0 && sum != 0) atomicAdd(out + 3 * (size_t)blockIdx.y + c, (unsigned long long)sum);
+    }
+}
+
+// Q15 gain of a candidate with sums sj for an output frame with sums sk (the rule above)
+__device__ __forceinline__ unsigned long long fill_gain_q15(unsigned long long sk, unsigned long long sj) {
+    if (sk == 0 || sj == 0) return 32768ull;
+    const unsigned long long g = (2ull * 32768ull * sk + sj) / (2ull * sj);
+    return min(max(g, 16384ull), 65536ull);
+}
+// every candidate entry c >= 1 of output frame o arrives with reserved = where its frame's three sums lie, entry 0 with where the output frame's
+// lie; the entries c >= 1 leave with their three gains packed (17 bits each)
+__global__ __launch_bounds__(64) void vs_k_fill_gains(vsk::FillCand* __restrict__ cands, int n_cand, int n_out) {
+    const int o = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (o >= n_out) return;
+    cands += (size_t)o * (size_t)n_cand;
+    const unsigned long long* const sk = (const unsigned long long*)(uintptr_t)cands[0].reserved;
+    for (int c = 1; c < n_cand; c++) {
+        if (!cands[c].src) break;
+        const unsigned long long* const sj = (const unsigned long long*)(uintptr_t)cands[c].reserved;
+        cands[c].reserved = fill_gain_q15(sk[0], sj[0]) | (fill_gain_q15(sk[1], sj[1]) << 17) | (fill_gain_q15(sk[2], sj[2]) << 34);
+    }
+}
+
+// candidate 0 (matrix M) has d >= m at every pixel of the nx x ny rectangle at (x0, y0) of the output window; m == 0: it covers every pixel
+// (cv_covers_rect: X >= 0 and X <= Xmax is sx >= 0 and sx + 1 <= w - 1).  Same guard on the table terms.
+__device__ __forceinline__ bool cv_deep_rect(const double M[6], vsk::Roi roi, int x0, int y0, int nx, int ny, int w, int h, int m) {
+    const int fxA = x0 + roi.x, fxB = x0 + nx - 1 + roi.x, fyA = y0 + roi.y, fyB = y0 + ny - 1 + roi.y;
+    const int adA = cv_delta(M[0], fxA), adB = cv_delta(M[0], fxB), bdA = cv_delta(M[3], fxA), bdB = cv_delta(M[3], fxB);
+    const int XA = cv_row_origin(M[1], M[2], fyA), XB = cv_row_origin(M[1], M[2], fyB);
+    const int YA = cv_row_origin(M[4], M[5], fyA), YB = cv_row_origin(M[4], M[5], fyB);
+    const int lim = 1 << 29;
+    const int lo = min(min(min(adA, adB), min(bdA, bdB)), min(min(XA, XB), min(YA, YB)));
+    const int hi = max(max(max(adA, adB), max(bdA, bdB)), max(max(XA, XB), max(YA, YB)));
+    const bool small = lo > -lim && hi < lim;
+    const int mnX = min(XA, XB) + min(adA, adB), mxX = max(XA, XB) + max(adA, adB);
+    const int mnY = min(YA, YB) + min(bdA, bdB), mxY = max(YA, YB) + max(bdA, bdB);
+    const int Xmax = (w - 1) * 32 - 1, Ymax = (h - 1) * 32 - 1;
+    return small && (mnX >> 5) >= m && (mxX >> 5) <= Xmax - m && (mnY >> 5) >= m && (mxY >> 5) <= Ymax - m;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_blend_c3(const vsk::FillCand* __restrict__ cands, int n_cand, int w, int h,
+                                                                              int src_stride, int maxv, int feather, T* __restrict__ dst,
+                                                                              int dst_stride, size_t dst_fs, vsk::Roi roi, int blocks_x) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int byi = (int)blockIdx.x / blocks_x, bxi = (int)blockIdx.x - byi * blocks_x;
+    const int bx0 = bxi * FL_BLOCK, by0 = byi * FL_BLOCK;
+    cands += (size_t)blockIdx.y * (size_t)n_cand;
+    dst += (size_t)blockIdx.y * dst_fs;
+    const int K = 32 << feather, margin = feather > 0 ? K - 1 : 0;         // feather == 0: K = 32 = k of every covered pixel, no band
+    const int Xmax = (w - 1) * 32 - 1, Ymax = (h - 1) * 32 - 1;
+    double M[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) M[k] = cands[0].m[k];
+    if (cv_deep_rect(M, roi, bx0, by0, min(FL_BLOCK, roi.w - bx0), min(FL_BLOCK, roi.h - by0), w, h, margin)) return;       // uniform
+#pragma unroll 1
+    for (int t = 0; t < (FL_BLOCK / FL_W) * (FL_BLOCK / (FL_ROWS * FL_WAVES)); t++) {
+        const int x0 = bx0 + (t % (FL_BLOCK / FL_W)) * FL_W, y0 = by0 + ((t / (FL_BLOCK / FL_W)) * FL_WAVES + wv) * FL_ROWS;     // this wave's strip
+        if (x0 >= roi.w || y0 >= roi.h) continue;                          // wave-uniform
+        const int nx = min(FL_W, roi.w - x0), ny = min(FL_ROWS, roi.h - y0);
+        if (cv_deep_rect(M, roi, x0, y0, nx, ny, w, h, margin)) continue;  // wave-uniform
+        const int x = x0 + lane;
+        const bool lane_in = lane < nx;
+        const int fx = min(x, roi.w - 1) + roi.x;
+        const int ad0 = cv_delta(M[0], fx), bd0 = cv_delta(M[3], fx);
+#pragma unroll 1
+        for (int r = 0; r < ny; r++) {
+            const int y = y0 + r, fy = y + roi.y;
+            const CvPos p0 = cv_pos(cv_row_origin(M[1], M[2], fy), cv_row_origin(M[4], M[5], fy), ad0, bd0);
+            const bool cov0 = cv_covers(p0, w, h);
+            // the plain value's weight k of a pixel candidate 0 covers (K: outside the band)
+            const int kk = cov0 && feather > 0 ? min(min(min(p0.X, Xmax - p0.X), min(p0.Y, Ymax - p0.Y)) + 1, K) : K;
+            bool open = lane_in && (!cov0 || kk < K);
+            T* const px = dst + (size_t)y * (size_t)dst_stride + (size_t)x * 3;
+#pragma unroll 1
+            for (int c = 1; c < n_cand; c++) {               // wave-uniform: the candidate's entry is read with scalar loads
+                if (__builtin_amdgcn_ballot_w64(open) == 0) break;
+                const T* const cs = (const T*)cands[c].src;
+                if (!cs) break;
+                double C[6];
+#pragma unroll
+                for (int k = 0; k < 6; k++) C[k] = cands[c].m[k];
+                const unsigned long long gains = cands[c].reserved;
+                const CvPos p = cv_pos(cv_row_origin(C[1], C[2], fy), cv_row_origin(C[4], C[5], fy), cv_delta(C[0], fx), cv_delta(C[3], fx));
+                if (open && cv_covers(p, w, h)) {
+                    T q[3];
+#ifdef VS_DEBUG_BOUNDS
+                    // the bounds build (vs_device.hpp), sites 523 / 524 / 525: the taps as in the fill kernel; the read-back and the store's last
+                    // sample lie inside the output window
+                    const bool taps_in = vsd::bounds_ok((long long)(p.Y >> 5) * src_stride + 3LL * (p.X >> 5) + src_stride + 5, (long long)(h - 1) * src_stride + 3LL * w, 523);
+                    cv_sample_inside(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, q);
+                    if (!vsd::bounds_ok((long long)y * dst_stride + 3LL * x + 2, (long long)(roi.h - 1) * dst_stride + 3LL * roi.w, cov0 ? 524 : 525)) continue;
+#else
+                    cv_sample_inside(cs, src_stride, p, maxv, q);
+#endif
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        const uint32_t G = (uint32_t)(gains >> (17 * ch)) & 0x1ffffu;
+                        uint32_t f = min(((uint32_t)q[ch] * G + 16384u) >> 15, (uint32_t)maxv);
+                        if (cov0) f = ((uint32_t)kk * (uint32_t)px[ch] + (uint32_t)(K - kk) * f + (uint32_t)(K >> 1)) >> (5 + feather);
+                        q[ch] = (T)f;
+                    }
+                    px[0] = q[0]; px[1] = q[1]; px[2] = q[2];
+                    open = false;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 VS_BOUNDS_TU(vs_bounds_fetch_fill)
@@ -169,6 +356,54 @@ hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_c3<uint16_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, (uint16_t*)dp, dst_stride, dst_fs, roi, blocks_x);
         else
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_c3<uint8_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, (uint8_t*)dp, dst_stride, dst_fs, roi, blocks_x);
+    }
+    return hipGetLastError();
+}
+
+unsigned long long fill_unit_gains() { return kUnitGains; }
+
+hipError_t bgr_channel_sums(const void* src, int w, int h, int src_stride, int bits, unsigned long long* out, int n_frames, size_t src_fs, hipStream_t s) {
+    if ((bits != 8 && bits != 16) || w < 1 || h < 1 || w > 32767 || h > 32767 || n_frames < 1) return hipErrorNotSupported;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)n_frames * 3 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const size_t esz = (size_t)bits / 8;
+    // dword loads where every row of every frame starts on a dword
+    const bool x4 = (((uintptr_t)src | ((size_t)src_stride * esz) | (n_frames > 1 ? src_fs * esz : 0)) & 3) == 0;
+    const int g = x4 ? (bits == 16 ? 2 : 4) : 1;
+    const int tiles_x = (w + 64 * g - 1) / (64 * g), tiles_y = (h + CS_ROWS * CS_WAVES - 1) / (CS_ROWS * CS_WAVES);
+    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
+        const int nf = std::min(n_frames - f0, 65535);
+        const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * CS_WAVES);
+        const char* sp = (const char*)src + (size_t)f0 * src_fs * esz;
+        unsigned long long* op = out + (size_t)f0 * 3;
+        if (x4 && bits == 16)
+            hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint16_t, true>), grid, block, 0, s, (const uint16_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
+        else if (x4)
+            hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint8_t, true>), grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
+        else if (bits == 16)
+            hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint16_t, false>), grid, block, 0, s, (const uint16_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
+        else
+            hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint8_t, false>), grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
+    }
+    return hipGetLastError();
+}
+
+hipError_t bgr_warp_cv_fill_blend_c3(FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, int feather, bool match, void* dst,
+                                     int dst_stride, int n_frames, size_t dst_fs, Roi roi, hipStream_t s) {
+    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (w > 32767 || h > 32767 || n_cand < 1 || feather < 0 || feather > 6) return hipErrorNotSupported;
+    if (match) hipLaunchKernelGGL(vs_k_fill_gains, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), 0, s, cands_dev, n_cand, n_frames);
+    const int blocks_x = (roi.w + FL_BLOCK - 1) / FL_BLOCK, blocks_y = (roi.h + FL_BLOCK - 1) / FL_BLOCK;
+    const size_t esz = (size_t)bits / 8;
+    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
+        const int nf = std::min(n_frames - f0, 65535);
+        const dim3 grid((unsigned)(blocks_x * blocks_y), (unsigned)nf), block(64 * FL_WAVES);
+        const FillCand* cp = cands_dev + (size_t)f0 * (size_t)n_cand;
+        char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
+        if (bits == 16)
+            hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_blend_c3<uint16_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, feather, (uint16_t*)dp, dst_stride, dst_fs, roi, blocks_x);
+        else
+            hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_blend_c3<uint8_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, feather, (uint8_t*)dp, dst_stride, dst_fs, roi, blocks_x);
     }
     return hipGetLastError();
 }

@@ -112,10 +112,11 @@ int finish_outputs(int mem, hipStream_t s, std::initializer_list<Staged*> outs);
 // VS_WARP_BILINEAR_CV with border fill (the rule: vs_fill.hip) on device-resident frames; vs_bgr_image_warp_fill_batch is the index-based wrapper over
 // it.  Output frame o = frame o of the batch at `src` warped by cand_t[o * n_cand]; its uncovered pixels come from candidates c = 1 .. n_cand-1:
 // the frame at cand_src[o * n_cand + c] (any device pointer, w x h, rows of src_stride elements; null ends the list; entry c == 0 is not read)
-// under cand_t[o * n_cand + c].  Host arrays; enqueue only.
+// under cand_t[o * n_cand + c].  Host arrays; enqueue only.  blend (NULL or {0, 0}: off, the plain fill launch for launch): the blend rule's two
+// switches; with match, cand_sums[o * n_cand + c] is where the three channel sums of that candidate's original frame lie in device memory.
 int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
                        const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
-                       int dst_stride, hipStream_t s);
+                       int dst_stride, hipStream_t s, const uint64_t* const* cand_sums = nullptr, const vs_fill_blend_params* blend = nullptr);
 
 // The deblur pass (the rule: vs_deblur.hip) on device-resident frames; vs_bgr_deblur_batch is the index-based wrapper over it.  Output frame o
 // = the frame at cand_src[o * n_cand] blended with its candidates c = 1 .. n_cand-1: the frame at cand_src[o * n_cand + c] (any device pointer,

@@ -72,6 +72,14 @@ hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bit
 struct FillCand { double m[6]; const void* src; unsigned long long reserved; };      // 64 bytes = four float4 slots of the parameter ring
 hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, void* dst, int dst_stride,
                                int n_frames, size_t dst_fs, Roi roi, hipStream_t s);
+// The fill with its seams blended (vs_fill.hip, THE BLEND RULE): feather 0 .. 6, match: gain matching from whole-frame channel sums.  With match
+// every entry arrives with `reserved` = where the three sums of its frame lie in device memory (entry 0: the output frame's) and a small kernel in
+// front turns them into packed Q15 gains; without it the entries c >= 1 carry fill_unit_gains().  cands_dev is written (the gains), so it is
+// not const.  bgr_channel_sums: out[3 i + c] (device) = the sum of channel c's samples of frame i; zeroes `out` on `s` first.
+unsigned long long fill_unit_gains();
+hipError_t bgr_channel_sums(const void* src, int w, int h, int src_stride, int bits, unsigned long long* out, int n_frames, size_t src_fs, hipStream_t s);
+hipError_t bgr_warp_cv_fill_blend_c3(FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, int feather, bool match, void* dst,
+                                     int dst_stride, int n_frames, size_t dst_fs, Roi roi, hipStream_t s);
 // Deblur by transfer from sharper frames (vs_deblur.hip: the rule and the kernels).
 // bgr_sharpness: out[i] (device, n_frames x uint64) = the gradient energy S of frame i; zeroes `out` on `s` first.
 // bgr_deblur: cands_dev = n_frames x n_cand entries in device memory; entry 0 of a frame is the target (frame and sharpness; matrix not read), a
