@@ -351,6 +351,50 @@ int vs_bgr_denoise_batch(const void* src, size_t src_frame_stride, int n_src, in
                          int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
                          const vs_denoise_params* params /* NULL = defaults */,
                          void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* DEFLICKER: a frame's exposure is pulled to the average exposure of a window of frames, the exposure ratio of two frames being measured
+ * at the same scene points through their measured motions (a pan changes a whole-frame sum because the content changes).  Interleaved
+ * BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as in the fill); s = bits - 8.  The rule:
+ *   - Candidates: output frame o has n_cand (1 .. 16) candidates (cand_frame, cand_t), exactly as in vs_bgr_denoise_batch.  Candidate 0
+ *     is the target frame k itself and its transform is ignored; a negative index ends the list; cand_t is in VS_WARP_BILINEAR_CV's
+ *     forward convention.
+ *   - Lattice: step is 1 .. 64 (default 4); lattice pixels are those with x % step == 0 && y % step == 0;
+ *     L = ceil(w / step) * ceil(h / step).
+ *   - Pair statistics of candidate j >= 1: with M = vs_cv_inverse_matrix(cand_t) lattice pixel (x, y) lies in candidate j at
+ *     qx = rint((M0 x + M1 y) + M2), qy = rint((M3 x + M4 y) + M5) (doubles, that order, no fma, ties to even: the deblur's
+ *     nearest-sample position).  The pair counts iff qx, qy are finite, 0 <= qx <= w-1, 0 <= qy <= h-1 and every one of the six samples
+ *     v (three of p = the target at (x, y), three of q = the candidate at (qx, qy)) has 0 < (v >> s) < 255: neither black nor clipped
+ *     at 8-bit precision, which also rejects samples above the format's maximum.  Per candidate seven uint64_t: count, a_c = sum p_c,
+ *     b_c = sum q_c (count < 2^30, sums < 2^46; integer sums, so the order of the reduction cannot matter).  A NaN or infinite map
+ *     counts nothing.
+ *   - Gains of output frame o, unsigned 64-bit with floor division: candidate j is USED iff count_j >= max(1, L / 16) (then every
+ *     a_j,c >= count_j > 0);  r_j,c = clamp((2 * 32768 * b_j,c + a_j,c) / (2 * a_j,c), 16384, 65536)  (every term below 2^63);  with m
+ *     used candidates  G_c = (2 * (32768 + sum_j r_j,c) + (1 + m)) / (2 * (1 + m)):  the rounded mean of the window's exposures
+ *     relative to k, with k itself included as 32768.  (Caller-made statistics with a_j,c == 0 under a used count, which the
+ *     statistics call cannot produce, give r_j,c = 32768.)
+ *   - Applied sample: min((v * G_c + 16384) >> 15, max_value) in unsigned 32-bit (65535 * 65536 + 16384 < 2^32).  A frame whose three
+ *     gains are all 32768 is left as it is, bit for bit, including samples above the maximum.
+ *   - Hence (a) n_cand == 1, a list that ends at once, candidates that lie outside the frame and candidates with fewer than
+ *     max(1, L / 16) counted pairs give the frame back bit for bit; (b) identical frames under identity maps come back bit for bit;
+ *     (c) constant frames of 100 (target) and 200 (one candidate) give r = 65536, G = 49152 and every sample 150;
+ *     (d) 16384 <= G_c <= 65536 whatever the content and the maps; (e) a candidate that is frame k under an integer shift with every
+ *     sample halved exactly gives r_j = 16384.
+ * A step outside 1 .. 64 is VS_ERR_ARG, before any device work. */
+typedef struct vs_deflicker_params { int step; } vs_deflicker_params;
+void vs_deflicker_params_default(vs_deflicker_params* p);   /* 4 */
+/* stats[(o*n_cand + j)*8 + {0: count, 1..3: a_B,a_G,a_R, 4..6: b_B,b_G,b_R, 7: 0}]; entry j = 0 is all zero; `stats` lives in `mem`;
+ * cand_frame and cand_t are host arrays of n_out * n_cand entries.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_exposure_stats_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride, int format,
+                                int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
+                                const vs_deflicker_params* params /* NULL = defaults */, uint64_t* stats, int mem, void* stream);
+/* gains[4*o + {0..2: G_B,G_G,G_R, 3: m}]; stats and gains live in `mem`.  Statistics in host memory beyond the rule's bounds
+ * (count >= 2^30, a sum >= 2^46) are VS_ERR_ARG; in device memory the arithmetic wraps modulo 2^64 and G_c keeps its range. */
+int vs_exposure_gains_batch(const uint64_t* stats, int n_out, int n_cand, int w, int h,
+                            const vs_deflicker_params* params /* NULL = defaults */, uint32_t* gains, int mem, void* stream);
+/* frame i scaled by gains[4*i ..] (gains[4*i + 3] is not read); dst may be src (in place: every sample is read and written by the same
+ * thread); w x h is the window the caller hands over, any size.  A gain outside 16384 .. 65536 in host memory is VS_ERR_ARG, before
+ * any device work; gains in device memory are never seen by the host: the kernel clamps them to that range. */
+int vs_bgr_gain_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
+                      const uint32_t* gains, void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* same sampling, float output (typed like image_warp); dst interleaved f32 */
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits,
                           const vs_transform* t, int mode, int border,
@@ -600,6 +644,17 @@ int   vs_stabilizer_get_deblur(const vs_stabilizer* s);
  * handle's lag or for a strength outside 1 .. 255.  get returns `ahead`. */
 int   vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params);
 int   vs_stabilizer_get_denoise(const vs_stabilizer* s);
+/* Deflicker (the rule: see vs_bgr_exposure_stats_batch).  0 (default): off -- the handle as it is without this call, launch for launch.
+ * 1 .. lag: every output frame's exposure is pulled to the average exposure of itself and the next `ahead` input frames; the exposure
+ * ratios are measured on the device at the same scene points through the measured motions (candidate j's transform is
+ * inverse(T_{k+1} o .. o T_j), as in the denoise), always between the ORIGINAL input frames, and never reach the host.  A frame whose
+ * alignment failed ends the list; frames beyond a reset, a clip boundary or a size change are never candidates.  Order: deblur,
+ * denoise, warp, border fill (with or without blend), then the gain pass, last, in place on the output window, for every warp_mode.
+ * The aligner always sees the original frames: transforms, vs_stabilizer_state and has_output do not depend on this setting.  params:
+ * NULL = defaults.  Takes effect with the next output frame.  VS_ERR_ARG beyond the handle's lag or for a step outside 1 .. 64.  get
+ * returns `ahead`. */
+int   vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params);
+int   vs_stabilizer_get_deflicker(const vs_stabilizer* s);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -86,6 +86,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("strength", C.c_int)]
 
 
+class DeflickerParams(C.Structure):
+    """vs_deflicker_params: the lattice step of the exposure statistics, 1 .. 64"""
+    _fields_ = [("step", C.c_int)]
+
+
 class FillBlendParams(C.Structure):
     """vs_fill_blend_params: feather 0 (off) or 1 .. 6; match 0 or 1"""
     _fields_ = [("feather", C.c_int), ("match", C.c_int)]
@@ -162,6 +167,11 @@ SIGNATURES = {
     "vs_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
     "vs_bgr_denoise_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DenoiseParams),
                                     _vp, _sz, _i32, _i32, _vp]),
+    "vs_deflicker_params_default": (None, [C.POINTER(DeflickerParams)]),
+    "vs_bgr_exposure_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeflickerParams),
+                                           _vp, _i32, _vp]),
+    "vs_exposure_gains_batch": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(DeflickerParams), _vp, _i32, _vp]),
+    "vs_bgr_gain_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
@@ -183,6 +193,8 @@ SIGNATURES = {
     "vs_stabilizer_get_deblur": (_i32, [_vp]),
     "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, C.POINTER(DenoiseParams)]),
     "vs_stabilizer_get_denoise": (_i32, [_vp]),
+    "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
+    "vs_stabilizer_get_deflicker": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
     "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
@@ -742,6 +754,83 @@ def denoise_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_fra
                                       C.c_void_p(stream) if stream else None))
 
 
+def deflicker_params(**kw):
+    p = DeflickerParams()
+    lib().vs_deflicker_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def exposure_stats_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None):
+    """the deflicker's pair statistics (include/vs_amd.h: vs_bgr_exposure_stats_batch).  src (n_src,h,w,3) numpy; cand_frame (n_out, n_cand) ints,
+    a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, n_cand, 8) uint64.  src_stride (elements): the call is
+    made on pitched copies of the frames"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    arr = (Transform * max(len(flat), 1))(*flat)
+    ss = w * c if src_stride is None else src_stride
+    buf = _pitched(src, ss)
+    out = np.full((max(n_out, 1), max(n_cand, 1), 8), 0xA5A5A5A5, np.uint64)
+    _check(lib().vs_bgr_exposure_stats_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                             C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    return out
+
+
+def exposure_stats_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, stats_ptr, params=None, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape
+    flat = [t for row in cand_t for t in row]
+    arr = (Transform * len(flat))(*flat)
+    _check(lib().vs_bgr_exposure_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             arr, C.byref(params) if params is not None else None, _p(stats_ptr), MEM_DEVICE,
+                                             C.c_void_p(stream) if stream else None))
+
+
+def exposure_gains_batch(stats, w, h, params=None):
+    """the deflicker's gains from its statistics (include/vs_amd.h: vs_exposure_gains_batch).  stats (n_out, n_cand, 8) uint64 -> (n_out, 4)
+    uint32: G_B, G_G, G_R, m"""
+    st = _c(stats, np.uint64)
+    n_out, n_cand = st.shape[0], st.shape[1]
+    out = np.full((n_out, 4), 0xA5A5A5A5, np.uint32)
+    _check(lib().vs_exposure_gains_batch(_p(st), n_out, n_cand, w, h, C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    return out
+
+
+def exposure_gains_batch_device(stats_ptr, n_out, n_cand, w, h, gains_ptr, params=None, stream=None):
+    _check(lib().vs_exposure_gains_batch(_p(stats_ptr), n_out, n_cand, w, h, C.byref(params) if params is not None else None, _p(gains_ptr), MEM_DEVICE,
+                                         C.c_void_p(stream) if stream else None))
+
+
+def bgr_gain_batch(src, gains, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """the deflicker's point-wise pass (include/vs_amd.h: vs_bgr_gain_batch).  src (n,h,w,3) numpy; gains (n,4) uint32 -> (n,h,w,3).  src_stride /
+    dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
+    buffer is returned as well"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    ds = w * c if dst_stride is None else dst_stride
+    buf = _pitched(src, ss)
+    g = _c(gains, np.uint32)
+    out = np.full((n, h, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_gain_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(g), _p(out), h * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:, :, :w * c]).reshape(n, h, w, c)
+    return (res, out) if guard is not None else res
+
+
+def bgr_gain_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, gains_ptr, dst_ptr, dst_fs, dst_stride, stream=None):
+    """device-resident form (dst_ptr may equal src_ptr): enqueue only"""
+    _check(lib().vs_bgr_gain_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(gains_ptr), _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
+                                   C.c_void_p(stream) if stream else None))
+
+
 def sharpness_batch_device(src_ptr, n, w, h, fmt, sharp_ptr, stream=None):
     _check(lib().vs_bgr_sharpness_batch(_p(src_ptr), h * w * 3, n, w, h, w * 3, fmt, _p(sharp_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
 
@@ -983,7 +1072,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 **params):
+                 deflicker=0, deflicker_params=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -998,6 +1087,16 @@ class Stabilizer:
             self.set_deblur(deblur, deblur_params)
         if denoise:
             self.set_denoise(denoise, denoise_params)
+        if deflicker:
+            self.set_deflicker(deflicker, deflicker_params)
+
+    def set_deflicker(self, ahead, params=None):
+        """0: off; 1 .. lag: every output frame's exposure is pulled to the mean exposure of itself and the next `ahead` input frames
+        (params: DeflickerParams, None = defaults)"""
+        _check(lib().vs_stabilizer_set_deflicker(self.h, int(ahead), C.byref(params) if params is not None else None))
+
+    def get_deflicker(self):
+        return _check(lib().vs_stabilizer_get_deflicker(self.h))
 
     def set_denoise(self, ahead, params=None):
         """0: off; 1 .. lag: every frame is averaged with what the next `ahead` input frames show at the same scene point before it is warped

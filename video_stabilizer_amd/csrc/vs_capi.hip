@@ -454,6 +454,7 @@ extern "C" int vs_bounds_fetch_flow(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_fill(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_deblur(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_denoise(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_deflicker(unsigned out[8], int reset);
 namespace {
 // the checker checked: element 11 of an 8-element LDS array through a Span -- reported under site 900, executed on element 0
 __global__ void vs_k_bounds_selftest(int* out) {
@@ -473,11 +474,12 @@ int vs_debug_bounds_check(void) try {
     if (!vsi::device_ready()) return VS_ERR_HIP;
     VS_HIP(hipDeviceSynchronize());
     int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_flow, vs_bounds_fetch_fill,
-                                            vs_bounds_fetch_deblur, vs_bounds_fetch_denoise, vs_bounds_fetch_capi};
-    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_fill.hip", "vs_deblur.hip", "vs_denoise.hip", "vs_capi.hip"};
+                                            vs_bounds_fetch_deblur, vs_bounds_fetch_denoise, vs_bounds_fetch_deflicker, vs_bounds_fetch_capi};
+    const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_fill.hip", "vs_deblur.hip", "vs_denoise.hip", "vs_deflicker.hip",
+                                 "vs_capi.hip"};
     unsigned total = 0;
     char msg[512] = "";
-    for (int k = 0; k < 8; k++) {
+    for (int k = 0; k < 9; k++) {
         unsigned r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fetch[k](r, 1) != 0) return set_error(VS_ERR_HIP, "bounds record of %s is not readable", names[k]);
         if (r[0] && !total)
@@ -1248,7 +1250,141 @@ int vs_bgr_denoise_batch(const void* src, size_t src_fs, int n_src, int w, int h
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
+// ---- deflicker (vs_deflicker.hip) ----
+static int deflicker_params_ok(const vs_deflicker_params* params, vs_deflicker_params* p) {
+    if (params) *p = *params; else vs_deflicker_params_default(p);
+    VS_ARG(p->step >= 1 && p->step <= 64);
+    return VS_OK;
+}
+static int deflicker_args_ok(int w, int h, int format, int n_cand, int* bits) {
+    VS_TRY(deblur_format_ok(format, bits));
+    VS_ARG(n_cand >= 1 && n_cand <= 16);
+    if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "deflicker: frames up to 32767 x 32767, as the border fill");
+    return VS_OK;
+}
+
+// The statistics pass on device-resident frames: the pairs of output frame o are the frame at cand_src[o * n_cand] with candidates
+// c = 1 .. n_cand-1 (the frame at cand_src[o * n_cand + c], null ends the list, under cand_t[o * n_cand + c]).  stats: n_out x n_cand x 8 words in
+// device memory, zeroed on `s` in front of the launches.  Host arrays; enqueue only.  Frame pointers and matrices travel as the denoise's entries do.
+static int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                               const vs_deflicker_params* params, uint64_t* stats, hipStream_t s) {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deflicker_args_ok(w, h, format, n_cand, &bits));
+    VS_ARG(cand_src && cand_t && stats && n_out >= 1 && src_stride >= w * 3);
+    vs_deflicker_params p;
+    VS_TRY(deflicker_params_ok(params, &p));
+    ParamRing* ring = param_ring();
+    if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
+    const size_t esz = bits > 8 ? 2 : 1;
+    static_assert(sizeof(vsk::FillCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
+    const int per_call = std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand);
+    std::vector<vsk::FillCand> dc;
+    for (int f0 = 0; f0 < n_out; f0 += per_call) {
+        const int nf = std::min(per_call, n_out - f0);
+        dc.assign((size_t)nf * n_cand, vsk::FillCand{});
+        for (int i = 0; i < nf; i++) {
+            vsk::FillCand* row = &dc[(size_t)i * n_cand];
+            const size_t base = (size_t)(f0 + i) * n_cand;
+            VS_ARG(cand_src[base]);
+            row[0].src = cand_src[base];
+            for (int c = 1; c < n_cand && cand_src[base + c]; c++) {
+                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
+                row[c].src = cand_src[base + c];
+            }
+        }
+        const size_t slots = dc.size() * 4;
+        float4* cdev = nullptr;
+        if (slots <= (size_t)kParamBlockSlots) {
+            ParamBlock blk{};
+            memcpy(blk.v, dc.data(), slots * sizeof(float4));
+            VS_TRY(ring->take(slots, s, &cdev));
+            hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, cdev, (int)slots);
+            VS_HIP(hipGetLastError());
+        } else
+            VS_TRY(ring->upload((const float*)dc.data(), slots, s, &cdev));
+        VS_HIP(vsk::exposure_stats((const vsk::FillCand*)cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, p.step,
+                                   (unsigned long long*)stats + (size_t)f0 * n_cand * 8, nf, s));
+        VS_TRY(ring->fence(cdev, s));
+    }
+    return VS_OK;
+}
+
+int vs_bgr_exposure_stats_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, int n_out, int n_cand,
+                                const int32_t* cand_frame, const vs_transform* cand_t, const vs_deflicker_params* params, uint64_t* stats, int mem,
+                                void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deflicker_args_ok(w, h, format, n_cand, &bits));
+    VS_ARG(src && stats && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && src_stride >= w * 3);
+    VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
+    for (int o = 0; o < n_out; o++) {
+        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
+        for (int c = 0; c < n_cand && cand_frame[(size_t)o * n_cand + c] >= 0; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
+    }
+    vs_deflicker_params p;
+    VS_TRY(deflicker_params_ok(params, &p));
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    Staged a, o;
+    VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(o.out(stats, (size_t)n_out * n_cand * 8 * sizeof(uint64_t), mem));
+    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
+    for (int i = 0; i < n_out; i++)
+        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
+            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
+    VS_TRY(exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.as<uint64_t>(), s));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+int vs_exposure_gains_batch(const uint64_t* stats, int n_out, int n_cand, int w, int h, const vs_deflicker_params* params, uint32_t* gains, int mem,
+                            void* stream) try {
+    VS_DIMS(w, h);
+    VS_ARG(stats && gains && n_out >= 1 && n_cand >= 1 && n_cand <= 16);
+    vs_deflicker_params p;
+    VS_TRY(deflicker_params_ok(params, &p));
+    if (mem == VS_MEM_HOST)                                             // the rule's bounds, where the host can see them
+        for (size_t e = 0; e < (size_t)n_out * n_cand; e++) {
+            VS_ARG(stats[e * 8] < (1ull << 30));
+            for (int k = 1; k < 7; k++) VS_ARG(stats[e * 8 + k] < (1ull << 46));
+        }
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    Staged a, o;
+    VS_TRY(a.in(stats, (size_t)n_out * n_cand * 8 * sizeof(uint64_t), mem, s));
+    VS_TRY(o.out(gains, (size_t)n_out * 4 * sizeof(uint32_t), mem));
+    VS_HIP(vsk::exposure_gains(a.as<unsigned long long>(), n_out, n_cand, w, h, p.step, o.as<uint32_t>(), s));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+int vs_bgr_gain_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, const uint32_t* gains, void* dst, size_t dst_fs,
+                      int dst_stride, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(deblur_format_ok(format, &bits));
+    VS_ARG(src && dst && gains && n >= 1 && src_stride >= w * 3 && dst_stride >= w * 3);
+    VS_ARG(n == 1 || (src_fs >= img_span(w, h, src_stride, 3) && dst_fs >= img_span(w, h, dst_stride, 3)));
+    if (mem == VS_MEM_HOST)
+        for (size_t i = 0; i < (size_t)n; i++)
+            for (int c = 0; c < 3; c++) VS_ARG(gains[4 * i + c] >= 16384u && gains[4 * i + c] <= 65536u);
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    Staged a, g, o;
+    VS_TRY(a.in(src, ((size_t)(n - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
+    VS_TRY(g.in(gains, (size_t)n * 4 * sizeof(uint32_t), mem, s));
+    VS_TRY(o.out_image(dst, (size_t)w * 3 * esz, (size_t)h, (size_t)dst_stride * esz, (size_t)n, dst_fs * esz, mem));
+    VS_HIP(vsk::bgr_gain(a.dev, w, h, src_stride, (int)esz * 8, vs_format_max_value(format), g.as<uint32_t>(), o.dev, dst_stride, n, src_fs, dst_fs, s));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
 }  // extern "C"
+
+int vsi::exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                             const vs_deflicker_params* params, uint64_t* stats, hipStream_t s) {
+    return ::exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, cand_src, cand_t, params, stats, s);
+}
 
 int vsi::bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
                           const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {

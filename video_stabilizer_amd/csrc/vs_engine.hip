@@ -1375,6 +1375,10 @@ struct vs_stabilizer {
     int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
     vs_denoise_params denoise_params{24};
     void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
+    // deflicker (vs_deflicker.hip)
+    int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
+    vs_deflicker_params deflicker_params{4};
+    void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
     struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
                   SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
@@ -1452,6 +1456,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
     if (s->deblur_buf) (void)hipFree(s->deblur_buf);
     if (s->denoise_buf) (void)hipFree(s->denoise_buf);
+    if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
@@ -1848,6 +1853,10 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     const int ndn = std::min(s->denoise, s->params.lag);
     std::vector<const void*> dn_src;
     std::vector<vs_transform> dn_t;
+    // deflicker (vs_deflicker.hip): per job 1 + nfk candidates likewise; candidate 0 stays the ORIGINAL frame whatever deblur and denoise do
+    const int nfk = std::min(s->deflicker, s->params.lag);
+    std::vector<const void*> fk_src;
+    std::vector<vs_transform> fk_t;
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
@@ -1950,6 +1959,19 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                     }
                     for (; c < ndn; c++) { dn_src.push_back(nullptr); dn_t.push_back(vs_transform{0, 0, 0, 0}); }
                 }
+                if (nfk > 0) {
+                    // the denoise's list: frame j shows frame k's scene points through inverse(T_{k+1} o .. o T_j); a failed alignment ends it
+                    fk_src.push_back(src.ptr); fk_t.push_back(vs_transform{0, 0, 0, 0});
+                    vs_transform chain{0, 0, 0, 0};
+                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
+                    int c = 0;
+                    for (; c < nfk && (size_t)c < avail && s->meas_ok[c]; c++) {
+                        chain = vs_transform_compose(&chain, &s->measurements[c]);
+                        fk_src.push_back(s->frames[c].ptr);
+                        fk_t.push_back(vs_transform_inverse(&chain));
+                    }
+                    for (; c < nfk; c++) { fk_src.push_back(nullptr); fk_t.push_back(vs_transform{0, 0, 0, 0}); }
+                }
             }
         }
     }
@@ -2012,6 +2034,26 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
             }
         }
+        uint32_t* fk_gains = nullptr;
+        if (nfk > 0) {
+            // the exposure statistics of every due frame against the frames that follow it -- the original input frames on both sides, read before
+            // their own jobs release them -- and its three gains: one statistics launch and one gains launch, on the warps' stream.  Nothing of it
+            // reaches the host; the gain pass behind each run's warp (and fill) reads the gains there.
+            hipStream_t ws = warps_apart ? s->warp_stream : st;
+            const size_t sbytes = jobs.size() * (size_t)(1 + nfk) * 8 * sizeof(uint64_t), need = sbytes + jobs.size() * 4 * sizeof(uint32_t);
+            if (s->flicker_bytes < need) {
+                VS_HIP(hipStreamSynchronize(ws));           // (gain passes of an earlier chunk may still read the block)
+                if (s->flicker_buf) (void)hipFree(s->flicker_buf);
+                s->flicker_buf = nullptr; s->flicker_bytes = 0;
+                VS_HIP(vsi::dev_alloc(&s->flicker_buf, need));
+                s->flicker_bytes = need;
+            }
+            fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf + sbytes);
+            const int fr = vsi::exposure_stats_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + nfk, fk_src.data(), fk_t.data(), &s->deflicker_params,
+                                                    (uint64_t*)s->flicker_buf, ws);
+            if (fr < 0) return fr;
+            VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf, (int)jobs.size(), 1 + nfk, w, h, s->deflicker_params.step, fk_gains, ws));
+        }
         std::vector<vs_transform> ts;
         for (size_t j = 0; j < jobs.size();) {
             size_t e = j + 1;
@@ -2036,6 +2078,9 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                                                  s->params.warp_mode, s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh,
                                                  dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws);
             if (wr < 0) return wr;
+            // deflicker: the run's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
+            if (nfk > 0)
+                VS_HIP(vsk::bgr_gain(dst, ow, oh, ow * 3, (int)esz * 8, vs_format_max_value(format), fk_gains + 4 * j, dst, ow * 3, (int)(e - j), dst_fs, dst_fs, ws));
             j = e;
         }
         for (size_t j = 0; j < jobs.size(); j++)
@@ -2176,6 +2221,19 @@ int vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_para
     s->denoise = ahead;
     s->denoise_params = p;
     return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_deflicker_params p;
+    if (params) p = *params; else vs_deflicker_params_default(&p);
+    VS_ARG(p.step >= 1 && p.step <= 64);
+    s->deflicker = ahead;
+    s->deflicker_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_deflicker(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->deflicker;
 } VS_CATCH_ALL
 int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
     VS_ARG(s);

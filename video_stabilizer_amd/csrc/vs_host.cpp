@@ -86,6 +86,10 @@ void vs_deblur_params_default(vs_deblur_params* p) {
 void vs_denoise_params_default(vs_denoise_params* p) {
     p->strength = 24;
 }
+// vs_deflicker.hip (DESIGN.md "Deflicker": a lattice of every fourth pixel a side reads a quarter of the cache lines and leaves thousands of pairs)
+void vs_deflicker_params_default(vs_deflicker_params* p) {
+    p->step = 4;
+}
 
 // imgproc.cpp:333-359
 vs_transform vs_transform_inverse(const vs_transform* t) {

@@ -131,6 +131,13 @@ int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_c
 int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
                      const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
 
+// The deflicker's statistics pass (the rule: vs_deflicker.hip) on device-resident frames; vs_bgr_exposure_stats_batch is the index-based wrapper
+// over it.  The pairs of output frame o: the frame at cand_src[o * n_cand] with its candidates c = 1 .. n_cand-1 (any device pointer, w x h, rows of
+// src_stride elements; null ends the list) under cand_t[o * n_cand + c].  stats: n_out x n_cand x 8 words of device memory, zeroed on `s` first.
+// Host arrays; enqueue only.
+int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                        const vs_deflicker_params* params, uint64_t* stats, hipStream_t s);
+
 bool device_ready();   // true when a HIP device is usable (sets last error otherwise)
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the

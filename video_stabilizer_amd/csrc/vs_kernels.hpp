@@ -95,6 +95,15 @@ hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, in
 // every target frame starts on a dword.
 hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int strength, void* dst,
                        int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s);
+// Deflicker (vs_deflicker.hip: the rule and the kernels).  exposure_stats: cands_dev = n_frames x n_cand entries in device memory (entry 0 of a
+// frame is the target, a null frame ends the list); stats = n_frames x n_cand x 8 words in device memory, zeroed on `s` first.  exposure_gains:
+// gains[4 o + {0..2: G_c, 3: m}] from the statistics.  bgr_gain: frame i scaled by gains[4 i ..] (clamped to 16384 .. 65536); dst may be src.
+size_t exposure_threshold(int w, int h, int step);         // max(1, L / 16)
+hipError_t exposure_stats(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int step, unsigned long long* stats,
+                          int n_frames, hipStream_t s);
+hipError_t exposure_gains(const unsigned long long* stats, int n_out, int n_cand, int w, int h, int step, uint32_t* gains, hipStream_t s);
+hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int max_value, const uint32_t* gains, void* dst, int dst_stride, int n_frames,
+                    size_t src_fs, size_t dst_fs, hipStream_t s);
 // host side of the tuned kernel's tile prologue: per frame {lo_x, hi_x, lo_y, hi_y} from the kernel parameters {A, B, TX, TY}, for the
 // tile of the kernel that bgr_warp_c3 launches for (bits, mode)
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4);

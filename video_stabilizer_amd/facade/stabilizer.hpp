@@ -19,6 +19,7 @@ struct VideoStabilizerParams {
     int border_fill = 0;                  // a knob of this build: 1 .. lag = fill what the corrected frame does not cover from that many following frames (vs_stabilizer_set_border_fill)
     int deblur = 0;                       // a knob of this build: 1 .. lag = deblur every frame from the sharper ones among that many following frames (vs_stabilizer_set_deblur, default parameters)
     int denoise = 0;                      // a knob of this build: 1 .. lag = average every frame with what that many following frames show at the same scene point (vs_stabilizer_set_denoise, default parameters)
+    int deflicker = 0;                    // a knob of this build: 1 .. lag = pull every frame's exposure to the mean exposure of itself and that many following frames (vs_stabilizer_set_deflicker, default parameters)
 };
 
 // stabilizer.hpp:32-56.  processFrame returns an empty vector until `lag` frames have arrived
@@ -51,6 +52,11 @@ public:
             const std::string why = vs_last_error();
             vs_stabilizer_destroy(h_);
             throw std::runtime_error("vs_stabilizer_set_denoise: " + why);
+        }
+        if (params.deflicker != 0 && vs_stabilizer_set_deflicker(h_, params.deflicker, nullptr) != VS_OK) {
+            const std::string why = vs_last_error();
+            vs_stabilizer_destroy(h_);
+            throw std::runtime_error("vs_stabilizer_set_deflicker: " + why);
         }
     }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
