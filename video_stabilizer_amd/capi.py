@@ -566,29 +566,44 @@ def bgr_image_warp_roi_batch(src, ts, roi, mode=WARP_LANCZOS2, border=BORDER_CLA
     return out
 
 
-def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_CONSTANT, max_value=None, src_stride=None, dst_stride=None):
-    """VS_WARP_BILINEAR_CV with border fill (include/vs_amd.h: vs_bgr_image_warp_fill_batch).  src (n_src,h,w,3) numpy; cand_frame
-    (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w, 3).
-    src_stride / dst_stride (elements): the call is made on pitched copies of the frames (the padding is not part of the result)"""
+def _pitched(src, stride):
+    """(n,h,w,c) -> (n,h,stride) with the rows' own elements in front (the padding is zero)"""
+    n, h, w, c = src.shape
+    if stride == w * c:
+        return src.reshape(n, h, w * c)
+    wide = np.zeros((n, h, stride), src.dtype)
+    wide[:, :, :w * c] = src.reshape(n, h, w * c)
+    return wide
+
+
+def _lookahead_args(src, cand_frame, cand_t, src_stride):
+    """what the host forms of the look-ahead passes (fill, deblur, denoise, exposure statistics) begin with: src (n_src,h,w,c) numpy, cand_frame
+    (n_out, n_cand) ints, cand_t n_out lists of n_cand Transforms -> the contiguous frames, the int32 indices, n_out, n_cand, the Transform
+    array, the source stride in elements and the frames as rows of that stride"""
     src = np.ascontiguousarray(src)
     n_src, h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
     idx = _c(cand_frame, np.int32)
     n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
     flat = [t for row in cand_t for t in row]
     assert len(flat) == n_out * n_cand
     arr = (Transform * max(len(flat), 1))(*flat)
-    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
     ss = w * c if src_stride is None else src_stride
+    return src, idx, n_out, n_cand, arr, ss, _pitched(src, ss)
+
+
+def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_CONSTANT, max_value=None, src_stride=None, dst_stride=None):
+    """VS_WARP_BILINEAR_CV with border fill (include/vs_amd.h: vs_bgr_image_warp_fill_batch).  src (n_src,h,w,3) numpy; cand_frame
+    (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w, 3).
+    src_stride / dst_stride (elements): the call is made on pitched copies of the frames (the padding is not part of the result)"""
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    n_src, h, w, c = src.shape
+    bits = 8 if src.dtype == np.uint8 else 16
+    if max_value is None:
+        max_value = 255 if bits == 8 else 65535
+    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
     ds = rw * c if dst_stride is None else dst_stride
-    if ss != w * c:
-        wide = np.zeros((n_src, h, ss), src.dtype)
-        wide[:, :, :w * c] = src.reshape(n_src, h, w * c)
-        src = wide
     out = np.zeros((max(n_out, 1), rh, ds), src.dtype)
-    _check(lib().vs_bgr_image_warp_fill_batch(_p(src), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+    _check(lib().vs_bgr_image_warp_fill_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                               arr, border, max_value, rx, ry, rw, rh, _p(out), rh * ds, ds, MEM_HOST, None))
     return np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
 
@@ -619,27 +634,17 @@ def bgr_image_warp_fill_blend_batch(src, cand_frame, cand_t, sums=None, feather=
     """the fill with its seams blended (include/vs_amd.h: vs_bgr_image_warp_fill_blend_batch).  Arguments as bgr_image_warp_fill_batch;
     sums (n_src,3) uint64 (None only with match == 0).  guard: a value the destination's padding is filled with first; the padded buffer
     is returned as well, so that the caller can see that the padding was left alone"""
-    src = np.ascontiguousarray(src)
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
     n_src, h, w, c = src.shape
     bits = 8 if src.dtype == np.uint8 else 16
     if max_value is None:
         max_value = 255 if bits == 8 else 65535
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
-    flat = [t for row in cand_t for t in row]
-    assert len(flat) == n_out * n_cand
-    arr = (Transform * max(len(flat), 1))(*flat)
     rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
-    ss = w * c if src_stride is None else src_stride
     ds = rw * c if dst_stride is None else dst_stride
-    if ss != w * c:
-        wide = np.zeros((n_src, h, ss), src.dtype)
-        wide[:, :, :w * c] = src.reshape(n_src, h, w * c)
-        src = wide
     sm = _c(sums, np.uint64) if sums is not None else None
     p = FillBlendParams(int(feather), int(match))
     out = np.full((max(n_out, 1), rh, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_image_warp_fill_blend_batch(_p(src), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+    _check(lib().vs_bgr_image_warp_fill_blend_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                                     arr, _p(sm) if sm is not None else None, C.byref(p), border, max_value, rx, ry, rw, rh, _p(out),
                                                     rh * ds, ds, MEM_HOST, None))
     res = np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
@@ -652,16 +657,6 @@ def deblur_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
-
-
-def _pitched(src, stride):
-    """(n,h,w,c) -> (n,h,stride) with the rows' own elements in front (the padding is zero)"""
-    n, h, w, c = src.shape
-    if stride == w * c:
-        return src.reshape(n, h, w * c)
-    wide = np.zeros((n, h, stride), src.dtype)
-    wide[:, :, :w * c] = src.reshape(n, h, w * c)
-    return wide
 
 
 def sharpness_batch(src, fmt=None, src_stride=None):
@@ -682,17 +677,10 @@ def bgr_deblur_batch(src, sharpness, cand_frame, cand_t, params=None, fmt=None, 
     (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).
     src_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with
     first; the padded buffer is returned as well, so that the caller can see that the padding was left alone"""
-    src = np.ascontiguousarray(src)
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
     n_src, h, w, c = src.shape
     fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
-    flat = [t for row in cand_t for t in row]
-    assert len(flat) == n_out * n_cand
-    arr = (Transform * max(len(flat), 1))(*flat)
-    ss = w * c if src_stride is None else src_stride
     ds = w * c if dst_stride is None else dst_stride
-    buf = _pitched(src, ss)
     sh = _c(sharpness, np.uint64)
     out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
     _check(lib().vs_bgr_deblur_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, _p(sh), n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
@@ -725,17 +713,10 @@ def denoise_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=Non
     ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).  src_stride / dst_stride
     (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer
     is returned as well, so that the caller can see that the padding was left alone"""
-    src = np.ascontiguousarray(src)
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
     n_src, h, w, c = src.shape
     fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
-    flat = [t for row in cand_t for t in row]
-    assert len(flat) == n_out * n_cand
-    arr = (Transform * max(len(flat), 1))(*flat)
-    ss = w * c if src_stride is None else src_stride
     ds = w * c if dst_stride is None else dst_stride
-    buf = _pitched(src, ss)
     out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
     _check(lib().vs_bgr_denoise_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
                                       C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
@@ -766,16 +747,9 @@ def exposure_stats_batch(src, cand_frame, cand_t, params=None, fmt=None, src_str
     """the deflicker's pair statistics (include/vs_amd.h: vs_bgr_exposure_stats_batch).  src (n_src,h,w,3) numpy; cand_frame (n_out, n_cand) ints,
     a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, n_cand, 8) uint64.  src_stride (elements): the call is
     made on pitched copies of the frames"""
-    src = np.ascontiguousarray(src)
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
     n_src, h, w, c = src.shape
     fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
-    flat = [t for row in cand_t for t in row]
-    assert len(flat) == n_out * n_cand
-    arr = (Transform * max(len(flat), 1))(*flat)
-    ss = w * c if src_stride is None else src_stride
-    buf = _pitched(src, ss)
     out = np.full((max(n_out, 1), max(n_cand, 1), 8), 0xA5A5A5A5, np.uint64)
     _check(lib().vs_bgr_exposure_stats_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
                                              C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))

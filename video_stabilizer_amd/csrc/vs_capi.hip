@@ -237,6 +237,8 @@ using vsi::set_error;
 
 #define VS_TRY(expr) do { int _r = (expr); if (_r != VS_OK) return _r; } while (0)
 #define VS_ARG(cond) do { if (!(cond)) return set_error(VS_ERR_ARG, "bad argument: %s (%s)", #cond, __func__); } while (0)
+// (inside a helper or a lambda: reported under the name of the function it checks for)
+#define VS_ARG_AS(cond, func) do { if (!(cond)) return set_error(VS_ERR_ARG, "bad argument: %s (%s)", #cond, func); } while (0)
 // every image extent an entry point takes: positive and at most 65535 a side (tile coordinates are 16-bit, row offsets are 24-bit multiplies, and
 // the products w * channels / roi.x + roi.w of the checks that follow stay inside int)
 #define VS_DIMS(w, h) VS_ARG((w) > 0 && (h) > 0 && (w) <= 65535 && (h) <= 65535)
@@ -434,6 +436,98 @@ hipError_t vsi::retire_stream(hipStream_t s) {
 
 static inline size_t img_span(int w, int h, int stride, int channels) {
     return (size_t)(h - 1) * stride + (size_t)w * channels;
+}
+
+// ---- the look-ahead passes' shared path: border fill, deblur, denoise, exposure statistics (DESIGN.md "Look-ahead passes: the shared path") ----
+// `slots` float4 at `src` reach the ring's device half on `s`: up to kParamBlockSlots by value (kernel arguments of vs_k_param_block, into a span
+// taken from the ring), more as one upload.  *dev: the span; the caller fence()s it behind the kernel that reads it.
+static int send_slots(ParamRing* ring, const void* src, size_t slots, hipStream_t s, float4** dev) {
+    if (slots > (size_t)kParamBlockSlots) return ring->upload((const float*)src, slots, s, dev);
+    ParamBlock blk{};
+    memcpy(blk.v, src, slots * sizeof(float4));
+    VS_TRY(ring->take(slots, s, dev));
+    hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, *dev, (int)slots);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// Output frames [first, first + n) of a pass, per_call at a time (what the pass lets into half the ring).  A group's entries (Cand: vsk::FillCand or
+// vsk::DeblurCand, four slots each, n_cand per frame, zeroed): entry 0 is the pass's own -- target(entry, o), which may refuse the frame;
+// candidates c = 1 .. get the inverse matrix of cand_t[o * n_cand + c] and the frame pointer until the list ends, at a null frame or where
+// side(entry, o * n_cand + c), which fills the entry's side word, says so.  Then on `s`, in this order: the entries' span (send_slots), with_ratios a
+// device-only span of a float per entry, launch(entries on the device, ratios, first frame, frames), the fences.  A group without a single
+// candidate is sent and launched only with launch_empty.  ents: scratch, the caller's so that it outlives the groups.
+template <typename Cand, typename Target, typename Side, typename Launch>
+static int cand_groups(ParamRing* ring, int first, int n, int per_call, int n_cand, const void* const* cand_src, const vs_transform* cand_t, int w, int h,
+                       bool with_ratios, bool launch_empty, hipStream_t s, std::vector<Cand>& ents, Target target, Side side, Launch launch) {
+    static_assert(sizeof(Cand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
+    for (int f0 = first; f0 < first + n; f0 += per_call) {
+        const int nf = std::min(per_call, first + n - f0);
+        ents.assign((size_t)nf * n_cand, Cand{});
+        bool any = false;
+        for (int i = 0; i < nf; i++) {
+            Cand* row = &ents[(size_t)i * n_cand];
+            const size_t base = (size_t)(f0 + i) * n_cand;
+            VS_TRY(target(row[0], f0 + i));
+            for (int c = 1; c < n_cand && cand_src[base + c] && side(row[c], base + c); c++) {
+                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
+                row[c].src = cand_src[base + c];
+                any = true;
+            }
+        }
+        if (!any && !launch_empty) continue;
+        float4 *cdev = nullptr, *rdev = nullptr;
+        VS_TRY(send_slots(ring, ents.data(), ents.size() * 4, s, &cdev));
+        if (with_ratios) VS_TRY(ring->take((ents.size() + 3) / 4, s, &rdev));
+        VS_TRY(launch((Cand*)cdev, (float*)rdev, f0, nf));
+        VS_TRY(ring->fence(cdev, s));
+        if (rdev) VS_TRY(ring->fence(rdev, s));
+    }
+    return VS_OK;
+}
+// every target (entry 0) of the group's frames starts on a dword
+static bool targets_aligned(const void* const* cand_src, int f0, int nf, int n_cand) {
+    for (int o = f0; o < f0 + nf; o++) if ((uintptr_t)cand_src[(size_t)o * n_cand] & 3) return false;
+    return true;
+}
+
+namespace {
+// The index-based entry points' lists: cand_frame[o * n_cand + c] is a frame of the batch at `src`, a negative index ends a list.
+struct CandIndex {
+    const int32_t* cand_frame;
+    int n_out, n_cand;
+    // candidate 0 is the frame itself and no index reaches n_src; behind_end: neither does one behind a negative index (the fill's and the deblur's
+    // rule; the denoise and the exposure statistics do not read there)
+    int check(int n_src, bool behind_end, const char* fn) const {
+        for (int o = 0; o < n_out; o++) {
+            VS_ARG_AS(cand_frame[(size_t)o * n_cand] >= 0, fn);
+            for (int c = 0; c < n_cand && (behind_end || cand_frame[(size_t)o * n_cand + c] >= 0); c++) VS_ARG_AS(cand_frame[(size_t)o * n_cand + c] < n_src, fn);
+        }
+        return VS_OK;
+    }
+    // index k -> base + k * stride bytes (a frame; a frame's sharpness; its three sums), null from the end of a list on
+    template <typename T> std::vector<const T*> pointers(const void* base, size_t stride) const {
+        std::vector<const T*> p((size_t)n_out * n_cand, nullptr);
+        for (int i = 0; i < n_out; i++)
+            for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
+                p[(size_t)i * n_cand + c] = (const T*)((const char*)base + (size_t)cand_frame[(size_t)i * n_cand + c] * stride);
+        return p;
+    }
+};
+}  // namespace
+
+// what every BGR-only entry point asks of its format
+static int bgr_format_ok(int format, int* bits) {
+    *bits = vs_format_bits(format);
+    VS_ARG(format != VS_FMT_GRAY8 && *bits != 0);
+    return VS_OK;
+}
+// what the passes built on cv::warpAffine's coordinates ask of their lists and frames; pass, why: the message
+static const char kCvShort[] = " (cv::warpAffine saturates source coordinates to short beyond)", kAsTheFill[] = ", as the border fill";
+static int lookahead_args_ok(const char* pass, const char* why, int w, int h, int n_cand) {
+    VS_ARG(n_cand >= 1 && n_cand <= 16);
+    if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "%s: frames up to 32767 x 32767%s", pass, why);
+    return VS_OK;
 }
 
 extern "C" {
@@ -802,43 +896,28 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
             if (mdev) VS_TRY(ring->fence(mdev, s));
             if (tdev) VS_TRY(tring->fence(tdev, s));
             if (fill && fill->n_cand > 1) {
-                // pass 2 on the same stream: the candidates' matrices and frame pointers travel like the other per-frame parameters (small groups as
-                // kernel arguments of vs_k_param_block, larger ones as one upload of the ring); a group without a single candidate launches nothing
+                // pass 2 on the same stream: entry 0 carries the matrix pass 1 warped the frame with (and, with match, its sums); a group without
+                // a single candidate launches nothing
                 const int nc = fill->n_cand;
                 const bool blend = fill->feather > 0 || fill->match != 0;
-                fc.assign((size_t)nf * nc, vsk::FillCand{});
-                bool any = false;
-                for (int i = 0; i < nf; i++) {
-                    vsk::FillCand* row = &fc[(size_t)i * nc];
-                    memcpy(row[0].m, &Mv[(size_t)i * 6], 6 * sizeof(double));
-                    if (fill->match) row[0].reserved = (unsigned long long)(uintptr_t)fill->sums[(size_t)(f0 + i) * nc];
-                    for (int c = 1; c < nc && fill->src[(size_t)(f0 + i) * nc + c]; c++) {
-                        vs_cv_inverse_matrix(&fill->t[(size_t)(f0 + i) * nc + c], w, h, row[c].m);
-                        row[c].src = fill->src[(size_t)(f0 + i) * nc + c];
-                        if (fill->match) row[c].reserved = (unsigned long long)(uintptr_t)fill->sums[(size_t)(f0 + i) * nc + c];
-                        else if (blend) row[c].reserved = vsk::fill_unit_gains();
-                        any = true;
-                    }
-                }
-                if (any) {
-                    static_assert(sizeof(vsk::FillCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
-                    const size_t slots = fc.size() * 4;
-                    float4* fdev = nullptr;
-                    if (slots <= (size_t)kParamBlockSlots) {
-                        ParamBlock blk{};
-                        memcpy(blk.v, fc.data(), slots * sizeof(float4));
-                        VS_TRY(ring->take(slots, s, &fdev));
-                        hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, fdev, (int)slots);
-                        VS_HIP(hipGetLastError());
-                    } else
-                        VS_TRY(ring->upload((const float*)fc.data(), slots, s, &fdev));
-                    if (blend)
-                        VS_HIP(vsk::bgr_warp_cv_fill_blend_c3((vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, fill->feather, fill->match != 0, dp, dst_stride,
-                                                              nf, dst_fs, roi, s));
-                    else
-                        VS_HIP(vsk::bgr_warp_cv_fill_c3((const vsk::FillCand*)fdev, nc, w, h, src_stride, bits, max_value, dp, dst_stride, nf, dst_fs, roi, s));
-                    VS_TRY(ring->fence(fdev, s));
-                }
+                VS_TRY(cand_groups(ring, f0, nf, nf, nc, fill->src, fill->t, w, h, false, false, s, fc,
+                    [&](vsk::FillCand& e, int o) {
+                        memcpy(e.m, &Mv[(size_t)(o - f0) * 6], 6 * sizeof(double));
+                        if (fill->match) e.reserved = (unsigned long long)(uintptr_t)fill->sums[(size_t)o * nc];
+                        return VS_OK;
+                    },
+                    [&](vsk::FillCand& e, size_t k) {
+                        if (fill->match) e.reserved = (unsigned long long)(uintptr_t)fill->sums[k];
+                        else if (blend) e.reserved = vsk::fill_unit_gains();
+                        return true;
+                    },
+                    [&](vsk::FillCand* fdev, float*, int, int) -> int {
+                        if (blend)
+                            VS_HIP(vsk::bgr_warp_cv_fill_blend_c3(fdev, nc, w, h, src_stride, bits, max_value, fill->feather, fill->match != 0, dp, dst_stride, nf, dst_fs, roi, s));
+                        else
+                            VS_HIP(vsk::bgr_warp_cv_fill_c3(fdev, nc, w, h, src_stride, bits, max_value, dp, dst_stride, nf, dst_fs, roi, s));
+                        return VS_OK;
+                    }));
             }
         }
         return vsi::finish_outputs(mem, s, {&o});
@@ -855,14 +934,7 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
     float4* pdev = nullptr;
     ParamRing* ring = param_ring();
     if (!ring) return set_error(VS_ERR_UNSUPPORTED, "no current HIP device with index < 16");
-    if (P.size() / 4 <= (size_t)kParamBlockSlots) {          // small calls: by value through a one-workgroup kernel (see vs_k_param_block)
-        ParamBlock blk{};
-        memcpy(blk.v, P.data(), P.size() * sizeof(float));
-        VS_TRY(ring->take(P.size() / 4, s, &pdev));
-        hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, pdev, (int)(P.size() / 4));
-        VS_HIP(hipGetLastError());
-    } else
-        VS_TRY(ring->upload(P.data(), P.size() / 4, s, &pdev));
+    VS_TRY(send_slots(ring, P.data(), P.size() / 4, s, &pdev));
     Staged a, o;
     const size_t in_bytes = ((size_t)(n_frames - 1) * src_fs + img_span(w, h, src_stride, channels)) * esz;
     VS_TRY(a.in(src, in_bytes, mem, s));
@@ -900,14 +972,7 @@ int vs_bgr_image_warp_roi_batch(const void* src, size_t src_fs, int n_frames, in
                            dst_fs, dst_stride, false, mem, (hipStream_t)stream, &roi);
 } VS_CATCH_ALL
 
-static int deblur_format_ok(int format, int* bits);
-// the checks the fill adds to bgr_warp_common's own
-static int fill_args_ok(int w, int h, int channels, int n_cand) {
-    VS_ARG(channels == 3 && n_cand >= 1 && n_cand <= 16);
-    if (w > 32767 || h > 32767)
-        return set_error(VS_ERR_UNSUPPORTED, "border fill: frames up to 32767 x 32767 (cv::warpAffine saturates source coordinates to short beyond)");
-    return VS_OK;
-}
+}  // extern "C" (the entry points below have it from their declarations in include/vs_amd.h; vsi's functions between them must not)
 
 static int fill_blend_params_ok(const vs_fill_blend_params* params, vs_fill_blend_params* p) {
     *p = params ? *params : vs_fill_blend_params{0, 0};
@@ -916,11 +981,11 @@ static int fill_blend_params_ok(const vs_fill_blend_params* params, vs_fill_blen
 }
 
 // cand_sums / blend: see FillSpec; blend == NULL or {0, 0}: the plain fill, launch for launch
-static int bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
-                              const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
-                              int dst_stride, hipStream_t s, const uint64_t* const* cand_sums = nullptr, const vs_fill_blend_params* blend = nullptr) {
+int vsi::bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
+                            const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
+                            int dst_stride, hipStream_t s, const uint64_t* const* cand_sums, const vs_fill_blend_params* blend) {
     VS_ARG(cand_src && cand_t && n_out >= 1);
-    VS_TRY(fill_args_ok(w, h, 3, n_cand));
+    VS_TRY(lookahead_args_ok("border fill", kCvShort, w, h, n_cand));
     vs_fill_blend_params bp;
     VS_TRY(fill_blend_params_ok(blend, &bp));
     if (bp.match) {                                      // every candidate that has a frame has its sums
@@ -943,7 +1008,8 @@ static int fill_batch_impl(const void* src, size_t src_fs, int n_src, int w, int
                                  int roi_h, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream, const uint64_t* sums, const vs_fill_blend_params* blend) {
     VS_DIMS(w, h);
     VS_ARG(src && dst && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && (bits == 8 || bits == 16));
-    VS_TRY(fill_args_ok(w, h, channels, n_cand));
+    VS_ARG(channels == 3);
+    VS_TRY(lookahead_args_ok("border fill", kCvShort, w, h, n_cand));
     vs_fill_blend_params bp;
     VS_TRY(fill_blend_params_ok(blend, &bp));
     VS_ARG(sums || !bp.match);
@@ -951,10 +1017,8 @@ static int fill_batch_impl(const void* src, size_t src_fs, int n_src, int w, int
     VS_ARG(src_stride >= w * 3 && dst_stride >= roi_w * 3);
     VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
     VS_ARG(n_out == 1 || dst_fs >= img_span(roi_w, roi_h, dst_stride, 3));
-    for (int o = 0; o < n_out; o++) {
-        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
-        for (int c = 0; c < n_cand; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
-    }
+    const CandIndex idx{cand_frame, n_out, n_cand};
+    VS_TRY(idx.check(n_src, true, __func__));
     if (!vsi::device_ready()) return VS_ERR_HIP;
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = (size_t)bits / 8;
@@ -962,21 +1026,16 @@ static int fill_batch_impl(const void* src, size_t src_fs, int n_src, int w, int
     VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
     if (bp.match) VS_TRY(sm.in(sums, (size_t)n_src * 3 * sizeof(uint64_t), mem, s));
     VS_TRY(o.out_image(dst, (size_t)roi_w * 3 * esz, (size_t)roi_h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
-    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
-    std::vector<const uint64_t*> sptrs(bp.match ? (size_t)n_out * n_cand : 0, nullptr);
-    for (int i = 0; i < n_out; i++)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++) {
-            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
-            if (bp.match) sptrs[(size_t)i * n_cand + c] = (const uint64_t*)sm.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * 3;
-        }
+    const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * esz);
+    const std::vector<const uint64_t*> sptrs = bp.match ? idx.pointers<uint64_t>(sm.dev, 3 * sizeof(uint64_t)) : std::vector<const uint64_t*>();
     // pass 1 warps runs of outputs whose own frames are consecutive in the batch as one launch each (n_cand == 1 with frames 0 .. n-1 is
     // vs_bgr_image_warp_roi_batch, launch for launch)
     for (int j = 0; j < n_out;) {
         int e = j + 1;
         while (e < n_out && cand_frame[(size_t)e * n_cand] == cand_frame[(size_t)(e - 1) * n_cand] + 1) e++;
-        VS_TRY(bgr_warp_fill_ptrs(ptrs[(size_t)j * n_cand], src_fs, e - j, w, h, src_stride, bits, n_cand, &ptrs[(size_t)j * n_cand],
-                                  &cand_t[(size_t)j * n_cand], border, max_value, roi_x, roi_y, roi_w, roi_h, (char*)o.dev + (size_t)j * dst_fs * esz,
-                                  dst_fs, dst_stride, s, bp.match ? &sptrs[(size_t)j * n_cand] : nullptr, &bp));
+        VS_TRY(vsi::bgr_warp_fill_ptrs(ptrs[(size_t)j * n_cand], src_fs, e - j, w, h, src_stride, bits, n_cand, &ptrs[(size_t)j * n_cand],
+                                       &cand_t[(size_t)j * n_cand], border, max_value, roi_x, roi_y, roi_w, roi_h, (char*)o.dev + (size_t)j * dst_fs * esz,
+                                       dst_fs, dst_stride, s, bp.match ? &sptrs[(size_t)j * n_cand] : nullptr, &bp));
         j = e;
     }
     return vsi::finish_outputs(mem, s, {&o});
@@ -1001,7 +1060,7 @@ int vs_bgr_image_warp_fill_blend_batch(const void* src, size_t src_fs, int n_src
 int vs_bgr_channel_sums_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, uint64_t* sums, int mem, void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deblur_format_ok(format, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
     VS_ARG(src && sums && n >= 1 && w >= 1 && h >= 1 && src_stride >= w * 3);
     if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "channel sums: frames up to 32767 x 32767, as the border fill");
     VS_ARG(n == 1 || src_fs >= img_span(w, h, src_stride, 3));
@@ -1036,17 +1095,12 @@ int vs_bgr_to_gray(const void* src, int w, int h, int src_stride, int bits, int 
 } VS_CATCH_ALL
 
 // ---- deblur by transfer (vs_deblur.hip) ----
-static int deblur_format_ok(int format, int* bits) {
-    *bits = vs_format_bits(format);
-    VS_ARG(format != VS_FMT_GRAY8 && *bits != 0);
-    return VS_OK;
-}
 
 int vs_bgr_sharpness_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, uint64_t* sharpness, int mem,
                            void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deblur_format_ok(format, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
     VS_ARG(src && sharpness && n >= 1 && src_stride >= w * 3);
     VS_ARG(n == 1 || src_fs >= img_span(w, h, src_stride, 3));
     if (!vsi::device_ready()) return VS_ERR_HIP;
@@ -1065,15 +1119,13 @@ static int deblur_params_ok(const vs_deblur_params* params, vs_deblur_params* p)
     return VS_OK;
 }
 
-// The deblur pass on device-resident frames: output frame o is the frame at cand_src[o * n_cand] deblurred from candidates c = 1 .. n_cand-1 (the
-// frame at cand_src[o * n_cand + c], null ends the list, under cand_t[o * n_cand + c]); cand_sharp[..]: where each frame's S lies in device
-// memory.  Host arrays; enqueue only.  Frame pointers, sharpness pointers and matrices travel like the fill's per-candidate entries (small groups
-// as kernel arguments of vs_k_param_block, larger ones as one upload of the ring); the ratios take a span of the same ring.
-static int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
-                           const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+// The deblur pass on device-resident frames (vs_internal.hpp).  The list also ends at a frame without a sharpness pointer; entries and ratios
+// together stay inside half the ring.
+int vsi::bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
+                         const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deblur_format_ok(format, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
     VS_ARG(cand_src && cand_sharp && cand_t && dst && n_out >= 1 && n_cand >= 1 && n_cand <= 16 && src_stride >= w * 3 && dst_stride >= w * 3);
     VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
     vs_deblur_params p;
@@ -1081,43 +1133,22 @@ static int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, 
     ParamRing* ring = param_ring();
     if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
     const size_t esz = bits > 8 ? 2 : 1;
-    static_assert(sizeof(vsk::DeblurCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
-    const int per_call = std::max(1, (int)(ParamRing::kSlots / 2 / 5) / n_cand);      // (entries and ratios together stay inside half the ring)
+    const char* const fn = __func__;
     std::vector<vsk::DeblurCand> dc;
-    for (int f0 = 0; f0 < n_out; f0 += per_call) {
-        const int nf = std::min(per_call, n_out - f0);
-        dc.assign((size_t)nf * n_cand, vsk::DeblurCand{});
-        bool aligned = true;                                             // every target of the group starts on a dword
-        for (int i = 0; i < nf; i++) {
-            vsk::DeblurCand* row = &dc[(size_t)i * n_cand];
-            const size_t base = (size_t)(f0 + i) * n_cand;
-            VS_ARG(cand_src[base] && cand_sharp[base]);
-            row[0].src = cand_src[base];
-            aligned = aligned && ((uintptr_t)cand_src[base] & 3) == 0;
-            row[0].sharp = (const unsigned long long*)cand_sharp[base];
-            for (int c = 1; c < n_cand && cand_src[base + c] && cand_sharp[base + c]; c++) {
-                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
-                row[c].src = cand_src[base + c];
-                row[c].sharp = (const unsigned long long*)cand_sharp[base + c];
-            }
-        }
-        const size_t slots = dc.size() * 4, rslots = (dc.size() + 3) / 4;
-        float4 *cdev = nullptr, *rdev = nullptr;
-        if (slots <= (size_t)kParamBlockSlots) {
-            ParamBlock blk{};
-            memcpy(blk.v, dc.data(), slots * sizeof(float4));
-            VS_TRY(ring->take(slots, s, &cdev));
-            hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, cdev, (int)slots);
-            VS_HIP(hipGetLastError());
-        } else
-            VS_TRY(ring->upload((const float*)dc.data(), slots, s, &cdev));
-        VS_TRY(ring->take(rslots, s, &rdev));
-        VS_HIP(vsk::bgr_deblur((const vsk::DeblurCand*)cdev, (float*)rdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format),
-                               p.sensitivity, p.max_ratio, (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, aligned, s));
-        VS_TRY(ring->fence(cdev, s));
-        VS_TRY(ring->fence(rdev, s));
-    }
-    return VS_OK;
+    return cand_groups(ring, 0, n_out, std::max(1, (int)(ParamRing::kSlots / 2 / 5) / n_cand), n_cand, cand_src, cand_t, w, h, true, true, s, dc,
+        [&](vsk::DeblurCand& e, int o) -> int {
+            const size_t base = (size_t)o * n_cand;
+            VS_ARG_AS(cand_src[base] && cand_sharp[base], fn);
+            e.src = cand_src[base];
+            e.sharp = (const unsigned long long*)cand_sharp[base];
+            return VS_OK;
+        },
+        [&](vsk::DeblurCand& e, size_t k) { return (e.sharp = (const unsigned long long*)cand_sharp[k]) != nullptr; },
+        [&](vsk::DeblurCand* cdev, float* rdev, int f0, int nf) -> int {
+            VS_HIP(vsk::bgr_deblur(cdev, rdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format), p.sensitivity, p.max_ratio,
+                                   (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, targets_aligned(cand_src, f0, nf, n_cand), s));
+            return VS_OK;
+        });
 }
 
 int vs_bgr_deblur_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, const uint64_t* sharpness, int n_out,
@@ -1125,15 +1156,13 @@ int vs_bgr_deblur_batch(const void* src, size_t src_fs, int n_src, int w, int h,
                         int dst_stride, int mem, void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deblur_format_ok(format, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
     VS_ARG(src && dst && sharpness && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && n_cand >= 1 && n_cand <= 16);
     VS_ARG(src_stride >= w * 3 && dst_stride >= w * 3);
     VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
     VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
-    for (int o = 0; o < n_out; o++) {
-        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
-        for (int c = 0; c < n_cand; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
-    }
+    const CandIndex idx{cand_frame, n_out, n_cand};
+    VS_TRY(idx.check(n_src, true, __func__));
     vs_deblur_params p;
     VS_TRY(deblur_params_ok(params, &p));
     if (!vsi::device_ready()) return VS_ERR_HIP;
@@ -1143,14 +1172,9 @@ int vs_bgr_deblur_batch(const void* src, size_t src_fs, int n_src, int w, int h,
     VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
     VS_TRY(sh.in(sharpness, (size_t)n_src * sizeof(uint64_t), mem, s));
     VS_TRY(o.out_image(dst, (size_t)w * 3 * esz, (size_t)h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
-    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
-    std::vector<const uint64_t*> sharp((size_t)n_out * n_cand, nullptr);
-    for (int i = 0; i < n_out; i++)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++) {
-            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
-            sharp[(size_t)i * n_cand + c] = (const uint64_t*)sh.dev + cand_frame[(size_t)i * n_cand + c];
-        }
-    VS_TRY(bgr_deblur_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), sharp.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
+    const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * esz);
+    const std::vector<const uint64_t*> sharp = idx.pointers<uint64_t>(sh.dev, sizeof(uint64_t));
+    VS_TRY(vsi::bgr_deblur_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), sharp.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
@@ -1160,23 +1184,14 @@ static int denoise_params_ok(const vs_denoise_params* params, vs_denoise_params*
     VS_ARG(p->strength >= 1 && p->strength <= 255);
     return VS_OK;
 }
-static int denoise_args_ok(int w, int h, int format, int n_cand, int* bits) {
-    VS_TRY(deblur_format_ok(format, bits));
-    VS_ARG(n_cand >= 1 && n_cand <= 16);
-    if (w > 32767 || h > 32767)
-        return set_error(VS_ERR_UNSUPPORTED, "denoise: frames up to 32767 x 32767 (cv::warpAffine saturates source coordinates to short beyond)");
-    return VS_OK;
-}
 
-// The denoise pass on device-resident frames: output frame o is the frame at cand_src[o * n_cand] averaged with candidates c = 1 .. n_cand-1 (the
-// frame at cand_src[o * n_cand + c], null ends the list, under cand_t[o * n_cand + c]).  Host arrays; enqueue only.  Frame pointers and matrices
-// travel like the fill's per-candidate entries (small groups as kernel arguments of vs_k_param_block, larger ones as one upload of the ring), in
-// groups of (kSlots / 2 / 4) / n_cand output frames: an entry is four slots and a group stays inside half the ring.
-static int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
-                            const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+// The denoise pass on device-resident frames (vs_internal.hpp), in groups of (kSlots / 2 / 4) / n_cand output frames: a group stays inside half the ring.
+int vsi::bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                          const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(denoise_args_ok(w, h, format, n_cand, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
+    VS_TRY(lookahead_args_ok("denoise", kCvShort, w, h, n_cand));
     VS_ARG(cand_src && cand_t && dst && n_out >= 1 && src_stride >= w * 3 && dst_stride >= w * 3);
     VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
     vs_denoise_params p;
@@ -1184,39 +1199,21 @@ static int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format,
     ParamRing* ring = param_ring();
     if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
     const size_t esz = bits > 8 ? 2 : 1;
-    static_assert(sizeof(vsk::FillCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
-    const int per_call = std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand);
+    const char* const fn = __func__;
     std::vector<vsk::FillCand> dc;
-    for (int f0 = 0; f0 < n_out; f0 += per_call) {
-        const int nf = std::min(per_call, n_out - f0);
-        dc.assign((size_t)nf * n_cand, vsk::FillCand{});
-        bool aligned = true;                                             // every target of the group starts on a dword
-        for (int i = 0; i < nf; i++) {
-            vsk::FillCand* row = &dc[(size_t)i * n_cand];
-            const size_t base = (size_t)(f0 + i) * n_cand;
-            VS_ARG(cand_src[base]);
-            row[0].src = cand_src[base];
-            aligned = aligned && ((uintptr_t)cand_src[base] & 3) == 0;
-            for (int c = 1; c < n_cand && cand_src[base + c]; c++) {
-                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
-                row[c].src = cand_src[base + c];
-            }
-        }
-        const size_t slots = dc.size() * 4;
-        float4* cdev = nullptr;
-        if (slots <= (size_t)kParamBlockSlots) {
-            ParamBlock blk{};
-            memcpy(blk.v, dc.data(), slots * sizeof(float4));
-            VS_TRY(ring->take(slots, s, &cdev));
-            hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, cdev, (int)slots);
-            VS_HIP(hipGetLastError());
-        } else
-            VS_TRY(ring->upload((const float*)dc.data(), slots, s, &cdev));
-        VS_HIP(vsk::bgr_denoise((const vsk::FillCand*)cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format), p.strength,
-                                (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, aligned, s));
-        VS_TRY(ring->fence(cdev, s));
-    }
-    return VS_OK;
+    return cand_groups(ring, 0, n_out, std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand), n_cand, cand_src, cand_t, w, h, false, true, s, dc,
+        [&](vsk::FillCand& e, int o) -> int {
+            const size_t base = (size_t)o * n_cand;
+            VS_ARG_AS(cand_src[base], fn);
+            e.src = cand_src[base];
+            return VS_OK;
+        },
+        [](vsk::FillCand&, size_t) { return true; },
+        [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
+            VS_HIP(vsk::bgr_denoise(cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format), p.strength,
+                                    (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, targets_aligned(cand_src, f0, nf, n_cand), s));
+            return VS_OK;
+        });
 }
 
 int vs_bgr_denoise_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, int n_out, int n_cand,
@@ -1224,16 +1221,14 @@ int vs_bgr_denoise_batch(const void* src, size_t src_fs, int n_src, int w, int h
                          int mem, void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(denoise_args_ok(w, h, format, n_cand, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
+    VS_TRY(lookahead_args_ok("denoise", kCvShort, w, h, n_cand));
     VS_ARG(src && dst && cand_frame && cand_t && n_src >= 1 && n_out >= 1);
     VS_ARG(src_stride >= w * 3 && dst_stride >= w * 3);
     VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
     VS_ARG(n_out == 1 || dst_fs >= img_span(w, h, dst_stride, 3));
-    for (int o = 0; o < n_out; o++) {
-        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
-        // (a negative index ends the list: what lies behind it is not read)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)o * n_cand + c] >= 0; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
-    }
+    const CandIndex idx{cand_frame, n_out, n_cand};
+    VS_TRY(idx.check(n_src, false, __func__));
     vs_denoise_params p;
     VS_TRY(denoise_params_ok(params, &p));
     if (!vsi::device_ready()) return VS_ERR_HIP;
@@ -1242,11 +1237,8 @@ int vs_bgr_denoise_batch(const void* src, size_t src_fs, int n_src, int w, int h
     Staged a, o;
     VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
     VS_TRY(o.out_image(dst, (size_t)w * 3 * esz, (size_t)h, (size_t)dst_stride * esz, (size_t)n_out, dst_fs * esz, mem));
-    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
-    for (int i = 0; i < n_out; i++)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
-            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
-    VS_TRY(bgr_denoise_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
+    const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * esz);
+    VS_TRY(vsi::bgr_denoise_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
@@ -1256,58 +1248,34 @@ static int deflicker_params_ok(const vs_deflicker_params* params, vs_deflicker_p
     VS_ARG(p->step >= 1 && p->step <= 64);
     return VS_OK;
 }
-static int deflicker_args_ok(int w, int h, int format, int n_cand, int* bits) {
-    VS_TRY(deblur_format_ok(format, bits));
-    VS_ARG(n_cand >= 1 && n_cand <= 16);
-    if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "deflicker: frames up to 32767 x 32767, as the border fill");
-    return VS_OK;
-}
 
-// The statistics pass on device-resident frames: the pairs of output frame o are the frame at cand_src[o * n_cand] with candidates
-// c = 1 .. n_cand-1 (the frame at cand_src[o * n_cand + c], null ends the list, under cand_t[o * n_cand + c]).  stats: n_out x n_cand x 8 words in
-// device memory, zeroed on `s` in front of the launches.  Host arrays; enqueue only.  Frame pointers and matrices travel as the denoise's entries do.
-static int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
-                               const vs_deflicker_params* params, uint64_t* stats, hipStream_t s) {
+// The statistics pass on device-resident frames (vs_internal.hpp); the entries travel in the denoise's groups.
+int vsi::exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
+                             const vs_deflicker_params* params, uint64_t* stats, hipStream_t s) {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deflicker_args_ok(w, h, format, n_cand, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
+    VS_TRY(lookahead_args_ok("deflicker", kAsTheFill, w, h, n_cand));
     VS_ARG(cand_src && cand_t && stats && n_out >= 1 && src_stride >= w * 3);
     vs_deflicker_params p;
     VS_TRY(deflicker_params_ok(params, &p));
     ParamRing* ring = param_ring();
     if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
     const size_t esz = bits > 8 ? 2 : 1;
-    static_assert(sizeof(vsk::FillCand) == 4 * sizeof(float4), "a candidate entry is four ring slots");
-    const int per_call = std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand);
+    const char* const fn = __func__;
     std::vector<vsk::FillCand> dc;
-    for (int f0 = 0; f0 < n_out; f0 += per_call) {
-        const int nf = std::min(per_call, n_out - f0);
-        dc.assign((size_t)nf * n_cand, vsk::FillCand{});
-        for (int i = 0; i < nf; i++) {
-            vsk::FillCand* row = &dc[(size_t)i * n_cand];
-            const size_t base = (size_t)(f0 + i) * n_cand;
-            VS_ARG(cand_src[base]);
-            row[0].src = cand_src[base];
-            for (int c = 1; c < n_cand && cand_src[base + c]; c++) {
-                vs_cv_inverse_matrix(&cand_t[base + c], w, h, row[c].m);
-                row[c].src = cand_src[base + c];
-            }
-        }
-        const size_t slots = dc.size() * 4;
-        float4* cdev = nullptr;
-        if (slots <= (size_t)kParamBlockSlots) {
-            ParamBlock blk{};
-            memcpy(blk.v, dc.data(), slots * sizeof(float4));
-            VS_TRY(ring->take(slots, s, &cdev));
-            hipLaunchKernelGGL(vs_k_param_block, dim3(1), dim3(kParamBlockSlots), 0, s, blk, cdev, (int)slots);
-            VS_HIP(hipGetLastError());
-        } else
-            VS_TRY(ring->upload((const float*)dc.data(), slots, s, &cdev));
-        VS_HIP(vsk::exposure_stats((const vsk::FillCand*)cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, p.step,
-                                   (unsigned long long*)stats + (size_t)f0 * n_cand * 8, nf, s));
-        VS_TRY(ring->fence(cdev, s));
-    }
-    return VS_OK;
+    return cand_groups(ring, 0, n_out, std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand), n_cand, cand_src, cand_t, w, h, false, true, s, dc,
+        [&](vsk::FillCand& e, int o) -> int {
+            const size_t base = (size_t)o * n_cand;
+            VS_ARG_AS(cand_src[base], fn);
+            e.src = cand_src[base];
+            return VS_OK;
+        },
+        [](vsk::FillCand&, size_t) { return true; },
+        [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
+            VS_HIP(vsk::exposure_stats(cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, p.step, (unsigned long long*)stats + (size_t)f0 * n_cand * 8, nf, s));
+            return VS_OK;
+        });
 }
 
 int vs_bgr_exposure_stats_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, int n_out, int n_cand,
@@ -1315,13 +1283,12 @@ int vs_bgr_exposure_stats_batch(const void* src, size_t src_fs, int n_src, int w
                                 void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deflicker_args_ok(w, h, format, n_cand, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
+    VS_TRY(lookahead_args_ok("deflicker", kAsTheFill, w, h, n_cand));
     VS_ARG(src && stats && cand_frame && cand_t && n_src >= 1 && n_out >= 1 && src_stride >= w * 3);
     VS_ARG(n_src == 1 || src_fs >= img_span(w, h, src_stride, 3));
-    for (int o = 0; o < n_out; o++) {
-        VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);                     // candidate 0 is the frame itself
-        for (int c = 0; c < n_cand && cand_frame[(size_t)o * n_cand + c] >= 0; c++) VS_ARG(cand_frame[(size_t)o * n_cand + c] < n_src);
-    }
+    const CandIndex idx{cand_frame, n_out, n_cand};
+    VS_TRY(idx.check(n_src, false, __func__));
     vs_deflicker_params p;
     VS_TRY(deflicker_params_ok(params, &p));
     if (!vsi::device_ready()) return VS_ERR_HIP;
@@ -1330,11 +1297,8 @@ int vs_bgr_exposure_stats_batch(const void* src, size_t src_fs, int n_src, int w
     Staged a, o;
     VS_TRY(a.in(src, ((size_t)(n_src - 1) * src_fs + img_span(w, h, src_stride, 3)) * esz, mem, s));
     VS_TRY(o.out(stats, (size_t)n_out * n_cand * 8 * sizeof(uint64_t), mem));
-    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
-    for (int i = 0; i < n_out; i++)
-        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++)
-            ptrs[(size_t)i * n_cand + c] = (const char*)a.dev + (size_t)cand_frame[(size_t)i * n_cand + c] * src_fs * esz;
-    VS_TRY(exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.as<uint64_t>(), s));
+    const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * esz);
+    VS_TRY(vsi::exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.as<uint64_t>(), s));
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
@@ -1362,7 +1326,7 @@ int vs_bgr_gain_batch(const void* src, size_t src_fs, int n, int w, int h, int s
                       int dst_stride, int mem, void* stream) try {
     VS_DIMS(w, h);
     int bits = 0;
-    VS_TRY(deblur_format_ok(format, &bits));
+    VS_TRY(bgr_format_ok(format, &bits));
     VS_ARG(src && dst && gains && n >= 1 && src_stride >= w * 3 && dst_stride >= w * 3);
     VS_ARG(n == 1 || (src_fs >= img_span(w, h, src_stride, 3) && dst_fs >= img_span(w, h, dst_stride, 3)));
     if (mem == VS_MEM_HOST)
@@ -1379,26 +1343,3 @@ int vs_bgr_gain_batch(const void* src, size_t src_fs, int n, int w, int h, int s
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
-}  // extern "C"
-
-int vsi::exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
-                             const vs_deflicker_params* params, uint64_t* stats, hipStream_t s) {
-    return ::exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, cand_src, cand_t, params, stats, s);
-}
-
-int vsi::bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
-                          const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
-    return ::bgr_denoise_ptrs(n_out, w, h, src_stride, format, n_cand, cand_src, cand_t, params, dst, dst_fs, dst_stride, s);
-}
-
-int vsi::bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const uint64_t* const* cand_sharp,
-                         const vs_transform* cand_t, const vs_deblur_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
-    return ::bgr_deblur_ptrs(n_out, w, h, src_stride, format, n_cand, cand_src, cand_sharp, cand_t, params, dst, dst_fs, dst_stride, s);
-}
-
-int vsi::bgr_warp_fill_ptrs(const void* src, size_t src_fs, int n_out, int w, int h, int src_stride, int bits, int n_cand, const void* const* cand_src,
-                            const vs_transform* cand_t, int border, int max_value, int roi_x, int roi_y, int roi_w, int roi_h, void* dst, size_t dst_fs,
-                            int dst_stride, hipStream_t s, const uint64_t* const* cand_sums, const vs_fill_blend_params* blend) {
-    return ::bgr_warp_fill_ptrs(src, src_fs, n_out, w, h, src_stride, bits, n_cand, cand_src, cand_t, border, max_value, roi_x, roi_y, roi_w, roi_h, dst,
-                                dst_fs, dst_stride, s, cand_sums, blend);
-}

@@ -59,13 +59,6 @@ constexpr int GN_ROWS = 16, GN_WAVES = 4;                  // gain pass: a wave 
 // row and column offsets, 547 / 548 the candidate's, 549 the statistics word; 550 the gains kernel's reads, 551 its stores; 552 the gain pass's
 // dword accesses (source and destination extents), 553 its per-sample ones.  The extents are written inside the macros' arguments.
 
-// a frame pointer out of a candidate entry: declared global, its gathers are global_load, not flat_load
-template <typename T> using GPtr = const __attribute__((address_space(1))) T*;
-
-__device__ __forceinline__ double readlane_f64(double v, int r) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), r), __builtin_amdgcn_readlane(__double2loint(v), r));
-}
-
 // neither black nor clipped at 8-bit precision
 __device__ __forceinline__ bool es_level_ok(uint32_t v, int shift) { return ((v >> shift) - 1u) < 254u; }
 

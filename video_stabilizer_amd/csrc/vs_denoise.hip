@@ -52,18 +52,6 @@ constexpr int DN_ROWS = 8, DN_ROWS_X4 = 4;                // rows of a strip: pe
 // and column offsets, 536 its gathers, 537 / 542 its store's row and column offsets; 538 / 543, 539, 540 / 544 likewise in the four-pixel kernel).
 // The extents are written inside the macros' arguments, which the regular build drops.
 
-// A candidate's frame: the pointer comes out of the candidate entry, and declared global its gathers are global_load, not flat_load
-template <typename T> using GPtr = const __attribute__((address_space(1))) T*;
-
-struct CvPos { int X, Y; };                                // 5 fraction bits each
-__device__ __forceinline__ CvPos cv_pos(int X0, int Y0, int ad, int bd) {
-    return CvPos{(int)((unsigned)X0 + (unsigned)ad) >> 5, (int)((unsigned)Y0 + (unsigned)bd) >> 5};
-}
-__device__ __forceinline__ bool cv_covers(CvPos p, int w, int h) {
-    const int sx = p.X >> 5, sy = p.Y >> 5;
-    return sx >= 0 && sx + 1 <= w - 1 && sy >= 0 && sy + 1 <= h - 1;
-}
-
 // VS_WARP_BILINEAR_CV's value at a position whose four taps lie inside the frame (vs_fill.hip's cv_sample_inside, operation for operation).
 // r0: the first tap
 __device__ __forceinline__ void cv_blend(GPtr<uint8_t> r0, int stride, CvPos p, int, uint32_t q[3]) {

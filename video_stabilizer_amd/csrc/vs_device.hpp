@@ -181,6 +181,23 @@ __device__ __forceinline__ int cv_delta(double m, int x) { return cv_round_sat(m
 __device__ __forceinline__ int cv_row_origin(double my, double mt, int y) {
     return (int)((unsigned)cv_round_sat((my * (double)y + mt) * 1024.0) + 16u);
 }
+// a sampling position: X0 + adelta[x], Y0 + bdelta[x] without the five INTER_BITS that cv::remap drops first (two's-complement wrap again)
+struct CvPos { int X, Y; };                                // 5 fraction bits each
+__device__ __forceinline__ CvPos cv_pos(int X0, int Y0, int ad, int bd) {
+    return CvPos{(int)((unsigned)X0 + (unsigned)ad) >> 5, (int)((unsigned)Y0 + (unsigned)bd) >> 5};
+}
+// all four taps of the position lie inside the w x h frame
+__device__ __forceinline__ bool cv_covers(CvPos p, int w, int h) {
+    const int sx = p.X >> 5, sy = p.Y >> 5;
+    return sx >= 0 && sx + 1 <= w - 1 && sy >= 0 && sy + 1 <= h - 1;
+}
+// a frame pointer out of a candidate entry (vsk::FillCand, vsk::DeblurCand): declared global, its gathers are global_load, not flat_load
+template <typename T> using GPtr = const __attribute__((address_space(1))) T*;
+
+// v of lane r, in every lane (wave-uniform r)
+__device__ __forceinline__ double readlane_f64(double v, int r) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), r), __builtin_amdgcn_readlane(__double2loint(v), r));
+}
 
 // Lanczos2 sample of a single-channel u8 image with clamp-to-edge addressing:
 // generators.cpp:672-697 (sparse_warpdiff) == :469-498 (sparse_ica).  rx inner, ry outer,

@@ -14,6 +14,7 @@
 //     iteration (the reference makes one Halide call per iteration, alignment.cpp:600-668).
 //   * The transform algebra inside the loop is fp64 on the device, written exactly as imgproc.cpp.
 #include "vs_internal.hpp"
+#include "vs_lookahead.hpp"
 #include "vs_kernels.hpp"
 #include "vs_phase.hpp"
 #include "vs_device.hpp"
@@ -1690,6 +1691,18 @@ static int stab_run_host_pipelined(vs_stabilizer* s, const void* frames, size_t 
     return produced;
 }
 
+// A scratch buffer of the handle grows to `need` bytes.  sync: work on `ws` may still read the old block.  The handle's fields are zeroed before
+// the allocation: after a failed one the handle holds no buffer and the next call starts over (tests/test_alloc_failure_gpu.py).
+static int grow(void** buf, size_t* bytes, size_t need, hipStream_t ws, bool sync) {
+    if (*bytes >= need) return VS_OK;
+    if (sync) VS_HIP(hipStreamSynchronize(ws));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *bytes = 0;
+    VS_HIP(vsi::dev_alloc(buf, need));
+    *bytes = need;
+    return VS_OK;
+}
+
 static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int w, int h, int stride,
                          int format, int mem, int out_mem, int slot_arg, void* out, size_t out_frame_stride, int32_t* has_output,
                          int* out_w, int* out_h) {
@@ -1776,18 +1789,26 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
         s->sharp_blocks.push_back(*out);
         return VS_OK;
     };
-    if (ndb > 0) {
+    // `per` values per frame, measured by launch(frames, where to, how many, frame stride): the call's n frames in one launch into a block of
+    // their own (*out), then every queued frame that lacks the value, one launch each, behind them in the same block
+    using Held = vs_stabilizer::Held;
+    auto measure = [&](size_t per, vs_stabilizer::SharpBlock* keep, vs_stabilizer::SharpBlock* Held::*blk, const unsigned long long* Held::*val, auto launch,
+                       vs_stabilizer::SharpBlock** out) -> int {
         size_t need = (size_t)n;
-        for (auto& f : s->frames) if (!f.sb) need++;
-        VS_TRY(take_block(need, nullptr, &sblk));
-        VS_HIP(vsk::bgr_sharpness(dense, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev, n, (size_t)w * h * 3, st));
+        for (auto& f : s->frames) if (!(f.*blk)) need++;
+        VS_TRY(take_block(per * need, keep, out));
+        VS_HIP(launch(dense, (*out)->dev, n, (size_t)w * h * 3));
         size_t k = (size_t)n;
         for (auto& f : s->frames) {
-            if (f.sb) continue;
-            VS_HIP(vsk::bgr_sharpness(f.ptr, w, h, w * 3, (int)esz * 8, fbits - 8, sblk->dev + k, 1, 0, st));
-            f.sb = sblk; f.sharp = sblk->dev + k; ++sblk->refs; k++;
+            if (f.*blk) continue;
+            VS_HIP(launch(f.ptr, (*out)->dev + per * k, 1, 0));
+            f.*blk = *out; f.*val = (*out)->dev + per * k; ++(*out)->refs; k++;
         }
-    }
+        return VS_OK;
+    };
+    if (ndb > 0)
+        VS_TRY(measure(1, nullptr, &Held::sb, &Held::sharp, [&](const void* p, unsigned long long* to, int m, size_t fs) {
+            return vsk::bgr_sharpness(p, w, h, w * 3, (int)esz * 8, fbits - 8, to, m, fs, st); }, &sblk));
     // fill blend with exposure match (vs_fill.hip): the three channel sums of the call's frames likewise -- one launch, a block of their own, the
     // values stay on the device.  (Queued frames that arrived while the match was off are summed here too, once: switching on mid-clip gives
     // what a handle that had it from the first frame gives.)
@@ -1795,18 +1816,9 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
     const bool blend_on = nfill > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
     const bool want_sums = nfill > 0 && s->fill_blend.match != 0;
     vs_stabilizer::SharpBlock* mblk = nullptr;
-    if (want_sums) {
-        size_t need = (size_t)n;
-        for (auto& f : s->frames) if (!f.mb) need++;
-        VS_TRY(take_block(3 * need, sblk, &mblk));
-        VS_HIP(vsk::bgr_channel_sums(dense, w, h, w * 3, (int)esz * 8, mblk->dev, n, (size_t)w * h * 3, st));
-        size_t k = (size_t)n;
-        for (auto& f : s->frames) {
-            if (f.mb) continue;
-            VS_HIP(vsk::bgr_channel_sums(f.ptr, w, h, w * 3, (int)esz * 8, mblk->dev + 3 * k, 1, 0, st));
-            f.mb = mblk; f.sums = mblk->dev + 3 * k; ++mblk->refs; k++;
-        }
-    }
+    if (want_sums)
+        VS_TRY(measure(3, sblk, &Held::mb, &Held::sums, [&](const void* p, unsigned long long* to, int m, size_t fs) {
+            return vsk::bgr_channel_sums(p, w, h, w * 3, (int)esz * 8, to, m, fs, st); }, &mblk));
     if ((ndb > 0 || want_sums) && warps_apart) {            // the deblur pass / the fill's gain kernel read the values on warp_stream
         VS_HIP(hipEventRecord(s->warp_ev, st));
         VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
@@ -1841,22 +1853,19 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
 
     struct Job { const void* src; vs_transform sampling; int i; void* release; };
     std::vector<Job> jobs;
-    // border fill (vs_fill.hip): per job 1 + nfill candidates -- the frame itself, then the frames that follow it in the queue
-    std::vector<const void*> cand_src;
-    std::vector<vs_transform> cand_t;
-    std::vector<const uint64_t*> cand_sums;        // (exposure match only) where each candidate's channel sums lie: the ORIGINAL frames' throughout
-    // deblur: per job 1 + ndb candidates likewise, with where each frame's sharpness lies
-    std::vector<const void*> db_src;
-    std::vector<const uint64_t*> db_sharp;
-    std::vector<vs_transform> db_t;
-    // denoise (vs_denoise.hip): per job 1 + ndn candidates likewise
-    const int ndn = std::min(s->denoise, s->params.lag);
-    std::vector<const void*> dn_src;
-    std::vector<vs_transform> dn_t;
-    // deflicker (vs_deflicker.hip): per job 1 + nfk candidates likewise; candidate 0 stays the ORIGINAL frame whatever deblur and denoise do
-    const int nfk = std::min(s->deflicker, s->params.lag);
-    std::vector<const void*> fk_src;
-    std::vector<vs_transform> fk_t;
+    // The look-ahead passes (DESIGN.md "Look-ahead passes: the shared path"): per job 1 + n_ahead candidates -- the frame itself, then the frames
+    // that follow it in the queue; null frames and zero transforms behind the end of a list.  `side`: where each candidate's side value lies.
+    struct Ahead {
+        int n;
+        std::vector<const void*> src;
+        std::vector<vs_transform> t;
+        std::vector<const uint64_t*> side;
+    };
+    Ahead fill{nfill};                              // border fill (vs_fill.hip); side (exposure match only): the channel sums, the ORIGINAL frames' throughout
+    Ahead db{ndb};                                  // deblur; side: the sharpness
+    Ahead dn{std::min(s->denoise, s->params.lag)};  // denoise (vs_denoise.hip)
+    Ahead fk{std::min(s->deflicker, s->params.lag)};    // deflicker (vs_deflicker.hip): candidate 0 stays the ORIGINAL frame whatever deblur and denoise do
+    const int ndn = dn.n, nfk = fk.n;
     for (int i = 0; i < n; i++) {
         if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
         ++s->frame_index;
@@ -1911,67 +1920,30 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 jobs.push_back(Job{src.ptr, s->params.warp_mode == VS_WARP_BILINEAR_CV ? correction : vs_transform_inverse(&correction), i,
                                    src.owned ? src.ptr : nullptr});
                 has_output[i] = 1;
-                if (nfill > 0) {
-                    // The queue now holds the frames k+1 .. behind this frame k, `measurements` their motions T_{k+1} .. (T_j: frame j-1 to j), entry
-                    // for entry.  Frame j shows this output through F_j = compose(inverse(T_{k+1} o .. o T_j), correction); a frame whose alignment
-                    // failed ends the list.  (The frames are read before their own jobs release them: releases follow all launches, below.)
-                    cand_src.push_back(src.ptr);
-                    cand_t.push_back(correction);
-                    if (want_sums) cand_sums.push_back((const uint64_t*)src.sums);
-                    vs_transform chain{0, 0, 0, 0};
-                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
-                    int c = 0;
-                    for (; c < nfill && (size_t)c < avail && s->meas_ok[c]; c++) {
-                        chain = vs_transform_compose(&chain, &s->measurements[c]);
-                        const vs_transform back = vs_transform_inverse(&chain);
-                        cand_src.push_back(s->frames[c].ptr);
-                        cand_t.push_back(vs_transform_compose(&back, &correction));
-                        if (want_sums) cand_sums.push_back((const uint64_t*)s->frames[c].sums);
-                    }
-                    for (; c < nfill; c++) {
-                        cand_src.push_back(nullptr); cand_t.push_back(vs_transform{0, 0, 0, 0});
-                        if (want_sums) cand_sums.push_back(nullptr);
-                    }
-                }
-                if (ndb > 0) {
-                    // the same chain without the correction: frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j)
-                    db_src.push_back(src.ptr); db_sharp.push_back((const uint64_t*)src.sharp); db_t.push_back(vs_transform{0, 0, 0, 0});
-                    vs_transform chain{0, 0, 0, 0};
-                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
-                    int c = 0;
-                    for (; c < ndb && (size_t)c < avail && s->meas_ok[c] && s->frames[c].sharp; c++) {
-                        chain = vs_transform_compose(&chain, &s->measurements[c]);
-                        db_src.push_back(s->frames[c].ptr); db_sharp.push_back((const uint64_t*)s->frames[c].sharp);
-                        db_t.push_back(vs_transform_inverse(&chain));
-                    }
-                    for (; c < ndb; c++) { db_src.push_back(nullptr); db_sharp.push_back(nullptr); db_t.push_back(vs_transform{0, 0, 0, 0}); }
-                }
-                if (ndn > 0) {
-                    // the deblur's list: frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j); a failed alignment ends it
-                    dn_src.push_back(src.ptr); dn_t.push_back(vs_transform{0, 0, 0, 0});
-                    vs_transform chain{0, 0, 0, 0};
-                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
-                    int c = 0;
-                    for (; c < ndn && (size_t)c < avail && s->meas_ok[c]; c++) {
-                        chain = vs_transform_compose(&chain, &s->measurements[c]);
-                        dn_src.push_back(s->frames[c].ptr);
-                        dn_t.push_back(vs_transform_inverse(&chain));
-                    }
-                    for (; c < ndn; c++) { dn_src.push_back(nullptr); dn_t.push_back(vs_transform{0, 0, 0, 0}); }
-                }
-                if (nfk > 0) {
-                    // the denoise's list: frame j shows frame k's scene points through inverse(T_{k+1} o .. o T_j); a failed alignment ends it
-                    fk_src.push_back(src.ptr); fk_t.push_back(vs_transform{0, 0, 0, 0});
-                    vs_transform chain{0, 0, 0, 0};
-                    const size_t avail = std::min(s->frames.size(), s->measurements.size());
-                    int c = 0;
-                    for (; c < nfk && (size_t)c < avail && s->meas_ok[c]; c++) {
-                        chain = vs_transform_compose(&chain, &s->measurements[c]);
-                        fk_src.push_back(s->frames[c].ptr);
-                        fk_t.push_back(vs_transform_inverse(&chain));
-                    }
-                    for (; c < nfk; c++) { fk_src.push_back(nullptr); fk_t.push_back(vs_transform{0, 0, 0, 0}); }
-                }
+                // The queue now holds the frames k+1 .. behind this frame k, `measurements` their motions T_{k+1} .. (T_j: frame j-1 to j), entry
+                // for entry.  Frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j), and -- the fill -- this output through F_j =
+                // compose(that, correction); a frame whose alignment failed ends the list (vs_lookahead.hpp).  (The frames are read before their
+                // own jobs release them: releases follow all launches, below.)
+                const size_t avail = std::min(s->frames.size(), s->measurements.size());
+                auto list = [&](Ahead& a, size_t have, const vs_transform& t0, const vs_transform* corr, const unsigned long long* Held::*side) {
+                    if (a.n <= 0) return;
+                    a.src.push_back(src.ptr);
+                    a.t.push_back(t0);
+                    const size_t at = a.t.size();
+                    a.t.resize(at + (size_t)a.n);
+                    const int live = vsi::lookahead_transforms(s->measurements, s->meas_ok, have, a.n, corr, &a.t[at]);
+                    for (int c = 0; c < a.n; c++) a.src.push_back(c < live ? s->frames[c].ptr : nullptr);
+                    if (!side) return;
+                    a.side.push_back((const uint64_t*)(src.*side));
+                    for (int c = 0; c < a.n; c++) a.side.push_back(c < live ? (const uint64_t*)(s->frames[c].*side) : nullptr);
+                };
+                const vs_transform none{0, 0, 0, 0};
+                list(fill, avail, correction, &correction, want_sums ? &Held::sums : nullptr);
+                size_t sharp_avail = 0;                     // the deblur's list also ends at a frame without a sharpness value
+                while (sharp_avail < avail && s->frames[sharp_avail].sharp) sharp_avail++;
+                list(db, sharp_avail, none, nullptr, &Held::sharp);
+                list(dn, avail, none, nullptr, nullptr);
+                list(fk, avail, none, nullptr, nullptr);
             }
         }
     }
@@ -1987,30 +1959,19 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
                 const hipError_t de = s->down[slot].get();
                 if (de != hipSuccess) return set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
             }
-            if (s->batch_out_bytes[slot] < obytes * jobs.size()) {
-                if (s->batch_out[slot]) (void)hipFree(s->batch_out[slot]);
-                s->batch_out[slot] = nullptr; s->batch_out_bytes[slot] = 0;
-                VS_HIP(vsi::dev_alloc(&s->batch_out[slot], obytes * jobs.size()));
-                s->batch_out_bytes[slot] = obytes * jobs.size();
-            }
+            VS_TRY(grow(&s->batch_out[slot], &s->batch_out_bytes[slot], obytes * jobs.size(), nullptr, false));    // (drained through down[slot], above)
         }
         if (ndb > 0) {
             // every due frame is deblurred into a scratch frame of its own, one launch, in front of the warps on their stream; the warps (and the
             // fill's candidate 0) then read the scratch frames.  The candidates are read before their own jobs release them: releases follow below.
             hipStream_t ws = warps_apart ? s->warp_stream : st;
-            if (s->deblur_bytes < fbytes * jobs.size()) {
-                VS_HIP(hipStreamSynchronize(ws));           // (warps of an earlier chunk may still read the area)
-                if (s->deblur_buf) (void)hipFree(s->deblur_buf);
-                s->deblur_buf = nullptr; s->deblur_bytes = 0;
-                VS_HIP(vsi::dev_alloc(&s->deblur_buf, fbytes * jobs.size()));
-                s->deblur_bytes = fbytes * jobs.size();
-            }
-            const int dr = vsi::bgr_deblur_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndb, db_src.data(), db_sharp.data(), db_t.data(), &s->deblur_params,
+            VS_TRY(grow(&s->deblur_buf, &s->deblur_bytes, fbytes * jobs.size(), ws, true));     // (warps of an earlier chunk may still read the area)
+            const int dr = vsi::bgr_deblur_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndb, db.src.data(), db.side.data(), db.t.data(), &s->deblur_params,
                                                 s->deblur_buf, (size_t)w * h * 3, w * 3, ws);
             if (dr < 0) return dr;
             for (size_t j = 0; j < jobs.size(); j++) {
                 jobs[j].src = (const uint8_t*)s->deblur_buf + j * fbytes;
-                if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
+                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
             }
         }
         if (ndn > 0) {
@@ -2018,20 +1979,14 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             // their stream; the warps (and the fill's candidate 0) then read the scratch frames.  The candidates are the original input frames,
             // read before their own jobs release them: releases follow below.
             hipStream_t ws = warps_apart ? s->warp_stream : st;
-            if (s->denoise_bytes < fbytes * jobs.size()) {
-                VS_HIP(hipStreamSynchronize(ws));           // (warps of an earlier chunk may still read the area)
-                if (s->denoise_buf) (void)hipFree(s->denoise_buf);
-                s->denoise_buf = nullptr; s->denoise_bytes = 0;
-                VS_HIP(vsi::dev_alloc(&s->denoise_buf, fbytes * jobs.size()));
-                s->denoise_bytes = fbytes * jobs.size();
-            }
-            for (size_t j = 0; j < jobs.size(); j++) dn_src[j * (1 + ndn)] = jobs[j].src;
-            const int dr = vsi::bgr_denoise_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndn, dn_src.data(), dn_t.data(), &s->denoise_params, s->denoise_buf,
+            VS_TRY(grow(&s->denoise_buf, &s->denoise_bytes, fbytes * jobs.size(), ws, true));   // (warps of an earlier chunk may still read the area)
+            for (size_t j = 0; j < jobs.size(); j++) dn.src[j * (1 + ndn)] = jobs[j].src;
+            const int dr = vsi::bgr_denoise_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndn, dn.src.data(), dn.t.data(), &s->denoise_params, s->denoise_buf,
                                                  (size_t)w * h * 3, w * 3, ws);
             if (dr < 0) return dr;
             for (size_t j = 0; j < jobs.size(); j++) {
                 jobs[j].src = (const uint8_t*)s->denoise_buf + j * fbytes;
-                if (nfill > 0) cand_src[j * (1 + nfill)] = jobs[j].src;
+                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
             }
         }
         uint32_t* fk_gains = nullptr;
@@ -2041,15 +1996,9 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             // reaches the host; the gain pass behind each run's warp (and fill) reads the gains there.
             hipStream_t ws = warps_apart ? s->warp_stream : st;
             const size_t sbytes = jobs.size() * (size_t)(1 + nfk) * 8 * sizeof(uint64_t), need = sbytes + jobs.size() * 4 * sizeof(uint32_t);
-            if (s->flicker_bytes < need) {
-                VS_HIP(hipStreamSynchronize(ws));           // (gain passes of an earlier chunk may still read the block)
-                if (s->flicker_buf) (void)hipFree(s->flicker_buf);
-                s->flicker_buf = nullptr; s->flicker_bytes = 0;
-                VS_HIP(vsi::dev_alloc(&s->flicker_buf, need));
-                s->flicker_bytes = need;
-            }
+            VS_TRY(grow(&s->flicker_buf, &s->flicker_bytes, need, ws, true));                   // (gain passes of an earlier chunk may still read the block)
             fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf + sbytes);
-            const int fr = vsi::exposure_stats_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + nfk, fk_src.data(), fk_t.data(), &s->deflicker_params,
+            const int fr = vsi::exposure_stats_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + nfk, fk.src.data(), fk.t.data(), &s->deflicker_params,
                                                     (uint64_t*)s->flicker_buf, ws);
             if (fr < 0) return fr;
             VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf, (int)jobs.size(), 1 + nfk, w, h, s->deflicker_params.step, fk_gains, ws));
@@ -2070,9 +2019,9 @@ static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t 
             struct SlotHint { bool& f; bool old; SlotHint(bool on) : f(vsi::warp_keeps_solver_slot()), old(f) { f = on; } ~SlotHint() { f = old; } } hint(s->overlap_warps);
             int wr;
             if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
-                wr = vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, (int)esz * 8, 1 + nfill, &cand_src[j * (1 + nfill)],
-                                             &cand_t[j * (1 + nfill)], s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh, dst, dst_fs,
-                                             ow * 3, ws, want_sums ? &cand_sums[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr);
+                wr = vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, (int)esz * 8, 1 + nfill, &fill.src[j * (1 + nfill)],
+                                             &fill.t[j * (1 + nfill)], s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh, dst, dst_fs,
+                                             ow * 3, ws, want_sums ? &fill.side[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr);
             else
                 wr = vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, (int)esz * 8, ts.data(),
                                                  s->params.warp_mode, s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh,

@@ -42,15 +42,6 @@ constexpr int FL_W = 64, FL_ROWS = 16, FL_WAVES = 4;      // a wave's strip: 64 
 constexpr int FL_BLOCK = 256;                              // a workgroup's block of output pixels (a side): 4 x 4 tiles
 static_assert(FL_BLOCK % FL_W == 0 && FL_BLOCK % (FL_ROWS * FL_WAVES) == 0, "whole tiles");
 
-struct CvPos { int X, Y; };                                // 5 fraction bits each
-__device__ __forceinline__ CvPos cv_pos(int X0, int Y0, int ad, int bd) {
-    return CvPos{(int)((unsigned)X0 + (unsigned)ad) >> 5, (int)((unsigned)Y0 + (unsigned)bd) >> 5};
-}
-__device__ __forceinline__ bool cv_covers(CvPos p, int w, int h) {
-    const int sx = p.X >> 5, sy = p.Y >> 5;
-    return sx >= 0 && sx + 1 <= w - 1 && sy >= 0 && sy + 1 <= h - 1;
-}
-
 // candidate 0 (matrix M) covers every pixel of the nx x ny rectangle at (x0, y0) of the output window.  Every table term within 2^29: the sums
 // cannot wrap, and with monotone terms the extremes of X and Y over the rectangle are sums of corner terms.
 __device__ __forceinline__ bool cv_covers_rect(const double M[6], vsk::Roi roi, int x0, int y0, int nx, int ny, int w, int h) {
