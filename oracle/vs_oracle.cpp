@@ -1107,6 +1107,44 @@ vso_stabilizer* vso_stabilizer_create(const vso_stabilizer_params* p) {
 }
 void vso_stabilizer_destroy(vso_stabilizer* s) { delete s; }
 
+/* the scalar bookkeeping of one processFrame (stabilizer.cpp:35-99): returns 1 when a measurement was finalised; *correction is then what the
+ * reference hands to its warp, inverse(the new accum) */
+int vso_stabilizer_step(vso_stabilizer* s, const vso_transform* meas, int success, int w, int h, vso_transform* correction) {
+    const vso_transform currentMeas = *meas;
+    bool reset = !success;
+    vso_transform earliestSmoothed{0, 0, 0, 0};
+    if (s->params.enable_smoother) vso_smoother_update(&s->smoother, &currentMeas, &earliestSmoothed);   /* :35, return ignored */
+    if (reset) s->accum = vso_transform{0, 0, 0, 0};
+    s->measurementBuffer.push_back(currentMeas);
+    bool hasFinalized = s->measurementBuffer.size() > (size_t)s->params.lag;
+    if (!hasFinalized) return 0;
+    vso_transform earliestMeas = s->measurementBuffer.front();
+    s->measurementBuffer.pop_front();
+    vso_transform jitter;
+    if (s->params.enable_smoother) {
+        vso_transform inv = vso_transform_inverse(&earliestSmoothed);
+        jitter = vso_transform_compose(&earliestMeas, &inv);
+    } else {
+        jitter = earliestMeas;
+    }
+    vso_transform newAccum = vso_transform_compose(&s->accum, &jitter);
+    double displacement = vso_transform_max_corner_displacement(&newAccum, w, h);
+    double decay = 1.0;
+    if (displacement > s->params.max_disp) {
+        decay = s->params.max_decay;
+    } else if (displacement > s->params.min_disp) {
+        double f = (displacement - s->params.min_disp) / (s->params.max_disp - s->params.min_disp);
+        f = std::max(0.0, std::min(1.0, f));
+        decay = s->params.min_decay * (1.0 - f) + s->params.max_decay * f;
+    } else {
+        decay = s->params.min_decay;
+    }
+    newAccum.TX *= decay; newAccum.TY *= decay; newAccum.A *= decay; newAccum.B *= decay;
+    s->accum = newAccum;
+    *correction = vso_transform_inverse(&newAccum);
+    return 1;
+}
+
 int vso_stabilizer_process(vso_stabilizer* s, const void* frame, int w, int h, int stride, int format, void* out,
                            int* out_w, int* out_h) {
     if (!s || !frame || format == VSO_FMT_GRAY8 || vso_format_bits(format) == 0) return -1;
@@ -1124,43 +1162,14 @@ int vso_stabilizer_process(vso_stabilizer* s, const void* frame, int w, int h, i
     bool success = vso_aligner_align_next(&s->aligner, frame, w, h, stride, format, &s->params.aligner, &currentMeas) == 1;
     s->lastMeas = currentMeas; s->lastSuccess = success ? 1 : 0;
 
-    bool reset = !success;
-    vso_transform earliestSmoothed{0, 0, 0, 0};
-    if (s->params.enable_smoother) vso_smoother_update(&s->smoother, &currentMeas, &earliestSmoothed);   /* :35, return ignored */
-    if (reset) s->accum = vso_transform{0, 0, 0, 0};
-    s->measurementBuffer.push_back(currentMeas);
-    bool hasFinalized = s->measurementBuffer.size() > (size_t)s->params.lag;
+    vso_transform correction;
     int produced = 0;
-    if (hasFinalized) {
-        vso_transform earliestMeas = s->measurementBuffer.front();
-        s->measurementBuffer.pop_front();
-        vso_transform jitter;
-        if (s->params.enable_smoother) {
-            vso_transform inv = vso_transform_inverse(&earliestSmoothed);
-            jitter = vso_transform_compose(&earliestMeas, &inv);
-        } else {
-            jitter = earliestMeas;
-        }
-        vso_transform newAccum = vso_transform_compose(&s->accum, &jitter);
-        double displacement = vso_transform_max_corner_displacement(&newAccum, w, h);
-        double decay = 1.0;
-        if (displacement > s->params.max_disp) {
-            decay = s->params.max_decay;
-        } else if (displacement > s->params.min_disp) {
-            double f = (displacement - s->params.min_disp) / (s->params.max_disp - s->params.min_disp);
-            f = std::max(0.0, std::min(1.0, f));
-            decay = s->params.min_decay * (1.0 - f) + s->params.max_decay * f;
-        } else {
-            decay = s->params.min_decay;
-        }
-        newAccum.TX *= decay; newAccum.TY *= decay; newAccum.A *= decay; newAccum.B *= decay;
-        s->accum = newAccum;
+    if (vso_stabilizer_step(s, &currentMeas, success ? 1 : 0, w, h, &correction)) {
         if (!s->frameBuffer.empty()) {
             std::vector<uint8_t> frameToStabilize = std::move(s->frameBuffer.front());
             s->frameBuffer.pop_front();
             /* :97-99: warpBySimilarityTransform(frame, correction) where cv::warpAffine
              * *inverts* the matrix it is given (imgproc.cpp:472) => sampling map = correction^-1 */
-            vso_transform correction = vso_transform_inverse(&newAccum);
             vso_transform sampling = vso_transform_inverse(&correction);
             std::vector<uint8_t> warped((size_t)w * h * 3 * esz);
             /* (VSO_WARP_BILINEAR_CV restates cv::warpAffine itself, inversion included: it takes the correction as the reference hands it over) */

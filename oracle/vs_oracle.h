@@ -190,6 +190,9 @@ void vso_stabilizer_destroy(vso_stabilizer*);
  * returns 1 if an output frame was produced, 0 if not yet, <0 error. */
 int  vso_stabilizer_process(vso_stabilizer*, const void* frame, int w, int h, int stride_elems, int format,
                             void* out, int* out_w, int* out_h);
+/* the scalar bookkeeping inside vso_stabilizer_process (stabilizer.cpp:35-99), callable on its own: the measurement of the next frame (w x h) and
+ * its success flag enter; returns 1 when a measurement was finalised, *correction = inverse(the new accum) then */
+int  vso_stabilizer_step(vso_stabilizer*, const vso_transform* meas, int success, int w, int h, vso_transform* correction);
 /* last measurement / accumulated correction, for parity of the scalar bookkeeping */
 void vso_stabilizer_state(const vso_stabilizer*, vso_transform* last_meas, vso_transform* accum, int* last_success);
 

@@ -1,6 +1,6 @@
 """The debug build with bounds-checked LDS / scratch indexing ("bounds asserts in debug kernels"; GPU
 AddressSanitizer is not available on this pool).  tools/build_variant.sh bounds compiles vs_engine / vs_warp / vs_fill / vs_deblur / vs_phase /
-vs_flow / vs_capi with -DVS_DEBUG_BOUNDS: the gathers and stores of the border fill and the deblur (global memory: element offsets within a frame, sites 501-522), the selection arrays (introselect_*, stable_select), the gather / exchange / staging indices of the fused
+vs_flow / vs_capi with -DVS_DEBUG_BOUNDS (vs_stabilizer, host code only, and the other objects come from the regular build): the gathers and stores of the border fill and the deblur (global memory: element offsets within a frame, sites 501-522), the selection arrays (introselect_*, stable_select), the gather / exchange / staging indices of the fused
 aligner kernel, the warp's tile fill and tap windows, the FFT lines and the dense flow's LDS tiles, histograms and per-thread scratch offsets are indexed through
 vsd::Span / VS_BOUNDS_CHECK / VS_IDX (vs_device.hpp).  A violation is recorded (site, index, limit, workgroup, thread) and redirected to element 0, never executed.
 

@@ -1,6 +1,6 @@
 """The stabilizer's scheduling machinery cannot change a byte.  Device-resident vs_stabilizer_process_clips / _batch run by default with
 the warps on a second stream, the next chunk's alignment prefetched, deferred buffer release and the small-footprint solver build
-(vs_engine.hip stab_run); every piece has a switch that is read ONCE per process (VS_STAB_OVERLAP, VS_STAB_PREFETCH,
+(vs_stabilizer.hip stab_run); every piece has a switch that is read ONCE per process (VS_STAB_OVERLAP, VS_STAB_PREFETCH,
 VS_GN_CORESIDENT), so each combination runs in a child process and prints a digest of its outputs: all must be equal -- to each other
 and to the frame-by-frame calls.  VS_GN_SELECT_DEPTH=2 on top sends every pair through the "libstdc++ would have heap-selected" exit
 (fail_reason 100 -> the chunk is redone through the per-level host path) while a prefetched chunk is in flight: still the same bytes.

@@ -1,5 +1,5 @@
-// vs_engine.hip -- engine level of the C ABI: VideoAligner (alignment.cpp:149-704) and
-// VideoStabilizer (stabilizer.cpp:9-117) as a device-resident, batched pipeline.
+// vs_engine.hip -- engine level of the C ABI: VideoAligner (alignment.cpp:149-704) as a device-resident, batched pipeline
+// (VideoStabilizer, stabilizer.cpp:9-117, on top of it: vs_stabilizer.hip).
 //
 // Design (DESIGN.md "Engine"):
 //   * Gray pyramids of every frame of a batch live in HBM in one slab: slot s, level l at
@@ -13,8 +13,7 @@
 //     device until it converges / diverges / runs out of iterations -- no host round trip per
 //     iteration (the reference makes one Halide call per iteration, alignment.cpp:600-668).
 //   * The transform algebra inside the loop is fp64 on the device, written exactly as imgproc.cpp.
-#include "vs_internal.hpp"
-#include "vs_lookahead.hpp"
+#include "vs_engine.hpp"
 #include "vs_kernels.hpp"
 #include "vs_phase.hpp"
 #include "vs_device.hpp"
@@ -25,18 +24,16 @@
 #include <mutex>
 #include <cmath>
 #include <cstring>
-#include <deque>
 #include <thread>
-#include <cstdlib>
-#include <future>
-#include <string>
 #include <vector>
 
 using vsi::set_error;
+using vsi::kSharedMinPairs;
+using vsi::run_async;
+using vsi::align_start;
+using vsi::align_finish;
+using vsi::align_abandon;
 using namespace vsd;
-
-#define VS_TRY(expr) do { int _r = (expr); if (_r < 0) return _r; } while (0)
-#define VS_ARG(cond) do { if (!(cond)) return set_error(VS_ERR_ARG, "bad argument: %s (%s)", #cond, __func__); } while (0)
 
 namespace {
 
@@ -269,7 +266,6 @@ constexpr int kGnThreads = 256, kGnVirt = 512;
 #undef VS_GN_FUSED_BOUNDS
 }  // namespace nt256v
 constexpr int kCoResidentMaxTiles = 128 * 256;          // introselect_block_g: 128 elements per thread (and <= kSelectCap)
-constexpr int kSharedMinPairs = 32;                    // VS_BATCH_SHARED: launches of at least this many pairs take the small-footprint build
 constexpr size_t kCoResidentDynMax = 32 * 1024;        // dynamic LDS of the small-footprint build; larger levels select on global scratch
 constexpr int kSmallWgTiles = 26000;     // largest level handled by the 512-thread kernels (<= kSelectCap <= 64 * 512)
 constexpr int kPipelineMaxPairs = 128;   // half the CUs
@@ -281,27 +277,7 @@ VS_BOUNDS_TU(vs_bounds_fetch_engine)
 // =================================================================================================
 // VideoAligner
 // =================================================================================================
-// host-resident video is uploaded in chunks of about this many bytes (192 MB = ~3.4 ms on PCIe 5 x16; measured on MI355X:
-// 24 / 48 / 96 / 192 MB chunks reach 0.70 / 0.80 / 0.90 / 0.91 of the pinned-copy rate on a 1.5 GB batch -- every chunk
-// costs a thread hand-over and a pipeline drain);
-// VS_INGEST_CHUNK_BYTES overrides it (the tests use it to run many small chunks through the pipeline)
-static size_t ingest_chunk_bytes() {
-    const char* e = getenv("VS_INGEST_CHUNK_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (size_t)v : (size_t)192 << 20;
-}
-#define kIngestBytes ingest_chunk_bytes()
-
-// Runs `fn(args...)` on a worker thread.  std::async may throw (std::system_error) when no thread can be started; no exception
-// may cross the C ABI, so in that case the task runs on the calling thread (std::launch::deferred) -- no overlap, same result.
-template <typename F, typename... A>
-static std::future<hipError_t> run_async(F&& fn, A&&... args) {
-    try {
-        return std::async(std::launch::async, fn, args...);
-    } catch (...) {
-        return std::async(std::launch::deferred, fn, args...);
-    }
-}
+#define kIngestBytes vsi::ingest_chunk_bytes()
 
 struct vs_aligner {
     int device = 0;
@@ -1150,7 +1126,7 @@ static void align_failed(vs_aligner* a) {
     for (vs_aligner::Span& sp : a->spans) { a->event_pool.push_back(sp.a); a->event_pool.push_back(sp.b); }
     a->spans.clear();
 }
-static int align_start(vs_aligner* a, const void* frames, size_t frame_stride, int n, int clip_frames, int w, int h, int stride, int format,
+int vsi::align_start(vs_aligner* a, const void* frames, size_t frame_stride, int n, int clip_frames, int w, int h, int stride, int format,
                        int mem, const vs_aligner_params* params, vs_transform* out, int32_t* status, bool async) {
     VS_ARG(a && clip_frames >= 0);
     if (a->started || a->ck.open) return set_error(VS_ERR_ARG, "an alignment is already in flight on this handle");
@@ -1163,7 +1139,7 @@ static int align_start(vs_aligner* a, const void* frames, size_t frame_stride, i
     if (r < 0) { a->started = false; align_close_clips(a); if (r != VS_ERR_ARG) align_failed(a); }
     return r;
 }
-static int align_finish(vs_aligner* a) {
+int vsi::align_finish(vs_aligner* a) {
     int r = a->started_result;
     if (a->started) {
         a->started = false;
@@ -1175,7 +1151,7 @@ static int align_finish(vs_aligner* a) {
     return r;
 }
 // an alignment that was started and will not be finished (an error elsewhere): drain the stream, forget the chunk
-static void align_abandon(vs_aligner* a) {
+void vsi::align_abandon(vs_aligner* a) {
     if (a->ck.open) { (void)hipStreamSynchronize(a->stream); a->ck.open = false; }
     a->started = false;
     align_close_clips(a);
@@ -1351,878 +1327,7 @@ int vs_aligner_read_level_jacobian(const vs_aligner* a, int i, int level, int se
 
 }  // extern "C"
 
-// =================================================================================================
-// VideoStabilizer (stabilizer.cpp:3-117): scalar bookkeeping on the host, frames stay in HBM
-// =================================================================================================
-struct vs_stabilizer {
-    vs_stabilizer_params params;
-    vs_aligner* aligner = nullptr;
-    vs_smoother* smoother = nullptr;
-    int frame_index = 0;
-    std::deque<vs_transform> measurements;
-    std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
-    int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
-    vs_fill_blend_params fill_blend{0, 0};   // vs_stabilizer_set_fill_blend.  With match on, the three channel sums of every queued frame lie in device
-                                   // memory like the sharpness below: in blocks of the same pool, under the same reference protocol (Held::mb / sums)
-    // deblur (vs_deblur.hip): the sharpness of every queued frame lies in device memory, one value per frame in a block taken per call; a block is
-    // free again when no queued frame and no launch in flight refers to it (refs; sharp_pending: references given up, counted down at the next point
-    // where every reader has been ordered before whatever may refill the block)
-    struct SharpBlock { unsigned long long* dev; size_t cap; int refs; };
-    std::vector<SharpBlock*> sharp_blocks, sharp_pending;
-    int deblur = 0;                // vs_stabilizer_set_deblur: following frames a frame is deblurred from (0: off)
-    vs_deblur_params deblur_params{2.0f, 4.0f};
-    void* deblur_buf = nullptr; size_t deblur_bytes = 0;     // the deblurred frames of the current call: the source of its warps
-    // temporal denoise (vs_denoise.hip)
-    int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
-    vs_denoise_params denoise_params{24};
-    void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
-    // deflicker (vs_deflicker.hip)
-    int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
-    vs_deflicker_params deflicker_params{4};
-    void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
-    struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
-                  SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
-    std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
-    std::vector<void*> pool;       // recycled frame buffers
-    size_t frame_bytes = 0;
-    void* batch_in = nullptr; size_t batch_in_bytes = 0;     // dense device copy of the current batch
-    // host callers: cropped outputs of the current chunk on their way down.  Two areas, used alternately by the chunks of a
-    // pipelined batch; a downloader thread drains area k on down_stream while the next chunk is computed into area k^1.
-    void* batch_out[2] = {nullptr, nullptr}; size_t batch_out_bytes[2] = {0, 0};
-    std::future<hipError_t> down[2];
-    hipEvent_t down_ev[2] = {nullptr, nullptr};
-    hipStream_t down_stream = nullptr, up_stream = nullptr;
-    void* pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_bytes = 0;     // upload areas of a pipelined host batch
-    // PITCHED host frames travel as ONE linear copy of their whole span (gaps included) into a device area and are made dense by device-to-device
-    // 2-D copies: the HIP runtime never gets a 2-D copy out of pageable caller memory (profiles/r06_flake.md); dense frames: one linear copy as ever
-    void* span_in[2] = {nullptr, nullptr}; size_t span_in_bytes[2] = {0, 0};
-    // device-resident clip batches: the warps of clip group g run on warp_stream under the alignment of group g + 1 (stab_run)
-    hipStream_t warp_stream = nullptr;
-    hipEvent_t warp_ev = nullptr;
-    bool overlap_warps = false;    // set by stab_run around the group / chunk calls
-    bool defer_own = false;        // set for all but the last time chunk of one long device-resident clip: frames still queued stay
-                                   // pointers into the caller's batch (it outlives the call), only the last chunk copies them out
-    std::vector<void*> held_release;   // buffers whose last reader is a warp on warp_stream: back into the pool after its synchronisation
-    // alignment results of the chunk being processed [tb] and of the chunk whose alignment is already running [tb ^ 1]
-    std::vector<vs_transform> t_buf[2];
-    std::vector<int32_t> st_buf[2];
-    int tb = 0;
-    bool prefetched = false;       // the alignment of the next stab_run_impl call's frames has been started by the previous call
-    const void* next_frames = nullptr; int next_n = 0;   // set by stab_run: the chunk after the one being processed (0: none)
-    vs_transform accum{0, 0, 0, 0}, last_meas{0, 0, 0, 0};
-    int last_success = 0;
-    int w = 0, h = 0, fmt = -1;
-};
-
-static void sharp_unhold(vs_stabilizer* s, vs_stabilizer::Held& f) {
-    if (f.sb) s->sharp_pending.push_back(f.sb);
-    if (f.mb) s->sharp_pending.push_back(f.mb);
-    f.sb = nullptr; f.sharp = nullptr;
-    f.mb = nullptr; f.sums = nullptr;
-}
-static void sharp_settle(vs_stabilizer* s) {
-    for (auto* b : s->sharp_pending) --b->refs;
-    s->sharp_pending.clear();
-}
-static void stab_drop_frames(vs_stabilizer* s) {
-    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) (void)hipFree(f.ptr); }
-    for (void* p : s->pool) (void)hipFree(p);
-    s->frames.clear();
-    s->pool.clear();
-}
-
-extern "C" {
-
-vs_stabilizer* vs_stabilizer_create(const vs_stabilizer_params* params, int device) try {
-    vs_stabilizer_params p;
-    if (params) p = *params; else vs_stabilizer_params_default(&p);
-    vs_aligner* a = vs_aligner_create(&p.aligner, device);
-    if (!a) return nullptr;
-    // the aligner owns streams and device slabs: whatever fails from here on releases it (a host allocation that throws included)
-    struct Guard { vs_aligner* a; ~Guard() { if (a) vs_aligner_destroy(a); } } guard{a};
-    vs_stabilizer* s = new vs_stabilizer();
-    s->params = p;
-    s->aligner = a;
-    guard.a = nullptr;                                     // (from here vs_stabilizer_destroy releases it)
-    s->smoother = vs_smoother_create(p.lag, p.smoother_memory, p.lambda);   // stabilizer.cpp:4
-    if (!s->smoother) { vs_stabilizer_destroy(s); return nullptr; }         // (last error: the smoother's)
-    return s;
-} VS_CATCH_ALL_NULL
-
-void vs_stabilizer_destroy(vs_stabilizer* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->aligner->device);
-    stab_drop_frames(s);
-    for (auto& f : s->down) if (f.valid()) (void)f.get();
-    for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
-    if (s->deblur_buf) (void)hipFree(s->deblur_buf);
-    if (s->denoise_buf) (void)hipFree(s->denoise_buf);
-    if (s->flicker_buf) (void)hipFree(s->flicker_buf);
-    if (s->batch_in) (void)hipFree(s->batch_in);
-    for (void* q : s->batch_out) if (q) (void)hipFree(q);
-    for (void* q : s->pipe_in) if (q) (void)hipFree(q);
-    for (void* q : s->span_in) if (q) (void)hipFree(q);
-    for (hipEvent_t e : s->down_ev) if (e) (void)hipEventDestroy(e);
-    if (s->warp_stream) { (void)vsi::retire_stream(s->warp_stream); (void)hipStreamDestroy(s->warp_stream); }
-    if (s->warp_ev) (void)hipEventDestroy(s->warp_ev);
-    if (s->down_stream) (void)hipStreamDestroy(s->down_stream);
-    if (s->up_stream) (void)hipStreamDestroy(s->up_stream);
-    vs_smoother_destroy(s->smoother);
-    vs_aligner_destroy(s->aligner);
-    delete s;
-}
-
-// n successive VideoStabilizer::processFrame calls (stabilizer.cpp:9-117) as one batch: one batched alignment,
-// the scalar bookkeeping on the host exactly as the reference orders it, then batched warps of every frame that
-// became due.  has_output[i] = 1 when input frame i produced an output, written to out + i*out_frame_stride.
-int vs_stabilizer_reset(vs_stabilizer* s);
-
-// n successive processFrame calls; clip_len > 0: the n frames are n / clip_len independent clips, each run through a
-// fresh stabilizer (reset before every clip and after the last), all of them aligned and warped together.
-static int stab_run_impl(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int w, int h, int stride,
-                         int format, int in_mem, int out_mem, int slot, void* out, size_t out_frame_stride, int32_t* has_output,
-                         int* out_w, int* out_h);
-static int stab_run_host_pipelined(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int chunk, int w,
-                                   int h, int stride, int format, void* out, size_t out_frame_stride, int32_t* has_output, int* out_w,
-                                   int* out_h);
-
-// While a batch is in flight the frame queue holds non-owned pointers into the caller's buffer (or into batch_in); they
-// become copies of our own only at the end of a successful run.  Whatever stops a run early -- a HIP error, a refused
-// warp -- must not leave such an entry behind for the next call to warp from: the stabilizer is reset to a clean
-// "new clip" state (and the stream drained, so nothing still reads the caller's frames), and the error is passed on.
-static int stab_run(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int w, int h, int stride,
-                    int format, int mem, void* out, size_t out_frame_stride, int32_t* has_output, int* out_w, int* out_h) {
-    // host-resident batches longer than one upload chunk run as a three-stage pipeline: upload / compute / download
-    int chunk = 0;
-    if (s && mem == VS_MEM_HOST && n > 1 && w > 0 && h > 0) {
-        const size_t fb = (size_t)w * h * 3 * (vs_format_bits(format) > 8 ? 2 : 1);
-        chunk = (int)std::max<size_t>(4, kIngestBytes / std::max<size_t>(1, fb));
-        if (clip_len > 0) chunk = std::max(clip_len, chunk - chunk % clip_len);
-    }
-    int r;
-    // Device-resident clip batches (vs_stabilizer_process_clips, VS_MEM_DEVICE, dense frames): the clips are cut into groups and the
-    // warps of group g go to a stream of their own, so that they run under the alignment of group g + 1 -- which then takes the
-    // small-footprint solver build (VS_BATCH_SHARED: it shares CUs with the warp grid).  Every group goes through stab_run_impl
-    // exactly as a process_clips call of its own would (clips are independent: stabilizer.cpp keeps no state across a reset), so
-    // the grouping cannot change results.  VS_STAB_OVERLAP=0 turns it off.
-    static const bool overlap_env = []() { const char* e = getenv("VS_STAB_OVERLAP"); return e ? atoi(e) != 0 : true; }();
-    static const bool prefetch_env = []() { const char* e = getenv("VS_STAB_PREFETCH"); return e ? atoi(e) != 0 : true; }();
-    // (the solver build under the overlapped warps: the small-footprint one beside a Lanczos2 warp, which fills the CUs for longer than the
-    // alignment pass takes; beside the fixed-point bilinear warp -- a quarter of the alignment pass -- the exclusive 512-thread build, whose
-    // shorter solver chain is worth more than the shared CUs: 1080p x 480 frames 101 k -> 120 k frames/s, 4K x 240 21.1 k -> 34.3 k
-    // (profiles/r05_stab_cv_solver.txt; VS_STAB_CV_SOLVER=1 selects the small build for an A/B))
-    static const int cv_solver_env = []() { const char* e = getenv("VS_STAB_CV_SOLVER"); return e && atoi(e) == VS_BATCH_SHARED ? VS_BATCH_SHARED : VS_BATCH_EXCLUSIVE; }();
-    const int overlap_mode = s && s->params.warp_mode == VS_WARP_BILINEAR_CV ? cv_solver_env : VS_BATCH_SHARED;
-    const int n_clips_all = clip_len > 0 ? n / clip_len : 0;
-    const bool dense_dev = s && mem == VS_MEM_DEVICE && w > 0 && stride == 3 * w && frame_stride == (size_t)h * stride;
-    int group_clips = 0;
-    if (overlap_env && dense_dev && clip_len >= 2 && n_clips_all >= 2 && n == n_clips_all * clip_len) {
-        // groups of at least kSharedMinPairs pairs (the small build's threshold), at most 4 groups (VS_STAB_GROUPS): every group boundary is a host
-        // synchronisation and a latency-bound solver launch -- c5 (8 clips x 60 x 4K 10-bit) 17.3-18.1 k frames/s with 8 groups, 18.9-19.5 k with 4
-        group_clips = std::max(1, (kSharedMinPairs + clip_len - 2) / (clip_len - 1));
-        // (beside the fixed-point bilinear warp, with the exclusive solver build: 2 groups -- c5 27.8 k frames/s with 4 groups, 28.9 k with 2, 24.8 k with 8)
-        static const int groups_env = []() { const char* e = getenv("VS_STAB_GROUPS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 0; }();
-        const int max_groups = groups_env ? groups_env : (overlap_mode == VS_BATCH_EXCLUSIVE ? 2 : 4);
-        group_clips = std::max(group_clips, (n_clips_all + max_groups - 1) / max_groups);
-        if (group_clips >= n_clips_all) group_clips = 0;
-    }
-    // one long clip: time chunks of >= 48 frames (the small solver build's threshold with room to spare), at most 4 of them (VS_STAB_TIME_CHUNKS:
-    // 1080p x480 64 k frames/s with 8 chunks, 70 k with 6, 72 k with 4 or 3, 69-71 k with 2; profiles/r04_stab_long_clip.txt)
-    int time_chunk = 0;
-    static const int max_time_chunks = []() { const char* e = getenv("VS_STAB_TIME_CHUNKS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 4; }();
-    // (with the exclusive solver build a chunk is a latency-bound chain of its own: chunks of >= 120 frames -- 4K x240 34.2 k frames/s in 4 chunks, 35.8 k in 2)
-    if (overlap_env && dense_dev && clip_len == 0 && n >= 96)
-        time_chunk = std::max(overlap_mode == VS_BATCH_EXCLUSIVE ? 120 : 48, (n + max_time_chunks - 1) / max_time_chunks);
-    if (time_chunk >= n) time_chunk = 0;
-    if (chunk > 0 && n > chunk)
-        r = vsi::guarded([&] { return stab_run_host_pipelined(s, frames, frame_stride, n, clip_len, chunk, w, h, stride, format, out, out_frame_stride,
-                                                              has_output, out_w, out_h); });
-    else if (group_clips > 0) {
-        vs_aligner* a = s->aligner;
-        r = 0;
-        hipError_t he = hipSetDevice(a->device);
-        if (he == hipSuccess && !s->warp_stream) he = hipStreamCreateWithFlags(&s->warp_stream, hipStreamNonBlocking);
-        if (he == hipSuccess && !s->warp_ev) he = hipEventCreateWithFlags(&s->warp_ev, hipEventDisableTiming);
-        // whatever the handle's stream was told to wait for (vs_stabilizer_wait_stream) holds for the warps too
-        if (he == hipSuccess) he = hipEventRecord(s->warp_ev, a->stream);
-        if (he == hipSuccess) he = hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0);
-        if (he != hipSuccess) r = set_error(VS_ERR_HIP, "stabilizer warp stream: %s", hipGetErrorString(he));
-        const int saved_mode = a->batch_mode;
-        a->batch_mode = overlap_mode;
-        s->overlap_warps = true;
-        const size_t esz = vs_format_bits(format) > 8 ? 2 : 1;
-        for (int c0 = 0; r >= 0 && c0 < n_clips_all; c0 += group_clips) {
-            const int nc = std::min(group_clips, n_clips_all - c0), f0 = c0 * clip_len;
-            const int nc_next = std::min(group_clips, n_clips_all - c0 - nc);
-            s->next_n = prefetch_env ? std::max(0, nc_next) * clip_len : 0;
-            s->next_frames = (const uint8_t*)frames + (size_t)(f0 + nc * clip_len) * frame_stride * esz;
-            const int rg = stab_run_impl(s, (const uint8_t*)frames + (size_t)f0 * frame_stride * esz, frame_stride, nc * clip_len, clip_len, w, h,
-                                         stride, format, mem, mem, -1, (uint8_t*)out + (size_t)f0 * out_frame_stride * esz, out_frame_stride,
-                                         has_output + f0, out_w, out_h);
-            r = rg < 0 ? rg : r + rg;
-        }
-        s->overlap_warps = false;
-        s->next_n = 0;
-        a->batch_mode = saved_mode;
-        const hipError_t we = s->warp_stream ? hipStreamSynchronize(s->warp_stream) : hipSuccess;   // every warp has landed before the call returns
-        if (we != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "stabilizer warps: %s", hipGetErrorString(we));
-        for (void* b : s->held_release) s->pool.push_back(b);
-        s->held_release.clear();
-        sharp_settle(s);
-    } else if (time_chunk > 0) {
-        // ONE long device-resident clip: cut in time.  The batched form is n successive process calls, so the chunks are the same
-        // calls in the same order; the warps of chunk c (on warp_stream) run under the alignment of chunk c + 1.  Frames still
-        // queued at a chunk boundary stay pointers into the caller's batch until the last chunk copies them out; buffers of
-        // earlier calls whose last reader is a warp on warp_stream return to the pool only after that stream's synchronisation.
-        vs_aligner* a = s->aligner;
-        r = 0;
-        hipError_t he = hipSetDevice(a->device);
-        if (he == hipSuccess && !s->warp_stream) he = hipStreamCreateWithFlags(&s->warp_stream, hipStreamNonBlocking);
-        if (he == hipSuccess && !s->warp_ev) he = hipEventCreateWithFlags(&s->warp_ev, hipEventDisableTiming);
-        if (he == hipSuccess) he = hipEventRecord(s->warp_ev, a->stream);
-        if (he == hipSuccess) he = hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0);
-        if (he != hipSuccess) r = set_error(VS_ERR_HIP, "stabilizer warp stream: %s", hipGetErrorString(he));
-        const int saved_mode = a->batch_mode;
-        a->batch_mode = overlap_mode;
-        s->overlap_warps = true;
-        const size_t esz = vs_format_bits(format) > 8 ? 2 : 1;
-        for (int f0 = 0; r >= 0 && f0 < n; f0 += time_chunk) {
-            const int m = std::min(time_chunk, n - f0);
-            s->defer_own = f0 + m < n;
-            s->next_n = prefetch_env ? std::max(0, std::min(time_chunk, n - f0 - m)) : 0;
-            s->next_frames = (const uint8_t*)frames + (size_t)(f0 + m) * frame_stride * esz;
-            const int rg = stab_run_impl(s, (const uint8_t*)frames + (size_t)f0 * frame_stride * esz, frame_stride, m, 0, w, h, stride, format, mem,
-                                         mem, -1, (uint8_t*)out + (size_t)f0 * out_frame_stride * esz, out_frame_stride, has_output + f0, out_w,
-                                         out_h);
-            r = rg < 0 ? rg : r + rg;
-        }
-        s->defer_own = false;
-        s->overlap_warps = false;
-        s->next_n = 0;
-        a->batch_mode = saved_mode;
-        const hipError_t we = s->warp_stream ? hipStreamSynchronize(s->warp_stream) : hipSuccess;
-        if (we != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "stabilizer warps: %s", hipGetErrorString(we));
-        for (void* b : s->held_release) s->pool.push_back(b);
-        s->held_release.clear();
-        sharp_settle(s);
-    } else
-        r = stab_run_impl(s, frames, frame_stride, n, clip_len, w, h, stride, format, mem, mem, -1, out, out_frame_stride, has_output,
-                          out_w, out_h);
-    if (s) for (auto& f : s->down) if (f.valid()) {          // every download has landed before the call returns
-        const hipError_t de = f.get();
-        if (de != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
-    }
-    if (r < 0 && s && s->aligner) {
-        const std::string why = vs_last_error();             // the reset below must not hide the cause
-        align_abandon(s->aligner);                           // (a next chunk's alignment may have been started)
-        s->prefetched = false; s->next_n = 0;
-        (void)hipStreamSynchronize(s->aligner->stream);
-        for (auto it = s->frames.begin(); it != s->frames.end();) it = it->owned ? it + 1 : s->frames.erase(it);
-        (void)vs_stabilizer_reset(s);
-        // (everything is quiet now: the sharpness blocks are referred to by what is still queued, if anything, and by nothing else)
-        s->sharp_pending.clear();
-        for (auto* b : s->sharp_blocks) b->refs = 0;
-        for (auto& f : s->frames) { if (f.sb) ++f.sb->refs; if (f.mb) ++f.mb->refs; }
-        set_error(r, "%s", why.c_str());
-    }
-    return r;
-}
-
-// The batch split into chunks of `chunk` frames (whole clips in clip mode): an uploader thread fills the other upload area
-// with chunk c+1 while chunk c is aligned and warped, and a downloader thread drains chunk c's outputs while chunk c+1 is
-// computed -- upload, compute and download overlap, and the link carries input and output at the same time (full duplex).
-// Every chunk goes through stab_run_impl exactly as a separate vs_stabilizer_process_batch call would, which is the
-// definition of the batched form ("n successive process calls"), so the results do not depend on the chunking.
-static int stab_run_host_pipelined(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int chunk, int w,
-                                   int h, int stride, int format, void* out, size_t out_frame_stride, int32_t* has_output, int* out_w,
-                                   int* out_h) {
-    VS_ARG(s && frames && out && has_output && out_w && out_h);
-    VS_ARG(w > 0 && h > 0 && w <= 65535 && h <= 65535);
-    VS_ARG(format != VS_FMT_GRAY8 && vs_format_bits(format) != 0 && stride >= 3 * w);
-    VS_ARG(frame_stride >= (size_t)(h - 1) * stride + (size_t)3 * w);
-    vs_aligner* a = s->aligner;
-    VS_HIP(hipSetDevice(a->device));
-    const size_t esz = vs_format_bits(format) > 8 ? 2 : 1;
-    const size_t fbytes = (size_t)w * h * 3 * esz;
-    if (s->pipe_in_bytes < fbytes * chunk) {
-        for (void*& q : s->pipe_in) { if (q) (void)hipFree(q); q = nullptr; }
-        s->pipe_in_bytes = 0;
-        VS_HIP(vsi::dev_alloc(&s->pipe_in[0], fbytes * chunk));
-        VS_HIP(vsi::dev_alloc(&s->pipe_in[1], fbytes * chunk));
-        s->pipe_in_bytes = fbytes * chunk;
-    }
-    if (!s->up_stream) VS_HIP(hipStreamCreateWithFlags(&s->up_stream, hipStreamNonBlocking));
-    const bool dense = stride == 3 * w && frame_stride == (size_t)h * stride;
-    auto upload = [=](int c) -> hipError_t {                 // chunk c -> pipe_in[c & 1], dense
-        const int off = c * chunk, m = std::min(chunk, n - off);
-        hipError_t e = hipSetDevice(a->device);
-        const uint8_t* src = (const uint8_t*)frames + (size_t)off * frame_stride * esz;
-        if (e == hipSuccess && dense) e = hipMemcpyAsync(s->pipe_in[c & 1], src, fbytes * m, hipMemcpyHostToDevice, s->up_stream);
-        if (e == hipSuccess && !dense) {                     // pitched: the chunk's span in one linear copy, then dense by device-to-device 2-D copies
-            const size_t span = ((size_t)(m - 1) * frame_stride + (size_t)(h - 1) * stride + (size_t)3 * w) * esz;
-            void*& area = s->span_in[c & 1];
-            if (s->span_in_bytes[c & 1] < span) {
-                if (area) (void)hipFree(area);
-                area = nullptr; s->span_in_bytes[c & 1] = 0;
-                e = vsi::dev_alloc(&area, span);
-                if (e == hipSuccess) s->span_in_bytes[c & 1] = span;
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(area, src, span, hipMemcpyHostToDevice, s->up_stream);
-            for (int i = 0; e == hipSuccess && i < m; i++)
-                e = hipMemcpy2DAsync((uint8_t*)s->pipe_in[c & 1] + (size_t)i * fbytes, (size_t)w * 3 * esz, (const uint8_t*)area + (size_t)i * frame_stride * esz,
-                                     (size_t)stride * esz, (size_t)w * 3 * esz, h, hipMemcpyDeviceToDevice, s->up_stream);
-        }
-        return e != hipSuccess ? e : hipStreamSynchronize(s->up_stream);
-    };
-    const int n_chunks = (n + chunk - 1) / chunk;
-    std::future<hipError_t> next = run_async(upload, 0);
-    int produced = 0;
-    for (int c = 0; c < n_chunks; c++) {
-        const int off = c * chunk, m = std::min(chunk, n - off);
-        const hipError_t ue = next.get();
-        if (c + 1 < n_chunks) next = run_async(upload, c + 1);
-        int r = ue == hipSuccess ? VS_OK : set_error(VS_ERR_HIP, "frame upload failed: %s", hipGetErrorString(ue));
-        if (r == VS_OK)
-            r = stab_run_impl(s, s->pipe_in[c & 1], (size_t)w * h * 3, m, clip_len, w, h, 3 * w, format, VS_MEM_DEVICE, VS_MEM_HOST, c & 1,
-                              (uint8_t*)out + (size_t)off * out_frame_stride * esz, out_frame_stride, has_output + off, out_w, out_h);
-        if (r < 0) { if (next.valid()) (void)next.get(); return r; }
-        produced += r;
-    }
-    return produced;
-}
-
-// A scratch buffer of the handle grows to `need` bytes.  sync: work on `ws` may still read the old block.  The handle's fields are zeroed before
-// the allocation: after a failed one the handle holds no buffer and the next call starts over (tests/test_alloc_failure_gpu.py).
-static int grow(void** buf, size_t* bytes, size_t need, hipStream_t ws, bool sync) {
-    if (*bytes >= need) return VS_OK;
-    if (sync) VS_HIP(hipStreamSynchronize(ws));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *bytes = 0;
-    VS_HIP(vsi::dev_alloc(buf, need));
-    *bytes = need;
-    return VS_OK;
-}
-
-static int stab_run_impl_unguarded(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int w, int h, int stride,
-                         int format, int mem, int out_mem, int slot_arg, void* out, size_t out_frame_stride, int32_t* has_output,
-                         int* out_w, int* out_h) {
-    // slot_arg >= 0: a chunk of the pipelined host batch -- its outputs leave through output area `slot_arg` and a downloader
-    // thread of their own, under the next chunk's compute.  slot_arg < 0: a call on its own (process / process_batch that fits
-    // one chunk): the copies go onto the handle's stream, nothing to overlap with, no thread.
-    const bool threaded_download = slot_arg >= 0;
-    const int slot = threaded_download ? slot_arg : 0;
-    VS_ARG(s && frames && out && has_output && out_w && out_h && n >= 1);
-    VS_ARG(format != VS_FMT_GRAY8 && vs_format_bits(format) != 0);
-    VS_ARG(w > 0 && h > 0 && w <= 65535 && h <= 65535);
-    VS_ARG(stride >= 3 * w);
-    const int crop = s->params.crop_pixels > 0 ? s->params.crop_pixels : 0;
-    VS_ARG(w > 2 * crop && h > 2 * crop);
-    const int ow = w - 2 * crop, oh = h - 2 * crop;
-    VS_ARG(n == 1 || (frame_stride >= (size_t)(h - 1) * stride + (size_t)3 * w && out_frame_stride >= (size_t)ow * oh * 3));
-    vs_aligner* a = s->aligner;
-    VS_HIP(hipSetDevice(a->device));
-    hipStream_t st = a->stream;
-    const int fbits = vs_format_bits(format);
-    const size_t esz = fbits > 8 ? 2 : 1;
-    const size_t fbytes = (size_t)w * h * 3 * esz;
-    if (s->w != w || s->h != h || s->fmt != format) {
-        // a size change restarts the aligner (alignment.cpp:155).  The reference would go on warping queued frames of the
-        // old size with measurements of the new one; here the change starts a new clip, cleanly: queued frames of the
-        // old size are dropped and the smoother, the accumulated correction and the frame counter start over.
-        stab_drop_frames(s);
-        VS_TRY(vs_stabilizer_reset(s));
-        s->w = w; s->h = h; s->fmt = format; s->frame_bytes = fbytes;
-    }
-    *out_w = ow; *out_h = oh;
-
-    // stabilizer.cpp:15: a private dense copy of every input frame, in device memory
-    const uint8_t* dense = nullptr;
-    const bool already_dense = mem == VS_MEM_DEVICE && stride == 3 * w && (n == 1 || frame_stride == (size_t)h * stride);
-    if (already_dense) {
-        dense = (const uint8_t*)frames;      // read in place during this call; the tail is copied out below
-    } else {
-        if (s->batch_in_bytes < fbytes * n) {
-            if (s->batch_in) (void)hipFree(s->batch_in);
-            s->batch_in = nullptr; s->batch_in_bytes = 0;
-            VS_HIP(vsi::dev_alloc(&s->batch_in, fbytes * n));
-            s->batch_in_bytes = fbytes * n;
-        }
-        const hipMemcpyKind kind = mem == VS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-        if (stride == 3 * w && (n == 1 || frame_stride == (size_t)h * stride)) {
-            VS_HIP(hipMemcpyAsync(s->batch_in, frames, fbytes * n, kind, st));   // dense input: one linear copy at the full link rate
-        } else {
-            const uint8_t* from = (const uint8_t*)frames;
-            if (mem == VS_MEM_HOST) {                       // pitched host frames: the span in one linear copy (see span_in), 2-D copies on the device only
-                const size_t span = ((size_t)(n - 1) * frame_stride + (size_t)(h - 1) * stride + (size_t)3 * w) * esz;
-                if (s->span_in_bytes[0] < span) {
-                    if (s->span_in[0]) (void)hipFree(s->span_in[0]);
-                    s->span_in[0] = nullptr; s->span_in_bytes[0] = 0;
-                    VS_HIP(vsi::dev_alloc(&s->span_in[0], span));
-                    s->span_in_bytes[0] = span;
-                }
-                VS_HIP(hipMemcpyAsync(s->span_in[0], frames, span, hipMemcpyHostToDevice, st));
-                from = (const uint8_t*)s->span_in[0];
-            }
-            for (int i = 0; i < n; i++)
-                VS_HIP(hipMemcpy2DAsync((uint8_t*)s->batch_in + (size_t)i * fbytes, (size_t)w * 3 * esz,
-                                        from + (size_t)i * frame_stride * esz, (size_t)stride * esz,
-                                        (size_t)w * 3 * esz, h, hipMemcpyDeviceToDevice, st));
-        }
-        dense = (const uint8_t*)s->batch_in;
-    }
-
-    // deblur (vs_deblur.hip): the sharpness of the call's frames, one launch over all of them, into a block of its own; the values stay on the
-    // device.  (Queued frames that arrived while deblur was off are measured here too, once.)
-    const int ndb = std::min(s->deblur, s->params.lag);
-    const bool warps_apart = s->overlap_warps && out_mem != VS_MEM_HOST;      // the warps of this call go to warp_stream
-    if (!s->overlap_warps) sharp_settle(s);
-    vs_stabilizer::SharpBlock* sblk = nullptr;
-    // an idle block of at least `need` values, or a new one (`keep`: a block taken earlier in this call, still without references)
-    auto take_block = [&](size_t need, vs_stabilizer::SharpBlock* keep, vs_stabilizer::SharpBlock** out) -> int {
-        for (auto* b : s->sharp_blocks) if (b != keep && b->refs == 0 && b->cap >= need) { *out = b; return VS_OK; }
-        for (auto it = s->sharp_blocks.begin(); it != s->sharp_blocks.end();)           // idle blocks that are too small make room
-            if (*it != keep && (*it)->refs == 0) { (void)hipFree((*it)->dev); delete *it; it = s->sharp_blocks.erase(it); } else ++it;
-        void* q = nullptr;
-        VS_HIP(vsi::dev_alloc(&q, need * sizeof(unsigned long long)));
-        s->sharp_blocks.reserve(s->sharp_blocks.size() + 1);
-        *out = new vs_stabilizer::SharpBlock{(unsigned long long*)q, need, 0};
-        s->sharp_blocks.push_back(*out);
-        return VS_OK;
-    };
-    // `per` values per frame, measured by launch(frames, where to, how many, frame stride): the call's n frames in one launch into a block of
-    // their own (*out), then every queued frame that lacks the value, one launch each, behind them in the same block
-    using Held = vs_stabilizer::Held;
-    auto measure = [&](size_t per, vs_stabilizer::SharpBlock* keep, vs_stabilizer::SharpBlock* Held::*blk, const unsigned long long* Held::*val, auto launch,
-                       vs_stabilizer::SharpBlock** out) -> int {
-        size_t need = (size_t)n;
-        for (auto& f : s->frames) if (!(f.*blk)) need++;
-        VS_TRY(take_block(per * need, keep, out));
-        VS_HIP(launch(dense, (*out)->dev, n, (size_t)w * h * 3));
-        size_t k = (size_t)n;
-        for (auto& f : s->frames) {
-            if (f.*blk) continue;
-            VS_HIP(launch(f.ptr, (*out)->dev + per * k, 1, 0));
-            f.*blk = *out; f.*val = (*out)->dev + per * k; ++(*out)->refs; k++;
-        }
-        return VS_OK;
-    };
-    if (ndb > 0)
-        VS_TRY(measure(1, nullptr, &Held::sb, &Held::sharp, [&](const void* p, unsigned long long* to, int m, size_t fs) {
-            return vsk::bgr_sharpness(p, w, h, w * 3, (int)esz * 8, fbits - 8, to, m, fs, st); }, &sblk));
-    // fill blend with exposure match (vs_fill.hip): the three channel sums of the call's frames likewise -- one launch, a block of their own, the
-    // values stay on the device.  (Queued frames that arrived while the match was off are summed here too, once: switching on mid-clip gives
-    // what a handle that had it from the first frame gives.)
-    const int nfill = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, s->params.lag) : 0;
-    const bool blend_on = nfill > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
-    const bool want_sums = nfill > 0 && s->fill_blend.match != 0;
-    vs_stabilizer::SharpBlock* mblk = nullptr;
-    if (want_sums)
-        VS_TRY(measure(3, sblk, &Held::mb, &Held::sums, [&](const void* p, unsigned long long* to, int m, size_t fs) {
-            return vsk::bgr_channel_sums(p, w, h, w * 3, (int)esz * 8, to, m, fs, st); }, &mblk));
-    if ((ndb > 0 || want_sums) && warps_apart) {            // the deblur pass / the fill's gain kernel read the values on warp_stream
-        VS_HIP(hipEventRecord(s->warp_ev, st));
-        VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
-    }
-
-    // stabilizer.cpp:18-19 for all n frames.  In a chunked device-resident batch (stab_run) the alignment of the NEXT chunk is
-    // started as soon as this one's results are in, so that it runs under this chunk's host work (smoother, correction chain, warp
-    // launches) as well as under its warps.
-    const int cur = s->tb;
-    if (s->prefetched) {
-        s->prefetched = false;              // started by the previous call, into [cur]
-    } else {
-        s->t_buf[cur].resize(n);
-        s->st_buf[cur].resize(n);
-        VS_TRY(align_start(a, dense, (size_t)w * h * 3, n, clip_len, w, h, w * 3, format, VS_MEM_DEVICE, &s->params.aligner,
-                           s->t_buf[cur].data(), s->st_buf[cur].data(), false));
-    }
-    {
-        const int r = align_finish(a);
-        if (r < 0) return r;
-    }
-    if (s->next_n > 0 && already_dense) {
-        s->t_buf[cur ^ 1].resize(s->next_n);
-        s->st_buf[cur ^ 1].resize(s->next_n);
-        VS_TRY(align_start(a, s->next_frames, (size_t)w * h * 3, s->next_n, clip_len, w, h, w * 3, format, VS_MEM_DEVICE, &s->params.aligner,
-                           s->t_buf[cur ^ 1].data(), s->st_buf[cur ^ 1].data(), true));
-        s->prefetched = true;
-        s->tb = cur ^ 1;
-    }
-    const std::vector<vs_transform>& t_buf = s->t_buf[cur];
-    const std::vector<int32_t>& st_buf = s->st_buf[cur];
-
-    struct Job { const void* src; vs_transform sampling; int i; void* release; };
-    std::vector<Job> jobs;
-    // The look-ahead passes (DESIGN.md "Look-ahead passes: the shared path"): per job 1 + n_ahead candidates -- the frame itself, then the frames
-    // that follow it in the queue; null frames and zero transforms behind the end of a list.  `side`: where each candidate's side value lies.
-    struct Ahead {
-        int n;
-        std::vector<const void*> src;
-        std::vector<vs_transform> t;
-        std::vector<const uint64_t*> side;
-    };
-    Ahead fill{nfill};                              // border fill (vs_fill.hip); side (exposure match only): the channel sums, the ORIGINAL frames' throughout
-    Ahead db{ndb};                                  // deblur; side: the sharpness
-    Ahead dn{std::min(s->denoise, s->params.lag)};  // denoise (vs_denoise.hip)
-    Ahead fk{std::min(s->deflicker, s->params.lag)};    // deflicker (vs_deflicker.hip): candidate 0 stays the ORIGINAL frame whatever deblur and denoise do
-    const int ndn = dn.n, nfk = fk.n;
-    for (int i = 0; i < n; i++) {
-        if (clip_len > 0 && i % clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
-        ++s->frame_index;
-        s->frames.push_back(vs_stabilizer::Held{(void*)(dense + (size_t)i * fbytes), false, sblk, sblk ? sblk->dev + i : nullptr, mblk,
-                                                mblk ? mblk->dev + 3 * (size_t)i : nullptr});
-        if (sblk) ++sblk->refs;
-        if (mblk) ++mblk->refs;
-        const vs_transform meas = t_buf[i];
-        const bool success = st_buf[i] == 1;
-        s->last_meas = meas; s->last_success = success ? 1 : 0;
-        has_output[i] = 0;
-
-        vs_transform earliest_smoothed{0, 0, 0, 0};
-        if (s->params.enable_smoother) (void)vs_smoother_update(s->smoother, &meas, &earliest_smoothed);   // :35
-        if (!success) s->accum = vs_transform{0, 0, 0, 0};                                                  // :39-41
-        s->measurements.push_back(meas);                                                                   // :44
-        s->meas_ok.push_back(success ? 1 : 0);
-        if (s->measurements.size() > (size_t)s->params.lag) {                                              // :48
-            vs_transform earliest = s->measurements.front();
-            s->measurements.pop_front();
-            s->meas_ok.pop_front();
-            vs_transform jitter;
-            if (s->params.enable_smoother) {
-                vs_transform inv = vs_transform_inverse(&earliest_smoothed);
-                jitter = vs_transform_compose(&earliest, &inv);                                            // :60
-            } else {
-                jitter = earliest;
-            }
-            vs_transform na = vs_transform_compose(&s->accum, &jitter);                                    // :66
-            const double disp = vs_transform_max_corner_displacement(&na, w, h);                           // :69-70
-            double decay;
-            if (disp > s->params.max_disp) {
-                decay = s->params.max_decay;
-            } else if (disp > s->params.min_disp) {
-                double f = (disp - s->params.min_disp) / (s->params.max_disp - s->params.min_disp);
-                f = std::max(0.0, std::min(1.0, f));
-                decay = s->params.min_decay * (1.0 - f) + s->params.max_decay * f;
-            } else {
-                decay = s->params.min_decay;
-            }
-            na.TX *= decay; na.TY *= decay; na.A *= decay; na.B *= decay;                                  // :88-91
-            s->accum = na;
-            if (!s->frames.empty()) {
-                vs_stabilizer::Held src = s->frames.front();
-                s->frames.pop_front();
-                if (src.sb) s->sharp_pending.push_back(src.sb);   // (the jobs' launches below still read it: counted down after them)
-                if (src.mb) s->sharp_pending.push_back(src.mb);
-                // :97-99: warpBySimilarityTransform(frame, accum^-1); cv::warpAffine without WARP_INVERSE_MAP
-                // inverts the matrix it is given (imgproc.cpp:472), so the sampling map is (accum^-1)^-1.
-                // (VS_WARP_BILINEAR_CV is cv::warpAffine itself, inversion included: it takes the correction as the reference hands it over)
-                vs_transform correction = vs_transform_inverse(&na);
-                jobs.push_back(Job{src.ptr, s->params.warp_mode == VS_WARP_BILINEAR_CV ? correction : vs_transform_inverse(&correction), i,
-                                   src.owned ? src.ptr : nullptr});
-                has_output[i] = 1;
-                // The queue now holds the frames k+1 .. behind this frame k, `measurements` their motions T_{k+1} .. (T_j: frame j-1 to j), entry
-                // for entry.  Frame j shows frame k's pixels through inverse(T_{k+1} o .. o T_j), and -- the fill -- this output through F_j =
-                // compose(that, correction); a frame whose alignment failed ends the list (vs_lookahead.hpp).  (The frames are read before their
-                // own jobs release them: releases follow all launches, below.)
-                const size_t avail = std::min(s->frames.size(), s->measurements.size());
-                auto list = [&](Ahead& a, size_t have, const vs_transform& t0, const vs_transform* corr, const unsigned long long* Held::*side) {
-                    if (a.n <= 0) return;
-                    a.src.push_back(src.ptr);
-                    a.t.push_back(t0);
-                    const size_t at = a.t.size();
-                    a.t.resize(at + (size_t)a.n);
-                    const int live = vsi::lookahead_transforms(s->measurements, s->meas_ok, have, a.n, corr, &a.t[at]);
-                    for (int c = 0; c < a.n; c++) a.src.push_back(c < live ? s->frames[c].ptr : nullptr);
-                    if (!side) return;
-                    a.side.push_back((const uint64_t*)(src.*side));
-                    for (int c = 0; c < a.n; c++) a.side.push_back(c < live ? (const uint64_t*)(s->frames[c].*side) : nullptr);
-                };
-                const vs_transform none{0, 0, 0, 0};
-                list(fill, avail, correction, &correction, want_sums ? &Held::sums : nullptr);
-                size_t sharp_avail = 0;                     // the deblur's list also ends at a frame without a sharpness value
-                while (sharp_avail < avail && s->frames[sharp_avail].sharp) sharp_avail++;
-                list(db, sharp_avail, none, nullptr, &Held::sharp);
-                list(dn, avail, none, nullptr, nullptr);
-                list(fk, avail, none, nullptr, nullptr);
-            }
-        }
-    }
-
-    // warp every due frame, runs of consecutive batch frames as one launch.  The crop of stabilizer.cpp:102-109 is the
-    // output window of the warp: the margin is never computed and no full-size intermediate frame exists.  Device callers
-    // get the window written straight into `out`; host callers through a dense staging buffer and one copy per frame.
-    if (!jobs.empty()) {
-        const size_t obytes = (size_t)ow * oh * 3 * esz;
-        const bool to_host = out_mem == VS_MEM_HOST;
-        if (to_host) {
-            if (s->down[slot].valid()) {                     // the previous user of this area has been drained
-                const hipError_t de = s->down[slot].get();
-                if (de != hipSuccess) return set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
-            }
-            VS_TRY(grow(&s->batch_out[slot], &s->batch_out_bytes[slot], obytes * jobs.size(), nullptr, false));    // (drained through down[slot], above)
-        }
-        if (ndb > 0) {
-            // every due frame is deblurred into a scratch frame of its own, one launch, in front of the warps on their stream; the warps (and the
-            // fill's candidate 0) then read the scratch frames.  The candidates are read before their own jobs release them: releases follow below.
-            hipStream_t ws = warps_apart ? s->warp_stream : st;
-            VS_TRY(grow(&s->deblur_buf, &s->deblur_bytes, fbytes * jobs.size(), ws, true));     // (warps of an earlier chunk may still read the area)
-            const int dr = vsi::bgr_deblur_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndb, db.src.data(), db.side.data(), db.t.data(), &s->deblur_params,
-                                                s->deblur_buf, (size_t)w * h * 3, w * 3, ws);
-            if (dr < 0) return dr;
-            for (size_t j = 0; j < jobs.size(); j++) {
-                jobs[j].src = (const uint8_t*)s->deblur_buf + j * fbytes;
-                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
-            }
-        }
-        if (ndn > 0) {
-            // every due frame (deblurred, if that pass is on) is denoised into a scratch frame of its own, one launch, in front of the warps on
-            // their stream; the warps (and the fill's candidate 0) then read the scratch frames.  The candidates are the original input frames,
-            // read before their own jobs release them: releases follow below.
-            hipStream_t ws = warps_apart ? s->warp_stream : st;
-            VS_TRY(grow(&s->denoise_buf, &s->denoise_bytes, fbytes * jobs.size(), ws, true));   // (warps of an earlier chunk may still read the area)
-            for (size_t j = 0; j < jobs.size(); j++) dn.src[j * (1 + ndn)] = jobs[j].src;
-            const int dr = vsi::bgr_denoise_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + ndn, dn.src.data(), dn.t.data(), &s->denoise_params, s->denoise_buf,
-                                                 (size_t)w * h * 3, w * 3, ws);
-            if (dr < 0) return dr;
-            for (size_t j = 0; j < jobs.size(); j++) {
-                jobs[j].src = (const uint8_t*)s->denoise_buf + j * fbytes;
-                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
-            }
-        }
-        uint32_t* fk_gains = nullptr;
-        if (nfk > 0) {
-            // the exposure statistics of every due frame against the frames that follow it -- the original input frames on both sides, read before
-            // their own jobs release them -- and its three gains: one statistics launch and one gains launch, on the warps' stream.  Nothing of it
-            // reaches the host; the gain pass behind each run's warp (and fill) reads the gains there.
-            hipStream_t ws = warps_apart ? s->warp_stream : st;
-            const size_t sbytes = jobs.size() * (size_t)(1 + nfk) * 8 * sizeof(uint64_t), need = sbytes + jobs.size() * 4 * sizeof(uint32_t);
-            VS_TRY(grow(&s->flicker_buf, &s->flicker_bytes, need, ws, true));                   // (gain passes of an earlier chunk may still read the block)
-            fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf + sbytes);
-            const int fr = vsi::exposure_stats_ptrs((int)jobs.size(), w, h, w * 3, format, 1 + nfk, fk.src.data(), fk.t.data(), &s->deflicker_params,
-                                                    (uint64_t*)s->flicker_buf, ws);
-            if (fr < 0) return fr;
-            VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf, (int)jobs.size(), 1 + nfk, w, h, s->deflicker_params.step, fk_gains, ws));
-        }
-        std::vector<vs_transform> ts;
-        for (size_t j = 0; j < jobs.size();) {
-            size_t e = j + 1;
-            while (e < jobs.size() && (const uint8_t*)jobs[e].src == (const uint8_t*)jobs[e - 1].src + fbytes &&
-                   jobs[e].i == jobs[e - 1].i + 1) e++;
-            ts.clear();
-            for (size_t k = j; k < e; k++) ts.push_back(jobs[k].sampling);
-            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot] + j * obytes)
-                                : (void*)((uint8_t*)out + (size_t)jobs[j].i * out_frame_stride * esz);
-            const size_t dst_fs = to_host ? (size_t)ow * oh * 3 : out_frame_stride;
-            // (device output of an overlapped clip batch: the warps go to warp_stream and run under the next group's alignment)
-            hipStream_t ws = (s->overlap_warps && !to_host) ? s->warp_stream : st;
-            // (beside the next group's alignment the Lanczos2 warp keeps its standard window: see vsi::warp_keeps_solver_slot)
-            struct SlotHint { bool& f; bool old; SlotHint(bool on) : f(vsi::warp_keeps_solver_slot()), old(f) { f = on; } ~SlotHint() { f = old; } } hint(s->overlap_warps);
-            int wr;
-            if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
-                wr = vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, (int)esz * 8, 1 + nfill, &fill.src[j * (1 + nfill)],
-                                             &fill.t[j * (1 + nfill)], s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh, dst, dst_fs,
-                                             ow * 3, ws, want_sums ? &fill.side[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr);
-            else
-                wr = vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, (int)esz * 8, ts.data(),
-                                                 s->params.warp_mode, s->params.warp_border, vs_format_max_value(format), crop, crop, ow, oh,
-                                                 dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws);
-            if (wr < 0) return wr;
-            // deflicker: the run's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
-            if (nfk > 0)
-                VS_HIP(vsk::bgr_gain(dst, ow, oh, ow * 3, (int)esz * 8, vs_format_max_value(format), fk_gains + 4 * j, dst, ow * 3, (int)(e - j), dst_fs, dst_fs, ws));
-            j = e;
-        }
-        for (size_t j = 0; j < jobs.size(); j++)
-            if (jobs[j].release) {
-                if (s->overlap_warps && !to_host) s->held_release.push_back(jobs[j].release);   // read on warp_stream, refilled on st
-                else s->pool.push_back(jobs[j].release);                                        // reused only by later work on this stream
-            }
-        if (to_host) {
-            const bool dense_out = out_frame_stride * esz == obytes;
-            if (!threaded_download) {
-                // runs of outputs that are contiguous on both sides as one copy, behind the warps on the same stream; the
-                // synchronisation at the end of this call covers them
-                for (size_t j = 0; j < jobs.size();) {
-                    size_t k = j + 1;
-                    while (dense_out && k < jobs.size() && jobs[k].i == jobs[k - 1].i + 1) k++;
-                    VS_HIP(hipMemcpyAsync((uint8_t*)out + (size_t)jobs[j].i * out_frame_stride * esz,
-                                          (const uint8_t*)s->batch_out[slot] + j * obytes, obytes * (k - j), hipMemcpyDeviceToHost, st));
-                    j = k;
-                }
-            } else {
-            // hand the area to the downloader: it waits (on its own stream) for the warps above, then copies every output
-            // to the caller's memory -- runs of outputs that are contiguous on both sides as one copy
-            if (!s->down_stream) VS_HIP(hipStreamCreateWithFlags(&s->down_stream, hipStreamNonBlocking));
-            if (!s->down_ev[slot]) VS_HIP(hipEventCreateWithFlags(&s->down_ev[slot], hipEventDisableTiming));
-            VS_HIP(hipEventRecord(s->down_ev[slot], st));
-            std::vector<int> idx(jobs.size());
-            for (size_t j = 0; j < jobs.size(); j++) idx[j] = jobs[j].i;
-            const int device = a->device;
-            const uint8_t* area = (const uint8_t*)s->batch_out[slot];
-            hipStream_t ds = s->down_stream;
-            hipEvent_t ev = s->down_ev[slot];
-            const bool out_dense = out_frame_stride * esz == obytes;
-            s->down[slot] = run_async([=]() -> hipError_t {
-                hipError_t e = hipSetDevice(device);
-                if (e == hipSuccess) e = hipStreamWaitEvent(ds, ev, 0);
-                for (size_t j = 0; e == hipSuccess && j < idx.size();) {
-                    size_t k = j + 1;
-                    while (out_dense && k < idx.size() && idx[k] == idx[k - 1] + 1) k++;
-                    e = hipMemcpyAsync((uint8_t*)out + (size_t)idx[j] * out_frame_stride * esz, area + j * obytes, obytes * (k - j),
-                                       hipMemcpyDeviceToHost, ds);
-                    j = k;
-                }
-                return e != hipSuccess ? e : hipStreamSynchronize(ds);
-            });
-            }
-        }
-    }
-    if (!warps_apart) sharp_settle(s);                  // (readers and the next writer share this stream)
-    if (clip_len > 0) VS_TRY(vs_stabilizer_reset(s));   // nothing carries over from the last clip
-    // frames of this batch that are still queued move into buffers of our own
-    for (auto& f : s->frames) {
-        if (f.owned || s->defer_own) continue;
-        void* copy = nullptr;
-        if (!s->pool.empty()) { copy = s->pool.back(); s->pool.pop_back(); }
-        else VS_HIP(vsi::dev_alloc(&copy, fbytes));
-        VS_HIP(hipMemcpyAsync(copy, f.ptr, fbytes, hipMemcpyDeviceToDevice, st));
-        f.ptr = copy; f.owned = true;
-    }
-    if (!s->prefetched) VS_HIP(hipStreamSynchronize(st));   // (with the next chunk's alignment in flight its completion is the next call's wait)
-    int produced = 0;
-    for (int i = 0; i < n; i++) produced += has_output[i];
-    return produced;
-}
-static int stab_run_impl(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int clip_len, int w, int h, int stride,
-                         int format, int mem, int out_mem, int slot_arg, void* out, size_t out_frame_stride, int32_t* has_output,
-                         int* out_w, int* out_h) {
-    // (guarded: an exception inside a chunk -- a host allocation that fails -- comes back as an error code, so that the callers' loops restore
-    // the handle's modes and stab_run's failure protocol runs)
-    return vsi::guarded([&] { return stab_run_impl_unguarded(s, frames, frame_stride, n, clip_len, w, h, stride, format, mem, out_mem, slot_arg, out, out_frame_stride, has_output, out_w, out_h); });
-}
-
-int vs_stabilizer_process_batch(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int w, int h, int stride,
-                                int format, int mem, void* out, size_t out_frame_stride, int32_t* has_output, int* out_w,
-                                int* out_h) try {
-    return stab_run(s, frames, frame_stride, n, 0, w, h, stride, format, mem, out, out_frame_stride, has_output, out_w, out_h);
-} VS_CATCH_ALL
-
-int vs_stabilizer_process_clips(vs_stabilizer* s, const void* frames, size_t frame_stride, int n_clips, int frames_per_clip,
-                                int w, int h, int stride, int format, int mem, void* out, size_t out_frame_stride,
-                                int32_t* has_output, int* out_w, int* out_h) try {
-    VS_ARG(n_clips >= 1 && frames_per_clip >= 1 && (long long)n_clips * frames_per_clip <= 0x7fffffff);
-    return stab_run(s, frames, frame_stride, n_clips * frames_per_clip, frames_per_clip, w, h, stride, format, mem, out,
-                    out_frame_stride, has_output, out_w, out_h);
-} VS_CATCH_ALL
-
-// forget the clip: the next frame starts a new sequence (device buffers are kept)
-void* vs_stabilizer_stream(const vs_stabilizer* s) { return s && s->aligner ? (void*)s->aligner->stream : nullptr; }
-int vs_stabilizer_set_select_mode(vs_stabilizer* s, int mode) try {
-    VS_ARG(s && s->aligner);
-    return vs_aligner_set_select_mode(s->aligner, mode);
-} VS_CATCH_ALL
-int vs_stabilizer_get_select_mode(const vs_stabilizer* s) try {
-    VS_ARG(s && s->aligner);
-    return s->aligner->select_mode;
-} VS_CATCH_ALL
-int vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead) try {
-    VS_ARG(s && ahead >= 0);
-    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "border fill: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
-    VS_ARG(ahead <= s->params.lag);
-    s->border_fill = ahead;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
-    VS_ARG(s);
-    return s->border_fill;
-} VS_CATCH_ALL
-int vs_stabilizer_set_fill_blend(vs_stabilizer* s, const vs_fill_blend_params* params) try {
-    VS_ARG(s);
-    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "fill blend: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
-    const vs_fill_blend_params p = params ? *params : vs_fill_blend_params{0, 0};
-    VS_ARG(p.feather >= 0 && p.feather <= 6 && (p.match == 0 || p.match == 1));
-    s->fill_blend = p;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* params) try {
-    VS_ARG(s && params);
-    *params = s->fill_blend;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
-    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
-    vs_deblur_params p;
-    if (params) p = *params; else vs_deblur_params_default(&p);
-    VS_ARG(vsi::deblur_params_finite(p.sensitivity, p.max_ratio));
-    s->deblur = ahead;
-    s->deblur_params = p;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_get_deblur(const vs_stabilizer* s) try {
-    VS_ARG(s);
-    return s->deblur;
-} VS_CATCH_ALL
-int vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params) try {
-    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
-    vs_denoise_params p;
-    if (params) p = *params; else vs_denoise_params_default(&p);
-    VS_ARG(p.strength >= 1 && p.strength <= 255);
-    s->denoise = ahead;
-    s->denoise_params = p;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params) try {
-    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
-    vs_deflicker_params p;
-    if (params) p = *params; else vs_deflicker_params_default(&p);
-    VS_ARG(p.step >= 1 && p.step <= 64);
-    s->deflicker = ahead;
-    s->deflicker_params = p;
-    return VS_OK;
-} VS_CATCH_ALL
-int vs_stabilizer_get_deflicker(const vs_stabilizer* s) try {
-    VS_ARG(s);
-    return s->deflicker;
-} VS_CATCH_ALL
-int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
-    VS_ARG(s);
-    return s->denoise;
-} VS_CATCH_ALL
-int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
-    VS_ARG(s && s->aligner);
-    return vs_aligner_wait_stream(s->aligner, producer_stream);
-} VS_CATCH_ALL
-
-int vs_stabilizer_reset(vs_stabilizer* s) try {
-    VS_ARG(s);
-    VS_HIP(hipSetDevice(s->aligner->device));
-    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) s->pool.push_back(f.ptr); }
-    s->frames.clear();
-    s->measurements.clear();
-    s->meas_ok.clear();
-    // (make the new smoother first: if that fails the handle keeps a valid, if stale, one -- never a null pointer for the next call to walk into)
-    vs_smoother* fresh = vs_smoother_create(s->params.lag, s->params.smoother_memory, s->params.lambda);
-    if (!fresh) return VS_ERR_NOMEM;
-    vs_smoother_destroy(s->smoother);
-    s->smoother = fresh;
-    s->accum = vs_transform{0, 0, 0, 0};
-    s->last_meas = vs_transform{0, 0, 0, 0};
-    s->last_success = 0;
-    s->frame_index = 0;
-    return vs_aligner_reset(s->aligner);
-} VS_CATCH_ALL
-
-int vs_stabilizer_process(vs_stabilizer* s, const void* frame, int w, int h, int stride, int format, int mem, void* out,
-                          int* out_w, int* out_h) try {
-    int32_t has = 0;
-    int r = vs_stabilizer_process_batch(s, frame, 0, 1, w, h, stride, format, mem, out, 0, &has, out_w, out_h);
-    return r < 0 ? r : has;
-} VS_CATCH_ALL
-
-void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success) {
-    if (last_meas) *last_meas = s->last_meas;
-    if (accum) *accum = s->accum;
-    if (last_success) *last_success = s->last_success;
-}
-
-}  // extern "C"
+// the stabilizer's side door (vs_engine.hpp)
+int vsi::aligner_device(const vs_aligner* a) { return a->device; }
+int vsi::aligner_batch_mode(const vs_aligner* a) { return a->batch_mode; }
+void vsi::aligner_set_batch_mode(vs_aligner* a, int mode) { a->batch_mode = mode; }

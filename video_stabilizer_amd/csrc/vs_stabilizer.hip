@@ -1,0 +1,817 @@
+// vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_deblur, vs_denoise, vs_deflicker).
+//
+// Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
+// then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
+// batches longer than one upload chunk run as an upload / compute / download pipeline (stab_run_host_pipelined), dense device-resident batches in
+// sub-batches whose warps run under the next sub-batch's alignment (stab_run_overlapped).
+#include "vs_engine.hpp"
+#include "vs_lookahead.hpp"
+#include "vs_stab_step.hpp"
+#include "vs_kernels.hpp"
+
+#include <algorithm>
+#include <deque>
+#include <numeric>
+#include <string>
+#include <vector>
+
+using vsi::set_error;
+using vsi::run_async;
+
+struct vs_stabilizer {
+    vs_stabilizer_params params;
+    vs_aligner* aligner = nullptr;
+    vs_smoother* smoother = nullptr;
+    int frame_index = 0;
+    std::deque<vs_transform> measurements;
+    std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
+    int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
+    vs_fill_blend_params fill_blend{0, 0};   // vs_stabilizer_set_fill_blend.  With match on, the three channel sums of every queued frame lie in device
+                                   // memory like the sharpness below: in blocks of the same pool, under the same reference protocol (Held::mb / sums)
+    // deblur (vs_deblur.hip): the sharpness of every queued frame lies in device memory, one value per frame in a block taken per call; a block is
+    // free again when no queued frame and no launch in flight refers to it (refs; sharp_pending: references given up, counted down at the next point
+    // where every reader has been ordered before whatever may refill the block)
+    struct SharpBlock { unsigned long long* dev; size_t cap; int refs; };
+    std::vector<SharpBlock*> sharp_blocks, sharp_pending;
+    int deblur = 0;                // vs_stabilizer_set_deblur: following frames a frame is deblurred from (0: off)
+    vs_deblur_params deblur_params{2.0f, 4.0f};
+    void* deblur_buf = nullptr; size_t deblur_bytes = 0;     // the deblurred frames of the current call: the source of its warps
+    // temporal denoise (vs_denoise.hip)
+    int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
+    vs_denoise_params denoise_params{24};
+    void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
+    // deflicker (vs_deflicker.hip)
+    int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
+    vs_deflicker_params deflicker_params{4};
+    void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
+    struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
+                  SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
+    std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
+    std::vector<void*> pool;       // recycled frame buffers
+    size_t frame_bytes = 0;
+    void* batch_in = nullptr; size_t batch_in_bytes = 0;     // dense device copy of the current batch
+    // host callers: cropped outputs of the current chunk on their way down.  Two areas, used alternately by the chunks of a
+    // pipelined batch; a downloader thread drains area k on down_stream while the next chunk is computed into area k^1.
+    void* batch_out[2] = {nullptr, nullptr}; size_t batch_out_bytes[2] = {0, 0};
+    std::future<hipError_t> down[2];
+    hipEvent_t down_ev[2] = {nullptr, nullptr};
+    hipStream_t down_stream = nullptr, up_stream = nullptr;
+    void* pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_bytes = 0;     // upload areas of a pipelined host batch
+    // PITCHED host frames travel as ONE linear copy of their whole span (gaps included) into a device area and are made dense by device-to-device
+    // 2-D copies: the HIP runtime never gets a 2-D copy out of pageable caller memory (profiles/r06_flake.md); dense frames: one linear copy as ever
+    void* span_in[2] = {nullptr, nullptr}; size_t span_in_bytes[2] = {0, 0};
+    // device-resident batches: the warps of sub-batch g run on warp_stream under the alignment of sub-batch g + 1 (stab_run_overlapped)
+    hipStream_t warp_stream = nullptr;
+    hipEvent_t warp_ev = nullptr;
+    bool overlap_warps = false;    // set by stab_run_overlapped around its sub-batches
+    bool defer_own = false;        // set for all but the last time chunk of one long device-resident clip: frames still queued stay
+                                   // pointers into the caller's batch (it outlives the call), only the last chunk copies them out
+    std::vector<void*> held_release;   // buffers whose last reader is a warp on warp_stream: back into the pool after its synchronisation
+    // alignment results of the chunk being processed [tb] and of the chunk whose alignment is already running [tb ^ 1]
+    std::vector<vs_transform> t_buf[2];
+    std::vector<int32_t> st_buf[2];
+    int tb = 0;
+    bool prefetched = false;       // the alignment of the next stab_run_impl call's frames has been started by the previous call
+    const void* next_frames = nullptr; int next_n = 0;   // set by stab_run_overlapped: the chunk after the one being processed (0: none)
+    vs_transform accum{0, 0, 0, 0}, last_meas{0, 0, 0, 0};
+    int last_success = 0;
+    int w = 0, h = 0, fmt = -1;
+};
+
+static void sharp_unhold(vs_stabilizer* s, vs_stabilizer::Held& f) {
+    if (f.sb) s->sharp_pending.push_back(f.sb);
+    if (f.mb) s->sharp_pending.push_back(f.mb);
+    f.sb = nullptr; f.sharp = nullptr;
+    f.mb = nullptr; f.sums = nullptr;
+}
+static void sharp_settle(vs_stabilizer* s) {
+    for (auto* b : s->sharp_pending) --b->refs;
+    s->sharp_pending.clear();
+}
+static void stab_drop_frames(vs_stabilizer* s) {
+    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) (void)hipFree(f.ptr); }
+    for (void* p : s->pool) (void)hipFree(p);
+    s->frames.clear();
+    s->pool.clear();
+}
+
+extern "C" {
+
+vs_stabilizer* vs_stabilizer_create(const vs_stabilizer_params* params, int device) try {
+    vs_stabilizer_params p;
+    if (params) p = *params; else vs_stabilizer_params_default(&p);
+    vs_aligner* a = vs_aligner_create(&p.aligner, device);
+    if (!a) return nullptr;
+    // the aligner owns streams and device slabs: whatever fails from here on releases it (a host allocation that throws included)
+    struct Guard { vs_aligner* a; ~Guard() { if (a) vs_aligner_destroy(a); } } guard{a};
+    vs_stabilizer* s = new vs_stabilizer();
+    s->params = p;
+    s->aligner = a;
+    guard.a = nullptr;                                     // (from here vs_stabilizer_destroy releases it)
+    s->smoother = vs_smoother_create(p.lag, p.smoother_memory, p.lambda);   // stabilizer.cpp:4
+    if (!s->smoother) { vs_stabilizer_destroy(s); return nullptr; }         // (last error: the smoother's)
+    return s;
+} VS_CATCH_ALL_NULL
+
+void vs_stabilizer_destroy(vs_stabilizer* s) {
+    if (!s) return;
+    (void)hipSetDevice(vsi::aligner_device(s->aligner));
+    stab_drop_frames(s);
+    for (auto& f : s->down) if (f.valid()) (void)f.get();
+    for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
+    if (s->deblur_buf) (void)hipFree(s->deblur_buf);
+    if (s->denoise_buf) (void)hipFree(s->denoise_buf);
+    if (s->flicker_buf) (void)hipFree(s->flicker_buf);
+    if (s->batch_in) (void)hipFree(s->batch_in);
+    for (void* q : s->batch_out) if (q) (void)hipFree(q);
+    for (void* q : s->pipe_in) if (q) (void)hipFree(q);
+    for (void* q : s->span_in) if (q) (void)hipFree(q);
+    for (hipEvent_t e : s->down_ev) if (e) (void)hipEventDestroy(e);
+    if (s->warp_stream) { (void)vsi::retire_stream(s->warp_stream); (void)hipStreamDestroy(s->warp_stream); }
+    if (s->warp_ev) (void)hipEventDestroy(s->warp_ev);
+    if (s->down_stream) (void)hipStreamDestroy(s->down_stream);
+    if (s->up_stream) (void)hipStreamDestroy(s->up_stream);
+    vs_smoother_destroy(s->smoother);
+    vs_aligner_destroy(s->aligner);
+    delete s;
+}
+
+}  // extern "C"
+
+// A scratch buffer of the handle grows to `need` bytes (`count` buffers that share one size field: pipe_in's two halves).  sync: work on `ws` may
+// still read the old block.  The handle's fields are zeroed before the allocation: after a failed one the handle holds no buffer and the next
+// call starts over (tests/test_alloc_failure_gpu.py).
+static hipError_t grow(void** buf, size_t* bytes, size_t need, hipStream_t ws = nullptr, bool sync = false, int count = 1) {
+    if (*bytes >= need) return hipSuccess;
+    hipError_t e = sync ? hipStreamSynchronize(ws) : hipSuccess;
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < count; k++) { if (buf[k]) (void)hipFree(buf[k]); buf[k] = nullptr; }
+    *bytes = 0;
+    for (int k = 0; e == hipSuccess && k < count; k++) e = vsi::dev_alloc(&buf[k], need);
+    if (e == hipSuccess) *bytes = need;
+    return e;
+}
+
+// One vs_stabilizer_process_batch / _clips call, or a run of its frames; strides in elements.  clip_len > 0: the n frames are n / clip_len
+// independent clips, each run through a fresh stabilizer (reset before every clip and after the last), all of them aligned and warped together.
+struct StabCall {
+    const void* frames; size_t frame_stride; int n, clip_len, w, h, stride, format, mem;
+    void* out; size_t out_frame_stride; int32_t* has_output; int* out_w; int* out_h;
+
+    size_t esz() const { return vs_format_bits(format) > 8 ? 2 : 1; }
+    size_t fbytes() const { return (size_t)w * h * 3 * esz(); }              // one dense frame
+    size_t span_bytes() const { return ((size_t)(n - 1) * frame_stride + (size_t)(h - 1) * stride + (size_t)3 * w) * esz(); }   // first to last sample
+    bool dense() const { return stride == 3 * w && (n == 1 || frame_stride == (size_t)h * stride); }
+    const uint8_t* frame(int i) const { return (const uint8_t*)frames + (size_t)i * frame_stride * esz(); }
+    uint8_t* out_frame(int i) const { return (uint8_t*)out + (size_t)i * out_frame_stride * esz(); }
+    // the call for frames f0 .. f0 + m; the same call with its frames dense in device memory at `p`
+    StabCall sub(int f0, int m) const { StabCall c = *this; c.frames = frame(f0); c.out = out_frame(f0); c.has_output = has_output + f0; c.n = m; return c; }
+    StabCall dense_at(const void* p) const { StabCall c = *this; c.frames = p; c.frame_stride = (size_t)w * h * 3; c.stride = 3 * w; c.mem = VS_MEM_DEVICE; return c; }
+};
+
+// The frames of `c` (host or device memory, any pitch) dense at `dst` in device memory, on `st`.  dense: they lie dense where they are -- one
+// linear copy at the full link rate.  Pitched host frames go through span_in[area] (see there); pitched device frames are 2-D copies.
+static hipError_t make_dense(vs_stabilizer* s, const StabCall& c, bool dense, int area, void* dst, hipStream_t st) {
+    const size_t esz = c.esz(), fbytes = c.fbytes(), row = (size_t)c.w * 3 * esz;
+    if (dense) return hipMemcpyAsync(dst, c.frames, fbytes * c.n, c.mem == VS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st);
+    const uint8_t* from = (const uint8_t*)c.frames;
+    hipError_t e = hipSuccess;
+    if (c.mem == VS_MEM_HOST) {
+        const size_t span = c.span_bytes();
+        e = grow(&s->span_in[area], &s->span_in_bytes[area], span);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->span_in[area], c.frames, span, hipMemcpyHostToDevice, st);
+        from = (const uint8_t*)s->span_in[area];
+    }
+    for (int i = 0; e == hipSuccess && i < c.n; i++)
+        e = hipMemcpy2DAsync((uint8_t*)dst + (size_t)i * fbytes, row, from + (size_t)i * c.frame_stride * esz, (size_t)c.stride * esz, row, c.h,
+                             hipMemcpyDeviceToDevice, st);
+    return e;
+}
+
+// The outputs of input frames idx[0], idx[1], .. lie dense in `area`, obytes each; down to the caller's frames on `st`, runs that are contiguous on
+// both sides as one copy.
+static hipError_t copy_outputs_down(const StabCall& c, const std::vector<int>& idx, const uint8_t* area, size_t obytes, hipStream_t st) {
+    const bool dense_out = c.out_frame_stride * c.esz() == obytes;
+    hipError_t e = hipSuccess;
+    for (size_t j = 0; e == hipSuccess && j < idx.size();) {
+        size_t k = j + 1;
+        while (dense_out && k < idx.size() && idx[k] == idx[k - 1] + 1) k++;
+        e = hipMemcpyAsync(c.out_frame(idx[j]), area + j * obytes, obytes * (k - j), hipMemcpyDeviceToHost, st);
+        j = k;
+    }
+    return e;
+}
+
+// ---- one chunk: n successive VideoStabilizer::processFrame calls (stabilizer.cpp:9-117) as one batch ---------------------------------------
+using Held = vs_stabilizer::Held;
+using SharpBlock = vs_stabilizer::SharpBlock;
+struct Job { const void* src; vs_transform sampling; int i; void* release; };   // frame i of the chunk is due: warp `src`, then `release` is free
+// The look-ahead passes (DESIGN.md "Look-ahead passes: the shared path"): per job 1 + n candidates -- the frame itself, then the frames
+// that follow it in the queue; null frames and zero transforms behind the end of a list.  `side`: where each candidate's side value lies.
+struct Ahead { int n; std::vector<const void*> src; std::vector<vs_transform> t; std::vector<const uint64_t*> side; };
+
+// an idle block of at least `need` values, or a new one (`keep`: a block taken earlier in this call, still without references)
+static int take_block(vs_stabilizer* s, size_t need, SharpBlock* keep, SharpBlock** out) {
+    for (auto* b : s->sharp_blocks) if (b != keep && b->refs == 0 && b->cap >= need) { *out = b; return VS_OK; }
+    for (auto it = s->sharp_blocks.begin(); it != s->sharp_blocks.end();)           // idle blocks that are too small make room
+        if (*it != keep && (*it)->refs == 0) { (void)hipFree((*it)->dev); delete *it; it = s->sharp_blocks.erase(it); } else ++it;
+    void* q = nullptr;
+    VS_HIP(vsi::dev_alloc(&q, need * sizeof(unsigned long long)));
+    s->sharp_blocks.reserve(s->sharp_blocks.size() + 1);
+    *out = new SharpBlock{(unsigned long long*)q, need, 0};
+    s->sharp_blocks.push_back(*out);
+    return VS_OK;
+}
+
+// One chunk in flight: what its steps share, and the steps in the order stab_chunk runs them.
+struct Chunk {
+    vs_stabilizer* s;
+    const StabCall& c;
+    int slot;                      // the output area (batch_out / down) that host outputs leave through
+    bool threaded_download;        // ... with a downloader thread of their own, under the next chunk's compute
+    bool to_host, warps_apart;     // the outputs go to host memory (a chunk of the pipelined host batch too); the warps go to warp_stream
+    hipStream_t st, ws;            // the handle's stream; the stream of the passes and the warps
+    int crop, ow, oh, w = c.w, h = c.h, fbits = vs_format_bits(c.format), bits = fbits > 8 ? 16 : 8;
+    size_t fbytes = c.fbytes(), obytes = (size_t)ow * oh * 3 * c.esz();
+    const uint8_t* dense = nullptr; bool already_dense = false;   // the chunk's frames, dense, in device memory; ... where the caller has them
+    SharpBlock *sblk = nullptr, *mblk = nullptr;   // the sharpness of the chunk's frames (deblur on); their channel sums (fill with exposure match)
+    bool blend_on = false, want_sums = false;
+    int cur = 0;                   // t_buf[cur] / st_buf[cur]: the chunk's alignment results
+    std::vector<Job> jobs;
+    Ahead fill{}, db{}, dn{}, fk{};    // border fill (side, exposure match only: the channel sums, the ORIGINAL frames' throughout); deblur (side: the
+                                       // sharpness); denoise; deflicker (candidate 0 stays the ORIGINAL frame whatever deblur and denoise do)
+    uint32_t* fk_gains = nullptr;  // deflicker: four words per job, in flicker_buf
+
+    // stabilizer.cpp:15: a private dense copy of every input frame, in device memory
+    int make_dense() {
+        already_dense = c.mem == VS_MEM_DEVICE && c.dense();
+        dense = (const uint8_t*)c.frames;                  // read in place during this call; the tail is copied out by own_queued
+        if (already_dense) return VS_OK;
+        VS_HIP(grow(&s->batch_in, &s->batch_in_bytes, fbytes * c.n));
+        VS_HIP(::make_dense(s, c, c.dense(), 0, s->batch_in, st));
+        dense = (const uint8_t*)s->batch_in;
+        return VS_OK;
+    }
+
+    // `per` values per frame, measured by launch(frames, where to, how many, frame stride): the call's n frames in one launch into a block of
+    // their own (*out), then every queued frame that lacks the value, one launch each, behind them in the same block
+    template <typename Launch>
+    int measure(size_t per, SharpBlock* keep, SharpBlock* Held::*blk, const unsigned long long* Held::*val, Launch launch, SharpBlock** out) {
+        size_t need = (size_t)c.n;
+        for (auto& f : s->frames) if (!(f.*blk)) need++;
+        VS_TRY(take_block(s, per * need, keep, out));
+        VS_HIP(launch(dense, (*out)->dev, c.n, (size_t)w * h * 3));
+        size_t at = (size_t)c.n;
+        for (auto& f : s->frames) {
+            if (f.*blk) continue;
+            VS_HIP(launch(f.ptr, (*out)->dev + per * at, 1, 0));
+            f.*blk = *out; f.*val = (*out)->dev + per * at; ++(*out)->refs; at++;
+        }
+        return VS_OK;
+    }
+    // The side values of the chunk's frames, one launch over all of them each, into a block of their own; the values stay on the device.
+    int measure_side_values() {
+        if (!s->overlap_warps) sharp_settle(s);
+        // deblur (vs_deblur.hip): the sharpness.  (Queued frames that arrived while deblur was off are measured here too, once.)
+        if (db.n > 0)
+            VS_TRY(measure(1, nullptr, &Held::sb, &Held::sharp, [&](const void* p, unsigned long long* to, int m, size_t fs) {
+                return vsk::bgr_sharpness(p, w, h, w * 3, bits, fbits - 8, to, m, fs, st); }, &sblk));
+        // fill blend with exposure match (vs_fill.hip): the three channel sums.  (Queued frames that arrived while the match was off are summed
+        // here too, once: switching on mid-clip gives what a handle that had it from the first frame gives.)
+        if (want_sums)
+            VS_TRY(measure(3, sblk, &Held::mb, &Held::sums, [&](const void* p, unsigned long long* to, int m, size_t fs) {
+                return vsk::bgr_channel_sums(p, w, h, w * 3, bits, to, m, fs, st); }, &mblk));
+        if ((db.n > 0 || want_sums) && warps_apart) {       // the deblur pass / the fill's gain kernel read the values on warp_stream
+            VS_HIP(hipEventRecord(s->warp_ev, st));
+            VS_HIP(hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0));
+        }
+        return VS_OK;
+    }
+
+    // stabilizer.cpp:18-19 for all n frames.  In a chunked device-resident batch (stab_run_overlapped) the alignment of the NEXT chunk is
+    // started as soon as this one's results are in, so that it runs under this chunk's host work (smoother, correction chain, warp
+    // launches) as well as under its warps.
+    int align() {
+        vs_aligner* a = s->aligner;
+        cur = s->tb;
+        auto start = [&](int into, const void* frames, int n, bool async) {
+            s->t_buf[into].resize(n);
+            s->st_buf[into].resize(n);
+            return vsi::align_start(a, frames, (size_t)w * h * 3, n, c.clip_len, w, h, w * 3, c.format, VS_MEM_DEVICE, &s->params.aligner,
+                                    s->t_buf[into].data(), s->st_buf[into].data(), async);
+        };
+        if (s->prefetched) s->prefetched = false;           // started by the previous call, into [cur]
+        else VS_TRY(start(cur, dense, c.n, false));
+        VS_TRY(vsi::align_finish(a));
+        if (s->next_n > 0 && already_dense) {
+            VS_TRY(start(cur ^ 1, s->next_frames, s->next_n, true));
+            s->prefetched = true;
+            s->tb = cur ^ 1;
+        }
+        return VS_OK;
+    }
+
+    // Frame `src` has left the queue, due under `correction`: its candidate lists.  The queue now holds the frames k+1 .. behind this frame k,
+    // `measurements` their motions T_{k+1} .. (T_j: frame j-1 to j), entry for entry.  Frame j shows frame k's pixels through
+    // inverse(T_{k+1} o .. o T_j), and -- the fill -- this output through F_j = compose(that, correction); a frame whose alignment failed ends
+    // the list (vs_lookahead.hpp).  (The frames are read before their own jobs release them: releases follow all launches.)
+    void lists(const Held& src, const vs_transform& correction) {
+        const size_t avail = std::min(s->frames.size(), s->measurements.size());
+        auto list = [&](Ahead& a, size_t have, const vs_transform& t0, const vs_transform* corr, const unsigned long long* Held::*side) {
+            if (a.n <= 0) return;
+            a.src.push_back(src.ptr);
+            a.t.push_back(t0);
+            const size_t at = a.t.size();
+            a.t.resize(at + (size_t)a.n);
+            const int live = vsi::lookahead_transforms(s->measurements, s->meas_ok, have, a.n, corr, &a.t[at]);
+            for (int i = 0; i < a.n; i++) a.src.push_back(i < live ? s->frames[i].ptr : nullptr);
+            if (!side) return;
+            a.side.push_back((const uint64_t*)(src.*side));
+            for (int i = 0; i < a.n; i++) a.side.push_back(i < live ? (const uint64_t*)(s->frames[i].*side) : nullptr);
+        };
+        const vs_transform none{0, 0, 0, 0};
+        list(fill, avail, correction, &correction, want_sums ? &Held::sums : nullptr);
+        size_t sharp_avail = 0;                     // the deblur's list also ends at a frame without a sharpness value
+        while (sharp_avail < avail && s->frames[sharp_avail].sharp) sharp_avail++;
+        list(db, sharp_avail, none, nullptr, &Held::sharp);
+        list(dn, avail, none, nullptr, nullptr);
+        list(fk, avail, none, nullptr, nullptr);
+    }
+    // The frame loop: every frame joins the queue, its measurement goes through the reference's bookkeeping (vs_stab_step.hpp), and the frame
+    // that becomes due leaves the queue as a job with its candidate lists.
+    int frame_loop() {
+        for (int i = 0; i < c.n; i++) {
+            if (c.clip_len > 0 && i % c.clip_len == 0) VS_TRY(vs_stabilizer_reset(s));   // a new clip: frames still queued are dropped
+            ++s->frame_index;
+            s->frames.push_back(Held{(void*)(dense + (size_t)i * fbytes), false, sblk, sblk ? sblk->dev + i : nullptr, mblk,
+                                     mblk ? mblk->dev + 3 * (size_t)i : nullptr});
+            if (sblk) ++sblk->refs;
+            if (mblk) ++mblk->refs;
+            const vs_transform meas = s->t_buf[cur][i];
+            const bool success = s->st_buf[cur][i] == 1;
+            s->last_meas = meas; s->last_success = success ? 1 : 0;
+            c.has_output[i] = 0;
+            vs_transform correction;
+            if (!vsi::stab_step(meas, success, w, h, s->params, s->smoother, s->measurements, s->meas_ok, s->accum, &correction)) continue;
+            if (s->frames.empty()) continue;
+            const Held src = s->frames.front();
+            s->frames.pop_front();
+            if (src.sb) s->sharp_pending.push_back(src.sb);   // (the jobs' launches still read it: counted down after them)
+            if (src.mb) s->sharp_pending.push_back(src.mb);
+            // :97-99: warpBySimilarityTransform(frame, accum^-1); cv::warpAffine without WARP_INVERSE_MAP
+            // inverts the matrix it is given (imgproc.cpp:472), so the sampling map is (accum^-1)^-1.
+            // (VS_WARP_BILINEAR_CV is cv::warpAffine itself, inversion included: it takes the correction as the reference hands it over)
+            jobs.push_back(Job{src.ptr, s->params.warp_mode == VS_WARP_BILINEAR_CV ? correction : vs_transform_inverse(&correction), i,
+                               src.owned ? src.ptr : nullptr});
+            c.has_output[i] = 1;
+            lists(src, correction);
+        }
+        return VS_OK;
+    }
+
+    // The look-ahead passes that run in front of the warps, on their stream, one launch each over every due frame.  The candidates are read
+    // before their own jobs release them: releases follow the warps.  (sync in grow: warps / gain passes of an earlier chunk may still read the
+    // area.)  Host callers first: the staging area's previous user has been drained (through down[slot]), and the area holds the jobs' outputs.
+    int passes() {
+        const int nj = (int)jobs.size(), nfill = fill.n;
+        if (to_host) {
+            if (s->down[slot].valid()) {
+                const hipError_t de = s->down[slot].get();
+                if (de != hipSuccess) return set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
+            }
+            VS_HIP(grow(&s->batch_out[slot], &s->batch_out_bytes[slot], obytes * jobs.size()));
+        }
+        // the jobs' frames now lie in `buf`, one after the other: the warps (and the fill's candidate 0) read them there
+        auto sources = [&](const void* buf) {
+            for (size_t j = 0; j < jobs.size(); j++) {
+                jobs[j].src = (const uint8_t*)buf + j * fbytes;
+                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
+            }
+        };
+        if (db.n > 0) {     // every due frame is deblurred into a scratch frame of its own
+            VS_HIP(grow(&s->deblur_buf, &s->deblur_bytes, fbytes * jobs.size(), ws, true));
+            VS_TRY(vsi::bgr_deblur_ptrs(nj, w, h, w * 3, c.format, 1 + db.n, db.src.data(), db.side.data(), db.t.data(), &s->deblur_params, s->deblur_buf,
+                                        (size_t)w * h * 3, w * 3, ws));
+            sources(s->deblur_buf);
+        }
+        if (dn.n > 0) {     // ... (deblurred, if that pass is on) denoised into a scratch frame of its own; the candidates are the original input frames
+            VS_HIP(grow(&s->denoise_buf, &s->denoise_bytes, fbytes * jobs.size(), ws, true));
+            for (size_t j = 0; j < jobs.size(); j++) dn.src[j * (1 + dn.n)] = jobs[j].src;
+            VS_TRY(vsi::bgr_denoise_ptrs(nj, w, h, w * 3, c.format, 1 + dn.n, dn.src.data(), dn.t.data(), &s->denoise_params, s->denoise_buf,
+                                         (size_t)w * h * 3, w * 3, ws));
+            sources(s->denoise_buf);
+        }
+        if (fk.n > 0) {
+            // the exposure statistics of every due frame against the frames that follow it -- the original input frames on both sides -- and
+            // its three gains: one statistics launch and one gains launch.  Nothing of it reaches the host; the gain pass behind each run's
+            // warp (and fill) reads the gains there.
+            const size_t sbytes = jobs.size() * (size_t)(1 + fk.n) * 8 * sizeof(uint64_t), need = sbytes + jobs.size() * 4 * sizeof(uint32_t);
+            VS_HIP(grow(&s->flicker_buf, &s->flicker_bytes, need, ws, true));
+            fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf + sbytes);
+            VS_TRY(vsi::exposure_stats_ptrs(nj, w, h, w * 3, c.format, 1 + fk.n, fk.src.data(), fk.t.data(), &s->deflicker_params,
+                                            (uint64_t*)s->flicker_buf, ws));
+            VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf, nj, 1 + fk.n, w, h, s->deflicker_params.step, fk_gains, ws));
+        }
+        return VS_OK;
+    }
+
+    // warp every due frame, runs of consecutive batch frames as one launch.  The crop of stabilizer.cpp:102-109 is the
+    // output window of the warp: the margin is never computed and no full-size intermediate frame exists.  Device callers
+    // get the window written straight into `out`; host callers into the staging area.
+    int warp_runs() {
+        const int nfill = fill.n, max_value = vs_format_max_value(c.format);
+        // (device output of an overlapped clip batch: the warps go to warp_stream and run under the next group's alignment; beside it the
+        // Lanczos2 warp keeps its standard window: see vsi::warp_keeps_solver_slot)
+        struct SlotHint { bool& f; bool old; SlotHint(bool on) : f(vsi::warp_keeps_solver_slot()), old(f) { f = on; } ~SlotHint() { f = old; } } hint(s->overlap_warps);
+        std::vector<vs_transform> ts;
+        for (size_t j = 0, e; j < jobs.size(); j = e) {
+            e = j + 1;
+            while (e < jobs.size() && (const uint8_t*)jobs[e].src == (const uint8_t*)jobs[e - 1].src + fbytes && jobs[e].i == jobs[e - 1].i + 1) e++;
+            ts.clear();
+            for (size_t q = j; q < e; q++) ts.push_back(jobs[q].sampling);
+            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot] + j * obytes) : (void*)c.out_frame(jobs[j].i);
+            const size_t dst_fs = to_host ? (size_t)ow * oh * 3 : c.out_frame_stride;
+            if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
+                VS_TRY(vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, bits, 1 + nfill, &fill.src[j * (1 + nfill)],
+                                               &fill.t[j * (1 + nfill)], s->params.warp_border, max_value, crop, crop, ow, oh, dst, dst_fs, ow * 3, ws,
+                                               want_sums ? &fill.side[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr));
+            else
+                VS_TRY(vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, bits, ts.data(), s->params.warp_mode,
+                                                   s->params.warp_border, max_value, crop, crop, ow, oh, dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws));
+            // deflicker: the run's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
+            if (fk.n > 0)
+                VS_HIP(vsk::bgr_gain(dst, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * j, dst, ow * 3, (int)(e - j), dst_fs, dst_fs, ws));
+        }
+        return VS_OK;
+    }
+
+    // the buffers of ours that the jobs' frames lay in are free again: read on warp_stream and refilled on st, they wait for that stream's
+    // synchronisation; else they are reused only by later work on this stream
+    void release() {
+        for (const Job& j : jobs) if (j.release) (warps_apart ? s->held_release : s->pool).push_back(j.release);
+    }
+
+    // Host callers: the staged outputs go down.  A call on its own: behind the warps on the same stream; the synchronisation at the end of the
+    // call covers them.  A chunk of the pipelined batch: the area is handed to a downloader thread, which waits (on its own stream) for the warps.
+    int download() {
+        if (!to_host) return VS_OK;
+        std::vector<int> idx(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) idx[j] = jobs[j].i;
+        const uint8_t* area = (const uint8_t*)s->batch_out[slot];
+        if (!threaded_download) { VS_HIP(copy_outputs_down(c, idx, area, obytes, st)); return VS_OK; }
+        if (!s->down_stream) VS_HIP(hipStreamCreateWithFlags(&s->down_stream, hipStreamNonBlocking));
+        if (!s->down_ev[slot]) VS_HIP(hipEventCreateWithFlags(&s->down_ev[slot], hipEventDisableTiming));
+        VS_HIP(hipEventRecord(s->down_ev[slot], st));
+        s->down[slot] = run_async([call = c, idx, area, obytes = obytes, device = vsi::aligner_device(s->aligner), ds = s->down_stream, ev = s->down_ev[slot]]() -> hipError_t {
+            hipError_t e = hipSetDevice(device);
+            if (e == hipSuccess) e = hipStreamWaitEvent(ds, ev, 0);
+            if (e == hipSuccess) e = copy_outputs_down(call, idx, area, obytes, ds);
+            return e != hipSuccess ? e : hipStreamSynchronize(ds);
+        });
+        return VS_OK;
+    }
+
+    // frames of this batch that are still queued move into buffers of our own
+    int own_queued() {
+        for (auto& f : s->frames) {
+            if (f.owned || s->defer_own) continue;
+            void* copy = nullptr;
+            if (!s->pool.empty()) { copy = s->pool.back(); s->pool.pop_back(); }
+            else VS_HIP(vsi::dev_alloc(&copy, fbytes));
+            VS_HIP(hipMemcpyAsync(copy, f.ptr, fbytes, hipMemcpyDeviceToDevice, st));
+            f.ptr = copy; f.owned = true;
+        }
+        return VS_OK;
+    }
+};
+
+// out_mem: where the outputs go.  slot_arg >= 0: a chunk of the pipelined host batch -- its outputs leave through output area `slot_arg` and a
+// downloader thread of their own, under the next chunk's compute.  slot_arg < 0: a call on its own (process / process_batch that fits one
+// chunk): the copies go onto the handle's stream, nothing to overlap with, no thread.
+static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot_arg) {
+    VS_ARG(s && c.frames && c.out && c.has_output && c.out_w && c.out_h && c.n >= 1);
+    VS_ARG(c.format != VS_FMT_GRAY8 && vs_format_bits(c.format) != 0);
+    VS_ARG(c.w > 0 && c.h > 0 && c.w <= 65535 && c.h <= 65535);
+    VS_ARG(c.stride >= 3 * c.w);
+    const int w = c.w, h = c.h, crop = s->params.crop_pixels > 0 ? s->params.crop_pixels : 0;
+    VS_ARG(w > 2 * crop && h > 2 * crop);
+    const int ow = w - 2 * crop, oh = h - 2 * crop, lag = s->params.lag;
+    VS_ARG(c.n == 1 || (c.frame_stride >= (size_t)(h - 1) * c.stride + (size_t)3 * w && c.out_frame_stride >= (size_t)ow * oh * 3));
+    VS_HIP(hipSetDevice(vsi::aligner_device(s->aligner)));
+    if (s->w != w || s->h != h || s->fmt != c.format) {
+        // a size change restarts the aligner (alignment.cpp:155).  The reference would go on warping queued frames of the
+        // old size with measurements of the new one; here the change starts a new clip, cleanly: queued frames of the
+        // old size are dropped and the smoother, the accumulated correction and the frame counter start over.
+        stab_drop_frames(s);
+        VS_TRY(vs_stabilizer_reset(s));
+        s->w = w; s->h = h; s->fmt = c.format; s->frame_bytes = c.fbytes();
+    }
+    *c.out_w = ow; *c.out_h = oh;
+
+    const bool to_host = out_mem == VS_MEM_HOST, warps_apart = s->overlap_warps && !to_host;
+    hipStream_t st = (hipStream_t)vs_aligner_stream(s->aligner);
+    Chunk k{s, c, std::max(slot_arg, 0), slot_arg >= 0, to_host, warps_apart, st, warps_apart ? s->warp_stream : st, crop, ow, oh};
+    k.fill.n = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, lag) : 0;
+    k.db.n = std::min(s->deblur, lag); k.dn.n = std::min(s->denoise, lag); k.fk.n = std::min(s->deflicker, lag);
+    k.blend_on = k.fill.n > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
+    k.want_sums = k.fill.n > 0 && s->fill_blend.match != 0;
+
+    VS_TRY(k.make_dense());
+    VS_TRY(k.measure_side_values());
+    VS_TRY(k.align());
+    VS_TRY(k.frame_loop());
+    if (!k.jobs.empty()) {
+        VS_TRY(k.passes());
+        VS_TRY(k.warp_runs());
+        k.release();
+        VS_TRY(k.download());
+    }
+    if (!warps_apart) sharp_settle(s);                    // (readers and the next writer share this stream)
+    if (c.clip_len > 0) VS_TRY(vs_stabilizer_reset(s));   // nothing carries over from the last clip
+    VS_TRY(k.own_queued());
+    if (!s->prefetched) VS_HIP(hipStreamSynchronize(st));   // (with the next chunk's alignment in flight its completion is the next call's wait)
+    return std::accumulate(c.has_output, c.has_output + c.n, 0);
+}
+// (guarded: an exception inside a chunk -- a host allocation that fails -- comes back as an error code, so that the callers' loops restore
+// the handle's modes and stab_run's failure protocol runs)
+static int stab_run_impl(vs_stabilizer* s, const StabCall& c, int out_mem, int slot) {
+    return vsi::guarded([&] { return stab_chunk(s, c, out_mem, slot); });
+}
+
+// The batch split into chunks of `chunk` frames (whole clips in clip mode): an uploader thread fills the other upload area
+// with chunk k+1 while chunk k is aligned and warped, and a downloader thread drains chunk k's outputs while chunk k+1 is
+// computed -- upload, compute and download overlap, and the link carries input and output at the same time (full duplex).
+// Every chunk goes through stab_run_impl exactly as a separate vs_stabilizer_process_batch call would, which is the
+// definition of the batched form ("n successive process calls"), so the results do not depend on the chunking.
+static int stab_run_host_pipelined(vs_stabilizer* s, const StabCall& c, int chunk) {
+    VS_ARG(s && c.frames && c.out && c.has_output && c.out_w && c.out_h);
+    VS_ARG(c.w > 0 && c.h > 0 && c.w <= 65535 && c.h <= 65535);
+    VS_ARG(c.format != VS_FMT_GRAY8 && vs_format_bits(c.format) != 0 && c.stride >= 3 * c.w);
+    VS_ARG(c.frame_stride >= (size_t)(c.h - 1) * c.stride + (size_t)3 * c.w);
+    const int device = vsi::aligner_device(s->aligner);
+    VS_HIP(hipSetDevice(device));
+    VS_HIP(grow(s->pipe_in, &s->pipe_in_bytes, c.fbytes() * chunk, nullptr, false, 2));
+    if (!s->up_stream) VS_HIP(hipStreamCreateWithFlags(&s->up_stream, hipStreamNonBlocking));
+    const bool dense = c.dense();
+    auto upload = [=](int k) -> hipError_t {                 // chunk k -> pipe_in[k & 1], dense
+        const int off = k * chunk;
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = make_dense(s, c.sub(off, std::min(chunk, c.n - off)), dense, k & 1, s->pipe_in[k & 1], s->up_stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(s->up_stream);
+    };
+    const int n_chunks = (c.n + chunk - 1) / chunk;
+    std::future<hipError_t> next = run_async(upload, 0);
+    int produced = 0;
+    for (int k = 0; k < n_chunks; k++) {
+        const int off = k * chunk;
+        const hipError_t ue = next.get();
+        if (k + 1 < n_chunks) next = run_async(upload, k + 1);
+        int r = ue == hipSuccess ? VS_OK : set_error(VS_ERR_HIP, "frame upload failed: %s", hipGetErrorString(ue));
+        if (r == VS_OK) r = stab_run_impl(s, c.sub(off, std::min(chunk, c.n - off)).dense_at(s->pipe_in[k & 1]), VS_MEM_HOST, k & 1);
+        if (r < 0) { if (next.valid()) (void)next.get(); return r; }
+        produced += r;
+    }
+    return produced;
+}
+
+// A dense device-resident batch in sub-batches of `step` frames, the warps on warp_stream: those of sub-batch g run under the alignment of
+// sub-batch g + 1 (started early with `prefetch`), which takes solver build `mode`.  Every sub-batch goes through stab_run_impl exactly as a call
+// of its own would.  defer: frames still queued at a boundary stay pointers into the caller's batch (it outlives the call) and only the last
+// sub-batch copies them out; buffers of earlier calls whose last reader is a warp on warp_stream return to the pool only after that stream's
+// synchronisation.
+static int stab_run_overlapped(vs_stabilizer* s, const StabCall& c, int step, bool defer, int mode, bool prefetch) {
+    vs_aligner* a = s->aligner;
+    hipStream_t st = (hipStream_t)vs_aligner_stream(a);
+    int r = 0;
+    hipError_t he = hipSetDevice(vsi::aligner_device(a));
+    if (he == hipSuccess && !s->warp_stream) he = hipStreamCreateWithFlags(&s->warp_stream, hipStreamNonBlocking);
+    if (he == hipSuccess && !s->warp_ev) he = hipEventCreateWithFlags(&s->warp_ev, hipEventDisableTiming);
+    // whatever the handle's stream was told to wait for (vs_stabilizer_wait_stream) holds for the warps too
+    if (he == hipSuccess) he = hipEventRecord(s->warp_ev, st);
+    if (he == hipSuccess) he = hipStreamWaitEvent(s->warp_stream, s->warp_ev, 0);
+    if (he != hipSuccess) r = set_error(VS_ERR_HIP, "stabilizer warp stream: %s", hipGetErrorString(he));
+    const int saved_mode = vsi::aligner_batch_mode(a);
+    vsi::aligner_set_batch_mode(a, mode);
+    s->overlap_warps = true;
+    for (int f0 = 0; r >= 0 && f0 < c.n; f0 += step) {
+        const int m = std::min(step, c.n - f0);
+        s->defer_own = defer && f0 + m < c.n;
+        s->next_n = prefetch ? std::min(step, c.n - f0 - m) : 0;
+        s->next_frames = c.frame(f0 + m);
+        const int rg = stab_run_impl(s, c.sub(f0, m), c.mem, -1);
+        r = rg < 0 ? rg : r + rg;
+    }
+    s->defer_own = false; s->overlap_warps = false; s->next_n = 0;
+    vsi::aligner_set_batch_mode(a, saved_mode);
+    const hipError_t we = s->warp_stream ? hipStreamSynchronize(s->warp_stream) : hipSuccess;   // every warp has landed before the call returns
+    if (we != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "stabilizer warps: %s", hipGetErrorString(we));
+    for (void* b : s->held_release) s->pool.push_back(b);
+    s->held_release.clear();
+    sharp_settle(s);
+    return r;
+}
+
+// While a batch is in flight the frame queue holds non-owned pointers into the caller's buffer (or into batch_in); they
+// become copies of our own only at the end of a successful run.  Whatever stops a run early -- a HIP error, a refused
+// warp -- must not leave such an entry behind for the next call to warp from: the stabilizer is reset to a clean
+// "new clip" state (and the stream drained, so nothing still reads the caller's frames), and the error is passed on.
+static int stab_run(vs_stabilizer* s, const StabCall& c) {
+    const int n = c.n, clip_len = c.clip_len;
+    // host-resident batches longer than one upload chunk run as a three-stage pipeline: upload / compute / download
+    int chunk = 0;
+    if (s && c.mem == VS_MEM_HOST && n > 1 && c.w > 0 && c.h > 0) {
+        chunk = (int)std::max<size_t>(4, vsi::ingest_chunk_bytes() / std::max<size_t>(1, c.fbytes()));
+        if (clip_len > 0) chunk = std::max(clip_len, chunk - chunk % clip_len);
+    }
+    // Device-resident clip batches (vs_stabilizer_process_clips, VS_MEM_DEVICE, dense frames): the clips are cut into groups and the
+    // warps of group g go to a stream of their own, so that they run under the alignment of group g + 1 -- which then takes the
+    // small-footprint solver build (VS_BATCH_SHARED: it shares CUs with the warp grid).  Every group goes through stab_run_impl
+    // exactly as a process_clips call of its own would (clips are independent: stabilizer.cpp keeps no state across a reset), so
+    // the grouping cannot change results.  VS_STAB_OVERLAP=0 turns it off.
+    static const bool overlap_env = []() { const char* e = getenv("VS_STAB_OVERLAP"); return e ? atoi(e) != 0 : true; }();
+    static const bool prefetch_env = []() { const char* e = getenv("VS_STAB_PREFETCH"); return e ? atoi(e) != 0 : true; }();
+    // (the solver build under the overlapped warps: the small-footprint one beside a Lanczos2 warp, which fills the CUs for longer than the
+    // alignment pass takes; beside the fixed-point bilinear warp -- a quarter of the alignment pass -- the exclusive 512-thread build, whose
+    // shorter solver chain is worth more than the shared CUs: 1080p x 480 frames 101 k -> 120 k frames/s, 4K x 240 21.1 k -> 34.3 k
+    // (profiles/r05_stab_cv_solver.txt; VS_STAB_CV_SOLVER=1 selects the small build for an A/B))
+    static const int cv_solver_env = []() { const char* e = getenv("VS_STAB_CV_SOLVER"); return e && atoi(e) == VS_BATCH_SHARED ? VS_BATCH_SHARED : VS_BATCH_EXCLUSIVE; }();
+    const int overlap_mode = s && s->params.warp_mode == VS_WARP_BILINEAR_CV ? cv_solver_env : VS_BATCH_SHARED;
+    const int n_clips_all = clip_len > 0 ? n / clip_len : 0;
+    const bool dense_dev = s && c.mem == VS_MEM_DEVICE && c.w > 0 && n > 1 && c.dense();
+    int group_clips = 0;
+    if (overlap_env && dense_dev && clip_len >= 2 && n_clips_all >= 2 && n == n_clips_all * clip_len) {
+        // groups of at least kSharedMinPairs pairs (the small build's threshold), at most 4 groups (VS_STAB_GROUPS): every group boundary is a host
+        // synchronisation and a latency-bound solver launch -- c5 (8 clips x 60 x 4K 10-bit) 17.3-18.1 k frames/s with 8 groups, 18.9-19.5 k with 4
+        group_clips = std::max(1, (vsi::kSharedMinPairs + clip_len - 2) / (clip_len - 1));
+        // (beside the fixed-point bilinear warp, with the exclusive solver build: 2 groups -- c5 27.8 k frames/s with 4 groups, 28.9 k with 2, 24.8 k with 8)
+        static const int groups_env = []() { const char* e = getenv("VS_STAB_GROUPS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 0; }();
+        const int max_groups = groups_env ? groups_env : (overlap_mode == VS_BATCH_EXCLUSIVE ? 2 : 4);
+        group_clips = std::max(group_clips, (n_clips_all + max_groups - 1) / max_groups);
+        if (group_clips >= n_clips_all) group_clips = 0;
+    }
+    // ONE long device-resident clip: cut in time.  The batched form is n successive process calls, so the chunks are the same calls in the same
+    // order.  Time chunks of >= 48 frames (the small solver build's threshold with room to spare), at most 4 of them (VS_STAB_TIME_CHUNKS:
+    // 1080p x480 64 k frames/s with 8 chunks, 70 k with 6, 72 k with 4 or 3, 69-71 k with 2; profiles/r04_stab_long_clip.txt)
+    int time_chunk = 0;
+    static const int max_time_chunks = []() { const char* e = getenv("VS_STAB_TIME_CHUNKS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 4; }();
+    // (with the exclusive solver build a chunk is a latency-bound chain of its own: chunks of >= 120 frames -- 4K x240 34.2 k frames/s in 4 chunks, 35.8 k in 2)
+    if (overlap_env && dense_dev && clip_len == 0 && n >= 96)
+        time_chunk = std::max(overlap_mode == VS_BATCH_EXCLUSIVE ? 120 : 48, (n + max_time_chunks - 1) / max_time_chunks);
+    if (time_chunk >= n) time_chunk = 0;
+    int r;
+    if (chunk > 0 && n > chunk)
+        r = vsi::guarded([&] { return stab_run_host_pipelined(s, c, chunk); });
+    else if (group_clips > 0)
+        r = stab_run_overlapped(s, c, group_clips * clip_len, false, overlap_mode, prefetch_env);
+    else if (time_chunk > 0)
+        r = stab_run_overlapped(s, c, time_chunk, true, overlap_mode, prefetch_env);
+    else
+        r = stab_run_impl(s, c, c.mem, -1);
+    if (s) for (auto& f : s->down) if (f.valid()) {          // every download has landed before the call returns
+        const hipError_t de = f.get();
+        if (de != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
+    }
+    if (r < 0 && s && s->aligner) {
+        const std::string why = vs_last_error();             // the reset below must not hide the cause
+        vsi::align_abandon(s->aligner);                      // (a next chunk's alignment may have been started)
+        s->prefetched = false; s->next_n = 0;
+        (void)hipStreamSynchronize((hipStream_t)vs_aligner_stream(s->aligner));
+        for (auto it = s->frames.begin(); it != s->frames.end();) it = it->owned ? it + 1 : s->frames.erase(it);
+        (void)vs_stabilizer_reset(s);
+        // (everything is quiet now: the sharpness blocks are referred to by what is still queued, if anything, and by nothing else)
+        s->sharp_pending.clear();
+        for (auto* b : s->sharp_blocks) b->refs = 0;
+        for (auto& f : s->frames) { if (f.sb) ++f.sb->refs; if (f.mb) ++f.mb->refs; }
+        set_error(r, "%s", why.c_str());
+    }
+    return r;
+}
+
+extern "C" {
+
+int vs_stabilizer_process_batch(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int w, int h, int stride,
+                                int format, int mem, void* out, size_t out_frame_stride, int32_t* has_output, int* out_w,
+                                int* out_h) try {
+    return stab_run(s, StabCall{frames, frame_stride, n, 0, w, h, stride, format, mem, out, out_frame_stride, has_output, out_w, out_h});
+} VS_CATCH_ALL
+
+int vs_stabilizer_process_clips(vs_stabilizer* s, const void* frames, size_t frame_stride, int n_clips, int frames_per_clip,
+                                int w, int h, int stride, int format, int mem, void* out, size_t out_frame_stride,
+                                int32_t* has_output, int* out_w, int* out_h) try {
+    VS_ARG(n_clips >= 1 && frames_per_clip >= 1 && (long long)n_clips * frames_per_clip <= 0x7fffffff);
+    return stab_run(s, StabCall{frames, frame_stride, n_clips * frames_per_clip, frames_per_clip, w, h, stride, format, mem, out, out_frame_stride,
+                                has_output, out_w, out_h});
+} VS_CATCH_ALL
+
+void* vs_stabilizer_stream(const vs_stabilizer* s) { return s ? vs_aligner_stream(s->aligner) : nullptr; }
+int vs_stabilizer_set_select_mode(vs_stabilizer* s, int mode) try {
+    VS_ARG(s && s->aligner);
+    return vs_aligner_set_select_mode(s->aligner, mode);
+} VS_CATCH_ALL
+int vs_stabilizer_get_select_mode(const vs_stabilizer* s) try {
+    VS_ARG(s && s->aligner);
+    return vs_aligner_get_select_mode(s->aligner);
+} VS_CATCH_ALL
+int vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead) try {
+    VS_ARG(s && ahead >= 0);
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "border fill: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    VS_ARG(ahead <= s->params.lag);
+    s->border_fill = ahead;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->border_fill;
+} VS_CATCH_ALL
+int vs_stabilizer_set_fill_blend(vs_stabilizer* s, const vs_fill_blend_params* params) try {
+    VS_ARG(s);
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "fill blend: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    const vs_fill_blend_params p = params ? *params : vs_fill_blend_params{0, 0};
+    VS_ARG(p.feather >= 0 && p.feather <= 6 && (p.match == 0 || p.match == 1));
+    s->fill_blend = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* params) try {
+    VS_ARG(s && params);
+    *params = s->fill_blend;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_deblur_params p;
+    if (params) p = *params; else vs_deblur_params_default(&p);
+    VS_ARG(vsi::deblur_params_finite(p.sensitivity, p.max_ratio));
+    s->deblur = ahead;
+    s->deblur_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_deblur(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->deblur;
+} VS_CATCH_ALL
+int vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_denoise_params p;
+    if (params) p = *params; else vs_denoise_params_default(&p);
+    VS_ARG(p.strength >= 1 && p.strength <= 255);
+    s->denoise = ahead;
+    s->denoise_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params) try {
+    VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
+    vs_deflicker_params p;
+    if (params) p = *params; else vs_deflicker_params_default(&p);
+    VS_ARG(p.step >= 1 && p.step <= 64);
+    s->deflicker = ahead;
+    s->deflicker_params = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_deflicker(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->deflicker;
+} VS_CATCH_ALL
+int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->denoise;
+} VS_CATCH_ALL
+int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
+    VS_ARG(s && s->aligner);
+    return vs_aligner_wait_stream(s->aligner, producer_stream);
+} VS_CATCH_ALL
+
+// forget the clip: the next frame starts a new sequence (device buffers are kept)
+int vs_stabilizer_reset(vs_stabilizer* s) try {
+    VS_ARG(s);
+    VS_HIP(hipSetDevice(vsi::aligner_device(s->aligner)));
+    for (auto& f : s->frames) { sharp_unhold(s, f); if (f.owned) s->pool.push_back(f.ptr); }
+    s->frames.clear();
+    s->measurements.clear();
+    s->meas_ok.clear();
+    // (make the new smoother first: if that fails the handle keeps a valid, if stale, one -- never a null pointer for the next call to walk into)
+    vs_smoother* fresh = vs_smoother_create(s->params.lag, s->params.smoother_memory, s->params.lambda);
+    if (!fresh) return VS_ERR_NOMEM;
+    vs_smoother_destroy(s->smoother);
+    s->smoother = fresh;
+    s->accum = vs_transform{0, 0, 0, 0};
+    s->last_meas = vs_transform{0, 0, 0, 0};
+    s->last_success = 0;
+    s->frame_index = 0;
+    return vs_aligner_reset(s->aligner);
+} VS_CATCH_ALL
+
+int vs_stabilizer_process(vs_stabilizer* s, const void* frame, int w, int h, int stride, int format, int mem, void* out,
+                          int* out_w, int* out_h) try {
+    int32_t has = 0;
+    int r = vs_stabilizer_process_batch(s, frame, 0, 1, w, h, stride, format, mem, out, 0, &has, out_w, out_h);
+    return r < 0 ? r : has;
+} VS_CATCH_ALL
+
+void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success) {
+    if (last_meas) *last_meas = s->last_meas;
+    if (accum) *accum = s->accum;
+    if (last_success) *last_success = s->last_success;
+}
+
+}  // extern "C"
