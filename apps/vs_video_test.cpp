@@ -1,9 +1,10 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear | --lanczos2] [--444]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear | --lanczos2] [--444]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
-// frame's own pixels over 2^N source pixels and --fill-match scales it to the frame's exposure (vs_stabilizer_set_fill_blend).  --deblur N: every frame is deblurred from
+// frame's own pixels over 2^N source pixels and --fill-match scales it to the frame's exposure (vs_stabilizer_set_fill_blend).  --inpaint: what
+// neither the frame nor a fill candidate covers is inpainted from the window's covered pixels (vs_stabilizer_set_inpaint).  --deblur N: every frame is deblurred from
 // the sharper ones among the next N input frames before it is warped (vs_stabilizer_set_deblur).  --denoise N: every frame is averaged
 // with what the next N input frames show at the same scene point (vs_stabilizer_set_denoise; --denoise-strength T: 1 .. 255, default 24).  --deflicker N: every
 // output frame's exposure is pulled to the mean exposure of itself and the next N input frames (vs_stabilizer_set_deflicker; --deflicker-step S: the lattice
@@ -18,7 +19,7 @@ namespace fs = std::filesystem;
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step) {
+                         int deflicker_step, bool inpaint) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -46,6 +47,11 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
     }
     if ((blend.feather != 0 || blend.match != 0) && vs_stabilizer_set_fill_blend(stab, &blend) != VS_OK) {
         std::cerr << "Error: vs_stabilizer_set_fill_blend: " << vs_last_error() << std::endl;
+        vs_stabilizer_destroy(stab);
+        return false;
+    }
+    if (inpaint && vs_stabilizer_set_inpaint(stab, 1) != VS_OK) {
+        std::cerr << "Error: vs_stabilizer_set_inpaint: " << vs_last_error() << std::endl;
         vs_stabilizer_destroy(stab);
         return false;
     }
@@ -109,6 +115,7 @@ int main(int argc, char** argv) {
     int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, denoise = 0, denoise_strength = 0, deflicker = 0, deflicker_step = 0, positional = 0;
     bool bilinear = false, lanczos2 = false, force444 = false;
     vs_fill_blend_params blend{0, 0};
+    bool inpaint = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--chunk" && i + 1 < argc) chunk = std::max(1, std::atoi(argv[++i]));
@@ -117,6 +124,7 @@ int main(int argc, char** argv) {
         else if (a == "--fill" && i + 1 < argc) fill = std::atoi(argv[++i]);
         else if (a == "--fill-feather" && i + 1 < argc) blend.feather = std::atoi(argv[++i]);
         else if (a == "--fill-match") blend.match = 1;
+        else if (a == "--inpaint") inpaint = true;
         else if (a == "--deblur" && i + 1 < argc) deblur = std::atoi(argv[++i]);
         else if (a == "--denoise" && i + 1 < argc) denoise = std::atoi(argv[++i]);
         else if (a == "--denoise-strength" && i + 1 < argc) denoise_strength = std::atoi(argv[++i]);
@@ -127,7 +135,7 @@ int main(int argc, char** argv) {
         else if (a == "--444") force444 = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -153,7 +161,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

@@ -395,6 +395,34 @@ int vs_exposure_gains_batch(const uint64_t* stats, int n_out, int n_cand, int w,
  * any device work; gains in device memory are never seen by the host: the kernel clamps them to that range. */
 int vs_bgr_gain_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
                       const uint32_t* gains, void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* ---- Inpaint of what the border fill leaves open: a coverage index and an exact-integer push-pull over the output window ----
+ * THE RULE.  VS_WARP_BILINEAR_CV conventions, 3 channels, 8- and 16-bit containers, every VS_FMT_BGR*, windows up to 32767 a side.
+ *   - COVERAGE INDEX.  Output frame o has n_cand (1 .. 16) candidates exactly as in vs_bgr_image_warp_fill_batch: each a forward
+ *     transform, a negative frame index ends the list, candidate 0 is the frame itself.  Only the sign of an index is looked at.  For
+ *     window pixel (x, y), cov = 1 + c, where c is the first candidate that COVERS the pixel by the fill's int32 rule, unchanged: the
+ *     positions X, Y of cv::warpAffine's tables, saturating cvRound with NaN -> 0, wrapping additions, all four taps inside w x h,
+ *     full-frame coordinates under the ROI.  cov = 0 if no candidate covers the pixel.
+ *   - INPAINT of one W x H window in place, given a byte mask m0 (non-zero = keep).  Pixel values outside the mask are never read.
+ *       Levels: W_0 = W, H_0 = H, W_{l+1} = (W_l + 1) >> 1, H_{l+1} = (H_l + 1) >> 1, up to the level L with W_L = H_L = 1.
+ *       Push, l -> l+1, per channel: the children of (X, Y) are the pixels (2X+i, 2Y+j), i, j in {0, 1}, that exist at level l and
+ *         have m_l != 0; n is their number and s their sum.  n == 0: m_{l+1} = 0 and the value is unused.  Otherwise m_{l+1} = 1 and
+ *         the value is (2 s + n) / (2 n), floor division: the rounded mean (unsigned 32-bit is enough; the result fits the container).
+ *       If m_L == 0 (no kept pixel in the window) the window is left untouched.
+ *       Pull, l = L-1 .. 0 (level l+1 is completely defined by then): a pixel (x, y) with m_l == 0 becomes
+ *         (9 P(px,py) + 3 P(qx,py) + 3 P(px,qy) + P(qx,qy) + 8) >> 4 over level l+1, where px = x >> 1,
+ *         qx = clamp(px + (x & 1 ? 1 : -1), 0, W_{l+1} - 1), and py, qy are formed the same way from y and H_{l+1}.
+ *   - Hence (a) kept pixels come back bit for bit; (b) every inpainted sample lies between the minimum and the maximum of the kept
+ *     samples of its channel, so max_value never comes into it; (c) if the kept pixels have one colour the whole window gets it; (d) an
+ *     all-kept window and an all-open window come back bit for bit; (e) the result does not depend on the prior content of open pixels.
+ * cov: n_out indices of roi_h rows of cov_stride bytes, cov_frame_stride bytes apart, in `mem`; cand_frame and cand_t are host arrays of
+ * n_out * n_cand entries.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_fill_coverage_batch(int w, int h, int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
+                               int roi_x, int roi_y, int roi_w, int roi_h, uint8_t* cov, size_t cov_frame_stride, int cov_stride,
+                               int mem, void* stream);
+/* n windows of w x h pixels in place (frame_stride, stride in elements; mask_frame_stride, mask_stride in bytes); img and mask live in
+ * `mem`.  The call takes its scratch from the device and returns when the work is done. */
+int vs_bgr_inpaint_batch(void* img, size_t frame_stride, int n, int w, int h, int stride, int format, const uint8_t* mask,
+                         size_t mask_frame_stride, int mask_stride, int mem, void* stream);
 /* same sampling, float output (typed like image_warp); dst interleaved f32 */
 int vs_bgr_image_warp_f32(const void* src, int w, int h, int src_stride, int channels, int bits,
                           const vs_transform* t, int mode, int border,
@@ -655,6 +683,15 @@ int   vs_stabilizer_get_denoise(const vs_stabilizer* s);
  * returns `ahead`. */
 int   vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params);
 int   vs_stabilizer_get_deflicker(const vs_stabilizer* s);
+/* Inpaint (the rule: see vs_bgr_fill_coverage_batch).  0 (default): off -- the handle as it is without this call, launch for launch.
+ * 1: what neither the frame itself nor a fill candidate covers in the output window is inpainted from the window's covered pixels, so
+ * that crop_pixels 0 leaves no border colour behind.  Works with the border fill on or off (off: the list is candidate 0 alone).
+ * Order: deblur, denoise, warp, border fill (with or without blend), coverage index from the fill's candidate list, inpaint in place
+ * on the output window, then the deflicker's gain pass, last.  A run of frames whose own source covers the whole window -- every frame
+ * at the default crop -- launches nothing for this pass.  VS_ERR_UNSUPPORTED on a handle with another warp_mode than
+ * VS_WARP_BILINEAR_CV; VS_ERR_ARG for a value other than 0 or 1.  Takes effect with the next output frame.  get returns the switch. */
+int   vs_stabilizer_set_inpaint(vs_stabilizer* s, int on);
+int   vs_stabilizer_get_inpaint(const vs_stabilizer* s);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -172,6 +172,8 @@ SIGNATURES = {
                                            _vp, _i32, _vp]),
     "vs_exposure_gains_batch": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(DeflickerParams), _vp, _i32, _vp]),
     "vs_bgr_gain_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_inpaint_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
@@ -195,6 +197,8 @@ SIGNATURES = {
     "vs_stabilizer_get_denoise": (_i32, [_vp]),
     "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
     "vs_stabilizer_get_deflicker": (_i32, [_vp]),
+    "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
+    "vs_stabilizer_get_inpaint": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
     "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
@@ -651,6 +655,56 @@ def bgr_image_warp_fill_blend_batch(src, cand_frame, cand_t, sums=None, feather=
     return (res, out) if guard is not None else res
 
 
+def bgr_fill_coverage_batch(w, h, cand_frame, cand_t, roi=None, cov_stride=None, guard=None):
+    """the inpaint's coverage index (include/vs_amd.h: vs_bgr_fill_coverage_batch).  cand_frame (n_out, n_cand) ints, a negative index ends a
+    list (only the sign is looked at); cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w) uint8: 1 + the first covering
+    candidate, 0 for none.  cov_stride (bytes): the call is made on a pitched buffer.  guard: a value the padding is filled with first; the
+    padded buffer is returned as well"""
+    _, idx, n_out, n_cand, arr, _, _ = _lookahead_args(np.zeros((1, 1, 1, 3), np.uint8), cand_frame, cand_t, None)
+    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
+    cs = rw if cov_stride is None else cov_stride
+    out = np.full((max(n_out, 1), rh, cs), 0xA5 if guard is None else guard, np.uint8)
+    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, rx, ry, rw, rh, _p(out), rh * cs, cs,
+                                            MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n_out, :, :rw])
+    return (res, out) if guard is not None else res
+
+
+def bgr_fill_coverage_batch_device(w, h, cand_frame, cand_t, roi, cov_ptr, cov_fs, cov_stride, stream=None):
+    """device-resident form: the index goes to device memory (strides in bytes), enqueue only"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape
+    flat = [t for row in cand_t for t in row]
+    arr = (Transform * len(flat))(*flat)
+    rx, ry, rw, rh = roi
+    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, rx, ry, rw, rh, _p(cov_ptr), cov_fs,
+                                            cov_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
+def bgr_inpaint_batch(img, mask, fmt=None, stride=None, mask_stride=None, guard=None):
+    """push-pull inpaint (include/vs_amd.h: vs_bgr_inpaint_batch).  img (n,h,w,3) numpy, mask (n,h,w) bytes (non-zero = keep) -> (n,h,w,3);
+    img is not changed.  stride (elements) / mask_stride (bytes): the call is made on pitched buffers.  guard: a value the image's padding is
+    filled with first; the padded buffer is returned as well"""
+    img = np.ascontiguousarray(img)
+    n, h, w, c = img.shape
+    fmt = _fmt_of(img.dtype, 3) if fmt is None else fmt
+    st = w * c if stride is None else stride
+    ms = w if mask_stride is None else mask_stride
+    buf = np.full((n, h, st), 0 if guard is None else guard, img.dtype)
+    buf[:, :, :w * c] = img.reshape(n, h, w * c)
+    mk = np.zeros((n, h, ms), np.uint8)
+    mk[:, :, :w] = _c(mask, np.uint8).reshape(n, h, w)
+    _check(lib().vs_bgr_inpaint_batch(_p(buf), h * st, n, w, h, st, fmt, _p(mk), h * ms, ms, MEM_HOST, None))
+    res = np.ascontiguousarray(buf[:, :, :w * c]).reshape(n, h, w, c)
+    return (res, buf) if guard is not None else res
+
+
+def bgr_inpaint_batch_device(img_ptr, frame_stride, n, w, h, stride, fmt, mask_ptr, mask_fs, mask_stride, stream=None):
+    """device-resident form: in place (frame_stride, stride in elements; the mask's in bytes)"""
+    _check(lib().vs_bgr_inpaint_batch(_p(img_ptr), frame_stride, n, w, h, stride, fmt, _p(mask_ptr), mask_fs, mask_stride, MEM_DEVICE,
+                                      C.c_void_p(stream) if stream else None))
+
+
 def deblur_params(**kw):
     p = DeblurParams()
     lib().vs_deblur_params_default(C.byref(p))
@@ -1046,7 +1100,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1063,6 +1117,15 @@ class Stabilizer:
             self.set_denoise(denoise, denoise_params)
         if deflicker:
             self.set_deflicker(deflicker, deflicker_params)
+        if inpaint:
+            self.set_inpaint(inpaint)
+
+    def set_inpaint(self, on=1):
+        """0: off; 1: what neither the frame nor a fill candidate covers in the output window is inpainted (VS_WARP_BILINEAR_CV handles)"""
+        _check(lib().vs_stabilizer_set_inpaint(self.h, int(on)))
+
+    def get_inpaint(self):
+        return _check(lib().vs_stabilizer_get_inpaint(self.h))
 
     def set_deflicker(self, ahead, params=None):
         """0: off; 1 .. lag: every output frame's exposure is pulled to the mean exposure of itself and the next `ahead` input frames

@@ -546,6 +546,7 @@ extern "C" int vs_bounds_fetch_warp(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_phase(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_flow(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_fill(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_inpaint(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_deblur(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_denoise(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_deflicker(unsigned out[8], int reset);
@@ -568,12 +569,12 @@ int vs_debug_bounds_check(void) try {
     if (!vsi::device_ready()) return VS_ERR_HIP;
     VS_HIP(hipDeviceSynchronize());
     int (*const fetch[])(unsigned*, int) = {vs_bounds_fetch_engine, vs_bounds_fetch_warp, vs_bounds_fetch_phase, vs_bounds_fetch_flow, vs_bounds_fetch_fill,
-                                            vs_bounds_fetch_deblur, vs_bounds_fetch_denoise, vs_bounds_fetch_deflicker, vs_bounds_fetch_capi};
+                                            vs_bounds_fetch_deblur, vs_bounds_fetch_denoise, vs_bounds_fetch_deflicker, vs_bounds_fetch_inpaint, vs_bounds_fetch_capi};
     const char* const names[] = {"vs_engine.hip", "vs_warp.hip", "vs_phase.hip", "vs_flow.hip", "vs_fill.hip", "vs_deblur.hip", "vs_denoise.hip", "vs_deflicker.hip",
-                                 "vs_capi.hip"};
+                                 "vs_inpaint.hip", "vs_capi.hip"};
     unsigned total = 0;
     char msg[512] = "";
-    for (int k = 0; k < 9; k++) {
+    for (int k = 0; k < 10; k++) {
         unsigned r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fetch[k](r, 1) != 0) return set_error(VS_ERR_HIP, "bounds record of %s is not readable", names[k]);
         if (r[0] && !total)
@@ -1343,3 +1344,80 @@ int vs_bgr_gain_batch(const void* src, size_t src_fs, int n, int w, int h, int s
     return vsi::finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
+
+// ---- inpaint of what the fill leaves open (vs_inpaint.hip) ----
+// The coverage index on the device (vs_internal.hpp); the entries travel in the denoise's groups.  Entry 0 carries the frame's own matrix.
+int vsi::fill_coverage_ptrs(int n_out, int w, int h, int n_cand, const void* const* cand_src, const vs_transform* cand_t, int roi_x, int roi_y, int roi_w,
+                            int roi_h, uint8_t* cov, size_t cov_fs, int cov_stride, uint32_t* open_count, hipStream_t s, const char* fn) {
+    VS_ARG_AS(w > 0 && h > 0 && n_cand >= 1 && n_cand <= 16, fn);
+    VS_TRY(lookahead_args_ok("fill coverage", kAsTheFill, w, h, n_cand));
+    VS_ARG_AS(cand_src && cand_t && cov && n_out >= 1, fn);
+    VS_ARG_AS(roi_x >= 0 && roi_y >= 0 && roi_w >= 1 && roi_h >= 1 && roi_w <= w && roi_h <= h && roi_x <= w - roi_w && roi_y <= h - roi_h, fn);
+    VS_ARG_AS(cov_stride >= roi_w && (n_out == 1 || cov_fs >= (size_t)(roi_h - 1) * cov_stride + (size_t)roi_w), fn);
+    ParamRing* ring = param_ring();
+    if (!ring) return set_error(VS_ERR_HIP, "no parameter ring for this device");
+    const vsk::Roi roi{roi_x, roi_y, roi_w, roi_h};
+    std::vector<vsk::FillCand> fc;
+    return cand_groups(ring, 0, n_out, std::max(1, (int)(ParamRing::kSlots / 2 / 4) / n_cand), n_cand, cand_src, cand_t, w, h, false, true, s, fc,
+        [&](vsk::FillCand& e, int o) -> int {
+            vs_cv_inverse_matrix(&cand_t[(size_t)o * n_cand], w, h, e.m);
+            return VS_OK;
+        },
+        [](vsk::FillCand&, size_t) { return true; },
+        [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
+            VS_HIP(vsk::fill_coverage(cdev, n_cand, w, h, cov + (size_t)f0 * cov_fs, cov_stride, nf, cov_fs, roi, open_count ? open_count + f0 : nullptr, s));
+            return VS_OK;
+        });
+}
+
+int vs_bgr_fill_coverage_batch(int w, int h, int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t, int roi_x, int roi_y, int roi_w,
+                               int roi_h, uint8_t* cov, size_t cov_frame_stride, int cov_stride, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    VS_ARG(n_cand >= 1 && n_cand <= 16);
+    VS_TRY(lookahead_args_ok("fill coverage", kAsTheFill, w, h, n_cand));
+    VS_ARG(cand_frame && cand_t && cov && n_out >= 1);
+    VS_ARG(roi_x >= 0 && roi_y >= 0 && roi_w >= 1 && roi_h >= 1 && roi_w <= w && roi_h <= h && roi_x <= w - roi_w && roi_y <= h - roi_h);
+    VS_ARG(cov_stride >= roi_w && (n_out == 1 || cov_frame_stride >= (size_t)(roi_h - 1) * cov_stride + (size_t)roi_w));
+    for (int o = 0; o < n_out; o++) VS_ARG(cand_frame[(size_t)o * n_cand] >= 0);       // candidate 0 is the frame itself
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    Staged o;
+    VS_TRY(o.out_image(cov, (size_t)roi_w, (size_t)roi_h, (size_t)cov_stride, (size_t)n_out, cov_frame_stride, mem));
+    // only the sign of an index is looked at: a live entry gets a frame pointer that is never followed
+    static const char live = 0;
+    std::vector<const void*> ptrs((size_t)n_out * n_cand, nullptr);
+    for (int i = 0; i < n_out; i++)
+        for (int c = 0; c < n_cand && cand_frame[(size_t)i * n_cand + c] >= 0; c++) ptrs[(size_t)i * n_cand + c] = &live;
+    VS_TRY(vsi::fill_coverage_ptrs(n_out, w, h, n_cand, ptrs.data(), cand_t, roi_x, roi_y, roi_w, roi_h, o.as<uint8_t>(), cov_frame_stride, cov_stride, nullptr, s,
+                                   __func__));
+    return vsi::finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+int vs_bgr_inpaint_batch(void* img, size_t frame_stride, int n, int w, int h, int stride, int format, const uint8_t* mask, size_t mask_frame_stride,
+                         int mask_stride, int mem, void* stream) try {
+    VS_DIMS(w, h);
+    int bits = 0;
+    VS_TRY(bgr_format_ok(format, &bits));
+    if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "inpaint: windows up to 32767 x 32767%s", kAsTheFill);
+    VS_ARG(img && mask && n >= 1 && stride >= w * 3 && mask_stride >= w);
+    VS_ARG(n == 1 || (frame_stride >= img_span(w, h, stride, 3) && mask_frame_stride >= img_span(w, h, mask_stride, 1)));
+    if (!vsi::device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bits > 8 ? 2 : 1;
+    const size_t span = ((size_t)(n - 1) * frame_stride + img_span(w, h, stride, 3)) * esz;
+    Staged a, m, o;
+    VS_TRY(a.in(img, span, mem, s));
+    VS_TRY(m.in(mask, (size_t)(n - 1) * mask_frame_stride + img_span(w, h, mask_stride, 1), mem, s));
+    VS_TRY(o.out_image(img, (size_t)w * 3 * esz, (size_t)h, (size_t)stride * esz, (size_t)n, frame_stride * esz, mem));
+    if (o.dev != a.dev) VS_HIP(hipMemcpyAsync(o.dev, a.dev, span, hipMemcpyDeviceToDevice, s));      // host memory: the windows are worked on in the output's block
+    // the open counts, then the pyramid (8-byte aligned behind them), in one block that lives until the work on `s` is done
+    const size_t cbytes = ((size_t)n * sizeof(unsigned int) + 255) & ~(size_t)255;
+    vsi::DevBuf scratch;
+    VS_HIP(scratch.alloc(cbytes + (size_t)n * vsk::inpaint_pyramid_bytes(w, h, (int)esz * 8)));
+    VS_HIP(vsk::mask_open_count(m.as<uint8_t>(), w, h, mask_stride, mask_frame_stride, n, scratch.as<unsigned int>(), s));
+    VS_HIP(vsk::bgr_inpaint(o.dev, frame_stride, n, w, h, stride, (int)esz * 8, m.as<uint8_t>(), mask_frame_stride, mask_stride, scratch.as<unsigned int>(),
+                            scratch.as<char>() + cbytes, s));
+    const int r = vsi::finish_outputs(mem, s, {&o});
+    if (mem != VS_MEM_HOST) VS_HIP(hipStreamSynchronize(s));             // (the scratch is released on return)
+    return r;
+} VS_CATCH_ALL

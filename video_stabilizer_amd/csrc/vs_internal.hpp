@@ -138,6 +138,14 @@ int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_
 int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
                         const vs_deflicker_params* params, uint64_t* stats, hipStream_t s);
 
+// The inpaint's coverage index (the rule: vs_inpaint.hip) on the device; vs_bgr_fill_coverage_batch is the index-based wrapper over it.  The
+// candidates of output frame o as bgr_warp_fill_ptrs takes them -- cand_t[o * n_cand + c], a null cand_src entry ends the list, entry 0 is the
+// frame itself; no frame is read.  cov: n_out indices of roi_h rows of cov_stride bytes, cov_fs bytes apart, in device memory; open_count (may
+// be null): n_out words of device memory, zeroed on `s` first, then every frame's number of zeros.  fn: the function that argument errors name.
+// Host arrays; enqueue only.
+int fill_coverage_ptrs(int n_out, int w, int h, int n_cand, const void* const* cand_src, const vs_transform* cand_t, int roi_x, int roi_y, int roi_w,
+                       int roi_h, uint8_t* cov, size_t cov_fs, int cov_stride, uint32_t* open_count, hipStream_t s, const char* fn);
+
 bool device_ready();   // true when a HIP device is usable (sets last error otherwise)
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the

@@ -104,6 +104,18 @@ hipError_t exposure_stats(const FillCand* cands_dev, int n_cand, int w, int h, i
 hipError_t exposure_gains(const unsigned long long* stats, int n_out, int n_cand, int w, int h, int step, uint32_t* gains, hipStream_t s);
 hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int max_value, const uint32_t* gains, void* dst, int dst_stride, int n_frames,
                     size_t src_fs, size_t dst_fs, hipStream_t s);
+// Inpaint of what the fill leaves open (vs_inpaint.hip: the rule and the kernels).  fill_coverage: cands_dev as the fill takes them (entry 0's
+// matrix; a null frame ends a list; no frame is read); cov[frame][y * cov_stride + x] = 1 + the first covering candidate, 0 for none;
+// open_count (device, may be null): zeroed on `s`, then the frame's number of zeros.  mask_open_count: the same count from a mask.
+// bgr_inpaint: n_frames w x h windows in place under their byte masks (non-zero = keep); counts: the frames' open counts in device memory (a
+// frame with 0 or w * h is left alone); pyramid: n_frames * inpaint_pyramid_bytes(w, h, bits) bytes of device scratch, 8-byte aligned,
+// written before it is read.
+hipError_t fill_coverage(const FillCand* cands_dev, int n_cand, int w, int h, uint8_t* cov, int cov_stride, int n_frames, size_t cov_fs, Roi roi,
+                         unsigned int* open_count, hipStream_t s);
+size_t inpaint_pyramid_bytes(int w, int h, int bits);
+hipError_t mask_open_count(const uint8_t* mask, int w, int h, int mask_stride, size_t mask_fs, int n_frames, unsigned int* counts, hipStream_t s);
+hipError_t bgr_inpaint(void* img, size_t img_fs, int n_frames, int w, int h, int stride, int bits, const uint8_t* mask, size_t mask_fs, int mask_stride,
+                       const unsigned int* counts, void* pyramid, hipStream_t s);
 // host side of the tuned kernel's tile prologue: per frame {lo_x, hi_x, lo_y, hi_y} from the kernel parameters {A, B, TX, TY}, for the
 // tile of the kernel that bgr_warp_c3 launches for (bits, mode)
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4);

@@ -1,5 +1,5 @@
 // vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
-// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_deblur, vs_denoise, vs_deflicker).
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_deflicker).
 //
 // Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
 // then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
@@ -45,6 +45,9 @@ struct vs_stabilizer {
     int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
     vs_deflicker_params deflicker_params{4};
     void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
+    // inpaint (vs_inpaint.hip)
+    int inpaint = 0;               // vs_stabilizer_set_inpaint: what no candidate covers in the output window is inpainted (0: off)
+    void* inpaint_buf = nullptr; size_t inpaint_bytes = 0;   // one group of frames: their open counts, their coverage indices, their pyramids
     struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
                   SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
@@ -123,6 +126,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     if (s->deblur_buf) (void)hipFree(s->deblur_buf);
     if (s->denoise_buf) (void)hipFree(s->denoise_buf);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
+    if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
@@ -416,6 +420,50 @@ struct Chunk {
         return VS_OK;
     }
 
+    // Inpaint of frames [j, e) of the jobs, whose output windows lie at `dst`: the coverage index from the run's fill list (fill off: candidate 0
+    // alone), then the push-pull in place.  A run whose frames all cover their window themselves launches nothing: the same int32 rectangle
+    // test as the kernels', on the host (vs_lookahead.hpp), so the default crop pays a handful of host operations per frame.  The frames go
+    // in groups whose scratch -- open counts, coverage indices (rows padded to dwords), pyramids -- stays within kInpaintScratch.  256 MB:
+    // thirteen 4K 8-bit frames (8.3 MB of index + 11 MB of pyramid each) or eight 4K 16-bit ones.  The pass is a chain of some fifteen
+    // launches per group whose length is set by latency, not by bytes (the rim blocks' strip walk, the small upper levels, the tail), so a
+    // group has to be large to amortise it: with 64 MB -- three frames -- a 4K frame paid 65-116 us instead of 45-56.  The deblur's and the denoise's scratch hold a
+    // full frame per due frame of the call; this stays below them.  A single frame that needs more gets what it needs.  Every byte of the
+    // scratch that is read has been written in the same group: the count by a memset, the index by the coverage kernel (every window
+    // pixel), a pyramid level by the push in front of its readers; idle frames' pyramids are never read.
+    static constexpr size_t kInpaintScratch = (size_t)256 << 20;
+    int inpaint_run(size_t j, size_t e, void* dst, size_t dst_fs) {
+        const int nfill = fill.n, nc = 1 + nfill;
+        std::vector<const void*> src1;
+        std::vector<vs_transform> t1;
+        const void* const* srcs; const vs_transform* tr;
+        if (nfill > 0) { srcs = &fill.src[j * nc]; tr = &fill.t[j * nc]; }
+        else {
+            for (size_t q = j; q < e; q++) { src1.push_back(jobs[q].src); t1.push_back(jobs[q].sampling); }
+            srcs = src1.data(); tr = t1.data();
+        }
+        bool all_covered = true;
+        for (size_t q = j; all_covered && q < e; q++) {
+            double M[6];
+            vs_cv_inverse_matrix(&tr[(q - j) * nc], w, h, M);
+            all_covered = vsi::cv_window_covered(M, crop, crop, ow, oh, w, h);
+        }
+        if (all_covered) return VS_OK;
+        const int ms = (ow + 3) & ~3;
+        const size_t mfs = (size_t)ms * oh, pbytes = (vsk::inpaint_pyramid_bytes(ow, oh, bits) + 15) & ~(size_t)15;
+        const size_t group = std::min(e - j, std::max<size_t>(1, kInpaintScratch / (mfs + pbytes + sizeof(uint32_t))));
+        const size_t cbytes = (group * sizeof(uint32_t) + 255) & ~(size_t)255;
+        VS_HIP(grow(&s->inpaint_buf, &s->inpaint_bytes, cbytes + group * (mfs + pbytes), ws, true));   // (an earlier run's kernels may still read the block)
+        uint32_t* const counts = (uint32_t*)s->inpaint_buf;
+        uint8_t* const cov = (uint8_t*)s->inpaint_buf + cbytes;
+        void* const pyr = cov + group * mfs;
+        for (size_t g = j; g < e; g += group) {
+            const int m = (int)std::min(group, e - g);
+            VS_TRY(vsi::fill_coverage_ptrs(m, w, h, nc, srcs + (g - j) * nc, tr + (g - j) * nc, crop, crop, ow, oh, cov, mfs, ms, counts, ws, "vs_stabilizer_set_inpaint"));
+            VS_HIP(vsk::bgr_inpaint((uint8_t*)dst + (g - j) * dst_fs * c.esz(), dst_fs, m, ow, oh, ow * 3, bits, cov, mfs, ms, counts, pyr, ws));
+        }
+        return VS_OK;
+    }
+
     // warp every due frame, runs of consecutive batch frames as one launch.  The crop of stabilizer.cpp:102-109 is the
     // output window of the warp: the margin is never computed and no full-size intermediate frame exists.  Device callers
     // get the window written straight into `out`; host callers into the staging area.
@@ -439,6 +487,7 @@ struct Chunk {
             else
                 VS_TRY(vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, bits, ts.data(), s->params.warp_mode,
                                                    s->params.warp_border, max_value, crop, crop, ow, oh, dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws));
+            if (s->inpaint) VS_TRY(inpaint_run(j, e, dst, dst_fs));
             // deflicker: the run's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
             if (fk.n > 0)
                 VS_HIP(vsk::bgr_gain(dst, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * j, dst, ow * 3, (int)(e - j), dst_fs, dst_fs, ws));
@@ -736,6 +785,16 @@ int vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* p
     VS_ARG(s && params);
     *params = s->fill_blend;
     return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_set_inpaint(vs_stabilizer* s, int on) try {
+    VS_ARG(s && (on == 0 || on == 1));
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "inpaint: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    s->inpaint = on;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_inpaint(const vs_stabilizer* s) try {
+    VS_ARG(s);
+    return s->inpaint;
 } VS_CATCH_ALL
 int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
