@@ -14,6 +14,8 @@
 //     iteration (the reference makes one Halide call per iteration, alignment.cpp:600-668).
 //   * The transform algebra inside the loop is fp64 on the device, written exactly as imgproc.cpp.
 #include "vs_engine.hpp"
+#define VS_ALIGN_PLAN_UNIT
+#include "vs_align_plan.hpp"
 #include "vs_kernels.hpp"
 #include "vs_phase.hpp"
 #include "vs_device.hpp"
@@ -28,7 +30,6 @@
 #include <vector>
 
 using vsi::set_error;
-using vsi::kSharedMinPairs;
 using vsi::run_async;
 using vsi::align_start;
 using vsi::align_finish;
@@ -37,48 +38,7 @@ using namespace vsd;
 
 namespace {
 
-constexpr int kMaxLevels = 16;
-// on-device selection keeps (abs_delta,index) u32 + a u16 rank table per tile in LDS: 6 B x tiles <= 160 KB less
-// the static part; index fits 16 bits; a thread's chunk fits a 32-bit mask
-constexpr int kSelectCap = 26000;
-
-struct LevelDims {
-    int w, h, ts, tx, ty, nt, nsel;
-    size_t img_off;   // bytes from the start of a frame's pyramid
-    size_t lm_off;    // u16 elements from the start of a frame's arg-max table (x-set); y-set follows at +2*nt
-    size_t jac_off;   // f32 elements from the start of a frame's Jacobian table (x-set); y-set at +4*nt
-};
-
-// per-pair solver state, device resident; copied back once per batch
-struct PairState {
-    double T[4];
-    int32_t status;        // 1 running/aligned, 0 failed
-    int32_t fail_reason;   // 2 max iters, 3 over displacement
-    int32_t fail_level;
-    int32_t pad;
-    int32_t iterations[kMaxLevels];
-    double condition[kMaxLevels];
-    double level_T[kMaxLevels][4];   // the estimate each level ended on (vs_align_info::level_transform)
-};
-
-struct PairDesc {
-    int32_t tmpl_slot;   // slot of the even (non-keyframe) frame: ScalePyramid[NonKeyframeIndex]
-    int32_t key_slot;    // slot of the odd (keyframe) frame:      ScalePyramid[KeyframeIndex]
-};
-
-// latency mode: the descriptors of a small launch travel in the kernel arguments (no upload in front of the launch)
-constexpr int kDirectMaxPairs = 16;
-struct PairDescPack { PairDesc d[kDirectMaxPairs]; };
-
-struct GnParams {
-    double threshold, max_displacement;
-    int max_iters;
-    int pipeline;   // 1: the one-barrier iteration loop on the LDS-resident level (latency mode, few pairs in flight)
-    int stall_helpers;   // test hook (VS_GN_STALL_HELPERS=1): helpers never report back, the leader's bounded wait must expire
-    int sel_depth_cap;   // test hook (VS_GN_SELECT_DEPTH=k > 0): the on-device introselect gets k partition rounds instead of 2 lg n, so
-                         // ordinary frames take the "libstdc++ would have heap-selected" exit (fail_reason 100 -> host redo)
-    int sel_stable;      // VS_SELECT_STABLE: smallest by (abs_delta, tile index), survivors in tile order (stable_select)
-};
+struct PairDescPack { PairDesc d[kDirectMaxPairs]; };   // latency mode: the descriptors travel in the kernel arguments
 
 // ---- phase-correlation start value (alignment.cpp:376-387) -----------------------------------------
 // detected_shift of the level-2 images scaled by (1 << PhaseLevel) / float(1 << PyramidLevels) becomes the initial TX,TY
@@ -161,6 +121,7 @@ __device__ __forceinline__ PointRecs pair_recs(uint8_t* recs, size_t recs_pair, 
     r.r0 = (float*)(base + (size_t)2 * nt_cap * 24);          // 2*nt_cap f32
     return r;
 }
+static_assert(kPointRecBytes == 28, "recs_pair_bytes (vs_align_plan.hpp) sizes the block pair_recs lays out");
 __device__ __forceinline__ void write_rec(const PointRecs& rc, int slot, const uint16_t* __restrict__ lm,
                                           const float* __restrict__ jac, int nt, int t, const uint8_t* __restrict__ tmpl,
                                           int w, int h, const float* __restrict__ wv_set) {
@@ -207,11 +168,6 @@ __global__ __launch_bounds__(256) void vs_k_gather_selected(const PairState* __r
 // not; a helper writes the packed keys of its slice and raises wd_done[g]; the leader reads all keys into LDS and goes on
 // alone.  `abort` releases helpers when the pair ends early.  All waits are bounded.
 constexpr int kMaxDevices = 64;              // devices the per-device launch caches index; beyond that they are bypassed
-constexpr int kCoopGroup = 16;         // workgroups per pair in latency mode (1080p: 8 and 16 alike; 4K: 16 is 3 % faster)
-constexpr int kCoopMaxGroup = 16;
-constexpr int kCoopMaxPairs = 128;     // helpers for launches of at most this many pairs (16 per pair up to 16 pairs, then as many as keep the launch within one workgroup per CU)
-constexpr int kChipCUs = 256;
-constexpr int kCoopMinTiles = 4096;    // levels with at least this many tiles are shared
 struct CoopLevel {
     int t_ready, nslices, pad[2];
     int assign[kCoopMaxGroup];         // slice number of helper g at this level, -1: not taking part
@@ -265,10 +221,8 @@ constexpr int kGnThreads = 256, kGnVirt = 512;
 #include "vs_align_kernels.inc"
 #undef VS_GN_FUSED_BOUNDS
 }  // namespace nt256v
-constexpr int kCoResidentMaxTiles = 128 * 256;          // introselect_block_g: 128 elements per thread (and <= kSelectCap)
-constexpr size_t kCoResidentDynMax = 32 * 1024;        // dynamic LDS of the small-footprint build; larger levels select on global scratch
-constexpr int kSmallWgTiles = 26000;     // largest level handled by the 512-thread kernels (<= kSelectCap <= 64 * 512)
-constexpr int kPipelineMaxPairs = 128;   // half the CUs
+static_assert(nt512::kGnThreads == kBuildThreads[kBuild512] && nt1024::kGnThreads == kBuildThreads[kBuild1024] &&
+              nt256v::kGnThreads == kBuildThreads[kBuild256v], "vs_align_plan.hpp plans with the builds' workgroup sizes");
 
 }  // namespace
 
@@ -277,9 +231,35 @@ VS_BOUNDS_TU(vs_bounds_fetch_engine)
 // =================================================================================================
 // VideoAligner
 // =================================================================================================
-#define kIngestBytes vsi::ingest_chunk_bytes()
+namespace {
 
-struct vs_aligner {
+void free_device(std::initializer_list<void**> ptrs) {
+    for (void** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+}
+
+// the builds of the level-by-level kernels, indexed like kBuildThreads by wg_build(tiles) (vs_align_plan.hpp)
+const decltype(&nt512::vs_k_gn_level) kGnLevelBuilds[2] = {nt512::vs_k_gn_level, nt1024::vs_k_gn_level};
+const decltype(&nt512::vs_k_select) kSelectBuilds[2] = {nt512::vs_k_select, nt1024::vs_k_select};
+const decltype(&nt512::vs_k_align_pairs) kAlignPairsBuilds[kBuilds] = {nt512::vs_k_align_pairs, nt1024::vs_k_align_pairs, nt256v::vs_k_align_pairs};
+
+// The dynamic-LDS limit belongs to (kernel, device) and is shared by every handle of the process: it is only ever raised, and only when a
+// launch needs more than was granted before (the call costs microseconds of host time).  slot: the kernel's row in the cache.
+enum { kDynAlignPairs = 0, kDynSelect = kBuilds, kDynSlots = kBuilds + 2 };
+int raise_dyn_lds(const void* kernel, int slot, int device, size_t bytes) {
+    static std::mutex dyn_mu;
+    static size_t dyn_set[kDynSlots][kMaxDevices];
+    std::lock_guard<std::mutex> g(dyn_mu);
+    size_t& granted = dyn_set[slot][std::min(std::max(device, 0), kMaxDevices - 1)];
+    if (granted < bytes || device >= kMaxDevices) {
+        VS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(bytes, granted)));
+        granted = std::max(bytes, granted);
+    }
+    return VS_OK;
+}
+
+}  // namespace
+
+struct vs_aligner : LevelTable {          // the level table of the configured size: levels, L[], pyr_frame, lm_frame, jac_frame, nt_max
     int device = 0;
     hipStream_t stream = nullptr;
     vs_aligner_params params;
@@ -290,12 +270,8 @@ struct vs_aligner {
 
     // sequence state (alignment.hpp:61-70)
     int W = -1, H = -1, fmt = -1;
-    int levels = 0;
-    LevelDims L[kMaxLevels];
     long long seq = 0;          // frames consumed since (re)initialisation
     int clip_len = 0;           // > 0 during vs_aligner_align_clips: the batch is independent clips of this many frames
-    size_t pyr_frame = 0, lm_frame = 0, jac_frame = 0;   // bytes / u16 elements / f32 elements per slot
-    int nt_max = 0;
 
     // device storage
     int cap = 0;                // frames per internal chunk (slots = cap + 1)
@@ -309,7 +285,7 @@ struct vs_aligner {
     int32_t* idx = nullptr;
     uint8_t* recs = nullptr;      // per pair: float4 j[2*nt_max] | u32 xy[2*nt_max] | f32 tv[2*nt_max]
     uint8_t* coop = nullptr;      // helper-workgroup control blocks + exchange buffers (kCoopMaxPairs pairs), see CoopCtrl
-    uint8_t* selbuf = nullptr; size_t selbuf_bytes = 0;   // small-footprint solver: per pair u32 keys[nt_max] | u16 ranks[nt_max] (levels that do not fit its LDS)
+    void* selbuf = nullptr; size_t selbuf_bytes = 0;   // small-footprint solver: per pair u32 keys[nt_max] | u16 ranks[nt_max] (levels that do not fit its LDS)
     int coop_epoch = 0;
     void* stage = nullptr; size_t stage_bytes = 0;   // host-frame upload area (single chunk)
     // host-resident video: two upload areas filled alternately by an uploader thread on its own stream, so the
@@ -375,19 +351,18 @@ struct vs_aligner {
     int configure(int w, int h, int format, const vs_aligner_params& p);
     int ensure_capacity(int n);
     int ensure_phase();
-    void release_phase();
+    void release_phase_buffers();
+    void release_phase() { release_phase_buffers(); phase.destroy(); }
     // One chunk = chunk_begin (everything up to and including the solver launch and the copy of its results towards the host: no
     // host synchronisation unless phase correlation is on) + chunk_end (wait, the rare host redo, conversion of the results).
     // run_chunk is the two back to back; the stabilizer puts a chunk's host work between the next chunk's begin and end.
     struct Chunk {
         bool open = false;
-        int n = 0, n_pairs = 0, epoch = 0;
-        long long seq0 = 0;
+        int n = 0, epoch = 0;
         vs_aligner_params p;
         vs_transform* out = nullptr; int32_t* status = nullptr; vs_align_info* infos = nullptr;
-        std::vector<int> pair_frame;
-        bool direct = false, use_host = false;
-        GnParams gp{};
+        ChunkFrames fr;      // sequence indices, keyframes, pairs
+        SolverPlan plan;     // how the pairs are solved
     } ck;
     int chunk_begin(const void* frames, size_t frame_stride, int n, int stride, int mem, const vs_aligner_params& p,
                     vs_transform* out, int32_t* status, vs_align_info* infos);
@@ -397,6 +372,22 @@ struct vs_aligner {
         VS_TRY(chunk_begin(frames, frame_stride, n, stride, mem, p, out, status, infos));
         return chunk_end();
     }
+    // the steps of chunk_begin, in stream order ...
+    int carry_over(uint8_t* dst_pyr, uint16_t* dst_lm, float* dst_jac);
+    int ingest_frames(const void* frames, size_t frame_stride, int stride, int mem);
+    int phase_spectra();
+    int keyframes();
+    int start_pairs();
+    int phase_start_values();
+    int launch_solver();
+    // ... and of chunk_end
+    int wait_solver();
+    int host_redo();
+    void convert_results();
+    void reset_states(int n_pairs) {
+        for (int q = 0; q < n_pairs; q++) { memset(&h_states[q], 0, sizeof(PairState)); h_states[q].status = 1; }
+    }
+    int launch_phase_apply();
     int select_host(int n_pairs, const LevelDims& l);
     // vs_aligner_align_batch / _clips in two halves (single-chunk device-resident batches run asynchronously in between; anything
     // else completes inside align_start)
@@ -405,12 +396,9 @@ struct vs_aligner {
     int32_t* started_status = nullptr;
 };
 
-void vs_aligner::release_phase() {
-    void* d[] = {pspec, pG, psurf, ppairs, pneg, pres};
-    for (void* p : d) if (p) (void)hipFree(p);
-    pspec = nullptr; pG = nullptr; psurf = nullptr; ppairs = nullptr; pneg = nullptr; pres = nullptr;
+void vs_aligner::release_phase_buffers() {
+    free_device({(void**)&pspec, (void**)&pG, (void**)&psurf, (void**)&ppairs, (void**)&pneg, (void**)&pres});
     phase_cap = 0;
-    phase.destroy();
 }
 
 // buffers of the phase-correlation mode for the current chunk capacity (PhaseLevel = 2, alignment.hpp:69)
@@ -424,9 +412,7 @@ int vs_aligner::ensure_phase() {
         VS_HIP(pe);                                     // (a refused allocation or a failed upload is a HIP error, not a size problem)
     }
     if (phase_cap >= cap) return VS_OK;
-    void* d[] = {pspec, pG, psurf, ppairs, pneg, pres};
-    for (void* p : d) if (p) (void)hipFree(p);
-    pspec = nullptr; pG = nullptr; psurf = nullptr; ppairs = nullptr; pneg = nullptr; pres = nullptr; phase_cap = 0;
+    release_phase_buffers();
     VS_HIP(vsi::dev_alloc((void**)&pspec, ((size_t)cap + 1) * phase.spec_frame() * sizeof(float2)));
     VS_HIP(vsi::dev_alloc((void**)&pG, (size_t)cap * phase.spec_frame() * sizeof(float2)));
     VS_HIP(vsi::dev_alloc((void**)&psurf, (size_t)cap * phase.surface_elems() * sizeof(float)));
@@ -439,53 +425,30 @@ int vs_aligner::ensure_phase() {
 
 void vs_aligner::release() {
     release_phase();
-    void* d[] = {pyr, lm, jac, states, descs, wd, wv, idx, recs, coop, stage, ingest[0], ingest[1], selbuf};
-    for (void* p : d) if (p) (void)hipFree(p);
-    selbuf = nullptr; selbuf_bytes = 0;
-    ingest[0] = ingest[1] = nullptr; ingest_bytes = 0;
-    void* hp[] = {h_wd, h_idx, h_states, h_descs};
-    for (void* p : hp) if (p) (void)hipHostFree(p);
-    pyr = nullptr; lm = nullptr; jac = nullptr; states = nullptr; descs = nullptr; wd = nullptr; wv = nullptr; idx = nullptr;
-    recs = nullptr; coop = nullptr; stage = nullptr; stage_bytes = 0; h_wd = nullptr; h_idx = nullptr; h_states = nullptr; h_descs = nullptr;
+    free_device({(void**)&pyr, (void**)&lm, (void**)&jac, (void**)&states, (void**)&descs, (void**)&wd, (void**)&wv, (void**)&idx,
+                 (void**)&recs, (void**)&coop, &stage, &ingest[0], &ingest[1], &selbuf});
+    stage_bytes = 0; ingest_bytes = 0; selbuf_bytes = 0;
+    for (void** p : {(void**)&h_wd, (void**)&h_idx, (void**)&h_states, (void**)&h_descs}) { if (*p) (void)hipHostFree(*p); *p = nullptr; }
     cap = 0;
 }
 
-// alignment.cpp:155-204: (re)initialisation on first use or size change
+// alignment.cpp:155-204: (re)initialisation on first use or size change.  The size is validated BEFORE anything of the old configuration is
+// released or overwritten: a refused size leaves the handle exactly as it was (the reference marks a failed setup with LastWidth = -1,
+// alignment.cpp:360)
 int vs_aligner::configure(int w, int h, int format, const vs_aligner_params& p) {
-    int lv = 0, ww = w, hh = h;
-    do { lv++; ww /= 2; hh /= 2; } while (ww >= p.pyramid_min_width && hh >= p.pyramid_min_height);
-    // PhaseLevel = 2 is indexed unconditionally in the reference (alignment.cpp:227): < 3 levels is UB there
-    if (lv < 3 || lv > kMaxLevels)
-        return set_error(VS_ERR_UNSUPPORTED, "%dx%d with pyramid_min %dx%d gives %d pyramid levels; 3..%d supported", w, h,
-                         p.pyramid_min_width, p.pyramid_min_height, lv, kMaxLevels);
-    if (w > 65535 || h > 65535) return set_error(VS_ERR_UNSUPPORTED, "frame larger than 65535 (u16 keypoints)");
-    // every level is validated BEFORE anything of the old configuration is released or overwritten: a refused size
-    // leaves the handle exactly as it was (the reference marks a failed setup with LastWidth = -1, alignment.cpp:360)
-    ww = w; hh = h;
-    for (int i = 0; i < lv; i++) {
-        if (i > 0) { ww /= 2; hh /= 2; }
-        const int ts = vs_tile_size(ww, hh);
-        if (ww < 4 || hh < 4 || (ww / ts) * (hh / ts) < 1)
-            return set_error(VS_ERR_UNSUPPORTED, "pyramid level %d is %dx%d: levels below 4x4 are not supported", i, ww, hh);
-    }
+    LevelTable t;
+    VS_TRY(build_levels(w, h, p, &t));
     release();
-    W = w; H = h; fmt = format; levels = lv; seq = 0;
-    size_t img = 0, lmo = 0, jo = 0;
-    nt_max = 0;
-    ww = w; hh = h;
-    for (int i = 0; i < lv; i++) {
-        if (i > 0) { ww /= 2; hh /= 2; }
-        LevelDims& l = L[i];
-        l.w = ww; l.h = hh;
-        l.ts = vs_tile_size(ww, hh);
-        l.tx = ww / l.ts; l.ty = hh / l.ts; l.nt = l.tx * l.ty;
-        l.nsel = (int)static_cast<size_t>((size_t)l.nt * p.smallest_fraction);   // alignment.cpp:464-465
-        l.img_off = img; img += ((size_t)ww * hh + 255) & ~(size_t)255;
-        l.lm_off = lmo; lmo += (size_t)l.nt * 4;     // x-set (2*nt) + y-set (2*nt)
-        l.jac_off = jo; jo += (size_t)l.nt * 8;      // x-set (4*nt) + y-set (4*nt)
-        nt_max = std::max(nt_max, l.nt);
-    }
-    pyr_frame = img; lm_frame = (lmo + 63) & ~(size_t)63; jac_frame = (jo + 63) & ~(size_t)63;
+    static_cast<LevelTable&>(*this) = t;
+    W = w; H = h; fmt = format; seq = 0;
+    return VS_OK;
+}
+
+// the previous chunk's last frame (slot last_n: pyramid + keyframe tables) becomes slot 0 of the slabs at dst_*
+int vs_aligner::carry_over(uint8_t* dst_pyr, uint16_t* dst_lm, float* dst_jac) {
+    VS_HIP(hipMemcpyAsync(dst_pyr, pyr + (size_t)last_n * pyr_frame, pyr_frame, hipMemcpyDeviceToDevice, stream));
+    VS_HIP(hipMemcpyAsync(dst_lm, lm + (size_t)last_n * lm_frame, lm_frame * 2, hipMemcpyDeviceToDevice, stream));
+    VS_HIP(hipMemcpyAsync(dst_jac, jac + (size_t)last_n * jac_frame, jac_frame * 4, hipMemcpyDeviceToDevice, stream));
     return VS_OK;
 }
 
@@ -512,19 +475,13 @@ int vs_aligner::ensure_capacity(int n) {
         slots * pyr_frame, slots * lm_frame * 2, slots * jac_frame * 4, sizeof(PairState) * newcap, sizeof(PairDesc) * newcap,
         (size_t)newcap * 2 * nt_max * sizeof(uint16_t), (size_t)newcap * 2 * nt_max * sizeof(int32_t),
         (size_t)newcap * 2 * nt_max * sizeof(float) * 2,      // samples of all pairs, then template pixels
-        (size_t)newcap * 2 * nt_max * 28, coop_bytes};
-    const size_t pinned_bytes[4] = {(size_t)newcap * 2 * nt_max * sizeof(uint16_t), (size_t)newcap * 2 * nt_max * sizeof(int32_t),
-                                    sizeof(PairState) * newcap, sizeof(PairDesc) * newcap};
+        (size_t)newcap * recs_pair_bytes(nt_max), coop_bytes};
+    const size_t pinned_bytes[4] = {dev_bytes[D_WD], dev_bytes[D_IDX], dev_bytes[D_STATES], dev_bytes[D_DESCS]};   // the host mirrors
     for (int i = 0; i < 10; i++) VS_HIP(vsi::dev_alloc(&ns.dev[i], dev_bytes[i]));
     for (int i = 0; i < 4; i++) VS_HIP(vsi::pinned_alloc(&ns.pinned[i], pinned_bytes[i]));
     VS_HIP(hipMemsetAsync(ns.dev[D_COOP], 0, coop_bytes, stream));
     const bool carry = pyr && seq > 0;
-    if (carry) {
-        // the previous chunk's last frame (slot last_n of the old slabs) becomes slot 0 of the new ones
-        VS_HIP(hipMemcpyAsync(ns.dev[D_PYR], pyr + (size_t)last_n * pyr_frame, pyr_frame, hipMemcpyDeviceToDevice, stream));
-        VS_HIP(hipMemcpyAsync(ns.dev[D_LM], lm + (size_t)last_n * lm_frame, lm_frame * 2, hipMemcpyDeviceToDevice, stream));
-        VS_HIP(hipMemcpyAsync(ns.dev[D_JAC], jac + (size_t)last_n * jac_frame, jac_frame * 4, hipMemcpyDeviceToDevice, stream));
-    }
+    if (carry) VS_TRY(carry_over((uint8_t*)ns.dev[D_PYR], (uint16_t*)ns.dev[D_LM], (float*)ns.dev[D_JAC]));
     VS_HIP(hipStreamSynchronize(stream));        // nothing reads the old set any more; nothing below can fail
     // ---- swap: the handle takes the new set, `ns` takes the old one and frees it on the way out ----
     void** dev_members[10] = {(void**)&pyr, (void**)&lm, (void**)&jac, (void**)&states, (void**)&descs, (void**)&wd, (void**)&idx,
@@ -594,35 +551,16 @@ int vs_aligner::select_host(int n_pairs, const LevelDims& l) {
     return VS_OK;
 }
 
-// One chunk (n <= cap frames): the result of n successive AlignNextFrame calls.
-int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int stride, int mem,
-                            const vs_aligner_params& p, vs_transform* out, int32_t* status, vs_align_info* infos) {
+// ---- ComputePyramid (alignment.cpp:149-235) for all n frames: upload, gray levels 0 and 1, the coarser levels ----
+int vs_aligner::ingest_frames(const void* frames, size_t frame_stride, int stride, int mem) {
     hipStream_t s = stream;
-    if (ck.open) return set_error(VS_ERR_ARG, "a chunk is already in flight on this handle");
-    ck.n = n; ck.p = p; ck.out = out; ck.status = status; ck.infos = infos; ck.seq0 = seq;
-    ck.n_pairs = 0; ck.direct = false; ck.use_host = false; ck.pair_frame.clear();
-    const int ch = fmt == VS_FMT_GRAY8 ? 1 : 3;
-    const int fbits = vs_format_bits(fmt);
+    const int n = ck.n, ch = fmt == VS_FMT_GRAY8 ? 1 : 3, fbits = vs_format_bits(fmt);
     const size_t esz = fbits > 8 ? 2 : 1;
-
-    // carry-over: the previous call's last frame (pyramid + keyframe tables) moves to slot 0
-    if (seq > 0 && last_n != 0) {
-        VS_HIP(hipMemcpyAsync(pyr, pyr + (size_t)last_n * pyr_frame, pyr_frame, hipMemcpyDeviceToDevice, s));
-        VS_HIP(hipMemcpyAsync(lm, lm + (size_t)last_n * lm_frame, lm_frame * 2, hipMemcpyDeviceToDevice, s));
-        VS_HIP(hipMemcpyAsync(jac, jac + (size_t)last_n * jac_frame, jac_frame * 4, hipMemcpyDeviceToDevice, s));
-    }
-
-    // ---- ComputePyramid (alignment.cpp:149-235) for all n frames ------------------------------
     const void* dframes = frames;
     t_begin(VS_STAGE_INGEST);
     if (mem == VS_MEM_HOST) {
         const size_t bytes = ((size_t)(n - 1) * frame_stride + (size_t)(H - 1) * stride + (size_t)W * ch) * esz;
-        if (bytes > stage_bytes) {
-            if (stage) (void)hipFree(stage);
-            stage = nullptr; stage_bytes = 0;
-            VS_HIP(vsi::dev_alloc(&stage, bytes));
-            stage_bytes = bytes;
-        }
+        VS_HIP(vsi::grow(&stage, &stage_bytes, bytes));
         VS_HIP(hipMemcpyAsync(stage, frames, bytes, hipMemcpyHostToDevice, s));
         dframes = stage;
     }
@@ -642,359 +580,264 @@ int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int 
         VS_HIP(vsk::pyr_down(slot1 + L[l - 1].img_off, L[l - 1].w, L[l - 1].h, L[l - 1].w, slot1 + L[l].img_off, L[l].w,
                              L[l].h, L[l].w, n, pyr_frame, pyr_frame, s));
     t_end(levels - (fmt == VS_FMT_GRAY8 ? 1 : 2));
+    return VS_OK;
+}
 
-    // ---- PhaseImage (alignment.cpp:225-229): half spectra of level 2, for the carry-over slot too ------------
-    if (p.phase_correlate) {
-        VS_TRY(ensure_phase());
-        t_begin(VS_STAGE_PHASE);
-        const int first = (seq > 0 && clip_len == 0) ? 0 : 1;
-        VS_HIP(phase.spectra(pyr + (size_t)first * pyr_frame + L[2].img_off, pyr_frame, L[2].w, n + 1 - first,
-                             pspec + (size_t)first * phase.spec_frame(), s));
-        t_end(2);
-    }
+// ---- PhaseImage (alignment.cpp:225-229): half spectra of level 2, for the carry-over slot too ------------
+int vs_aligner::phase_spectra() {
+    VS_TRY(ensure_phase());
+    t_begin(VS_STAGE_PHASE);
+    const int first = (seq > 0 && clip_len == 0) ? 0 : 1;
+    VS_HIP(phase.spectra(pyr + (size_t)first * pyr_frame + L[2].img_off, pyr_frame, L[2].w, ck.n + 1 - first,
+                         pspec + (size_t)first * phase.spec_frame(), stream));
+    t_end(2);
+    return VS_OK;
+}
 
-    // ---- ComputeKeyFrame (alignment.cpp:237-276) for the odd frames of the sequence -----------
-    // frame i of this chunk sits in slot i + 1; its index in its sequence is g(i) = seq + i, or i mod clip_len
-    // when the batch is a set of independent clips (every clip starts its own sequence at 0)
-    auto gidx = [&](int i) -> long long { return clip_len > 0 ? (long long)(i % clip_len) : seq + i; };
-    {
-        // runs of frames (first, count) whose odd members form a stride-2 progression
-        std::vector<std::pair<int, int>> runs;
-        if (clip_len > 0 && (clip_len & 1)) for (int c0 = 0; c0 < n; c0 += clip_len) runs.emplace_back(c0, std::min(clip_len, n - c0));
-        else runs.emplace_back(0, n);
-        bool any = false;
-        int kf_launches = 0;
-        for (auto& r : runs) {
-            const int first_odd = r.first + ((gidx(r.first) & 1) ? 0 : 1);
-            const int n_odd = first_odd < r.first + r.second ? (r.first + r.second - first_odd + 1) / 2 : 0;
-            if (n_odd <= 0) continue;
-            if (!any) { t_begin(VS_STAGE_KEYFRAME); any = true; }
-            const size_t so = (size_t)(first_odd + 1);
-            vsk::KeyframeLevels KL{};
-            KL.n = levels;
-            for (int l = 0; l < levels; l++)
-                KL.lv[l] = vsk::KeyframeLevel{L[l].w, L[l].h, L[l].ts, L[l].tx, L[l].ty, 0, 0, L[l].img_off, L[l].lm_off, L[l].jac_off};
-            if (vsk::keyframe_levels_supported(KL)) {
-                // one launch for every level of every keyframe of the run
-                VS_HIP(vsk::keyframe_levels(pyr + so * pyr_frame, lm + so * lm_frame, jac + so * jac_frame, KL, n_odd, 2 * pyr_frame,
-                                            2 * lm_frame, 2 * jac_frame, s));
-                kf_launches += 1;
-            } else {
-                for (int l = 0; l < levels; l++) {
-                    uint16_t* lmx = lm + so * lm_frame + L[l].lm_off;
-                    float* jx = jac + so * jac_frame + L[l].jac_off;
-                    VS_HIP(vsk::keyframe(pyr + so * pyr_frame + L[l].img_off, L[l].w, L[l].h, L[l].w, L[l].ts, lmx,
-                                         lmx + 2 * (size_t)L[l].nt, jx, jx + 4 * (size_t)L[l].nt, n_odd, 2 * pyr_frame,
-                                         2 * lm_frame, 2 * jac_frame, s, true));
-                }
-                kf_launches += levels;
-            }
-        }
-        if (any) t_end(kf_launches);
-    }
-
-    // ---- frame pairs --------------------------------------------------------------------------
-    // a pair exists for chunk frame i when g(i) >= 1: frames (g-1, g) = slots (i, i+1)
-    std::vector<int>& pair_frame = ck.pair_frame;
-    pair_frame.reserve(n);
-    for (int i = 0; i < n; i++) {
-        memset(&infos[i], 0, sizeof(vs_align_info));
-        infos[i].levels = levels;
-        out[i] = vs_transform{0, 0, 0, 0};
-        status[i] = 0;
-        if (gidx(i) >= 1) pair_frame.push_back(i);
-        else infos[i].fail_reason = 1;            // alignment.cpp:231-234: first frame of a sequence
-    }
-    const int n_pairs = (int)pair_frame.size();
-    ck.n_pairs = n_pairs;
-    if (n_pairs > 0) {
-        PairDesc* hd = h_descs;
-        for (int q = 0; q < n_pairs; q++) {
-            const int i = pair_frame[q];
-            const int cur = i + 1, prev = i;
-            if (gidx(i) & 1) { hd[q].key_slot = cur; hd[q].tmpl_slot = prev; }
-            else { hd[q].key_slot = prev; hd[q].tmpl_slot = cur; }
-        }
-        for (int q = 0; q < n_pairs; q++) {
-            memset(&h_states[q], 0, sizeof(PairState));
-            h_states[q].status = 1;
-        }
-        // Latency mode (a few pairs, device-side selection, identity start): no copies around the launch at all -- the
-        // descriptors travel in the kernel arguments, the kernel starts from the identity itself and writes its result straight
-        // into the pinned host block the host reads after the synchronisation.
-        const bool direct = n_pairs <= kDirectMaxPairs && !p.phase_correlate && select_mode != VS_SELECT_STL_HOST && nt_max <= kSelectCap;
-        ck.direct = direct;
-        if (!direct) {
-            VS_HIP(hipMemcpyAsync(descs, hd, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, s));
-            VS_HIP(hipMemcpyAsync(states, h_states, sizeof(PairState) * n_pairs, hipMemcpyHostToDevice, s));
-        }
-        // alignment.cpp:369-388: cv::phaseCorrelate(PhaseImage[Prev], PhaseImage[Curr]) starts TX,TY of every pair
-        std::vector<vsp::Pair> hp;
-        std::vector<uint8_t> hneg;
-        const float phase_scale = (1 << 2) / float(1 << levels);
-        auto apply_phase = [&]() -> int {
-            hipLaunchKernelGGL(vs_k_phase_apply, dim3((n_pairs + 255) / 256), dim3(256), 0, s, states, pres, pneg, n_pairs,
-                               p.phase_correlate_threshold, phase_scale);
-            VS_HIP(hipGetLastError());
-            return VS_OK;
-        };
-        if (p.phase_correlate) {
-            hp.resize(n_pairs); hneg.resize(n_pairs);
-            for (int q = 0; q < n_pairs; q++) {
-                const int i = pair_frame[q];
-                hp[q] = vsp::Pair{i, i + 1};
-                hneg[q] = (gidx(i) & 1) ? 1 : 0;          // CurrFrameIndex == KeyframeIndex
-            }
-            VS_HIP(hipMemcpyAsync(ppairs, hp.data(), sizeof(vsp::Pair) * n_pairs, hipMemcpyHostToDevice, s));
-            VS_HIP(hipMemcpyAsync(pneg, hneg.data(), (size_t)n_pairs, hipMemcpyHostToDevice, s));
-            t_begin(VS_STAGE_PHASE);
-            VS_HIP(phase.correlate(pspec, ppairs, n_pairs, pG, psurf, pres, s));
-            VS_TRY(apply_phase());
-            t_end(4);
-            h_pres.resize(n_pairs);
-            VS_HIP(hipMemcpyAsync(h_pres.data(), pres, sizeof(vsp::Result) * n_pairs, hipMemcpyDeviceToHost, s));
-        }
-        // (the descriptors and the start states come from pinned memory that is not touched again before the final
-        // synchronisation of this call: no host synchronisation in front of the launch -- it would expose the launch latency)
-        if (p.phase_correlate) VS_HIP(hipStreamSynchronize(s));   // hp, hneg go out of use
-
-        const size_t recs_pair = (size_t)2 * nt_max * 28;
-        // The pipelined iteration loop shortens one pair's critical path at the price of a speculative sampling pass per level:
-        // worth it while the launch does not fill the chip (the results are bit-identical either way).
-        static const int pipe_env = []() { const char* e = getenv("VS_GN_PIPELINE"); return e ? atoi(e) : -1; }();
-        const int pipeline = pipe_env >= 0 ? pipe_env : (n_pairs <= kPipelineMaxPairs ? 1 : 0);
-        static const int stall_env = []() { const char* e = getenv("VS_GN_STALL_HELPERS"); return e ? atoi(e) : 0; }();
-        static const int depth_env = []() { const char* e = getenv("VS_GN_SELECT_DEPTH"); return e ? atoi(e) : 0; }();
-        GnParams gp{p.threshold, p.max_displacement, p.max_iters, pipeline, stall_env, depth_env, select_mode == VS_SELECT_STABLE ? 1 : 0};
-        ck.gp = gp;
-        const bool use_host = select_mode == VS_SELECT_STL_HOST || nt_max > kSelectCap;
-        ck.use_host = use_host;
-        if (!use_host) {
-            // VS_SELECT_DEVICE: every level of every pair in one launch (selection = on-device introselect)
-            FusedLevels fl;
-            fl.levels = levels;
+// ---- ComputeKeyFrame (alignment.cpp:237-276) for the odd frames of the sequence -----------
+int vs_aligner::keyframes() {
+    hipStream_t s = stream;
+    if (ck.fr.key_runs.empty()) return VS_OK;
+    t_begin(VS_STAGE_KEYFRAME);
+    int kf_launches = 0;
+    for (const std::pair<int, int>& r : ck.fr.key_runs) {
+        const int n_odd = r.second;
+        const size_t so = (size_t)(r.first + 1);
+        vsk::KeyframeLevels KL{};
+        KL.n = levels;
+        for (int l = 0; l < levels; l++)
+            KL.lv[l] = vsk::KeyframeLevel{L[l].w, L[l].h, L[l].ts, L[l].tx, L[l].ty, 0, 0, L[l].img_off, L[l].lm_off, L[l].jac_off};
+        if (vsk::keyframe_levels_supported(KL)) {
+            // one launch for every level of every keyframe of the run
+            VS_HIP(vsk::keyframe_levels(pyr + so * pyr_frame, lm + so * lm_frame, jac + so * jac_frame, KL, n_odd, 2 * pyr_frame,
+                                        2 * lm_frame, 2 * jac_frame, s));
+            kf_launches += 1;
+        } else {
             for (int l = 0; l < levels; l++) {
-                fl.w[l] = L[l].w; fl.h[l] = L[l].h; fl.nt[l] = L[l].nt; fl.nsel[l] = L[l].nsel; fl.tx[l] = L[l].tx;
-                fl.img_off[l] = L[l].img_off; fl.lm_off[l] = L[l].lm_off; fl.jac_off[l] = L[l].jac_off;
+                uint16_t* lmx = lm + so * lm_frame + L[l].lm_off;
+                float* jx = jac + so * jac_frame + L[l].jac_off;
+                VS_HIP(vsk::keyframe(pyr + so * pyr_frame + L[l].img_off, L[l].w, L[l].h, L[l].w, L[l].ts, lmx,
+                                     lmx + 2 * (size_t)L[l].nt, jx, jx + 4 * (size_t)L[l].nt, n_odd, 2 * pyr_frame,
+                                     2 * lm_frame, 2 * jac_frame, s, true));
             }
-            // selection arrays in LDS: 6 B per tile for one point set; 12 B when both sets fit, so that they are selected
-            // side by side (introselect_dual) -- always for 1080p, for every level but the finest at 4K
-            size_t dyn = (((size_t)nt_max * ((size_t)nt_max * 12 <= 150 * 1024 ? 12 : 6) + 15) & ~(size_t)15);
-            // ... and room for the coarsest level's image if it fits next to the static LDS (the kernel stages it for the
-            // Gauss-Newton iterations): 480x270 at 1080p / 4K with pyramid_min_width 256
-            {
-                const size_t img_bytes = (size_t)L[levels - 1].w * L[levels - 1].h + 8;     // the coarsest level
-                if (img_bytes <= 150 * 1024) dyn = std::max(dyn, (img_bytes + 15) & ~(size_t)15);
-                // ... and its selection arrays behind the image, so that the level's sparse_warpdiff samples from LDS too
-                const size_t both = ((img_bytes + 15) & ~(size_t)15) + (size_t)L[levels - 1].nt * 12;
-                if (both <= 150 * 1024) dyn = std::max(dyn, (both + 15) & ~(size_t)15);
-            }
-            dyn = std::max<size_t>(dyn, 512);       // (tiny levels: the wave-level selection rounds use 128 bytes behind the keys as scratch)
-            const bool small_wg = nt_max <= kSmallWgTiles;
-            // latency mode: helper workgroups for the large levels of a pair (see CoopCtrl)
-            static const int coop_env = []() { const char* e = getenv("VS_GN_HELPERS"); return e ? atoi(e) : -1; }();
-            int group = 1;
-            if (coop_ok && n_pairs <= kCoopMaxPairs && L[0].nt >= kCoopMinTiles)
-                group = coop_env >= 0 ? std::max(1, std::min(coop_env, kCoopMaxGroup)) : std::max(1, std::min(kCoopGroup, cu_count / n_pairs));
-            // full batches of a handle in VS_BATCH_SHARED mode: the small-footprint build (shares CUs with whatever else is
-            // running, e.g. the previous clip's warp launch); VS_GN_CORESIDENT=0 / 1 overrides the rule (1: every launch, helpers off)
-            static const int cores_env = []() { const char* e = getenv("VS_GN_CORESIDENT"); return e ? atoi(e) : -1; }();
-            const bool cores = small_wg && nt_max <= kCoResidentMaxTiles &&
-                    (cores_env >= 0 ? cores_env != 0 : (batch_mode == VS_BATCH_SHARED && n_pairs >= kSharedMinPairs));
-            const size_t selbuf_pair = (((size_t)nt_max * 6 + 255) & ~(size_t)255);
-            if (cores) {
-                group = 1;
-                dyn = 16;
-                bool need_global = false;
-                for (int l = 0; l < levels; l++) {
-                    const size_t nt = (size_t)L[l].nt;
-                    const size_t need = ((nt <= 32 * (nt256v::kGnThreads / 2) && nt * 12 <= kCoResidentDynMax ? nt * 12 : nt * 6) + 15) & ~(size_t)15;
-                    if (need <= kCoResidentDynMax) dyn = std::max(dyn, need); else need_global = true;
-                }
-                dyn = std::max<size_t>(dyn, 512);
-                // (the kernel takes a non-null scratch pointer as "LDS block sized per level": always passed in this mode)
-                const size_t want = need_global ? selbuf_pair * (size_t)std::max(cap, n_pairs) : 256;
-                if (selbuf_bytes < want) {
-                    if (selbuf) (void)hipFree(selbuf);
-                    selbuf = nullptr; selbuf_bytes = 0;
-                    VS_HIP(vsi::dev_alloc((void**)&selbuf, want));
-                    selbuf_bytes = want;
-                }
-            }
-            const auto kernel = cores ? nt256v::vs_k_align_pairs : (small_wg ? nt512::vs_k_align_pairs : nt1024::vs_k_align_pairs);
-            const int kthreads = cores ? nt256v::kGnThreads : (small_wg ? nt512::kGnThreads : nt1024::kGnThreads);
-            {   // The limit belongs to (kernel, device) and is shared by every handle of the process: it is only ever raised,
-                // and only when a launch needs more than was granted before (the call costs microseconds of host time).
-                static std::mutex dyn_mu;
-                static size_t dyn_set[3][kMaxDevices];
-                std::lock_guard<std::mutex> g(dyn_mu);
-                size_t& granted = dyn_set[cores ? 2 : (small_wg ? 0 : 1)][std::min(std::max(device, 0), kMaxDevices - 1)];
-                if (granted < dyn || device >= kMaxDevices) {
-                    VS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(dyn, granted)));
-                    granted = std::max(dyn, granted);
-                }
-            }
-            t_begin(VS_STAGE_GN);
-            const int epoch = ++coop_epoch;
-            ck.epoch = epoch;
-            PairDescPack dpack{};
-            if (direct) for (int q = 0; q < n_pairs; q++) dpack.d[q] = hd[q];
-            hipLaunchKernelGGL(kernel, dim3(n_pairs * group), dim3(kthreads), dyn, s,
-                               direct ? h_states : states, descs, pyr, pyr_frame, lm, lm_frame, jac, jac_frame, recs, recs_pair, nt_max, (int)dyn,
-                               fl, gp, group, coop, epoch, wv, dpack, direct ? 1 : 0, cores ? selbuf : nullptr, selbuf_pair);
-            VS_HIP(hipGetLastError());
-            t_end(1);
-            if (!direct) VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
+            kf_launches += levels;
         }
+    }
+    t_end(kf_launches);
+    return VS_OK;
+}
+
+// ---- frame pairs: empty results for every frame, then the descriptors and start states of the pairs ----
+// (the descriptors and the start states come from pinned memory that is not touched again before the final synchronisation of this
+// call: no host synchronisation in front of the launch -- it would expose the launch latency)
+int vs_aligner::start_pairs() {
+    for (int i = 0; i < ck.n; i++) {
+        memset(&ck.infos[i], 0, sizeof(vs_align_info));
+        ck.infos[i].levels = levels;
+        ck.out[i] = vs_transform{0, 0, 0, 0};
+        ck.status[i] = 0;
+        if (ck.fr.first(i)) ck.infos[i].fail_reason = 1;
+    }
+    const int n_pairs = ck.fr.n_pairs();
+    ck.plan = SolverPlan{};
+    if (n_pairs == 0) return VS_OK;
+    ck.plan = plan_solver(*this, n_pairs, cap, ck.p, select_mode, batch_mode, cu_count, coop_ok, solver_knobs());
+    for (int q = 0; q < n_pairs; q++) h_descs[q] = ck.fr.desc(q);
+    reset_states(n_pairs);
+    if (!ck.plan.direct) {
+        VS_HIP(hipMemcpyAsync(descs, h_descs, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, stream));
+        VS_HIP(hipMemcpyAsync(states, h_states, sizeof(PairState) * n_pairs, hipMemcpyHostToDevice, stream));
+    }
+    return VS_OK;
+}
+
+// detected_shift of the level-2 images scaled by (1 << PhaseLevel) / float(1 << PyramidLevels) becomes the start TX,TY of every pair
+int vs_aligner::launch_phase_apply() {
+    const int n_pairs = ck.fr.n_pairs();
+    const float phase_scale = (1 << 2) / float(1 << levels);
+    hipLaunchKernelGGL(vs_k_phase_apply, dim3((n_pairs + 255) / 256), dim3(256), 0, stream, states, pres, pneg, n_pairs,
+                       ck.p.phase_correlate_threshold, phase_scale);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// alignment.cpp:369-388: cv::phaseCorrelate(PhaseImage[Prev], PhaseImage[Curr]) starts TX,TY of every pair
+int vs_aligner::phase_start_values() {
+    hipStream_t s = stream;
+    const int n_pairs = ck.fr.n_pairs();
+    std::vector<vsp::Pair> hp(n_pairs);
+    std::vector<uint8_t> hneg(n_pairs);
+    for (int q = 0; q < n_pairs; q++) {
+        const int i = ck.fr.pair_frame[q];
+        hp[q] = vsp::Pair{i, i + 1};
+        hneg[q] = ck.fr.negate(q) ? 1 : 0;
+    }
+    VS_HIP(hipMemcpyAsync(ppairs, hp.data(), sizeof(vsp::Pair) * n_pairs, hipMemcpyHostToDevice, s));
+    VS_HIP(hipMemcpyAsync(pneg, hneg.data(), (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    t_begin(VS_STAGE_PHASE);
+    VS_HIP(phase.correlate(pspec, ppairs, n_pairs, pG, psurf, pres, s));
+    VS_TRY(launch_phase_apply());
+    t_end(4);
+    h_pres.resize(n_pairs);
+    VS_HIP(hipMemcpyAsync(h_pres.data(), pres, sizeof(vsp::Result) * n_pairs, hipMemcpyDeviceToHost, s));
+    VS_HIP(hipStreamSynchronize(s));   // hp, hneg go out of use
+    return VS_OK;
+}
+
+// VS_SELECT_DEVICE / VS_SELECT_STABLE: every level of every pair in one launch (selection = on-device introselect), as ck.plan has it
+int vs_aligner::launch_solver() {
+    hipStream_t s = stream;
+    const SolverPlan& pl = ck.plan;
+    const int n_pairs = ck.fr.n_pairs();
+    FusedLevels fl;
+    fl.levels = levels;
+    for (int l = 0; l < levels; l++) {
+        fl.w[l] = L[l].w; fl.h[l] = L[l].h; fl.nt[l] = L[l].nt; fl.nsel[l] = L[l].nsel; fl.tx[l] = L[l].tx;
+        fl.img_off[l] = L[l].img_off; fl.lm_off[l] = L[l].lm_off; fl.jac_off[l] = L[l].jac_off;
+    }
+    if (pl.cores) VS_HIP(vsi::grow(&selbuf, &selbuf_bytes, pl.selbuf_bytes));
+    const auto kernel = kAlignPairsBuilds[pl.build];
+    VS_TRY(raise_dyn_lds((const void*)kernel, kDynAlignPairs + pl.build, device, pl.dyn));
+    t_begin(VS_STAGE_GN);
+    ck.epoch = ++coop_epoch;
+    PairDescPack dpack{};
+    if (pl.direct) for (int q = 0; q < n_pairs; q++) dpack.d[q] = h_descs[q];
+    hipLaunchKernelGGL(kernel, dim3(n_pairs * pl.group), dim3(pl.threads), pl.dyn, s,
+                       pl.direct ? h_states : states, descs, pyr, pyr_frame, lm, lm_frame, jac, jac_frame, recs, pl.recs_pair, nt_max, (int)pl.dyn,
+                       fl, pl.gp, pl.group, coop, ck.epoch, wv, dpack, pl.direct ? 1 : 0, pl.cores ? (uint8_t*)selbuf : nullptr, pl.selbuf_pair);
+    VS_HIP(hipGetLastError());
+    t_end(1);
+    if (!pl.direct) VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
+    return VS_OK;
+}
+
+// One chunk (n <= cap frames): the result of n successive AlignNextFrame calls.
+int vs_aligner::chunk_begin(const void* frames, size_t frame_stride, int n, int stride, int mem,
+                            const vs_aligner_params& p, vs_transform* out, int32_t* status, vs_align_info* infos) {
+    if (ck.open) return set_error(VS_ERR_ARG, "a chunk is already in flight on this handle");
+    ck.n = n; ck.p = p; ck.out = out; ck.status = status; ck.infos = infos;
+    ck.fr.assign(seq, clip_len, n);
+    if (seq > 0 && last_n != 0) VS_TRY(carry_over(pyr, lm, jac));
+    VS_TRY(ingest_frames(frames, frame_stride, stride, mem));
+    if (p.phase_correlate) VS_TRY(phase_spectra());
+    VS_TRY(keyframes());
+    VS_TRY(start_pairs());
+    if (ck.fr.n_pairs() > 0) {
+        if (p.phase_correlate) VS_TRY(phase_start_values());
+        if (!ck.plan.use_host) VS_TRY(launch_solver());
     }
     ck.open = true;
     return VS_OK;
 }
 
-int vs_aligner::chunk_end() {
-    if (!ck.open) return set_error(VS_ERR_ARG, "no chunk in flight on this handle");
-    ck.open = false;
-    hipStream_t s = stream;
-    const int n = ck.n, n_pairs = ck.n_pairs, epoch = ck.epoch;
-    const vs_aligner_params& p = ck.p;
-    vs_transform* out = ck.out; int32_t* status = ck.status; vs_align_info* infos = ck.infos;
-    const std::vector<int>& pair_frame = ck.pair_frame;
-    const bool direct = ck.direct;
-    bool use_host = ck.use_host;
-    const GnParams gp = ck.gp;
-    const long long seq0 = ck.seq0;
-    auto gidx = [&](int i) -> long long { return clip_len > 0 ? (long long)(i % clip_len) : seq0 + i; };
-    if (n_pairs > 0) {
-        PairDesc* hd = h_descs;
-        static const bool poll_done = []() { const char* e = getenv("VS_GN_POLL"); return e ? atoi(e) != 0 : true; }();
-        const float phase_scale = (1 << 2) / float(1 << levels);
-        auto apply_phase = [&]() -> int {
-            hipLaunchKernelGGL(vs_k_phase_apply, dim3((n_pairs + 255) / 256), dim3(256), 0, s, states, pres, pneg, n_pairs,
-                               p.phase_correlate_threshold, phase_scale);
-            VS_HIP(hipGetLastError());
-            return VS_OK;
-        };
-        const size_t wd_pair = (size_t)2 * nt_max, recs_pair = (size_t)2 * nt_max * 28;
-        if (!use_host) {
-            if (direct && poll_done && !timing) {
-                // the kernel writes a pair's `pad` word last, behind a system-scope fence: the results are in host memory when
-                // every pair's word has arrived -- the host spins on them instead of sleeping in the runtime (the stream itself
-                // is ordered by the next enqueue); after ~2 ms it falls back to the synchronisation, which also reports faults
-                const auto t0 = std::chrono::steady_clock::now();
-                bool all = false;
-                while (!all) {
-                    all = true;
-                    for (int q = 0; q < n_pairs; q++)
-                        if (reinterpret_cast<volatile int32_t*>(&h_states[q].pad)[0] != (int32_t)epoch) { all = false; break; }
-                    if (!all && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
-                if (!all) VS_HIP(hipStreamSynchronize(s));
-                else {
-                    // the results are in; helper workgroups may still be winding down, and a fault in any of them must be this
-                    // call's error, not the next one's: one non-blocking look at the stream
-                    const hipError_t qe = hipStreamQuery(s);
-                    if (qe != hipSuccess && qe != hipErrorNotReady) VS_HIP(qe);
-                }
-            } else {
-                VS_HIP(hipStreamSynchronize(s));
-            }
-            for (int q = 0; q < n_pairs; q++)
-                if (h_states[q].fail_reason >= 100) use_host = true;   // 100: libstdc++ would have heap-selected; 101: a helper workgroup timed out -- redo on the host
-            if (use_host) {
-                for (int q = 0; q < n_pairs; q++) { memset(&h_states[q], 0, sizeof(PairState)); h_states[q].status = 1; }
-                if (direct) VS_HIP(hipMemcpyAsync(descs, hd, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, s));
-                VS_HIP(hipMemcpyAsync(states, h_states, sizeof(PairState) * n_pairs, hipMemcpyHostToDevice, s));
-                if (p.phase_correlate) VS_TRY(apply_phase());
-                VS_HIP(hipStreamSynchronize(s));
-            }
-        }
-        for (int l = levels - 1; use_host && l >= 0; l--) {
-            const LevelDims& ld = L[l];
-            t_begin(VS_STAGE_WARPDIFF);
-            hipLaunchKernelGGL(vs_k_warpdiff_batch, dim3((ld.nt + 255) / 256, n_pairs, 2), dim3(256), 0, s, states, descs, pyr,
-                               pyr_frame, ld.img_off, ld.w, ld.h, lm, lm_frame, ld.lm_off, ld.nt, wd, wv, wd_pair);
-            VS_HIP(hipGetLastError());
-            t_end(1);
-            {
-                const auto t0 = std::chrono::steady_clock::now();
-                VS_HIP(hipMemcpyAsync(h_wd, wd, (size_t)n_pairs * wd_pair * 2, hipMemcpyDeviceToHost, s));
-                VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
-                VS_HIP(hipStreamSynchronize(s));
-                VS_TRY(select_host(n_pairs, ld));
-                VS_HIP(hipMemcpyAsync(idx, h_idx, (size_t)n_pairs * wd_pair * 4, hipMemcpyHostToDevice, s));
-                if (timing) tm.ms[VS_STAGE_SELECT] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            }
-            if (ld.nsel > 0) {
-                t_begin(VS_STAGE_GATHER);
-                hipLaunchKernelGGL(vs_k_gather_selected, dim3((ld.nsel + 255) / 256, n_pairs, 2), dim3(256), 0, s, states,
-                                   descs, pyr, pyr_frame, ld.img_off, ld.w, ld.h, lm, lm_frame, ld.lm_off, jac, jac_frame,
-                                   ld.jac_off, ld.nt, ld.nsel, idx, wd_pair, wv, recs, recs_pair, nt_max);
-                VS_HIP(hipGetLastError());
-                t_end(1);
-            }
-            t_begin(VS_STAGE_GN);
-            if (nt_max <= kSmallWgTiles)
-                hipLaunchKernelGGL(nt512::vs_k_gn_level, dim3(n_pairs), dim3(nt512::kGnThreads), 0, s, states, descs, pyr, pyr_frame,
-                                   ld.img_off, ld.w, ld.h, ld.nsel, recs, recs_pair, nt_max, l, gp);
-            else
-                hipLaunchKernelGGL(nt1024::vs_k_gn_level, dim3(n_pairs), dim3(nt1024::kGnThreads), 0, s, states, descs, pyr, pyr_frame,
-                                   ld.img_off, ld.w, ld.h, ld.nsel, recs, recs_pair, nt_max, l, gp);
-            VS_HIP(hipGetLastError());
-            t_end(1);
-        }
-        if (use_host) {
-            VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
-            VS_HIP(hipStreamSynchronize(s));
-        }
-        for (int q = 0; q < n_pairs; q++) {
-            const int i = pair_frame[q];
-            const PairState& st = h_states[q];
-            vs_align_info& inf = infos[i];
-            inf.status = st.status; inf.fail_reason = st.fail_reason; inf.fail_level = st.fail_level;
-            for (int l = 0; l < levels; l++) {
-                inf.iterations[l] = st.iterations[l]; inf.condition[l] = st.condition[l]; tm.gn_iterations += st.iterations[l];
-                if (st.iterations[l] > 0) {      // the level was reached (a level always runs at least one iteration)
-                    inf.selected_x[l] = L[l].nsel; inf.selected_y[l] = L[l].nsel;      // alignment.cpp:464-465: both sets keep size * fraction
-                    inf.level_transform[l] = vs_transform{st.level_T[l][0], st.level_T[l][1], st.level_T[l][2], st.level_T[l][3]};
-                }
-            }
-            if (p.phase_correlate) { inf.phase_dx = h_pres[q].dx; inf.phase_dy = h_pres[q].dy; inf.phase_response = h_pres[q].response; }
-            vs_transform t{st.T[0], st.T[1], st.T[2], st.T[3]};
-            if (st.status == 1) {
-                if ((gidx(i) & 1) == 0) t = vs_transform_inverse(&t);   // alignment.cpp:690-693
-                status[i] = 1;
-            }
-            // on failure the reference returns false with `transform` left at the estimate it had reached
-            // (alignment.cpp:661-667,674-677: no level rescale, no inversion) -- and VideoStabilizer feeds that value to
-            // the smoother all the same (stabilizer.cpp:18-44), so it is part of the observable behaviour
-            out[i] = t;
-        }
-    } else {
-        VS_HIP(hipStreamSynchronize(s));
+// The fused launch's results reach the host.
+int vs_aligner::wait_solver() {
+    const int n_pairs = ck.fr.n_pairs();
+    if (!(ck.plan.direct && solver_knobs().poll && !timing)) { VS_HIP(hipStreamSynchronize(stream)); return VS_OK; }
+    // the kernel writes a pair's `pad` word last, behind a system-scope fence: the results are in host memory when
+    // every pair's word has arrived -- the host spins on them instead of sleeping in the runtime (the stream itself
+    // is ordered by the next enqueue); after ~2 ms it falls back to the synchronisation, which also reports faults
+    const auto t0 = std::chrono::steady_clock::now();
+    bool all = false;
+    while (!all) {
+        all = true;
+        for (int q = 0; q < n_pairs; q++)
+            if (reinterpret_cast<volatile int32_t*>(&h_states[q].pad)[0] != (int32_t)ck.epoch) { all = false; break; }
+        if (!all && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
-    if (timing) { t_collect(); tm.frames += n; }
-    seq = seq0 + n;
-    last_n = n;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!all) VS_HIP(hipStreamSynchronize(stream));
+    else {
+        // the results are in; helper workgroups may still be winding down, and a fault in any of them must be this
+        // call's error, not the next one's: one non-blocking look at the stream
+        const hipError_t qe = hipStreamQuery(stream);
+        if (qe != hipSuccess && qe != hipErrorNotReady) VS_HIP(qe);
+    }
     return VS_OK;
 }
 
-extern "C" {
+// The level-by-level form with the selection on the host: per level one warpdiff launch, select_host, one gather launch and one
+// persistent Gauss-Newton launch.
+int vs_aligner::host_redo() {
+    hipStream_t s = stream;
+    const int n_pairs = ck.fr.n_pairs();
+    const size_t wd_pair = (size_t)2 * nt_max, recs_pair = ck.plan.recs_pair;
+    const int build = wg_build(nt_max);
+    for (int l = levels - 1; l >= 0; l--) {
+        const LevelDims& ld = L[l];
+        t_begin(VS_STAGE_WARPDIFF);
+        hipLaunchKernelGGL(vs_k_warpdiff_batch, dim3((ld.nt + 255) / 256, n_pairs, 2), dim3(256), 0, s, states, descs, pyr,
+                           pyr_frame, ld.img_off, ld.w, ld.h, lm, lm_frame, ld.lm_off, ld.nt, wd, wv, wd_pair);
+        VS_HIP(hipGetLastError());
+        t_end(1);
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            VS_HIP(hipMemcpyAsync(h_wd, wd, (size_t)n_pairs * wd_pair * 2, hipMemcpyDeviceToHost, s));
+            VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
+            VS_HIP(hipStreamSynchronize(s));
+            VS_TRY(select_host(n_pairs, ld));
+            VS_HIP(hipMemcpyAsync(idx, h_idx, (size_t)n_pairs * wd_pair * 4, hipMemcpyHostToDevice, s));
+            if (timing) tm.ms[VS_STAGE_SELECT] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (ld.nsel > 0) {
+            t_begin(VS_STAGE_GATHER);
+            hipLaunchKernelGGL(vs_k_gather_selected, dim3((ld.nsel + 255) / 256, n_pairs, 2), dim3(256), 0, s, states,
+                               descs, pyr, pyr_frame, ld.img_off, ld.w, ld.h, lm, lm_frame, ld.lm_off, jac, jac_frame,
+                               ld.jac_off, ld.nt, ld.nsel, idx, wd_pair, wv, recs, recs_pair, nt_max);
+            VS_HIP(hipGetLastError());
+            t_end(1);
+        }
+        t_begin(VS_STAGE_GN);
+        hipLaunchKernelGGL(kGnLevelBuilds[build], dim3(n_pairs), dim3(kBuildThreads[build]), 0, s, states, descs, pyr, pyr_frame,
+                           ld.img_off, ld.w, ld.h, ld.nsel, recs, recs_pair, nt_max, l, ck.plan.gp);
+        VS_HIP(hipGetLastError());
+        t_end(1);
+    }
+    VS_HIP(hipMemcpyAsync(h_states, states, sizeof(PairState) * n_pairs, hipMemcpyDeviceToHost, s));
+    VS_HIP(hipStreamSynchronize(s));
+    return VS_OK;
+}
+
+void vs_aligner::convert_results() {
+    for (int q = 0; q < ck.fr.n_pairs(); q++) {
+        const int i = ck.fr.pair_frame[q];
+        vs_align_info& inf = ck.infos[i];
+        tm.gn_iterations += convert_result(h_states[q], ck.fr.g(i), *this, &inf, &ck.out[i], &ck.status[i]);
+        if (ck.p.phase_correlate) { inf.phase_dx = h_pres[q].dx; inf.phase_dy = h_pres[q].dy; inf.phase_response = h_pres[q].response; }
+    }
+}
+
+int vs_aligner::chunk_end() {
+    if (!ck.open) return set_error(VS_ERR_ARG, "no chunk in flight on this handle");
+    ck.open = false;
+    const int n_pairs = ck.fr.n_pairs();
+    if (n_pairs > 0) {
+        bool redo = ck.plan.use_host;
+        if (!redo) {
+            VS_TRY(wait_solver());
+            for (int q = 0; q < n_pairs; q++)
+                if (h_states[q].fail_reason >= 100) redo = true;   // 100: libstdc++ would have heap-selected; 101: a helper workgroup timed out -- redo on the host
+            if (redo) {   // the pairs start over for host_redo
+                reset_states(n_pairs);
+                if (ck.plan.direct) VS_HIP(hipMemcpyAsync(descs, h_descs, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, stream));
+                VS_HIP(hipMemcpyAsync(states, h_states, sizeof(PairState) * n_pairs, hipMemcpyHostToDevice, stream));
+                if (ck.p.phase_correlate) VS_TRY(launch_phase_apply());
+                VS_HIP(hipStreamSynchronize(stream));
+            }
+        }
+        if (redo) VS_TRY(host_redo());
+        convert_results();
+    } else {
+        VS_HIP(hipStreamSynchronize(stream));
+    }
+    if (timing) { t_collect(); tm.frames += ck.n; }
+    seq = ck.fr.seq0 + ck.n;
+    last_n = ck.n;
+    return VS_OK;
+}
 
 // Kernel-level form of the keep-best-fraction step (alignment.cpp:435-492) for n_arrays independent
 // warpdiff tables: out_idx[a*tx*ty + 0..count) = tile_y*tx+tile_x of the survivors in std::nth_element's order.
-static int select_smallest_impl(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx,
-                                int32_t* status, int mem, void* stream, int rule);
-int vs_select_smallest(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx,
-                       int32_t* status, int mem, void* stream) try {
-    VS_ARG(status);
-    return select_smallest_impl(warpdiff, n_arrays, tx, ty, fraction, out_idx, status, mem, stream, 0);
-} VS_CATCH_ALL
-// ... under VS_SELECT_STABLE's rule: smallest by (abs_delta, tile index), the survivors in ascending tile order
-int vs_select_smallest_stable(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx, int mem,
-                              void* stream) try {
-    return select_smallest_impl(warpdiff, n_arrays, tx, ty, fraction, out_idx, nullptr, mem, stream, 1);
-} VS_CATCH_ALL
 static int select_smallest_impl(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx,
                                 int32_t* status, int mem, void* stream, int rule) {
     VS_ARG(warpdiff && out_idx && (status || rule) && n_arrays >= 1 && tx >= 1 && ty >= 1 && fraction > 0.0f && fraction <= 1.0f);
@@ -1009,16 +852,30 @@ static int select_smallest_impl(const uint16_t* warpdiff, int n_arrays, int tx, 
     if (status) VS_TRY(st.out(status, (size_t)n_arrays * 4, mem));
     // (a | posR; the wave-level rounds use the first 128 bytes of posR as scratch whatever the array length)
     const size_t dyn = std::max<size_t>((((size_t)nt * 6 + 15) & ~(size_t)15), (((size_t)nt * 4 + 128 + 15) & ~(size_t)15));
-    const bool small_wg = nt <= kSmallWgTiles;
-    const auto kernel = small_wg ? nt512::vs_k_select : nt1024::vs_k_select;
-    VS_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(kernel, dim3(n_arrays), dim3(small_wg ? nt512::kGnThreads : nt1024::kGnThreads), dyn, s, a.as<uint16_t>(), nt,
+    const int build = wg_build(nt);
+    int device = 0;
+    VS_HIP(hipGetDevice(&device));
+    VS_TRY(raise_dyn_lds((const void*)kSelectBuilds[build], kDynSelect + build, device, dyn));
+    hipLaunchKernelGGL(kSelectBuilds[build], dim3(n_arrays), dim3(kBuildThreads[build]), dyn, s, a.as<uint16_t>(), nt,
                        nsel, o.as<int32_t>(), status ? st.as<int32_t>() : (int32_t*)nullptr, rule);
     VS_HIP(hipGetLastError());
     if (status) VS_TRY(vsi::finish_outputs(mem, s, {&o, &st}));
     else VS_TRY(vsi::finish_outputs(mem, s, {&o}));
     return nsel;
 }
+
+extern "C" {
+
+int vs_select_smallest(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx,
+                       int32_t* status, int mem, void* stream) try {
+    VS_ARG(status);
+    return select_smallest_impl(warpdiff, n_arrays, tx, ty, fraction, out_idx, status, mem, stream, 0);
+} VS_CATCH_ALL
+// ... under VS_SELECT_STABLE's rule: smallest by (abs_delta, tile index), the survivors in ascending tile order
+int vs_select_smallest_stable(const uint16_t* warpdiff, int n_arrays, int tx, int ty, float fraction, int32_t* out_idx, int mem,
+                              void* stream) try {
+    return select_smallest_impl(warpdiff, n_arrays, tx, ty, fraction, out_idx, nullptr, mem, stream, 1);
+} VS_CATCH_ALL
 
 vs_aligner* vs_aligner_create(const vs_aligner_params* params, int device) try {
     if (!vsi::device_ready()) return nullptr;
@@ -1107,12 +964,93 @@ int vs_aligner_wait_stream(vs_aligner* a, void* producer_stream) try {
 
 }  // extern "C"
 
+// One align call: strides in elements of esz bytes.
+struct AlignCall {
+    const void* frames; size_t frame_stride; int n, stride, mem; size_t esz;
+    const vs_aligner_params& p;
+    vs_transform* out; int32_t* status;
+};
+
+// Host-resident frames, more than one upload's worth: pipelined ingest.  The batch is cut into chunks of host_chunk frames (about
+// vsi::ingest_chunk_bytes()); an uploader thread copies chunk c+1 into the other upload area (its own stream) while chunk c runs through
+// the pipeline from device memory.  Same chunks, same arithmetic as the device-resident path: results are identical.
+static int align_host_pipelined(vs_aligner* a, const AlignCall& c, int host_chunk, size_t step_bytes, size_t frame_bytes) {
+    const int n = c.n;
+    VS_HIP(vsi::grow(a->ingest, &a->ingest_bytes, (size_t)(host_chunk - 1) * step_bytes + frame_bytes, nullptr, false, 2));
+    if (!a->copy_stream) VS_HIP(hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking));
+    auto upload = [a, frames = c.frames, step_bytes, frame_bytes, n, host_chunk](int k) -> hipError_t {
+        const int off = chunk_span(n, host_chunk, k).off, m = chunk_span(n, host_chunk, k).len;
+        hipError_t e = hipSetDevice(a->device);
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(a->ingest[k & 1], (const uint8_t*)frames + (size_t)off * step_bytes, (size_t)(m - 1) * step_bytes + frame_bytes,
+                           hipMemcpyHostToDevice, a->copy_stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(a->copy_stream);
+    };
+    const int n_chunks = chunk_count(n, host_chunk);
+    std::future<hipError_t> next = run_async(upload, 0);
+    for (int k = 0; k < n_chunks; k++) {
+        const int off = chunk_span(n, host_chunk, k).off, m = chunk_span(n, host_chunk, k).len;
+        const hipError_t ue = next.get();                 // chunk k is in ingest[k & 1]
+        if (k + 1 < n_chunks) next = run_async(upload, k + 1);   // chunk k-1 (same area) has been consumed
+        int r = ue == hipSuccess ? VS_OK : set_error(VS_ERR_HIP, "frame upload failed: %s", hipGetErrorString(ue));
+        if (r == VS_OK) r = a->ensure_capacity(m);
+        if (r == VS_OK) r = a->run_chunk(a->ingest[k & 1], c.frame_stride, m, c.stride, VS_MEM_DEVICE, c.p, c.out + off, c.status + off, a->info.data() + off);
+        if (r != VS_OK) { if (next.valid()) (void)next.get(); return r; }
+    }
+    return VS_OK;
+}
+
+// A device-resident batch that fits one chunk is only enqueued; align_finish completes it.
+static int align_async_chunk(vs_aligner* a, const AlignCall& c) {
+    VS_TRY(a->ensure_capacity(c.n));
+    VS_TRY(a->chunk_begin(c.frames, c.frame_stride, c.n, c.stride, c.mem, c.p, c.out, c.status, a->info.data()));
+    a->started = true; a->started_n = c.n; a->started_status = c.status;
+    return VS_OK;
+}
+
+// Chunk after chunk, each completed before the next begins.
+static int align_chunk_loop(vs_aligner* a, const AlignCall& c, int max_chunk) {
+    for (int k = 0; k < chunk_count(c.n, max_chunk); k++) {
+        const int off = chunk_span(c.n, max_chunk, k).off, m = chunk_span(c.n, max_chunk, k).len;
+        VS_TRY(a->ensure_capacity(m));
+        const uint8_t* base = (const uint8_t*)c.frames + (size_t)off * c.frame_stride * c.esz;
+        VS_TRY(a->run_chunk(base, c.frame_stride, m, c.stride, c.mem, c.p, c.out + off, c.status + off, a->info.data() + off));
+    }
+    return VS_OK;
+}
+
 // First half of vs_aligner_align_batch (clip_frames == 0) / vs_aligner_align_clips (clip_frames > 0).  With `async`, a
 // device-resident batch that fits one chunk is only enqueued (vs_aligner::chunk_begin) and align_finish completes it: the caller
 // may do unrelated host work in between, but nothing on this handle.  Every other case completes here and align_finish just
 // hands out the result.
 static int align_start_impl(vs_aligner* a, const void* frames, size_t frame_stride, int n, int w, int h, int stride, int format, int mem,
-                            const vs_aligner_params* params, vs_transform* out, int32_t* status, bool async);
+                            const vs_aligner_params* params, vs_transform* out, int32_t* status, bool async) {
+    VS_ARG(a && frames && out && status && n >= 1 && w >= 8 && h >= 8);
+    VS_ARG(w <= 65535 && h <= 65535);                      // (tile coordinates are 16-bit; keeps w * ch and the frame spans below inside their types)
+    VS_ARG(vs_format_bits(format) != 0);
+    const int ch = format == VS_FMT_GRAY8 ? 1 : 3;
+    VS_ARG(stride >= w * ch);
+    VS_ARG(n == 1 || frame_stride >= (size_t)(h - 1) * stride + (size_t)w * ch);
+    const vs_aligner_params& p = params ? *params : a->params;
+    VS_ARG(p.max_iters >= 1 && p.smallest_fraction > 0.0f && p.smallest_fraction <= 1.0f);
+    VS_HIP(hipSetDevice(a->device));
+    if (a->W != w || a->H != h || a->fmt != format) VS_TRY(a->configure(w, h, format, p));   // alignment.cpp:155
+    a->set_fraction(p.smallest_fraction);
+    a->info.assign(n, vs_align_info{});
+    const AlignCall c{frames, frame_stride, n, stride, mem, (size_t)(vs_format_bits(format) > 8 ? 2 : 1), p, out, status};
+    int max_chunk = 0;
+    VS_TRY(max_chunk_frames(a->pyr_frame, a->clip_len, &max_chunk));
+    const size_t frame_bytes = ((size_t)(h - 1) * stride + (size_t)w * ch) * c.esz;
+    const size_t step_bytes = n > 1 ? frame_stride * c.esz : frame_bytes;
+    const int host_chunk = host_chunk_frames(max_chunk, vsi::ingest_chunk_bytes(), step_bytes, a->clip_len);
+    if (mem == VS_MEM_HOST && n > host_chunk) VS_TRY(align_host_pipelined(a, c, host_chunk, step_bytes, frame_bytes));
+    else if (async && mem == VS_MEM_DEVICE && n <= max_chunk) return align_async_chunk(a, c);
+    else VS_TRY(align_chunk_loop(a, c, max_chunk));
+    int aligned = 0;
+    for (int i = 0; i < n; i++) aligned += status[i];
+    a->started_result = aligned;
+    return VS_OK;
+}
 static void align_close_clips(vs_aligner* a) {
     if (a->started_clips) { a->started_clips = false; a->clip_len = 0; a->seq = 0; }
 }
@@ -1164,88 +1102,6 @@ int vs_aligner_align_batch(vs_aligner* a, const void* frames, size_t frame_strid
     const int r = align_start(a, frames, frame_stride, n, 0, w, h, stride, format, mem, params, out, status, false);
     return r < 0 ? r : align_finish(a);
 } VS_CATCH_ALL
-
-}  // extern "C"
-
-static int align_start_impl(vs_aligner* a, const void* frames, size_t frame_stride, int n, int w, int h, int stride, int format, int mem,
-                            const vs_aligner_params* params, vs_transform* out, int32_t* status, bool async) {
-    VS_ARG(a && frames && out && status && n >= 1 && w >= 8 && h >= 8);
-    VS_ARG(w <= 65535 && h <= 65535);                      // (tile coordinates are 16-bit; keeps w * ch and the frame spans below inside their types)
-    VS_ARG(vs_format_bits(format) != 0);
-    const int ch = format == VS_FMT_GRAY8 ? 1 : 3;
-    VS_ARG(stride >= w * ch);
-    VS_ARG(n == 1 || frame_stride >= (size_t)(h - 1) * stride + (size_t)w * ch);
-    const vs_aligner_params& p = params ? *params : a->params;
-    VS_ARG(p.max_iters >= 1 && p.smallest_fraction > 0.0f && p.smallest_fraction <= 1.0f);
-    VS_HIP(hipSetDevice(a->device));
-    if (a->W != w || a->H != h || a->fmt != format) VS_TRY(a->configure(w, h, format, p));   // alignment.cpp:155
-    // nsel follows the *current* params like the reference (alignment.cpp:464-465)
-    for (int l = 0; l < a->levels; l++)
-        a->L[l].nsel = (int)static_cast<size_t>((size_t)a->L[l].nt * p.smallest_fraction);
-    a->info.assign(n, vs_align_info{});
-    const size_t esz = vs_format_bits(format) > 8 ? 2 : 1;
-    // chunking bounds device memory: at most ~6 GiB of pyramids per handle
-    int max_chunk = (int)std::max<size_t>(2, std::min<size_t>(1024, ((size_t)6 << 30) / std::max<size_t>(1, a->pyr_frame)));
-    if (a->clip_len > 0) {   // whole clips per chunk
-        if (a->clip_len > max_chunk) return set_error(VS_ERR_UNSUPPORTED, "clips of %d frames exceed the %d-frame chunk", a->clip_len, max_chunk);
-        max_chunk -= max_chunk % a->clip_len;
-    }
-    int aligned = 0;
-    // Host-resident frames, more than one upload's worth: pipelined ingest.  The batch is cut into chunks of ~kIngestBytes;
-    // an uploader thread copies chunk c+1 into the other upload area (its own stream) while chunk c runs through the
-    // pipeline from device memory.  Same chunks, same arithmetic as the device-resident path: results are identical.
-    const size_t frame_bytes = ((size_t)(h - 1) * stride + (size_t)w * ch) * esz;
-    const size_t step_bytes = n > 1 ? frame_stride * esz : frame_bytes;
-    int host_chunk = (int)std::min<size_t>((size_t)max_chunk, std::max<size_t>(4, kIngestBytes / std::max<size_t>(1, step_bytes)));
-    if (a->clip_len > 0) host_chunk = std::max(a->clip_len, host_chunk - host_chunk % a->clip_len);
-    if (mem == VS_MEM_HOST && n > host_chunk) {
-        const size_t area = (size_t)(host_chunk - 1) * step_bytes + frame_bytes;
-        if (a->ingest_bytes < area) {
-            for (void*& q : a->ingest) { if (q) (void)hipFree(q); q = nullptr; }
-            a->ingest_bytes = 0;
-            VS_HIP(vsi::dev_alloc(&a->ingest[0], area));
-            VS_HIP(vsi::dev_alloc(&a->ingest[1], area));
-            a->ingest_bytes = area;
-        }
-        if (!a->copy_stream) VS_HIP(hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking));
-        auto upload = [a, frames, step_bytes, frame_bytes, n, host_chunk](int c) -> hipError_t {
-            const int off = c * host_chunk, m = std::min(host_chunk, n - off);
-            hipError_t e = hipSetDevice(a->device);
-            if (e != hipSuccess) return e;
-            e = hipMemcpyAsync(a->ingest[c & 1], (const uint8_t*)frames + (size_t)off * step_bytes, (size_t)(m - 1) * step_bytes + frame_bytes,
-                               hipMemcpyHostToDevice, a->copy_stream);
-            return e != hipSuccess ? e : hipStreamSynchronize(a->copy_stream);
-        };
-        const int n_chunks = (n + host_chunk - 1) / host_chunk;
-        std::future<hipError_t> next = run_async(upload, 0);
-        for (int c = 0; c < n_chunks; c++) {
-            const int off = c * host_chunk, m = std::min(host_chunk, n - off);
-            const hipError_t ue = next.get();                 // chunk c is in ingest[c & 1]
-            if (c + 1 < n_chunks) next = run_async(upload, c + 1);   // chunk c-1 (same area) has been consumed
-            int r = ue == hipSuccess ? VS_OK : set_error(VS_ERR_HIP, "frame upload failed: %s", hipGetErrorString(ue));
-            if (r == VS_OK) r = a->ensure_capacity(m);
-            if (r == VS_OK) r = a->run_chunk(a->ingest[c & 1], frame_stride, m, stride, VS_MEM_DEVICE, p, out + off, status + off, a->info.data() + off);
-            if (r != VS_OK) { if (next.valid()) (void)next.get(); return r; }
-        }
-    } else if (async && mem == VS_MEM_DEVICE && n <= max_chunk) {
-        VS_TRY(a->ensure_capacity(n));
-        VS_TRY(a->chunk_begin(frames, frame_stride, n, stride, mem, p, out, status, a->info.data()));
-        a->started = true; a->started_n = n; a->started_status = status;
-        return VS_OK;
-    } else {
-        for (int off = 0; off < n; off += max_chunk) {
-            const int m = std::min(max_chunk, n - off);
-            VS_TRY(a->ensure_capacity(m));
-            const uint8_t* base = (const uint8_t*)frames + (size_t)off * frame_stride * esz;
-            VS_TRY(a->run_chunk(base, frame_stride, m, stride, mem, p, out + off, status + off, a->info.data() + off));
-        }
-    }
-    for (int i = 0; i < n; i++) aligned += status[i];
-    a->started_result = aligned;
-    return VS_OK;
-}
-
-extern "C" {
 
 // n_clips independent clips of frames_per_clip frames each, back to back in memory: the results of aligning every
 // clip with its own fresh VideoAligner, computed together (every stage is one launch over all clips, so short

@@ -26,6 +26,7 @@ inline bool deblur_params_finite(float sensitivity, float max_ratio) {
     const double r = (double)max_ratio < 9007199254740992.0 ? (double)max_ratio : 9007199254740992.0;
     return r * r <= (double)sensitivity * 0x1p100;
 }
+constexpr int kSharedMinPairs = 32;   // VS_BATCH_SHARED: launches of at least this many pairs take the aligner's small-footprint solver build
 }  // namespace vsi
 #define VS_CATCH_ALL catch (...) { return vsi::caught(); }
 #define VS_CATCH_ALL_NULL catch (...) { (void)vsi::caught(); return nullptr; }
@@ -46,6 +47,20 @@ namespace vsi {
 // (vs_test_fail_alloc, include/vs_amd.h).  On failure *p is nullptr.
 hipError_t dev_alloc(void** p, size_t bytes);
 hipError_t pinned_alloc(void** p, size_t bytes);
+
+// A scratch buffer of a handle grows to `need` bytes (`count` buffers that share one size field).  sync: work on `ws` may still read the old
+// block.  The handle's fields are zeroed before the allocation: after a failed one the handle holds no buffer and the next call starts over
+// (tests/test_alloc_failure_gpu.py).
+inline hipError_t grow(void** buf, size_t* bytes, size_t need, hipStream_t ws = nullptr, bool sync = false, int count = 1) {
+    if (*bytes >= need) return hipSuccess;
+    hipError_t e = sync ? hipStreamSynchronize(ws) : hipSuccess;
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < count; k++) { if (buf[k]) (void)hipFree(buf[k]); buf[k] = nullptr; }
+    *bytes = 0;
+    for (int k = 0; e == hipSuccess && k < count; k++) e = dev_alloc(&buf[k], need);
+    if (e == hipSuccess) *bytes = need;
+    return e;
+}
 
 // RAII device allocation used by the host-staged (VS_MEM_HOST) form of the kernel-level calls.
 struct DevBuf {

@@ -18,6 +18,7 @@
 
 using vsi::set_error;
 using vsi::run_async;
+using vsi::grow;
 
 struct vs_stabilizer {
     vs_stabilizer_params params;
@@ -142,20 +143,6 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
 }
 
 }  // extern "C"
-
-// A scratch buffer of the handle grows to `need` bytes (`count` buffers that share one size field: pipe_in's two halves).  sync: work on `ws` may
-// still read the old block.  The handle's fields are zeroed before the allocation: after a failed one the handle holds no buffer and the next
-// call starts over (tests/test_alloc_failure_gpu.py).
-static hipError_t grow(void** buf, size_t* bytes, size_t need, hipStream_t ws = nullptr, bool sync = false, int count = 1) {
-    if (*bytes >= need) return hipSuccess;
-    hipError_t e = sync ? hipStreamSynchronize(ws) : hipSuccess;
-    if (e != hipSuccess) return e;
-    for (int k = 0; k < count; k++) { if (buf[k]) (void)hipFree(buf[k]); buf[k] = nullptr; }
-    *bytes = 0;
-    for (int k = 0; e == hipSuccess && k < count; k++) e = vsi::dev_alloc(&buf[k], need);
-    if (e == hipSuccess) *bytes = need;
-    return e;
-}
 
 // One vs_stabilizer_process_batch / _clips call, or a run of its frames; strides in elements.  clip_len > 0: the n frames are n / clip_len
 // independent clips, each run through a fresh stabilizer (reset before every clip and after the last), all of them aligned and warped together.
