@@ -116,6 +116,58 @@ def test_quality_on_the_fills_own_scene(oracle):
     assert mae["inpaint"] < mae["constant"]
 
 
+def test_premises_of_the_hostile_cases(oracle):
+    """every builder of tests/_inpaint_cases.py asserts its premise (what makes its input reach the code in question) on the references
+    alone; the shapes and formats are those of tests/test_inpaint_hostile_gpu.py"""
+    import _inpaint_cases as IC
+    O = oracle
+    for w, h in ((300, 270), (520, 70)):
+        for n_cand in (5, 16):
+            IC.rotation_case(O, w, h, n_cand)
+        IC.rotation_rois(w, h)
+    IC.hostile_case(O)
+    IC.nothing_covered_cases(O)
+    IC.sixteen_case(O)
+    for n_cand, extra in ((16, 3), (1, 1)):
+        IC.seam_case(O, n_cand, extra)
+    for fmt in ("u8", "bgr10", "bgr16"):
+        for w, h in ((63, 65), (300, 270)):
+            for high in (0, 1):
+                for open_share in (0.5, 0.9):
+                    IC.rounding_case(w, h, fmt, high, open_share)
+    for fmt in ("bgr10", "bgr12"):
+        for w, h in ((131, 77), (300, 270)):
+            IC.out_of_range_case(w, h, fmt)
+    for fmt in ("u8", "bgr16"):
+        for w, h in ((300, 270), (60, 50)):
+            IC.idle_and_busy_batch(w, h, fmt)
+    # the 2 x 2 closed form is the rule on every mask pattern
+    rng = np.random.default_rng(2)
+    imgs = rng.integers(0, 256, (16, 2, 2, 3)).astype(np.uint8)
+    masks = np.array([[(k >> b) & 1 for b in range(4)] for k in range(16)], np.uint8).reshape(16, 2, 2) * 0x80
+    assert np.array_equal(IC.inpaint_2x2(imgs, masks), R.inpaint_batch(imgs, masks))
+    # the windowed coverage is the rule's, cropped
+    for t in ((0.02, -0.03, 7.0, -5.0), IC.ZOOM_IN, (-1 + 1e-9, 1e-9, 3.0, 2.0), (0.0, 0.0, 6e5, 0.0)):
+        for roi in ((0, 0, 64, 48), (5, 7, 20, 11), (63, 47, 1, 1)):
+            cov, _ = IC.covered_window(O, O.Transform.of(*t), 64, 48, roi)
+            assert np.array_equal(cov, F.covered(O, O.Transform.of(*t), 64, 48)[roi[1]:roi[1] + roi[3], roi[0]:roi[0] + roi[2]])
+
+
+def test_the_tails_lds_holds_every_shape_it_is_given():
+    """vs_inpaint.hip's make_plan starts the tail at the first level of at most 4096 texels (kTailTexels); the tail keeps that level and all
+    below it in 8192 texels of LDS (kTailLds).  Enumerated: over every W x H <= 4096 the levels from there down sum to at most 8191, reached at
+    1 x 4096 and 4096 x 1 -- so the plan's second condition never moves the tail, and the shapes of tests/test_inpaint_hostile_gpu.py hold the
+    maximum"""
+    def below(w, h):
+        t = w * h
+        while w > 1 or h > 1:
+            w, h = (w + 1) >> 1, (h + 1) >> 1
+            t += w * h
+        return t
+    worst = max((below(w, h), w, h) for w in range(1, 4097) for h in range(1, 4096 // w + 1))
+    assert worst[0] == 8191 and {(w, h) for w in range(1, 4097) for h in range(1, 4096 // w + 1) if below(w, h) == 8191} == {(1, 4096), (4096, 1)}
+
+
 def test_library_exports_the_inpaint_symbols(vs):
     L = ctypes.CDLL(vs.LIB_PATH)
     for name in ("vs_bgr_fill_coverage_batch", "vs_bgr_inpaint_batch", "vs_stabilizer_set_inpaint", "vs_stabilizer_get_inpaint"):

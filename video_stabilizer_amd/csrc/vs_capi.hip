@@ -35,7 +35,7 @@ bool device_ready() {
 // environment for programs that cannot call the hook.
 // The ENVIRONMENT-driven hooks (VS_TEST_FAIL_ALLOC, VS_TEST_POISON_*) are honoured only when VS_TEST_HOOKS=1 is set as well: a stray
 // variable in a production environment must not make a real allocation fail or cost every allocation a memset.
-static const char* test_env(const char* name) {
+const char* test_env(const char* name) {
     static const bool on = []() { const char* h = getenv("VS_TEST_HOOKS"); return h && atoi(h) == 1; }();
     return on ? getenv(name) : nullptr;
 }

@@ -47,6 +47,8 @@ namespace vsi {
 // (vs_test_fail_alloc, include/vs_amd.h).  On failure *p is nullptr.
 hipError_t dev_alloc(void** p, size_t bytes);
 hipError_t pinned_alloc(void** p, size_t bytes);
+// getenv(name) for the environment-driven test hooks: null unless VS_TEST_HOOKS=1 is set as well (that gate is read once per process)
+const char* test_env(const char* name);
 
 // A scratch buffer of a handle grows to `need` bytes (`count` buffers that share one size field).  sync: work on `ws` may still read the old
 // block.  The handle's fields are zeroed before the allocation: after a failed one the handle holds no buffer and the next call starts over

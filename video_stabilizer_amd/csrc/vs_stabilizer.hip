@@ -437,7 +437,10 @@ struct Chunk {
         if (all_covered) return VS_OK;
         const int ms = (ow + 3) & ~3;
         const size_t mfs = (size_t)ms * oh, pbytes = (vsk::inpaint_pyramid_bytes(ow, oh, bits) + 15) & ~(size_t)15;
-        const size_t group = std::min(e - j, std::max<size_t>(1, kInpaintScratch / (mfs + pbytes + sizeof(uint32_t))));
+        // (test hook, read at every call: VS_TEST_INPAINT_SCRATCH_BYTES in place of the budget, so that clips of a few frames run in several groups)
+        const char* const hook = vsi::test_env("VS_TEST_INPAINT_SCRATCH_BYTES");
+        const size_t budget = hook ? (size_t)strtoull(hook, nullptr, 0) : kInpaintScratch;
+        const size_t group = std::min(e - j, std::max<size_t>(1, budget / (mfs + pbytes + sizeof(uint32_t))));
         const size_t cbytes = (group * sizeof(uint32_t) + 255) & ~(size_t)255;
         VS_HIP(grow(&s->inpaint_buf, &s->inpaint_bytes, cbytes + group * (mfs + pbytes), ws, true));   // (an earlier run's kernels may still read the block)
         uint32_t* const counts = (uint32_t*)s->inpaint_buf;
