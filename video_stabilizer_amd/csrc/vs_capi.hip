@@ -940,15 +940,23 @@ static int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, 
     const size_t in_bytes = ((size_t)(n_frames - 1) * src_fs + img_span(w, h, src_stride, channels)) * esz;
     VS_TRY(a.in(src, in_bytes, mem, s));
     VS_TRY(o.out_image(dst, (size_t)roi.w * channels * osz, (size_t)roi.h, (size_t)dst_stride * osz, (size_t)n_frames, dst_fs * osz, mem));
+    // the float-tile Lanczos2 forms' per-launch tables (tile windows, row terms: vsk::bgr_warp_c3) from the table ring, 16-byte aligned; a call whose
+    // tables do not fit half the ring goes without them (the kernel then works the same numbers out itself)
+    int* tdev = nullptr;
+    TableRing* tring = nullptr;
+    const size_t tab_ints = with_extents ? vsk::bgr_warp_c3_table_bytes(bits, mode, roi) / 4 * (size_t)n_frames : 0;
+    if (tab_ints && tab_ints + 3 <= TableRing::kInts / 2 && (tring = table_ring())) VS_TRY(tring->take(tab_ints + 3, s, &tdev));
+    void* const tab = tdev ? (void*)(((uintptr_t)tdev + 15) & ~(uintptr_t)15) : nullptr;
     hipError_t e = hipErrorNotSupported;
     if (tuned)
-        e = vsk::bgr_warp_c3(a.dev, w, h, src_stride, bits, pdev, with_extents ? pdev + n_frames : nullptr, mode, border, max_value, o.dev,
+        e = vsk::bgr_warp_c3(a.dev, w, h, src_stride, bits, pdev, with_extents ? pdev + n_frames : nullptr, tab, mode, border, max_value, o.dev,
                              dst_stride, n_frames, src_fs, dst_fs, roi, compact, s);
     if (e == hipErrorNotSupported)   // layouts without a tuned kernel (other channel counts, float output): one thread per pixel, same arithmetic
         e = vsk::bgr_warp_generic(a.dev, w, h, src_stride, channels, bits, pdev, mode, border, max_value,
                                   o.dev, dst_stride, f32out, n_frames, src_fs, dst_fs, roi, s);
     VS_HIP(e);
     VS_TRY(ring->fence(pdev, s));
+    if (tdev) VS_TRY(tring->fence(tdev, s));
     return vsi::finish_outputs(mem, s, {&o});
 }
 

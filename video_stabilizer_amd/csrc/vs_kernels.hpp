@@ -49,9 +49,12 @@ hipError_t bgr_warp_generic(const void* src, int w, int h, int src_stride, int c
                             bool f32out, int n_frames, size_t src_frame_stride, size_t dst_frame_stride, Roi roi, hipStream_t s);
 // tuned interleaved 3-channel path, u8 or u16 (vs_warp.hip); hipErrorNotSupported when the grid would overflow
 // compact: 0 the standard window; 1 / 2: every frame fits the 20-row windows of the contracted / separable forms' six- / seven-wave instantiations (bgr_warp_c3_compact_shape on the extents)
-hipError_t bgr_warp_c3(const void* src, int w, int h, int src_stride, int bits, const float4* params_dev, const float4* extents_dev,
+// tab_dev: device scratch of n_frames * bgr_warp_c3_table_bytes(bits, mode, roi) bytes (16-byte aligned) or null -- the float-tile Lanczos2 forms' per-launch
+// tables (tile windows, row position terms), written by a small kernel in front of the warp launch on the same stream; read only together with the extents
+hipError_t bgr_warp_c3(const void* src, int w, int h, int src_stride, int bits, const float4* params_dev, const float4* extents_dev, void* tab_dev,
                        int mode, int border, int max_value, void* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, Roi roi,
                        int compact, hipStream_t s);
+size_t bgr_warp_c3_table_bytes(int bits, int mode, Roi roi);
 int bgr_warp_c3_compact_shape(const float* E4, int n_frames);
 // VS_WARP_BILINEAR_CV (cv::warpAffine's fixed-point bilinear): minv_dev = n_frames x 6 doubles, the output -> source matrix of each frame
 // (vs_cv_inverse_matrix).  Generic: any channel count, u8 / u16 containers; tuned (vs_warp.hip): interleaved 8-bit BGR saturating at 255,

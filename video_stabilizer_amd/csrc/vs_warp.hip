@@ -34,6 +34,7 @@
 // four SIMDs read).  The exact mode needs 248 separately rounded fp32 operations per pixel (112 Horner, 16 weight products, 96 tap
 // multiply / adds, 16 den adds, 8 selects) = 128 packed instructions = ~590 cycles per 64 pixels before any overhead.
 #include "vs_kernels.hpp"
+#include "vs_warp_table.hpp"
 #include <algorithm>
 #include <cmath>
 #include "vs_device.hpp"
@@ -508,8 +509,9 @@ template <typename T, int MODE, int BORDER, int SHAPE = 0>
 __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : SHAPE == 1 ? 6 : FAST_MINWAVES) : (MODE == 1 ? 8 : EXACT_MINWAVES)) void vs_k_bgr_warp_c3(
     const T* __restrict__ src, int w, int h, int src_stride, const float4* __restrict__ params, T* __restrict__ dst,
     int dst_stride, size_t src_fs, size_t dst_fs, int tiles_x, uint32_t tiles_x_magic, int tiles_per_frame, int chunk,
-    float maxv, vsk::Roi roi, const float4* __restrict__ extents) {
+    float maxv, vsk::Roi roi, const float4* __restrict__ extents, const int4* __restrict__ tab) {
     constexpr bool RAWTILE = MODE == 1;                                  // bilinear: the tile holds source bytes / words, not floats (both depths)
+    constexpr bool TAB = MODE == 2 || MODE == 3;                         // the forms that read the launch's tables (vs_k_warp_c3_tables) when they are passed
     constexpr int PXD = sizeof(T) == 1 ? 1 : 2;                          // ... dwords per staged pixel
     // this kernel's tile height and what follows from it (the namespace-scope values are those of the 16-row kernels)
     constexpr int WT_H = tile_h_of((int)sizeof(T) * 8, MODE), RPW = WT_H / 4, WS_H = WT_H + (RAWTILE ? 8 : (SHAPE ? 4 : WS_EXTRA));
@@ -534,8 +536,17 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     const float A1 = 1.0f + P.x, B = P.y, TX = P.z, TY = P.w;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool src_aligned = ((((uintptr_t)src) | (uintptr_t)((size_t)src_stride * sizeof(T))) & 3) == 0;   // uniform
+    // What is the same in all 64 lanes costs a vector instruction all the same (no scalar float unit), so the float-tile Lanczos2 forms read the
+    // tile's window and their rows' position terms from the launch's tables (vs_k_warp_c3_tables, one thread per entry in front of this launch,
+    // the expressions below unchanged) with scalar loads: per frame tiles_per_frame entries {sx_lo, sy_lo, rows | groups << 16, fits | interior << 1},
+    // then {fl(B * fy), fl(A1 * fy)} per output row, the run padded to whole 4-row blocks.  tab == nullptr: everything in here, as before.
+    const bool tabled = TAB && tab != nullptr;                                             // (uniform)
+    const int tab_rows = (roi.h + 3) & ~3;
+    const int4* __restrict__ const tabf = tab + (size_t)frame * (size_t)(tiles_per_frame + (tab_rows >> 1));
     float4 E = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (extents != nullptr) E = extents[frame];
+    if (extents != nullptr && !tabled) E = extents[frame];
+    static_assert(!TAB || RPW == RB, "the tabled forms: a wave's rows are one block, one aligned 32-byte run of the row table");
+    float4 rterm[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};    // (tabled) {B fy, A1 fy} of this wave's four rows, loaded in front of the fill
 
     // everything about a tile that the fill and the sampler blocks need; all of it wave-uniform
     struct Geom { int x0, y0, sx_lo, sy_lo, rows, groups; bool fits, interior; };
@@ -545,6 +556,10 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     // output pixel (x, y) of the window is pixel (x + roi.x, y + roi.y) of the full frame: the sampling position is
     // computed from the full-frame coordinate, so a window equals the same rows / columns cut out of the whole warp
     const int x0 = txi * WT_W, y0 = tyi * WT_H;
+    if (tabled) {                                           // (uniform) one scalar load
+        const int4 e = tabf[tl];
+        return Geom{x0, y0, e.x, e.y, e.z & 0xffff, e.z >> 16, (e.w & 1) != 0, (e.w & 2) != 0};
+    }
     const int x1 = min(x0 + WT_W, roi.w) - 1, y1 = min(y0 + WT_H, roi.h) - 1;
 
     // source footprint of the tile.  Wx = fl(fl(A1*x) - fl(B*y)) + TX is monotone in x and in y (rounding is monotone), so its
@@ -791,20 +806,38 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     // cannot feed the very next VALU instruction without a wait state on gfx950, and the other row's operation fills it
     f2 fr_all[RB];
     lds_f4 t_all[RB];
+    // (the whole tap window of the pixel -- 4 x 4 staged pixels from boff, 2 x 2 for the bilinear mode -- lies inside the tile)
+    auto place = [&](int k, float Wx, float Wy) {
+        const float flx = floorf(Wx), fly = floorf(Wy);
+        fr_all[k] = f2{Wx - flx, Wy - fly};
+        const int boff = RAWTILE ? VS_DEBUG_CLAMP_BYTES((int)__builtin_fmaf(fly, 4.0f * PXD * WS_RS8, __builtin_fmaf(flx, 4.0f * PXD, c0)), 4 * PXD * (WS_H * WS_RS8 - (WS_RS8 + 1)), 205)
+                                : VS_DEBUG_CLAMP_BYTES((int)__builtin_fmaf(fly, 16.0f * KRS, __builtin_fmaf(flx, 16.0f, c0)),
+                                                       16 * (WS_H * KRS - (MODE == 1 ? KRS + 1 : 3 * KRS + 3)), 202);
+        t_all[k] = RAWTILE ? (lds_f4)((const __attribute__((address_space(3))) char*)tile_raw + boff)
+                          : (lds_f4)((const __attribute__((address_space(3))) char*)tile + boff);
+    };
+    if (tabled) {                                            // (uniform) the rows' products come from the table: the same two roundings per coordinate
+        const float rb[4] = {rterm[0].x, rterm[0].z, rterm[1].x, rterm[1].z}, ra[4] = {rterm[0].y, rterm[0].w, rterm[1].y, rterm[1].w};
+        float Wx[RB], Wy[RB];
+#pragma unroll
+        for (int k = 0; k < RB; k++) {
+            Wx[k] = (A1x - rb[k & 3]) + TX;
+            Wy[k] = (Bx + ra[k & 3]) + TY;
+        }
+        // the positions are final in this branch: without the pin the compiler sinks the subtractions and adds below the join and hands them
+        // the row terms through eight vector moves
+#pragma unroll
+        for (int k = 0; k < RB; k++) asm volatile("" : "+v"(Wx[k]), "+v"(Wy[k]));
+#pragma unroll
+        for (int k = 0; k < RB; k++) place(k, Wx[k], Wy[k]);
+    } else
 #pragma unroll
     for (int k = 0; k < RB; k++) {
         const int yq = min(yw + k, roi.h - 1);               // rows below the window repeat its last row (masked below)
         const float fy = (float)(yq + roi.y);
         const float Wx = A1x - B * fy + TX;                  // generators.cpp:141
         const float Wy = Bx + A1 * fy + TY;                  // generators.cpp:142
-        const float flx = floorf(Wx), fly = floorf(Wy);
-        fr_all[k] = f2{Wx - flx, Wy - fly};
-        // (the whole tap window of the pixel -- 4 x 4 staged pixels from boff, 2 x 2 for the bilinear mode -- lies inside the tile)
-        const int boff = RAWTILE ? VS_DEBUG_CLAMP_BYTES((int)__builtin_fmaf(fly, 4.0f * PXD * WS_RS8, __builtin_fmaf(flx, 4.0f * PXD, c0)), 4 * PXD * (WS_H * WS_RS8 - (WS_RS8 + 1)), 205)
-                                : VS_DEBUG_CLAMP_BYTES((int)__builtin_fmaf(fly, 16.0f * KRS, __builtin_fmaf(flx, 16.0f, c0)),
-                                                       16 * (WS_H * KRS - (MODE == 1 ? KRS + 1 : 3 * KRS + 3)), 202);
-        t_all[k] = RAWTILE ? (lds_f4)((const __attribute__((address_space(3))) char*)tile_raw + boff)
-                          : (lds_f4)((const __attribute__((address_space(3))) char*)tile + boff);
+        place(k, Wx, Wy);
     }
     if (MODE == 2) {
         fast_rows_pipelined<RB, COMPACT ? PIPE_AHEAD_COMPACT : PIPE_AHEAD, KRS>(t_all, fr_all, maxv, num, o, all_ok);
@@ -899,9 +932,55 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
 
     // (one tile per workgroup; geom / fill / sample_tile stay lambdas: written out inline, the same code compiles to different machine code)
     const Geom g = geom(tl);
+    if (tabled) {                                            // (waves below the window's last row leave without sampling: any block of the run serves them)
+        const float4* __restrict__ const rp = (const float4*)(tabf + tiles_per_frame) + (min(g.y0 + wv * RPW, tab_rows - RB) >> 1);
+        rterm[0] = rp[0];
+        rterm[1] = rp[1];
+    }
     if (g.fits) fill(g);
     __syncthreads();
     sample_tile(g);
+}
+
+// The tables of a float-tile Lanczos2 launch (see the kernel's prologue): per frame tiles_per_frame 16-byte tile entries, then tab_rows
+// (= the window's rows rounded up to whole 4-row blocks) pairs {fl(B * fy), fl(A1 * fy)}; rows beyond the window repeat its last row, as the
+// sampler's own clamp does.  One thread per entry, each THE expressions of the kernel's geom() on the extents path (ws_h / kg: the staged rows
+// and column groups of the instantiation that will be launched) and of its sampler block, in the same -ffp-contract=off build: the same
+// IEEE operations on the same operands, formed once instead of in every wave (tile entries) / in every lane (row terms).
+__global__ __launch_bounds__(256) void vs_k_warp_c3_tables(const float4* __restrict__ params, const float4* __restrict__ extents, int4* __restrict__ tab,
+                                                           int tiles_x, int tiles_per_frame, int ws_h, int kg, vsk::Roi roi, int w, int h,
+                                                           unsigned long long src_addr, unsigned long long src_fs_bytes, unsigned long long src_stride_bytes) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x), frame = blockIdx.y;
+    const int tab_rows = (roi.h + 3) & ~3;
+    int4* const tabf = tab + (size_t)frame * (size_t)(tiles_per_frame + (tab_rows >> 1));
+    const float4 P = params[frame], E = extents[frame];
+    const float A1 = 1.0f + P.x, B = P.y, TX = P.z, TY = P.w;
+    if (i < tiles_per_frame) {
+        const int tyi = i / tiles_x, txi = i - tyi * tiles_x;
+        const int x0 = txi * WT_W, y0 = tyi * WT_H;
+        const float fx0 = (float)(x0 + roi.x), fy0 = (float)(y0 + roi.y);
+        const float Wx00 = A1 * fx0 - B * fy0 + TX, Wy00 = B * fx0 + A1 * fy0 + TY;
+        const float mnx = Wx00 + E.x, mxx = Wx00 + E.y, mny = Wy00 + E.z, mxy = Wy00 + E.w;
+        bool fits = fmaxf(fmaxf(fabsf(mnx), fabsf(mxx)), fmaxf(fabsf(mny), fabsf(mxy))) < 1.0e6f;
+        int sx_lo = 0, sy_lo = 0, rows = 0, groups = 0;
+        if (fits) {
+            sx_lo = ((int)floorf(mnx) - 1) & ~3;
+            const int sx_hi = (int)floorf(mxx) + 2;
+            sy_lo = (int)floorf(mny) - 1;
+            const int sy_hi = (int)floorf(mxy) + 2;
+            rows = sy_hi - sy_lo + 1;
+            groups = (sx_hi - sx_lo + 4) >> 2;
+            fits = groups <= kg && rows <= ws_h;
+        }
+        const bool src_aligned = (((src_addr + (unsigned long long)frame * src_fs_bytes) | src_stride_bytes) & 3) == 0;
+        const bool interior = fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h;
+        // (a tile that does not fit is sampled per pixel and reads none of the four numbers)
+        tabf[i] = fits ? int4{sx_lo, sy_lo, rows | (groups << 16), 1 | (interior ? 2 : 0)} : int4{0, 0, 0, 0};
+    }
+    if (i < tab_rows) {
+        const float fy = (float)(min(i, roi.h - 1) + roi.y);
+        ((float2*)(tabf + tiles_per_frame))[i] = float2{B * fy, A1 * fy};
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -1473,7 +1552,7 @@ VS_BOUNDS_TU(vs_bounds_fetch_warp)
 namespace vsk {
 
 template <typename T>
-static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const float4* params_dev, const float4* extents_dev, int mode,
+static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const float4* params_dev, const float4* extents_dev, void* tab_dev, int mode,
                             int border, T* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, float maxv, Roi roi, int compact, hipStream_t s) {
     const int th = tile_h_of((int)sizeof(T) * 8, mode);
     const int tiles_x = (roi.w + WT_W - 1) / WT_W, tiles_y = (roi.h + th - 1) / th;
@@ -1490,14 +1569,25 @@ static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const fl
         const float4* pp = params_dev + f0;
         const float4* ep = extents_dev ? extents_dev + f0 : nullptr;
         dim3 grid((unsigned)(chunk * 8), (unsigned)nf), block(256);
+        // the float-tile Lanczos2 forms' tables (tile windows for the shape launched below, row terms): one small launch in front of the warp's
+        const int4* tp = nullptr;
+        if (tab_dev && ep && (mode == 2 || mode == 3)) {
+            const size_t per16 = bgr_warp_c3_table_bytes((int)sizeof(T) * 8, mode, roi) / 16;
+            int4* const tw = (int4*)tab_dev + (size_t)f0 * per16;
+            const int tab_rows = (roi.h + 3) & ~3, entries = std::max((int)tpf, tab_rows);
+            hipLaunchKernelGGL(vs_k_warp_c3_tables, dim3((unsigned)((entries + 255) / 256), (unsigned)nf), dim3(256), 0, s, pp, ep, tw, tiles_x, (int)tpf,
+                               WT_H + (compact ? 4 : WS_EXTRA), compact == 2 && mode == 3 ? 18 : WS_W / 4, roi, w, h, (unsigned long long)(uintptr_t)sp,
+                               (unsigned long long)(src_fs * sizeof(T)), (unsigned long long)((size_t)src_stride * sizeof(T)));
+            tp = tw;
+        }
 #define VS_LAUNCH(M, Bd) \
         hipLaunchKernelGGL((vs_k_bgr_warp_c3<T, M, Bd>), grid, block, 0, s, sp, w, h, src_stride, pp, dp, dst_stride, src_fs, dst_fs, \
-                           tiles_x, magic, (int)tpf, chunk, maxv, roi, ep)
+                           tiles_x, magic, (int)tpf, chunk, maxv, roi, ep, tp)
         if (mode == 0 && border == 0) VS_LAUNCH(0, 0);
         else if (mode == 0) VS_LAUNCH(0, 1);
 #define VS_LAUNCH_C(M, Bd, Sh) \
         hipLaunchKernelGGL((vs_k_bgr_warp_c3<T, M, Bd, Sh>), grid, block, 0, s, sp, w, h, src_stride, pp, dp, dst_stride, src_fs, dst_fs, \
-                           tiles_x, magic, (int)tpf, chunk, maxv, roi, ep)
+                           tiles_x, magic, (int)tpf, chunk, maxv, roi, ep, tp)
         else if (mode == 2 && compact && border == 0) VS_LAUNCH_C(2, 0, 1);
         else if (mode == 2 && compact) VS_LAUNCH_C(2, 1, 1);
         else if (mode == 3 && compact == 2 && border == 0) VS_LAUNCH_C(3, 0, 2);
@@ -1516,16 +1606,16 @@ static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const fl
     return hipGetLastError();
 }
 
-hipError_t bgr_warp_c3(const void* src, int w, int h, int src_stride, int bits, const float4* params_dev, const float4* extents_dev,
+hipError_t bgr_warp_c3(const void* src, int w, int h, int src_stride, int bits, const float4* params_dev, const float4* extents_dev, void* tab_dev,
                        int mode, int border, int max_value, void* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, Roi roi,
                        int compact, hipStream_t s) {
     static const int compact_env = []() { const char* e = getenv("VS_WARP_COMPACT"); return e ? atoi(e) : -1; }();       // (A/B switch: 0 never, 1 the six-wave shape at most, 2 / unset: whatever the extents allow)
     if (extents_dev == nullptr || !(mode == 2 || mode == 3)) compact = 0;
     if (compact_env >= 0) compact = std::min(compact, compact_env);
     if (bits == 8)
-        return launch_c3<uint8_t>((const uint8_t*)src, w, h, src_stride, params_dev, extents_dev, mode, border, (uint8_t*)dst, dst_stride,
+        return launch_c3<uint8_t>((const uint8_t*)src, w, h, src_stride, params_dev, extents_dev, tab_dev, mode, border, (uint8_t*)dst, dst_stride,
                                   n_frames, src_fs, dst_fs, (float)max_value, roi, compact, s);
-    return launch_c3<uint16_t>((const uint16_t*)src, w, h, src_stride, params_dev, extents_dev, mode, border, (uint16_t*)dst, dst_stride,
+    return launch_c3<uint16_t>((const uint16_t*)src, w, h, src_stride, params_dev, extents_dev, tab_dev, mode, border, (uint16_t*)dst, dst_stride,
                                n_frames, src_fs, dst_fs, (float)max_value, roi, compact, s);
 }
 
@@ -1538,6 +1628,14 @@ int bgr_warp_c3_compact_shape(const float* E4, int n_frames) {
         if (!((double)E4[4 * f + 1] - (double)E4[4 * f + 0] < 64.99)) shape = 1;
     }
     return shape;
+}
+
+// bytes of table per frame for (bits, mode, window): what bgr_warp_c3's caller reserves (n_frames times) for `tab_dev`; 0: the mode reads no table.
+// (the layout: vs_warp_table.hpp)
+static_assert(kWarpTabTileW == WT_W && kWarpTabTileH == tile_h_of(8, 2) && kWarpTabTileH == tile_h_of(16, 3) && kWarpTabRowBlock == RB, "the table's tiles and row blocks are the kernel's");
+size_t bgr_warp_c3_table_bytes(int bits, int mode, Roi roi) {
+    if (!(mode == 2 || mode == 3) || !(bits == 8 || bits == 16)) return 0;
+    return warp_c3_table_layout(roi.w, roi.h).bytes;
 }
 
 // ints of table per frame for (bits, window): what bgr_warp_cv_c3's caller reserves (n_frames times) for `tab_dev`
