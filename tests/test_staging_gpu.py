@@ -1,4 +1,4 @@
-"""The staging pool behind the VS_MEM_HOST form of the kernel-level calls (vs_capi.hip, round 6): device block + pinned host mirror, leased per argument,
+"""The staging pool behind the VS_MEM_HOST form of the kernel-level calls (vs_runtime.hip, round 6): device block + pinned host mirror, leased per argument,
 one dense copy each way, rows scattered by the CPU.  (i) every allocation of a first call can fail and the pool stays usable: the call reports the
 failure, the next call is right; (ii) threads lease and release concurrently with arguments of many sizes and every result equals the CPU restatement;
 (iii) a pitched output leaves the caller's bytes between the rows alone for every alignment of the destination."""

@@ -81,7 +81,7 @@ struct DevBuf {
 };
 
 // Staging for the host-memory (VS_MEM_HOST) form of the kernel-level calls.  A block = device memory + a PINNED host mirror of the same size,
-// leased from a process-wide pool (vs_capi.hip): no hipMalloc / hipFree per call, and the HIP runtime never sees the caller's pageable memory --
+// leased from a process-wide pool (vs_runtime.hip): no hipMalloc / hipFree per call, and the HIP runtime never sees the caller's pageable memory --
 // inputs are copied into the mirror by the CPU and travel as one dense pinned H2D copy; outputs come back as one dense D2H copy into the mirror
 // and the CPU scatters the rows into the caller's buffer after the stream has been synchronised.  (Until round 5 outputs went back with one
 // hipMemcpy2DAsync per frame straight into pageable, possibly 2-byte-aligned caller memory: profiles/r06_flake.md.)
