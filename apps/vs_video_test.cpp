@@ -1,5 +1,5 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear | --lanczos2] [--444]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--bilinear | --lanczos2] [--444]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
@@ -8,7 +8,8 @@
 // the sharper ones among the next N input frames before it is warped (vs_stabilizer_set_deblur).  --denoise N: every frame is averaged
 // with what the next N input frames show at the same scene point (vs_stabilizer_set_denoise; --denoise-strength T: 1 .. 255, default 24).  --deflicker N: every
 // output frame's exposure is pulled to the mean exposure of itself and the next N input frames (vs_stabilizer_set_deflicker; --deflicker-step S: the lattice
-// step of the exposure statistics, 1 .. 64, default 4).  Frames go to the GPU in
+// step of the exposure statistics, 1 .. 64, default 4).  --rolling-shutter R: every frame is corrected for a rolling shutter whose readout takes the
+// share R (-1 .. 1, negative: bottom-up) of the frame period, by the motion to the following frame (vs_stabilizer_set_rolling_shutter).  Frames go to the GPU in
 // chunks of N (default 64) and through vs_stabilizer_process_batch, which is defined as N successive processFrame calls.
 #include <chrono>
 #include <filesystem>
@@ -19,7 +20,7 @@ namespace fs = std::filesystem;
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step, bool inpaint) {
+                         int deflicker_step, bool inpaint, double rolling) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -80,6 +81,14 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
             return false;
         }
     }
+    if (rolling != 0.0) {
+        const vs_rolling_params rp{rolling};
+        if (vs_stabilizer_set_rolling_shutter(stab, &rp) != VS_OK) {
+            std::cerr << "Error: vs_stabilizer_set_rolling_shutter: " << vs_last_error() << std::endl;
+            vs_stabilizer_destroy(stab);
+            return false;
+        }
+    }
 
     long frame_count = 0, written = 0, next_report = 100;
     const auto t0 = std::chrono::steady_clock::now();
@@ -116,6 +125,7 @@ int main(int argc, char** argv) {
     bool bilinear = false, lanczos2 = false, force444 = false;
     vs_fill_blend_params blend{0, 0};
     bool inpaint = false;
+    double rolling = 0.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--chunk" && i + 1 < argc) chunk = std::max(1, std::atoi(argv[++i]));
@@ -130,12 +140,13 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-strength" && i + 1 < argc) denoise_strength = std::atoi(argv[++i]);
         else if (a == "--deflicker" && i + 1 < argc) deflicker = std::atoi(argv[++i]);
         else if (a == "--deflicker-step" && i + 1 < argc) deflicker_step = std::atoi(argv[++i]);
+        else if (a == "--rolling-shutter" && i + 1 < argc) rolling = std::atof(argv[++i]);
         else if (a == "--bilinear") bilinear = true;
         else if (a == "--lanczos2") lanczos2 = true;
         else if (a == "--444") force444 = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -161,7 +172,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint, rolling)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

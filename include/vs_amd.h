@@ -351,6 +351,74 @@ int vs_bgr_denoise_batch(const void* src, size_t src_frame_stride, int n_src, in
                          int n_out, int n_cand, const int32_t* cand_frame, const vs_transform* cand_t,
                          const vs_denoise_params* params /* NULL = defaults */,
                          void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* ROLLING-SHUTTER CORRECTION: a rolling-shutter sensor exposes a frame row by row, so camera motion shears and bends the frame from inside.
+ * Every row is resampled to what a global shutter would have shown at the middle row's time, from the motion to the frame that follows.
+ * THE RULE.
+ * Interleaved BGR, every `VS_FMT_BGR*`, frames up to 32767 x 32767. Beyond that the call returns `VS_ERR_UNSUPPORTED`, as the denoise does.
+ *
+ * Inputs
+ *
+ * - Output frame `o` has exactly two candidate entries `(cand_frame, cand_t)`, laid out as in `vs_bgr_denoise_batch` with `n_cand == 2`.
+ * - Entry 0 is the frame to correct. Its transform is ignored.
+ * - Entry 1 carries the motion to the frame that follows it, in `VS_WARP_BILINEAR_CV`'s forward convention.
+ * - For entry 1 only the sign of `cand_frame` is looked at. That frame's pixels are never read.
+ * - A negative index means "no motion known".
+ * - `M[0..5] = vs_cv_inverse_matrix(cand_t[1], w, h)` is where pixel `(x, y)` of the frame lies in the following frame.
+ * - `readout` (`rho`) is the share of the frame period that the sensor takes to scan the frame from row 0 to row `h - 1`. Its range is
+ *   -1 .. 1; negative values mean bottom-up scanning. NaN or a value outside the range is `VS_ERR_ARG`.
+ *
+ * Row time
+ *
+ * `tau(y) = rho * ((double)(2 * y - (h - 1)) / (double)(2 * h))`.
+ *
+ * It is zero at the frame's middle. Every product and sum rounds once, in the order written: the build's `-ffp-contract=off`, no explicit FMA.
+ *
+ * Row matrix (fp64, same order)
+ *
+ * - `r0 = 1 + tau * (M0 - 1)`, `r1 = tau * M1`, `r2 = tau * M2`
+ * - `r3 = tau * M3`, `r4 = 1 + tau * (M4 - 1)`, `r5 = tau * M5`
+ *
+ * The row matrix is again of similarity form. The scene point that a global shutter would have shown at `(x, y)` sits in the raw frame at
+ * `r(y) * (x, y, 1)`. This is first order in the intra-frame motion.
+ *
+ * Position
+ *
+ * The position rule is `VS_WARP_BILINEAR_CV`'s own int32 rule, with the row's matrix in place of the frame's.
+ *
+ * - `X = (cv_row_origin(r1, r2, y) + cv_delta(r0, x)) >> 5`, `Y` likewise from `r4, r5, r3`. This is `cv_pos` of `vs_device.hpp`.
+ * - It keeps that rule's saturating `cvRound`, NaN -> 0, wrapping sums and arithmetic shifts.
+ * - The position has 5 fraction bits.
+ *
+ * Sample
+ *
+ * The blend is `VS_WARP_BILINEAR_CV`'s blend of the four taps at `(X >> 5, Y >> 5)` with fractions `X & 31`, `Y & 31`.
+ *
+ * - 8-bit containers: integer weights, `(sum + 512) >> 10`.
+ * - 16-bit containers: weights `a * b / 1024` in fp32, `rintf`, saturated to `vs_format_max_value(format)`.
+ * - Border: each tap's column is clamped to `0 .. w - 1` and its row to `0 .. h - 1`. The weights are unchanged.
+ * - No border colour can enter a corrected frame, so `warp_border` plays no part.
+ *
+ * Hence
+ *
+ * - (a) No motion: the frame comes back bit for bit, as a dword copy where the rows allow it.
+ * - (b) `rho == 0`: bit for bit.
+ * - (c) A motion of `{0, 0, 0, 0}`: bit for bit.
+ * - (d) For odd `h`, row `(h - 1) / 2` comes back bit for bit whatever the motion.
+ * - (e) Every output sample lies between the minimum and the maximum of the frame's samples in that channel.
+ * - (f) The rule defines every sample for every input the call accepts: NaN, singular and saturating matrices included.
+ * ((b) - (d): for samples up to the format's maximum and a finite motion -- the blend at zero fraction is the sample, which a 16-bit container
+ * then saturates, and tau * NaN is NaN whatever tau.)
+ * The default readout, 0.5, is a PLACEHOLDER in the middle of what phone and action-camera sensors do, not a measured sensor value: take the
+ * figure from the sensor's data sheet (line time x rows / frame period) or calibrate it. */
+typedef struct vs_rolling_params { double readout; } vs_rolling_params;
+void vs_rolling_params_default(vs_rolling_params* p);   /* 0.5: a placeholder, see above */
+/* cand_frame and cand_t are host arrays of n_out * 2 entries; dst holds full w x h frames.  VS_MEM_DEVICE only enqueues.  The entries
+ * reach the device in the denoise's groups (2048 frames); a destination whose rows do not all start on dwords, or a width that is no
+ * multiple of 4, takes the one-pixel-per-lane kernel, with the same result. */
+int vs_bgr_rolling_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride, int format,
+                         int n_out, const int32_t* cand_frame, const vs_transform* cand_t,
+                         const vs_rolling_params* params /* NULL = defaults */,
+                         void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* DEFLICKER: a frame's exposure is pulled to the average exposure of a window of frames, the exposure ratio of two frames being measured
  * at the same scene points through their measured motions (a pan changes a whole-frame sum because the content changes).  Interleaved
  * BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as in the fill); s = bits - 8.  The rule:
@@ -672,6 +740,17 @@ int   vs_stabilizer_get_deblur(const vs_stabilizer* s);
  * handle's lag or for a strength outside 1 .. 255.  get returns `ahead`. */
 int   vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params);
 int   vs_stabilizer_get_denoise(const vs_stabilizer* s);
+/* Rolling-shutter correction (the rule: see vs_bgr_rolling_batch).  NULL or readout == 0 (default): off -- the handle as it is without this
+ * call, launch for launch, and no scratch.  Otherwise every frame is corrected, before it is warped, by the motion the aligner measured to
+ * the input frame that follows it (candidate 1's transform of the look-ahead lists, inverse(T_{k+1})): no latency, no second alignment, no
+ * host synchronisation, one scratch frame per output frame of the call.  A failed alignment of the following frame, or lag == 0, means no
+ * motion: the frame passes bit for bit.  Order: deblur, denoise, rolling shutter, warp, border fill, inpaint, gain pass.  The frame
+ * corrected is the one deblur and denoise leave; the warp (every warp_mode), the fill's candidate 0 and the coverage index take the
+ * corrected frame; the fill's other candidates and the deblur's, denoise's and deflicker's samples stay the raw input frames.  The aligner
+ * always sees the original frames: transforms, vs_stabilizer_state and has_output do not depend on this setting.  Takes effect with the
+ * next output frame.  VS_ERR_ARG for a readout that is NaN or outside -1 .. 1.  get: the parameters in force (readout 0: off). */
+int   vs_stabilizer_set_rolling_shutter(vs_stabilizer* s, const vs_rolling_params* params);
+int   vs_stabilizer_get_rolling_shutter(const vs_stabilizer* s, vs_rolling_params* params);
 /* Deflicker (the rule: see vs_bgr_exposure_stats_batch).  0 (default): off -- the handle as it is without this call, launch for launch.
  * 1 .. lag: every output frame's exposure is pulled to the average exposure of itself and the next `ahead` input frames; the exposure
  * ratios are measured on the device at the same scene points through the measured motions (candidate j's transform is

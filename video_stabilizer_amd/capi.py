@@ -86,6 +86,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("strength", C.c_int)]
 
 
+class RollingParams(C.Structure):
+    """vs_rolling_params: readout, the share of the frame period the sensor takes from row 0 to row h - 1, -1 .. 1"""
+    _fields_ = [("readout", C.c_double)]
+
+
 class DeflickerParams(C.Structure):
     """vs_deflicker_params: the lattice step of the exposure statistics, 1 .. 64"""
     _fields_ = [("step", C.c_int)]
@@ -167,6 +172,9 @@ SIGNATURES = {
     "vs_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
     "vs_bgr_denoise_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DenoiseParams),
                                     _vp, _sz, _i32, _i32, _vp]),
+    "vs_rolling_params_default": (None, [C.POINTER(RollingParams)]),
+    "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(RollingParams),
+                                    _vp, _sz, _i32, _i32, _vp]),
     "vs_deflicker_params_default": (None, [C.POINTER(DeflickerParams)]),
     "vs_bgr_exposure_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeflickerParams),
                                            _vp, _i32, _vp]),
@@ -195,6 +203,8 @@ SIGNATURES = {
     "vs_stabilizer_get_deblur": (_i32, [_vp]),
     "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, C.POINTER(DenoiseParams)]),
     "vs_stabilizer_get_denoise": (_i32, [_vp]),
+    "vs_stabilizer_set_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
+    "vs_stabilizer_get_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
     "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
     "vs_stabilizer_get_deflicker": (_i32, [_vp]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
@@ -789,6 +799,43 @@ def denoise_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_fra
                                       C.c_void_p(stream) if stream else None))
 
 
+def rolling_params(**kw):
+    p = RollingParams()
+    lib().vs_rolling_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def rolling_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """rolling-shutter correction (include/vs_amd.h: vs_bgr_rolling_batch).  src (n_src,h,w,3) numpy; cand_frame (n_out, 2) ints: the frame,
+    then any index >= 0 (a motion is known) or a negative one (none); cand_t: n_out lists of 2 Transforms, the second the motion to the
+    following frame.  -> (n_out, h, w, 3).  src_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the
+    destination's padding is filled with first; the padded buffer is returned as well"""
+    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    assert n_cand == 2
+    n_src, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ds = w * c if dst_stride is None else dst_stride
+    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_rolling_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                      C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
+    return (res, out) if guard is not None else res
+
+
+def rolling_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape
+    assert n_cand == 2
+    flat = [t for row in cand_t for t in row]
+    arr = (Transform * len(flat))(*flat)
+    _check(lib().vs_bgr_rolling_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                      C.byref(params) if params is not None else None, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
+                                      C.c_void_p(stream) if stream else None))
+
+
 def deflicker_params(**kw):
     p = DeflickerParams()
     lib().vs_deflicker_params_default(C.byref(p))
@@ -1100,7 +1147,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, inpaint=0, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1119,6 +1166,19 @@ class Stabilizer:
             self.set_deflicker(deflicker, deflicker_params)
         if inpaint:
             self.set_inpaint(inpaint)
+        if rolling_shutter:
+            self.set_rolling_shutter(rolling_shutter)
+
+    def set_rolling_shutter(self, readout):
+        """None or 0: off; else every frame is corrected for a rolling shutter of that readout share (-1 .. 1) by the motion to the next input
+        frame, before it is warped"""
+        p = RollingParams(float(readout)) if readout is not None else None
+        _check(lib().vs_stabilizer_set_rolling_shutter(self.h, C.byref(p) if p is not None else None))
+
+    def get_rolling_shutter(self):
+        p = RollingParams()
+        _check(lib().vs_stabilizer_get_rolling_shutter(self.h, C.byref(p)))
+        return p.readout
 
     def set_inpaint(self, on=1):
         """0: off; 1: what neither the frame nor a fill candidate covers in the output window is inpainted (VS_WARP_BILINEAR_CV handles)"""

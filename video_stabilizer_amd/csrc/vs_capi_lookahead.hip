@@ -1,5 +1,5 @@
 // vs_capi_lookahead.hip -- the look-ahead passes of the C ABI (include/vs_amd.h) next to the border fill (vs_capi_warp.hip): channel sums,
-// sharpness and deblur, denoise, exposure statistics / gains / gain, coverage index and inpaint.  Each pass that takes candidate lists is a
+// sharpness and deblur, denoise, rolling-shutter correction, exposure statistics / gains / gain, coverage index and inpaint.  Each pass that takes candidate lists is a
 // *_ptrs function in vsi (device-resident frames, enqueue only: the engine's form) and an index-based *_batch wrapper over it; what brings a
 // list to a kernel is cand_groups (vs_capi.hpp).
 #include "vs_capi.hpp"
@@ -42,6 +42,11 @@ int deblur_params_ok(const vs_deblur_params* params, vs_deblur_params* p) {
 int denoise_params_ok(const vs_denoise_params* params, vs_denoise_params* p) {
     if (params) *p = *params; else vs_denoise_params_default(p);
     VS_ARG(p->strength >= 1 && p->strength <= 255);
+    return VS_OK;
+}
+int rolling_params_ok(const vs_rolling_params* params, vs_rolling_params* p) {
+    if (params) *p = *params; else vs_rolling_params_default(p);
+    VS_ARG(p->readout >= -1.0 && p->readout <= 1.0);                 // (a NaN fails both)
     return VS_OK;
 }
 int deflicker_params_ok(const vs_deflicker_params* params, vs_deflicker_params* p) {
@@ -119,6 +124,29 @@ int vsi::bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, i
         [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
             VS_HIP(vsk::bgr_denoise(cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format), p.strength,
                                     (char*)dst + (size_t)f0 * dst_fs * esz, dst_stride, nf, dst_fs, targets_aligned(cand_src, f0, nf, n_cand), s));
+            return VS_OK;
+        });
+}
+
+// ---- rolling-shutter correction (vs_rolling.hip) ----
+// The rolling-shutter pass on device-resident frames (vs_internal.hpp); two entries per frame, in the denoise's groups.  Entry 1's frame pointer
+// only says whether a motion is known: the kernel never follows it.
+int vsi::bgr_rolling_ptrs(int n_out, int w, int h, int src_stride, int format, const void* const* cand_src, const vs_transform* cand_t,
+                          const vs_rolling_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+    const int bits = vs_format_bits(format);
+    const plan::Batch out{dst, dst_fs, n_out, w, h, dst_stride, 3, bits};
+    VS_TRY(pass_args_ok(__func__, "rolling shutter", kCvShort, w, h, format, 2, cand_src && cand_t && dst, n_out, src_stride, &out));
+    vs_rolling_params p;
+    VS_TRY(rolling_params_ok(params, &p));
+    ParamRing* ring = param_ring();
+    if (!ring) return no_ring();
+    const size_t esz = plan::elem_size(bits);
+    std::vector<vsk::FillCand> rc;
+    return cand_groups(ring, 0, n_out, plan::frames_per_group_entries(2, 4), 2, cand_src, cand_t, w, h, false, true, s, rc,
+        FrameIsEntry0{cand_src, 2, __func__}, no_side_word,
+        [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
+            VS_HIP(vsk::bgr_rolling(cdev, w, h, src_stride, (int)esz * 8, vs_format_max_value(format), p.readout, (char*)dst + (size_t)f0 * dst_fs * esz,
+                                    dst_stride, nf, dst_fs, s));
             return VS_OK;
         });
 }
@@ -247,6 +275,31 @@ int vs_bgr_denoise_batch(const void* src, size_t src_fs, int n_src, int w, int h
     VS_TRY(stage_out(o, out, mem, out.esz()));
     const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * in.esz());
     VS_TRY(bgr_denoise_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
+    return finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+int vs_bgr_rolling_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, int n_out, const int32_t* cand_frame,
+                         const vs_transform* cand_t, const vs_rolling_params* params, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+    const int bits = vs_format_bits(format);
+    const plan::Batch in{src, src_fs, n_src, w, h, src_stride, 3, bits}, out{dst, dst_fs, n_out, w, h, dst_stride, 3, bits};
+    VS_TRY(pass_args_ok(__func__, "rolling shutter", kCvShort, w, h, format, 2, cand_frame && cand_t && dst, n_out, src_stride, &out));
+    // only the sign of entry 1's index is looked at: a live entry 1 stands for the frame itself, whose pointer is never followed
+    std::vector<int32_t> live((size_t)n_out * 2);
+    for (int o = 0; o < n_out; o++) {
+        live[2 * (size_t)o] = cand_frame[2 * (size_t)o];
+        live[2 * (size_t)o + 1] = cand_frame[2 * (size_t)o + 1] >= 0 ? cand_frame[2 * (size_t)o] : -1;
+    }
+    const plan::CandIndex idx{live.data(), n_out, 2};
+    VS_TRY(indexed_args_ok(__func__, in, idx, false));
+    vs_rolling_params p;
+    VS_TRY(rolling_params_ok(params, &p));
+    if (!device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    Staged a, o;
+    VS_TRY(stage_in(a, in, mem, s));
+    VS_TRY(stage_out(o, out, mem, out.esz()));
+    const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * in.esz());
+    VS_TRY(bgr_rolling_ptrs(n_out, w, h, src_stride, format, ptrs.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
     return finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 

@@ -86,6 +86,10 @@ void vs_deblur_params_default(vs_deblur_params* p) {
 void vs_denoise_params_default(vs_denoise_params* p) {
     p->strength = 24;
 }
+// vs_rolling.hip (DESIGN.md "Rolling-shutter correction": a placeholder in the middle of the usual range, not a measured sensor value)
+void vs_rolling_params_default(vs_rolling_params* p) {
+    p->readout = 0.5;
+}
 // vs_deflicker.hip (DESIGN.md "Deflicker": a lattice of every fourth pixel a side reads a quarter of the cache lines and leaves thousands of pairs)
 void vs_deflicker_params_default(vs_deflicker_params* p) {
     p->step = 4;

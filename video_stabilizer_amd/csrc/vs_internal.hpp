@@ -148,6 +148,13 @@ int bgr_deblur_ptrs(int n_out, int w, int h, int src_stride, int format, int n_c
 int bgr_denoise_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
                      const vs_denoise_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
 
+// The rolling-shutter pass (the rule: vs_rolling.hip) on device-resident frames; vs_bgr_rolling_batch is the index-based wrapper over it.  Output
+// frame o = the frame at cand_src[2 o] (any device pointer, w x h, rows of src_stride elements) corrected by the motion cand_t[2 o + 1] to the frame
+// that follows it; cand_src[2 o + 1] is only compared with null (null: no motion known, the frame is copied) and never followed.  dst: full frames.
+// Host arrays; enqueue only.
+int bgr_rolling_ptrs(int n_out, int w, int h, int src_stride, int format, const void* const* cand_src, const vs_transform* cand_t,
+                     const vs_rolling_params* params, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
+
 // The deflicker's statistics pass (the rule: vs_deflicker.hip) on device-resident frames; vs_bgr_exposure_stats_batch is the index-based wrapper
 // over it.  The pairs of output frame o: the frame at cand_src[o * n_cand] with its candidates c = 1 .. n_cand-1 (any device pointer, w x h, rows of
 // src_stride elements; null ends the list) under cand_t[o * n_cand + c].  stats: n_out x n_cand x 8 words of device memory, zeroed on `s` first.

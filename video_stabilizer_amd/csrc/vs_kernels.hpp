@@ -98,6 +98,11 @@ hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, in
 // every target frame starts on a dword.
 hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int strength, void* dst,
                        int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s);
+// Rolling-shutter correction (vs_rolling.hip: the rule and the kernel).  cands_dev = n_frames x 2 entries in device memory: entry 0 of a frame
+// is the frame to correct (its matrix is not read); entry 1 carries vs_cv_inverse_matrix of the motion to the following frame, and a null frame
+// there means "no motion known" (the frame is copied; a non-null one is never followed).  dst: full w x h frames.  readout: -1 .. 1.
+hipError_t bgr_rolling(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int max_value, double readout, void* dst, int dst_stride,
+                       int n_frames, size_t dst_fs, hipStream_t s);
 // Deflicker (vs_deflicker.hip: the rule and the kernels).  exposure_stats: cands_dev = n_frames x n_cand entries in device memory (entry 0 of a
 // frame is the target, a null frame ends the list); stats = n_frames x n_cand x 8 words in device memory, zeroed on `s` first.  exposure_gains:
 // gains[4 o + {0..2: G_c, 3: m}] from the statistics.  bgr_gain: frame i scaled by gains[4 i ..] (clamped to 16384 .. 65536); dst may be src.

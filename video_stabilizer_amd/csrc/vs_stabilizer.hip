@@ -1,5 +1,5 @@
 // vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
-// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_deflicker).
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_deflicker).
 //
 // Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
 // then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
@@ -42,6 +42,9 @@ struct vs_stabilizer {
     int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
     vs_denoise_params denoise_params{24};
     void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
+    // rolling-shutter correction (vs_rolling.hip)
+    vs_rolling_params rolling{0.0};   // vs_stabilizer_set_rolling_shutter: readout 0: off
+    void* rolling_buf = nullptr; size_t rolling_bytes = 0;   // the corrected frames of the current call: the source of its warps
     // deflicker (vs_deflicker.hip)
     int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
     vs_deflicker_params deflicker_params{4};
@@ -126,6 +129,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
     if (s->deblur_buf) (void)hipFree(s->deblur_buf);
     if (s->denoise_buf) (void)hipFree(s->denoise_buf);
+    if (s->rolling_buf) (void)hipFree(s->rolling_buf);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
@@ -232,6 +236,7 @@ struct Chunk {
     std::vector<Job> jobs;
     Ahead fill{}, db{}, dn{}, fk{};    // border fill (side, exposure match only: the channel sums, the ORIGINAL frames' throughout); deblur (side: the
                                        // sharpness); denoise; deflicker (candidate 0 stays the ORIGINAL frame whatever deblur and denoise do)
+    Ahead rs{};                        // rolling shutter: depth min(1, lag) -- the motion to the frame that follows (that frame's pixels are not read)
     uint32_t* fk_gains = nullptr;  // deflicker: four words per job, in flicker_buf
 
     // stabilizer.cpp:15: a private dense copy of every input frame, in device memory
@@ -328,6 +333,7 @@ struct Chunk {
         list(db, sharp_avail, none, nullptr, &Held::sharp);
         list(dn, avail, none, nullptr, nullptr);
         list(fk, avail, none, nullptr, nullptr);
+        list(rs, avail, none, nullptr, nullptr);
     }
     // The frame loop: every frame joins the queue, its measurement goes through the reference's bookkeeping (vs_stab_step.hpp), and the frame
     // that becomes due leaves the queue as a job with its candidate lists.
@@ -392,6 +398,12 @@ struct Chunk {
             VS_TRY(vsi::bgr_denoise_ptrs(nj, w, h, w * 3, c.format, 1 + dn.n, dn.src.data(), dn.t.data(), &s->denoise_params, s->denoise_buf,
                                          (size_t)w * h * 3, w * 3, ws));
             sources(s->denoise_buf);
+        }
+        if (rs.n > 0) {     // ... (deblurred, denoised) corrected for the rolling shutter into a scratch frame of its own, by the motion to the next input frame
+            VS_HIP(grow(&s->rolling_buf, &s->rolling_bytes, fbytes * jobs.size(), ws, true));
+            for (size_t j = 0; j < jobs.size(); j++) rs.src[j * 2] = jobs[j].src;
+            VS_TRY(vsi::bgr_rolling_ptrs(nj, w, h, w * 3, c.format, rs.src.data(), rs.t.data(), &s->rolling, s->rolling_buf, (size_t)w * h * 3, w * 3, ws));
+            sources(s->rolling_buf);
         }
         if (fk.n > 0) {
             // the exposure statistics of every due frame against the frames that follow it -- the original input frames on both sides -- and
@@ -553,6 +565,7 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
     Chunk k{s, c, std::max(slot_arg, 0), slot_arg >= 0, to_host, warps_apart, st, warps_apart ? s->warp_stream : st, crop, ow, oh};
     k.fill.n = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, lag) : 0;
     k.db.n = std::min(s->deblur, lag); k.dn.n = std::min(s->denoise, lag); k.fk.n = std::min(s->deflicker, lag);
+    k.rs.n = s->rolling.readout != 0.0 ? std::min(1, lag) : 0;
     k.blend_on = k.fill.n > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
     k.want_sums = k.fill.n > 0 && s->fill_blend.match != 0;
 
@@ -824,6 +837,18 @@ int vs_stabilizer_get_deflicker(const vs_stabilizer* s) try {
 int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
     VS_ARG(s);
     return s->denoise;
+} VS_CATCH_ALL
+int vs_stabilizer_set_rolling_shutter(vs_stabilizer* s, const vs_rolling_params* params) try {
+    VS_ARG(s);
+    const vs_rolling_params p = params ? *params : vs_rolling_params{0.0};
+    VS_ARG(p.readout >= -1.0 && p.readout <= 1.0);                   // (a NaN fails both)
+    s->rolling = p;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_rolling_shutter(const vs_stabilizer* s, vs_rolling_params* params) try {
+    VS_ARG(s && params);
+    *params = s->rolling;
+    return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);

@@ -20,6 +20,7 @@ struct VideoStabilizerParams {
     int deblur = 0;                       // a knob of this build: 1 .. lag = deblur every frame from the sharper ones among that many following frames (vs_stabilizer_set_deblur, default parameters)
     int denoise = 0;                      // a knob of this build: 1 .. lag = average every frame with what that many following frames show at the same scene point (vs_stabilizer_set_denoise, default parameters)
     int deflicker = 0;                    // a knob of this build: 1 .. lag = pull every frame's exposure to the mean exposure of itself and that many following frames (vs_stabilizer_set_deflicker, default parameters)
+    double rolling_shutter = 0.0;         // a knob of this build: the sensor's readout share of the frame period, -1 .. 1, 0 = off; every frame is corrected for its rolling shutter by the motion to the following frame (vs_stabilizer_set_rolling_shutter)
 };
 
 // stabilizer.hpp:32-56.  processFrame returns an empty vector until `lag` frames have arrived
@@ -58,6 +59,14 @@ public:
             vs_stabilizer_destroy(h_);
             throw std::runtime_error("vs_stabilizer_set_deflicker: " + why);
         }
+        if (params.rolling_shutter != 0.0) {
+            try { setRollingShutter(params.rolling_shutter); } catch (...) { vs_stabilizer_destroy(h_); throw; }
+        }
+    }
+    // 0: off; else the sensor's readout share of the frame period, -1 .. 1 (negative: bottom-up); takes effect with the next output frame
+    void setRollingShutter(double readout) {
+        const vs_rolling_params rp{readout};
+        if (vs_stabilizer_set_rolling_shutter(h_, &rp) != VS_OK) throw std::runtime_error(std::string("vs_stabilizer_set_rolling_shutter: ") + vs_last_error());
     }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
     VideoStabilizer(const VideoStabilizer&) = delete;
