@@ -64,8 +64,9 @@ def test_selection_warp_phase_and_config_tests_pass_on_the_bounds_build_with_a_c
     # (every fresh device allocation of these runs starts filled with 0xA5: nothing compared against the oracle may depend on it)
     env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1", VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")
     # (round 5: the separable Lanczos2 tests replace the contracted ones -- the two forms share the tile, fill and store code, the sweeps below still
-    # draw all three -- and the fixed-point bilinear kernels' tests join: byte / word tiles, coordinate tables, sites 211-216)
-    runs = [(["tests/test_select_gpu.py", "tests/test_select_stable_gpu.py", "tests/test_warp_sep_gpu.py", "tests/test_warp_cv_gpu.py", "tests/test_warp_cv_hostile_gpu.py", "tests/test_phase_gpu.py",
+    # draw all three -- and the fixed-point bilinear kernels' tests join: byte / word tiles, coordinate tables, sites 211-216; then the float-tile warps' table
+    # tests and their hostile suite -- far rows, every staged shape's limits, the routes without extents and without tables: sites 201-209)
+    runs = [(["tests/test_select_gpu.py", "tests/test_select_stable_gpu.py", "tests/test_warp_sep_gpu.py", "tests/test_warp_cv_gpu.py", "tests/test_warp_cv_hostile_gpu.py", "tests/test_warp_tables_gpu.py", "tests/test_warp_c3_hostile_gpu.py", "tests/test_phase_gpu.py",
               "tests/test_warp_sweep_gpu.py", "tests/test_engine_sweep_gpu.py"], "not 4k_frame"),   # (the kernel-chain sweep runs the un-instrumented stage kernels of vs_kernels.hip: not here)   # (the 4K frames' time is the CPU oracle's; the second group has a 4K frame)
             (["tests/test_latency_mode_gpu.py", "tests/test_configs_gpu.py"],
              "coresident_build_at_4k or sixteen_pairs or c3_4k_bgr_lanczos2_warp or c5_one_gpus_share"),

@@ -39,6 +39,7 @@
 #include <cmath>
 #include "vs_device.hpp"
 #include "vs_cv_window.hpp"
+#include "vs_c3_window.hpp"
 
 using namespace vsd;
 
@@ -561,38 +562,18 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
         const int4 e = tabf[tl];
         return Geom{x0, y0, e.x, e.y, e.z & 0xffff, e.z >> 16, (e.w & 1) != 0, (e.w & 2) != 0};
     }
-    const int x1 = min(x0 + WT_W, roi.w) - 1, y1 = min(y0 + WT_H, roi.h) - 1;
-
     // source footprint of the tile.  Wx = fl(fl(A1*x) - fl(B*y)) + TX is monotone in x and in y (rounding is monotone), so its
     // extremes over the tile sit at corners chosen by the signs of A1 and B: 4 evaluations -- or, when the host has sent the
     // frame's extents (vsk::bgr_warp_c3: the range of A1*i - B*j and B*i + A1*j over a full tile (64 x WT_H), widened by a bound on
     // the fp32 rounding of the position arithmetic), ONE evaluation at the tile origin plus four adds: every position a pixel
     // of the tile computes lies inside [W00 + lo, W00 + hi], which is all the footprint has to guarantee (it may come out a
     // pixel larger than the exact one; the window has 8 columns and 3 rows to spare for near-identity transforms).
-    const float fx0 = (float)(x0 + roi.x), fx1 = (float)(x1 + roi.x), fy0 = (float)(y0 + roi.y), fy1 = (float)(y1 + roi.y);
-    float mnx, mxx, mny, mxy;
-    if (extents != nullptr) {                               // (uniform)
-        const float Wx00 = A1 * fx0 - B * fy0 + TX, Wy00 = B * fx0 + A1 * fy0 + TY;
-        mnx = Wx00 + E.x; mxx = Wx00 + E.y; mny = Wy00 + E.z; mxy = Wy00 + E.w;
-    } else {
-    const float xa = A1 >= 0.f ? fx0 : fx1, xb = A1 >= 0.f ? fx1 : fx0;     // x minimising / maximising A1*x
-    const float ya = B >= 0.f ? fy0 : fy1, yb = B >= 0.f ? fy1 : fy0;       // y minimising / maximising B*y
-    mnx = A1 * xa - B * yb + TX; mxx = A1 * xb - B * ya + TX;
-    const float xc = B >= 0.f ? fx0 : fx1, xd = B >= 0.f ? fx1 : fx0;       // x minimising / maximising B*x
-    const float yc = A1 >= 0.f ? fy0 : fy1, yd = A1 >= 0.f ? fy1 : fy0;
-    mny = B * xc + A1 * yc + TY; mxy = B * xd + A1 * yd + TY;
-    }
-    bool fits = fmaxf(fmaxf(fabsf(mnx), fabsf(mxx)), fmaxf(fabsf(mny), fabsf(mxy))) < 1.0e6f;
-    int sx_lo = 0, sy_lo = 0, rows = 0, groups = 0;
-    if (fits) {
-        sx_lo = ((int)floorf(mnx) - 1) & ~3;               // first staged column: a multiple of 4 pixels (12 bytes)
-        const int sx_hi = (int)floorf(mxx) + 2;
-        sy_lo = (int)floorf(mny) - 1;
-        const int sy_hi = (int)floorf(mxy) + 2;
-        rows = sy_hi - sy_lo + 1;
-        groups = (sx_hi - sx_lo + 4) >> 2;                 // column groups of 4 pixels
-        fits = groups <= KG && rows <= WS_H;
-    }
+    // (the decision -- the footprint, whether it fits WS_H rows and KG column groups, and whether the sampler's fp32 tile offset is exact
+    // that far from the origin -- is vs_c3_window.hpp's, the one copy the tables kernel calls too, tested on the host: tests/test_c3_window_cpp.py)
+    const C3Window cw = c3_tile_window(C3Tile{x0, y0, WT_W, WT_H}, C3Roi{roi.x, roi.y, roi.w, roi.h}, C3Params{A1, B, TX, TY}, extents != nullptr,
+                                       C3Extents{E.x, E.y, E.z, E.w}, C3Staged{WS_H, KG, RAWTILE ? WS_RS8 : KRS, RAWTILE ? 0 : 1});
+    const bool fits = cw.fits;
+    const int sx_lo = cw.sx_lo, sy_lo = cw.sy_lo, rows = cw.rows, groups = cw.groups;
     // interior tiles (the whole staged window lies inside an aligned frame: all but the frame's rim): no clamps and no border
     // tests per item, one offset from a uniform base
     const bool interior = fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h;   // uniform
@@ -791,7 +772,8 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
     const int xq = min(x, roi.w - 1);                        // lanes right of the window sample its last column (masked below)
     const float fx = (float)(xq + roi.x);
     const float A1x = A1 * fx, Bx = B * fx;
-    // LDS byte offset of the window origin = 16 * ((fly - oy) * WS_RS + (flx - ox)); all terms are small integers, exact in fp32
+    // LDS byte offset of the window origin = 16 * ((fly - oy) * WS_RS + (flx - ox)); all terms are integers below 2^24, exact in fp32: a tile
+    // fits only if they are (vs_c3_window.hpp refuses windows whose row origin times the pitch comes within a pitch of 2^24)
     constexpr int org = (MODE == 1) ? 0 : 1;                 // Lanczos windows start one pixel up / left of floor()
     const float c0 = RAWTILE ? -4.0f * PXD * (float)(sy_lo * WS_RS8 + sx_lo) : -16.0f * (float)((sy_lo + org) * KRS + (sx_lo + org));
     const bool lane_in = x < roi.w;
@@ -945,9 +927,10 @@ __global__ __launch_bounds__(256, (MODE == 2 || MODE == 3) ? (SHAPE == 2 ? 7 : S
 
 // The tables of a float-tile Lanczos2 launch (see the kernel's prologue): per frame tiles_per_frame 16-byte tile entries, then tab_rows
 // (= the window's rows rounded up to whole 4-row blocks) pairs {fl(B * fy), fl(A1 * fy)}; rows beyond the window repeat its last row, as the
-// sampler's own clamp does.  One thread per entry, each THE expressions of the kernel's geom() on the extents path (ws_h / kg: the staged rows
-// and column groups of the instantiation that will be launched) and of its sampler block, in the same -ffp-contract=off build: the same
-// IEEE operations on the same operands, formed once instead of in every wave (tile entries) / in every lane (row terms).
+// sampler's own clamp does.  One thread per entry: a tile entry is the call of vsd::c3_tile_window that the kernel's geom() makes on the extents
+// path (ws_h / kg: the staged rows and column groups of the instantiation that will be launched), a row entry the expressions of the sampler
+// block, in the same -ffp-contract=off build: the same IEEE operations on the same operands, formed once instead of in every wave (tile
+// entries) / in every lane (row terms).
 __global__ __launch_bounds__(256) void vs_k_warp_c3_tables(const float4* __restrict__ params, const float4* __restrict__ extents, int4* __restrict__ tab,
                                                            int tiles_x, int tiles_per_frame, int ws_h, int kg, vsk::Roi roi, int w, int h,
                                                            unsigned long long src_addr, unsigned long long src_fs_bytes, unsigned long long src_stride_bytes) {
@@ -959,20 +942,11 @@ __global__ __launch_bounds__(256) void vs_k_warp_c3_tables(const float4* __restr
     if (i < tiles_per_frame) {
         const int tyi = i / tiles_x, txi = i - tyi * tiles_x;
         const int x0 = txi * WT_W, y0 = tyi * WT_H;
-        const float fx0 = (float)(x0 + roi.x), fy0 = (float)(y0 + roi.y);
-        const float Wx00 = A1 * fx0 - B * fy0 + TX, Wy00 = B * fx0 + A1 * fy0 + TY;
-        const float mnx = Wx00 + E.x, mxx = Wx00 + E.y, mny = Wy00 + E.z, mxy = Wy00 + E.w;
-        bool fits = fmaxf(fmaxf(fabsf(mnx), fabsf(mxx)), fmaxf(fabsf(mny), fabsf(mxy))) < 1.0e6f;
-        int sx_lo = 0, sy_lo = 0, rows = 0, groups = 0;
-        if (fits) {
-            sx_lo = ((int)floorf(mnx) - 1) & ~3;
-            const int sx_hi = (int)floorf(mxx) + 2;
-            sy_lo = (int)floorf(mny) - 1;
-            const int sy_hi = (int)floorf(mxy) + 2;
-            rows = sy_hi - sy_lo + 1;
-            groups = (sx_hi - sx_lo + 4) >> 2;
-            fits = groups <= kg && rows <= ws_h;
-        }
+        // (the float tile's pitch is 4 kg + 1 staged pixels -- 81, or the seven-wave shape's 73 -- and its tap windows start one pixel up / left of floor())
+        const C3Window cw = c3_tile_window(C3Tile{x0, y0, WT_W, WT_H}, C3Roi{roi.x, roi.y, roi.w, roi.h}, C3Params{A1, B, TX, TY}, true,
+                                           C3Extents{E.x, E.y, E.z, E.w}, C3Staged{ws_h, kg, 4 * kg + 1, 1});
+        const bool fits = cw.fits;
+        const int sx_lo = cw.sx_lo, sy_lo = cw.sy_lo, rows = cw.rows, groups = cw.groups;
         const bool src_aligned = (((src_addr + (unsigned long long)frame * src_fs_bytes) | src_stride_bytes) & 3) == 0;
         const bool interior = fits && src_aligned && sx_lo >= 0 && sx_lo + 4 * groups <= w && sy_lo >= 0 && sy_lo + rows <= h;
         // (a tile that does not fit is sampled per pixel and reads none of the four numbers)
@@ -1597,16 +1571,8 @@ hipError_t bgr_warp_c3(const void* src, int w, int h, int src_stride, int bits, 
                                n_frames, src_fs, dst_fs, (float)max_value, roi, compact, s);
 }
 
-// -> 0: the standard window; 1: every frame's tile footprint stays under 16 source rows (E4 = bgr_warp_c3_extents' output): the 20-row windows hold floor(max) - floor(min) + 4 <= 20
-// rows for every tile; 2: ... and under 65 source columns: floor(max) - floor(min) + 4 taps + 3 of alignment <= 72 = the 18 column groups of the seven-wave shape
-int bgr_warp_c3_compact_shape(const float* E4, int n_frames) {
-    int shape = 2;
-    for (int f = 0; f < n_frames; f++) {
-        if (!((double)E4[4 * f + 3] - (double)E4[4 * f + 2] < 15.999)) return 0;
-        if (!((double)E4[4 * f + 1] - (double)E4[4 * f + 0] < 64.99)) shape = 1;
-    }
-    return shape;
-}
+// the launcher's window shape for a call's extents: vsd::c3_compact_shape (vs_c3_window.hpp: 0 the standard window, 1 / 2 the 20-row windows)
+int bgr_warp_c3_compact_shape(const float* E4, int n_frames) { return vsd::c3_compact_shape(E4, n_frames); }
 
 // bytes of table per frame for (bits, mode, window): what bgr_warp_c3's caller reserves (n_frames times) for `tab_dev`; 0: the mode reads no table.
 // (the layout: vs_warp_table.hpp)
@@ -1668,29 +1634,10 @@ hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bit
     return hipGetLastError();
 }
 
-// The per-frame extents the tuned kernel's tile prologue adds to the position of a tile's origin (see the kernel): for the kernel
-// parameters P = {A, B, TX, TY} of a frame, {min, max of A1*i - B*j, min, max of B*i + A1*j} over i in [0, 63], j in [0, tile height - 1],
-// widened by eps = 2^-20 * M, M = a bound on every intermediate of the fp32 position arithmetic over the output window (the
-// arithmetic makes four roundings of relative size 2^-24 on values below M, for the pixel and for the tile origin: 8 * 2^-24 * M;
-// eps doubles that and covers the adds below), and rounded outward to float.
+// The per-frame extents the tuned kernel's tile prologue adds to the position of a tile's origin: vsd::c3_extents (vs_c3_window.hpp) for the
+// tile of the kernel that (bits, mode) selects
 void bgr_warp_c3_extents(const float* P4, int n_frames, Roi roi, int bits, int mode, float* E4) {
-    const int th = tile_h_of(bits, mode);                  // the tile of the kernel that (bits, mode) selects
-    for (int f = 0; f < n_frames; f++) {
-        const double A1 = (double)(1.0f + P4[4 * f]), B = (double)P4[4 * f + 1], TX = (double)P4[4 * f + 2], TY = (double)P4[4 * f + 3];
-        const double X = (double)(roi.x + roi.w) + 64.0, Y = (double)(roi.y + roi.h) + (double)th;
-        const double M = std::max(std::fabs(A1) * X + std::fabs(B) * Y + std::fabs(TX), std::fabs(B) * X + std::fabs(A1) * Y + std::fabs(TY)) + 1.0;
-        const double eps = M * (1.0 / 1048576.0);
-        const double ax = A1 * (WT_W - 1), bx = -B * (th - 1), ay = B * (WT_W - 1), by = A1 * (th - 1);
-        const double lo_x = std::min(0.0, ax) + std::min(0.0, bx) - eps, hi_x = std::max(0.0, ax) + std::max(0.0, bx) + eps;
-        const double lo_y = std::min(0.0, ay) + std::min(0.0, by) - eps, hi_y = std::max(0.0, ay) + std::max(0.0, by) + eps;
-        const double v[4] = {lo_x, hi_x, lo_y, hi_y};
-        for (int k = 0; k < 4; k++) {
-            float q = (float)v[k];
-            if (!std::isfinite(v[k]) || !std::isfinite(q)) q = (k & 1) ? 3.0e38f : -3.0e38f;      // (the kernel's |.| < 1e6 test then refuses the window)
-            else if ((k & 1) ? (double)q < v[k] : (double)q > v[k]) q = std::nextafterf(q, (k & 1) ? INFINITY : -INFINITY);
-            E4[4 * f + k] = q;
-        }
-    }
+    vsd::c3_extents(P4, n_frames, vsd::C3Roi{roi.x, roi.y, roi.w, roi.h}, WT_W, tile_h_of(bits, mode), E4);
 }
 
 }  // namespace vsk
