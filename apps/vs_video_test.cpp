@@ -1,5 +1,5 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--bilinear | --lanczos2] [--444]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
@@ -9,7 +9,9 @@
 // with what the next N input frames show at the same scene point (vs_stabilizer_set_denoise; --denoise-strength T: 1 .. 255, default 24).  --deflicker N: every
 // output frame's exposure is pulled to the mean exposure of itself and the next N input frames (vs_stabilizer_set_deflicker; --deflicker-step S: the lattice
 // step of the exposure statistics, 1 .. 64, default 4).  --rolling-shutter R: every frame is corrected for a rolling shutter whose readout takes the
-// share R (-1 .. 1, negative: bottom-up) of the frame period, by the motion to the following frame (vs_stabilizer_set_rolling_shutter).  Frames go to the GPU in
+// share R (-1 .. 1, negative: bottom-up) of the frame period, by the motion to the following frame (vs_stabilizer_set_rolling_shutter).
+// --lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]: every frame is corrected for that lens's distortion in front of everything (the camera matrix in
+// pixels, then OpenCV's distCoeffs in their order; --lens-zoom Z scales the output camera's focal lengths, default 1; vs_stabilizer_set_lens).  Frames go to the GPU in
 // chunks of N (default 64) and through vs_stabilizer_process_batch, which is defined as N successive processFrame calls.
 #include <chrono>
 #include <filesystem>
@@ -20,7 +22,7 @@ namespace fs = std::filesystem;
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step, bool inpaint, double rolling) {
+                         int deflicker_step, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -89,6 +91,18 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
             return false;
         }
     }
+    if (!lens.empty()) {
+        vs_lens_params lp;
+        vs_lens_params_default(&lp, fin.w, fin.h);
+        double* const field[12] = {&lp.fx, &lp.fy, &lp.cx, &lp.cy, &lp.k1, &lp.k2, &lp.p1, &lp.p2, &lp.k3, &lp.k4, &lp.k5, &lp.k6};
+        for (size_t k = 0; k < lens.size(); k++) *field[k] = lens[k];
+        lp.zoom = lens_zoom;
+        if (vs_stabilizer_set_lens(stab, &lp, fin.w, fin.h) != VS_OK) {
+            std::cerr << "Error: vs_stabilizer_set_lens: " << vs_last_error() << std::endl;
+            vs_stabilizer_destroy(stab);
+            return false;
+        }
+    }
 
     long frame_count = 0, written = 0, next_report = 100;
     const auto t0 = std::chrono::steady_clock::now();
@@ -125,7 +139,8 @@ int main(int argc, char** argv) {
     bool bilinear = false, lanczos2 = false, force444 = false;
     vs_fill_blend_params blend{0, 0};
     bool inpaint = false;
-    double rolling = 0.0;
+    double rolling = 0.0, lens_zoom = 1.0;
+    std::vector<double> lens;                              // --lens: 8, 9 or 12 numbers
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--chunk" && i + 1 < argc) chunk = std::max(1, std::atoi(argv[++i]));
@@ -141,12 +156,24 @@ int main(int argc, char** argv) {
         else if (a == "--deflicker" && i + 1 < argc) deflicker = std::atoi(argv[++i]);
         else if (a == "--deflicker-step" && i + 1 < argc) deflicker_step = std::atoi(argv[++i]);
         else if (a == "--rolling-shutter" && i + 1 < argc) rolling = std::atof(argv[++i]);
+        else if (a == "--lens" && i + 1 < argc) {
+            lens.clear();
+            for (const char* p = argv[++i]; *p;) {
+                char* e;
+                lens.push_back(std::strtod(p, &e));
+                if (e == p) { lens.clear(); break; }
+                p = *e == ',' ? e + 1 : e;
+                if (*e && *e != ',') { lens.clear(); break; }
+            }
+            if (lens.size() != 8 && lens.size() != 9 && lens.size() != 12) { std::cerr << "Error: --lens takes fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]\n"; return EXIT_FAILURE; }
+        }
+        else if (a == "--lens-zoom" && i + 1 < argc) lens_zoom = std::atof(argv[++i]);
         else if (a == "--bilinear") bilinear = true;
         else if (a == "--lanczos2") lanczos2 = true;
         else if (a == "--444") force444 = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -172,7 +199,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint, rolling)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint, rolling, lens, lens_zoom)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

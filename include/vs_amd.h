@@ -419,6 +419,58 @@ int vs_bgr_rolling_batch(const void* src, size_t src_frame_stride, int n_src, in
                          int n_out, const int32_t* cand_frame, const vs_transform* cand_t,
                          const vs_rolling_params* params /* NULL = defaults */,
                          void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* REMAP and LENS-DISTORTION CORRECTION: a lens bends the frame from inside in a way that is constant per clip and calibrated once, which no
+ * transform per frame removes.  The correction is a remap through a map of fixed-point positions made once; callers with a fisheye or any
+ * other calibrated model bring their own map.
+ * THE MAP FORMAT.  A map for `ow x oh` output pixels is `int32_t` pairs `(X, Y)`.
+ *
+ * - Pixel `(u, v)` is at `map[v * map_stride + 2 * u]` and `+ 1`.
+ * - `map_stride` is in `int32_t` elements and is `>= 2 * ow`.
+ * - `X` and `Y` are source positions with 5 fraction bits: exactly what `vsd::cv_pos` produces (`CvPos`), `VS_WARP_BILINEAR_CV`'s own positions.
+ * - Every int32 value is legal.
+ *
+ * THE SAMPLE RULE of `vs_bgr_remap_batch`.  Interleaved BGR, every `VS_FMT_BGR*`; `w, h, ow, oh` in 1 .. 32767, `VS_ERR_UNSUPPORTED` beyond,
+ * as the rolling-shutter pass does.  One map serves all `n` frames; the map lives where the frames live (`mem`).
+ *
+ * - Taps sit at `(X >> 5, Y >> 5)` and the three neighbours to the right and below. Fractions are `X & 31`, `Y & 31`.
+ * - The blend is `VS_WARP_BILINEAR_CV`'s, operation for operation.
+ *   - 8-bit containers: integer weights, `(sum + 512) >> 10`.
+ *   - 16-bit containers: fp32 weights `a * b / 1024`, `rintf`, saturated to `vs_format_max_value(format)`.
+ * - `VS_BORDER_CLAMP`: each tap's column is clamped to `0 .. w - 1` and its row to `0 .. h - 1`, with weights unchanged. This is the
+ *   rolling-shutter pass's rule.
+ * - `VS_BORDER_CONSTANT`: a tap outside the frame counts as 0, with weights unchanged. This is `VS_WARP_BILINEAR_CV`'s rule under that border.
+ * - Tap index sums are taken so that no int32 `X` or `Y` overflows (`X >> 5` is below 2^26).
+ *
+ * Hence
+ *
+ * - (a) The map `X = 32 u, Y = 32 v` with `ow == w, oh == h` returns every frame bit for bit. This holds for samples up to the format's maximum.
+ * - (b) Under the clamp border, every output sample lies between the minimum and maximum of the frame's samples in its channel.
+ * - (c) Every sample is defined for every map.
+ * VS_MEM_DEVICE only enqueues.  A destination whose rows do not all start on dwords, or an `ow` that is no multiple of 4, takes the
+ * one-pixel-per-lane kernel, with the same result. */
+int vs_bgr_remap_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
+                       const int32_t* map, int map_stride, int ow, int oh, int border,
+                       void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* THE RADIAL MAP: the Brown-Conrady model with a rational radial term, the same eight coefficients in the same order as OpenCV's distCoeffs
+ * (k1, k2, p1, p2, k3, k4, k5, k6).  The output camera is the input camera with its focal lengths scaled by `zoom`.  `border` is what the
+ * stabilizer's correction remaps with; the map itself does not depend on it.  Defaults: fx = fy = max(w, h), cx = (w - 1) / 2,
+ * cy = (h - 1) / 2, all coefficients 0, zoom 1, VS_BORDER_CLAMP: the identity lens.
+ * The rule, per output pixel (u, v).  All arithmetic is fp64, every operation rounds once in the order written, and there is no FMA:
+ *   x = ((double)u - cx) / (fx * zoom);      y = ((double)v - cy) / (fy * zoom);
+ *   r2 = x * x + y * y;
+ *   kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+ *   xy2 = 2 * (x * y);
+ *   xd = x * kr + (p1 * xy2 + p2 * (r2 + 2 * (x * x)));
+ *   yd = y * kr + (p1 * (r2 + 2 * (y * y)) + p2 * xy2);
+ *   X = cv_round_sat((fx * xd + cx) * 32);   Y = cv_round_sat((fy * yd + cy) * 32);
+ * cv_round_sat: ties to even, NaN -> 0, saturating to the int32 range.  Only + - * / and rint: VS_MEM_HOST (computed on the host, no device
+ * needed) and VS_MEM_DEVICE (a small kernel, enqueue only) give the same bits.  A parameter that is not finite, or an fx, fy or zoom that is
+ * not > 0, is VS_ERR_ARG before any work; a denominator that reaches 0 at some pixel is legal input (the rule defines the position through
+ * cv_round_sat).  With all eight coefficients 0 and zoom 1 the map is (32 u, 32 v).  w, h in 1 .. 32767; map_stride >= 2 * w.
+ * The fisheye (equidistant) model needs a transcendental that is not bit-reproducible and is left to the caller's own map. */
+typedef struct vs_lens_params { double fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, zoom; int border; } vs_lens_params;
+void vs_lens_params_default(vs_lens_params* p, int w, int h);
+int  vs_lens_map(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride, int mem, void* stream);
 /* DEFLICKER: a frame's exposure is pulled to the average exposure of a window of frames, the exposure ratio of two frames being measured
  * at the same scene points through their measured motions (a pan changes a whole-frame sum because the content changes).  Interleaved
  * BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as in the fill); s = bits - 8.  The rule:
@@ -751,6 +803,19 @@ int   vs_stabilizer_get_denoise(const vs_stabilizer* s);
  * next output frame.  VS_ERR_ARG for a readout that is NaN or outside -1 .. 1.  get: the parameters in force (readout 0: off). */
 int   vs_stabilizer_set_rolling_shutter(vs_stabilizer* s, const vs_rolling_params* params);
 int   vs_stabilizer_get_rolling_shutter(const vs_stabilizer* s, vs_rolling_params* params);
+/* Lens-distortion correction (the map: see vs_lens_map; the sample rule: see vs_bgr_remap_batch).  NULL params, or all eight coefficients 0
+ * with zoom 1 (the identity lens): off -- the handle as it is without this call, launch for launch, allocation for allocation.  Otherwise
+ * every arriving w x h frame is remapped through the lens map, under params->border, IN FRONT OF EVERYTHING: the aligner, the sharpness and
+ * channel-sum measurements, the queue and every pass see corrected frames.  The definition: a handle with the correction on, fed raw frames,
+ * returns bit for bit -- outputs, has_output, vs_stabilizer_state -- what a handle with it off returns when fed
+ * vs_bgr_remap_batch(raw, vs_lens_map(params)).  The map is made once per (params, w, h) on the device, kept in the handle and dropped by
+ * this call.  While the pass is on, frames of another size are VS_ERR_ARG before any work.  Device frames are read in place by the remap;
+ * host frames are staged first.  Dense device-resident batches take the plain route while the pass is on: the warps do not run under the
+ * next sub-batch's alignment.  Takes effect with the next frame; frames already queued stay as they arrived.  VS_ERR_ARG for parameters
+ * vs_lens_map refuses or a border other than VS_BORDER_*.  get: returns 1 (on: the parameters and the size in force) or 0 (off: the
+ * identity lens, size 0 x 0). */
+int   vs_stabilizer_set_lens(vs_stabilizer* s, const vs_lens_params* params, int w, int h);
+int   vs_stabilizer_get_lens(const vs_stabilizer* s, vs_lens_params* params, int* w, int* h);
 /* Deflicker (the rule: see vs_bgr_exposure_stats_batch).  0 (default): off -- the handle as it is without this call, launch for launch.
  * 1 .. lag: every output frame's exposure is pulled to the average exposure of itself and the next `ahead` input frames; the exposure
  * ratios are measured on the device at the same scene points through the measured motions (candidate j's transform is

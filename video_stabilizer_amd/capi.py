@@ -91,6 +91,15 @@ class RollingParams(C.Structure):
     _fields_ = [("readout", C.c_double)]
 
 
+class LensParams(C.Structure):
+    """vs_lens_params: the radial lens model (OpenCV's distCoeffs order k1, k2, p1, p2, k3, k4, k5, k6), the output camera's zoom and the border
+    the stabilizer's correction remaps with"""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6", "zoom")] + [("border", C.c_int)]
+
+    def tup(self):
+        return tuple(getattr(self, k) for k, _ in self._fields_)
+
+
 class DeflickerParams(C.Structure):
     """vs_deflicker_params: the lattice step of the exposure statistics, 1 .. 64"""
     _fields_ = [("step", C.c_int)]
@@ -175,6 +184,9 @@ SIGNATURES = {
     "vs_rolling_params_default": (None, [C.POINTER(RollingParams)]),
     "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(RollingParams),
                                     _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_remap_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_lens_params_default": (None, [C.POINTER(LensParams), _i32, _i32]),
+    "vs_lens_map": (_i32, [C.POINTER(LensParams), _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_deflicker_params_default": (None, [C.POINTER(DeflickerParams)]),
     "vs_bgr_exposure_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeflickerParams),
                                            _vp, _i32, _vp]),
@@ -205,6 +217,8 @@ SIGNATURES = {
     "vs_stabilizer_get_denoise": (_i32, [_vp]),
     "vs_stabilizer_set_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
     "vs_stabilizer_get_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
+    "vs_stabilizer_set_lens": (_i32, [_vp, C.POINTER(LensParams), _i32, _i32]),
+    "vs_stabilizer_get_lens": (_i32, [_vp, C.POINTER(LensParams), _IP, _IP]),
     "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
     "vs_stabilizer_get_deflicker": (_i32, [_vp]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
@@ -836,6 +850,62 @@ def rolling_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_fra
                                       C.c_void_p(stream) if stream else None))
 
 
+REMAP_SLICE = 8                                     # vsk::kRemapSlice: the frames a workgroup of the remap takes a pixel through
+
+
+def lens_params(w, h, **kw):
+    """the identity lens of a w x h frame (vs_lens_params_default), fields overridden by keyword"""
+    p = LensParams()
+    lib().vs_lens_params_default(C.byref(p), int(w), int(h))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("LensParams has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def lens_map(params, w, h, map_stride=None, guard=None):
+    """the radial map on the host (include/vs_amd.h: vs_lens_map, VS_MEM_HOST: no device needed) -> (h, w, 2) int32 positions (X, Y) with 5
+    fraction bits.  map_stride (int32 elements): the map is made in pitched rows.  guard: a value the buffer -- two rows in front, two behind and
+    the padding -- is filled with first; the whole buffer (h + 4, map_stride) is returned as well"""
+    ms = 2 * w if map_stride is None else map_stride
+    buf = np.full((h + 4, ms), 0 if guard is None else guard, np.int32)
+    _check(lib().vs_lens_map(C.byref(params), w, h, _p(buf[2:]), ms, MEM_HOST, None))
+    res = np.ascontiguousarray(buf[2:h + 2, :2 * w]).reshape(h, w, 2)
+    return (res, buf) if guard is not None else res
+
+
+def lens_map_device(params, w, h, map_ptr, map_stride=None, stream=None):
+    """device-resident form: the map is written at map_ptr (int32, rows of map_stride elements), enqueue only"""
+    _check(lib().vs_lens_map(C.byref(params), w, h, _p(map_ptr), 2 * w if map_stride is None else map_stride, MEM_DEVICE,
+                             C.c_void_p(stream) if stream else None))
+
+
+def remap_batch(src, pos, border=BORDER_CLAMP, fmt=None, src_stride=None, dst_stride=None, map_stride=None, guard=None):
+    """remap through a map of fixed-point positions (include/vs_amd.h: vs_bgr_remap_batch).  src (n,h,w,3) numpy; pos (oh, ow, 2) int32 (X, Y)
+    with 5 fraction bits, one map for every frame -> (n, oh, ow, 3).  src_stride / dst_stride (elements), map_stride (int32 elements): the call
+    is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer is returned as well"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    pos = _c(pos, np.int32)
+    oh, ow, _ = pos.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    ds = ow * c if dst_stride is None else dst_stride
+    ms = 2 * ow if map_stride is None else map_stride
+    mp = _pitched(pos.reshape(1, oh, ow, 2), ms)
+    out = np.full((n, oh, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_remap_batch(_p(_pitched(src, ss)), h * ss, n, w, h, ss, fmt, _p(mp), ms, ow, oh, border, _p(out), oh * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:, :, :ow * c]).reshape(n, oh, ow, c)
+    return (res, out) if guard is not None else res
+
+
+def remap_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, map_ptr, map_stride, ow, oh, dst_ptr, dst_fs, dst_stride, border=BORDER_CLAMP, stream=None):
+    """device-resident form: frames and map in device memory, frame strides and row strides in elements, enqueue only"""
+    _check(lib().vs_bgr_remap_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(map_ptr), map_stride, ow, oh, border, _p(dst_ptr), dst_fs, dst_stride,
+                                    MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
 def deflicker_params(**kw):
     p = DeflickerParams()
     lib().vs_deflicker_params_default(C.byref(p))
@@ -1147,7 +1217,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1168,6 +1238,19 @@ class Stabilizer:
             self.set_inpaint(inpaint)
         if rolling_shutter:
             self.set_rolling_shutter(rolling_shutter)
+        if lens is not None:
+            self.set_lens(*lens)
+
+    def set_lens(self, params, w=0, h=0):
+        """None (or the identity lens): off; else every arriving w x h frame is remapped through the lens map of `params` (LensParams) in front of
+        everything: the aligner and every pass see corrected frames"""
+        _check(lib().vs_stabilizer_set_lens(self.h, C.byref(params) if params is not None else None, int(w), int(h)))
+
+    def get_lens(self):
+        """None (off) or (LensParams, w, h)"""
+        p, w, h = LensParams(), C.c_int(), C.c_int()
+        on = _check(lib().vs_stabilizer_get_lens(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return (p, w.value, h.value) if on else None
 
     def set_rolling_shutter(self, readout):
         """None or 0: off; else every frame is corrected for a rolling shutter of that readout share (-1 .. 1) by the motion to the next input

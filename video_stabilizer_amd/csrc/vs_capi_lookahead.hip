@@ -1,8 +1,11 @@
 // vs_capi_lookahead.hip -- the look-ahead passes of the C ABI (include/vs_amd.h) next to the border fill (vs_capi_warp.hip): channel sums,
-// sharpness and deblur, denoise, rolling-shutter correction, exposure statistics / gains / gain, coverage index and inpaint.  Each pass that takes candidate lists is a
+// sharpness and deblur, denoise, rolling-shutter correction, remap and lens map, exposure statistics / gains / gain, coverage index and inpaint.  Each pass that takes candidate lists is a
 // *_ptrs function in vsi (device-resident frames, enqueue only: the engine's form) and an index-based *_batch wrapper over it; what brings a
 // list to a kernel is cand_groups (vs_capi.hpp).
 #include "vs_capi.hpp"
+#include "vs_lens.hpp"
+
+#include <cstdlib>
 
 using namespace vsi;
 
@@ -300,6 +303,38 @@ int vs_bgr_rolling_batch(const void* src, size_t src_fs, int n_src, int w, int h
     VS_TRY(stage_out(o, out, mem, out.esz()));
     const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * in.esz());
     VS_TRY(bgr_rolling_ptrs(n_out, w, h, src_stride, format, ptrs.data(), cand_t, &p, o.dev, dst_fs, dst_stride, s));
+    return finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+// ---- remap and the radial lens map (vs_remap.hip) ----
+int vs_lens_map(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride, int mem, void* stream) try {
+    if (mem == VS_MEM_HOST) return lens_map_host(p, w, h, map, map_stride);
+    VS_ARG(mem == VS_MEM_DEVICE);
+    VS_ARG(p && map && w >= 1 && h >= 1 && w <= 32767 && h <= 32767 && map_stride >= 2 * w && vsl::params_ok(*p));
+    if (!device_ready()) return VS_ERR_HIP;
+    VS_HIP(vsk::lens_map(*p, w, h, map, map_stride, (hipStream_t)stream));
+    return VS_OK;
+} VS_CATCH_ALL
+
+int vs_bgr_remap_batch(const void* src, size_t src_fs, int n, int w, int h, int src_stride, int format, const int32_t* map, int map_stride, int ow, int oh,
+                       int border, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+    const int bits = vs_format_bits(format);
+    const plan::Batch in{src, src_fs, n, w, h, src_stride, 3, bits}, out{dst, dst_fs, n, ow, oh, dst_stride, 3, bits};
+    VS_TRY(batch_args_ok(__func__, format, src && map && dst, in, &out));
+    VS_ARG(ow > 0 && oh > 0 && ow <= 65535 && oh <= 65535 && map_stride >= 2 * ow && (border == VS_BORDER_CLAMP || border == VS_BORDER_CONSTANT));
+    if (w > 32767 || h > 32767 || ow > 32767 || oh > 32767) return set_error(VS_ERR_UNSUPPORTED, "remap: frames and maps up to 32767 x 32767%s", kAsTheFill);
+    VS_ARG(in.strides_ok() && out.strides_ok());
+    if (!device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    // how many frames a workgroup takes a pixel through: tools/lens_bench.py times other lengths through the test hooks
+    const char* const hook = test_env("VS_TEST_REMAP_SLICE");
+    const int slice = hook && atoi(hook) >= 1 ? atoi(hook) : vsk::kRemapSlice;
+    Staged a, m, o;
+    VS_TRY(stage_in(a, in, mem, s));
+    VS_TRY(m.in(map, ((size_t)(oh - 1) * (size_t)map_stride + 2 * (size_t)ow) * sizeof(int32_t), mem, s));
+    VS_TRY(stage_out(o, out, mem, out.esz()));
+    VS_HIP(vsk::bgr_remap(a.dev, src_fs, n, w, h, src_stride, (int)in.esz() * 8, vs_format_max_value(format), m.as<int32_t>(), map_stride, ow, oh, border, o.dev,
+                          dst_fs, dst_stride, slice, s));
     return finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 

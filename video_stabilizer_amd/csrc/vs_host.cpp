@@ -1,6 +1,7 @@
 // vs_host.cpp -- the host-only part of the C ABI: scalar algebra the reference also keeps on the
 // CPU (SimilarityTransform, tile-size rule, L1 smoother).  No device calls in this file.
 #include "vs_internal.hpp"
+#include "vs_lens.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -24,6 +25,16 @@ int caught() noexcept {
     catch (const std::bad_alloc&) { return set_error(VS_ERR_NOMEM, "host allocation failed (std::bad_alloc)"); }
     catch (const std::exception& e) { return set_error(VS_ERR_NOMEM, "C++ exception stopped at the C boundary: %s", e.what()); }
     catch (...) { return set_error(VS_ERR_NOMEM, "unknown C++ exception stopped at the C boundary"); }
+}
+// vs_lens_map in host memory (the rule: vs_lens.hpp); the device form is vsk::lens_map, the same function in a kernel
+int lens_map_host(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride) {
+    if (!p || !map || w < 1 || h < 1 || w > 32767 || h > 32767 || map_stride < 2 * w || !vsl::params_ok(*p))
+        return set_error(VS_ERR_ARG, "bad argument: a lens map needs finite parameters with fx, fy, zoom > 0, w, h in 1 .. 32767 and map_stride >= 2 w (vs_lens_map)");
+    for (int v = 0; v < h; v++) {
+        int32_t* const row = map + (size_t)v * (size_t)map_stride;
+        for (int u = 0; u < w; u++) vsl::position(*p, u, v, &row[2 * u], &row[2 * u + 1]);
+    }
+    return VS_OK;
 }
 }  // namespace vsi
 
@@ -89,6 +100,15 @@ void vs_denoise_params_default(vs_denoise_params* p) {
 // vs_rolling.hip (DESIGN.md "Rolling-shutter correction": a placeholder in the middle of the usual range, not a measured sensor value)
 void vs_rolling_params_default(vs_rolling_params* p) {
     p->readout = 0.5;
+}
+// vs_remap.hip (DESIGN.md "Lens-distortion correction": the identity lens -- a calibration replaces every field)
+void vs_lens_params_default(vs_lens_params* p, int w, int h) {
+    p->fx = p->fy = (double)std::max(w, h);
+    p->cx = (w - 1) / 2.0;
+    p->cy = (h - 1) / 2.0;
+    p->k1 = p->k2 = p->p1 = p->p2 = p->k3 = p->k4 = p->k5 = p->k6 = 0.0;
+    p->zoom = 1.0;
+    p->border = VS_BORDER_CLAMP;
 }
 // vs_deflicker.hip (DESIGN.md "Deflicker": a lattice of every fourth pixel a side reads a quarter of the cache lines and leaves thousands of pairs)
 void vs_deflicker_params_default(vs_deflicker_params* p) {

@@ -26,6 +26,8 @@ inline bool deblur_params_finite(float sensitivity, float max_ratio) {
     const double r = (double)max_ratio < 9007199254740992.0 ? (double)max_ratio : 9007199254740992.0;
     return r * r <= (double)sensitivity * 0x1p100;
 }
+// vs_lens_map with VS_MEM_HOST (vs_host.cpp; the rule: vs_lens.hpp): checks its arguments, needs no device
+int lens_map_host(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride);
 constexpr int kSharedMinPairs = 32;   // VS_BATCH_SHARED: launches of at least this many pairs take the aligner's small-footprint solver build
 }  // namespace vsi
 #define VS_CATCH_ALL catch (...) { return vsi::caught(); }

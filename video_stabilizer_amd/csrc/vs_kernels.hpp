@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct vs_lens_params;      // include/vs_amd.h
+
 namespace vsk {
 
 // output window of a warp: output pixel (x, y), x < w, y < h, is pixel (x + Roi.x, y + Roi.y) of the full output frame
@@ -103,6 +105,14 @@ hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int 
 // there means "no motion known" (the frame is copied; a non-null one is never followed).  dst: full w x h frames.  readout: -1 .. 1.
 hipError_t bgr_rolling(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int max_value, double readout, void* dst, int dst_stride,
                        int n_frames, size_t dst_fs, hipStream_t s);
+// Remap through a map of fixed-point positions and the radial lens map (vs_remap.hip: the format, the sample rule and the kernels).  bgr_remap:
+// n_frames w x h frames -> n_frames ow x oh frames through ONE map of ow x oh (X, Y) pairs in device memory, rows of map_stride ints; border:
+// VS_BORDER_*; slice: how many frames a workgroup takes a pixel through (kRemapSlice unless a measurement says otherwise).  lens_map: the map of
+// vs_lens.hpp's rule for a w x h frame.
+constexpr int kRemapSlice = 8;
+hipError_t bgr_remap(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const int32_t* map,
+                     int map_stride, int ow, int oh, int border, void* dst, size_t dst_fs, int dst_stride, int slice, hipStream_t s);
+hipError_t lens_map(const vs_lens_params& p, int w, int h, int32_t* map, int map_stride, hipStream_t s);
 // Deflicker (vs_deflicker.hip: the rule and the kernels).  exposure_stats: cands_dev = n_frames x n_cand entries in device memory (entry 0 of a
 // frame is the target, a null frame ends the list); stats = n_frames x n_cand x 8 words in device memory, zeroed on `s` first.  exposure_gains:
 // gains[4 o + {0..2: G_c, 3: m}] from the statistics.  bgr_gain: frame i scaled by gains[4 i ..] (clamped to 16384 .. 65536); dst may be src.

@@ -1,5 +1,5 @@
 // vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
-// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_deflicker).
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_remap, vs_deflicker).
 //
 // Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
 // then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
@@ -9,6 +9,7 @@
 #include "vs_lookahead.hpp"
 #include "vs_stab_step.hpp"
 #include "vs_kernels.hpp"
+#include "vs_lens.hpp"
 
 #include <algorithm>
 #include <deque>
@@ -45,6 +46,12 @@ struct vs_stabilizer {
     // rolling-shutter correction (vs_rolling.hip)
     vs_rolling_params rolling{0.0};   // vs_stabilizer_set_rolling_shutter: readout 0: off
     void* rolling_buf = nullptr; size_t rolling_bytes = 0;   // the corrected frames of the current call: the source of its warps
+    // lens-distortion correction (vs_remap.hip), in front of everything: the chunk's frames land, corrected, in batch_in
+    bool lens_on = false;          // vs_stabilizer_set_lens: NULL or the identity lens: off
+    vs_lens_params lens{};
+    int lens_w = 0, lens_h = 0;    // the frame size the lens was calibrated for; frames of another size are refused while the pass is on
+    void* lens_map = nullptr; size_t lens_map_bytes = 0;     // the map, made once per (params, w, h) on the device
+    bool lens_map_made = false;
     // deflicker (vs_deflicker.hip)
     int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
     vs_deflicker_params deflicker_params{4};
@@ -130,6 +137,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     if (s->deblur_buf) (void)hipFree(s->deblur_buf);
     if (s->denoise_buf) (void)hipFree(s->denoise_buf);
     if (s->rolling_buf) (void)hipFree(s->rolling_buf);
+    if (s->lens_map) (void)hipFree(s->lens_map);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
     if (s->batch_in) (void)hipFree(s->batch_in);
@@ -240,12 +248,35 @@ struct Chunk {
     uint32_t* fk_gains = nullptr;  // deflicker: four words per job, in flicker_buf
 
     // stabilizer.cpp:15: a private dense copy of every input frame, in device memory
+    // With the lens correction on the frames land there corrected: the remap reads device frames in place, whatever their pitch, and host frames
+    // from span_in[0], where their whole span travels as one linear copy; the aligner, the side values, the queue and every pass then see
+    // corrected frames only.  (already_dense stays false: no next chunk's alignment is started on the caller's uncorrected frames.)
     int make_dense() {
+        if (s->lens_on) return make_dense_corrected();
         already_dense = c.mem == VS_MEM_DEVICE && c.dense();
         dense = (const uint8_t*)c.frames;                  // read in place during this call; the tail is copied out by own_queued
         if (already_dense) return VS_OK;
         VS_HIP(grow(&s->batch_in, &s->batch_in_bytes, fbytes * c.n));
         VS_HIP(::make_dense(s, c, c.dense(), 0, s->batch_in, st));
+        dense = (const uint8_t*)s->batch_in;
+        return VS_OK;
+    }
+
+    int make_dense_corrected() {
+        if (!s->lens_map_made) {                           // once per (params, w, h): vs_stabilizer_set_lens drops it
+            VS_HIP(grow(&s->lens_map, &s->lens_map_bytes, (size_t)w * h * 2 * sizeof(int32_t)));
+            VS_HIP(vsk::lens_map(s->lens, w, h, (int32_t*)s->lens_map, 2 * w, st));
+            s->lens_map_made = true;
+        }
+        const void* from = c.frames;
+        if (c.mem == VS_MEM_HOST) {
+            VS_HIP(grow(&s->span_in[0], &s->span_in_bytes[0], c.span_bytes()));
+            VS_HIP(hipMemcpyAsync(s->span_in[0], c.frames, c.span_bytes(), hipMemcpyHostToDevice, st));
+            from = s->span_in[0];
+        }
+        VS_HIP(grow(&s->batch_in, &s->batch_in_bytes, fbytes * c.n));
+        VS_HIP(vsk::bgr_remap(from, c.frame_stride, c.n, w, h, c.stride, bits, vs_format_max_value(c.format), (const int32_t*)s->lens_map, 2 * w, w, h,
+                              s->lens.border, s->batch_in, (size_t)w * h * 3, w * 3, vsk::kRemapSlice, st));
         dense = (const uint8_t*)s->batch_in;
         return VS_OK;
     }
@@ -670,6 +701,9 @@ static int stab_run_overlapped(vs_stabilizer* s, const StabCall& c, int step, bo
 // "new clip" state (and the stream drained, so nothing still reads the caller's frames), and the error is passed on.
 static int stab_run(vs_stabilizer* s, const StabCall& c) {
     const int n = c.n, clip_len = c.clip_len;
+    // the lens was calibrated for one frame size: another one is refused before any work, and leaves the handle as it is
+    if (s && s->lens_on && (c.w != s->lens_w || c.h != s->lens_h))
+        return set_error(VS_ERR_ARG, "bad argument: lens correction is set for %d x %d frames, this call brings %d x %d (vs_stabilizer_set_lens)", s->lens_w, s->lens_h, c.w, c.h);
     // host-resident batches longer than one upload chunk run as a three-stage pipeline: upload / compute / download
     int chunk = 0;
     if (s && c.mem == VS_MEM_HOST && n > 1 && c.w > 0 && c.h > 0) {
@@ -690,7 +724,9 @@ static int stab_run(vs_stabilizer* s, const StabCall& c) {
     static const int cv_solver_env = []() { const char* e = getenv("VS_STAB_CV_SOLVER"); return e && atoi(e) == VS_BATCH_SHARED ? VS_BATCH_SHARED : VS_BATCH_EXCLUSIVE; }();
     const int overlap_mode = s && s->params.warp_mode == VS_WARP_BILINEAR_CV ? cv_solver_env : VS_BATCH_SHARED;
     const int n_clips_all = clip_len > 0 ? n / clip_len : 0;
-    const bool dense_dev = s && c.mem == VS_MEM_DEVICE && c.w > 0 && n > 1 && c.dense();
+    // (lens correction on: the plain route.  The overlapped routes align s->next_frames, the caller's uncorrected frames, ahead of time, and their
+    // deferred queue entries would point into batch_in, which the next sub-batch's corrected frames overwrite)
+    const bool dense_dev = s && !s->lens_on && c.mem == VS_MEM_DEVICE && c.w > 0 && n > 1 && c.dense();
     int group_clips = 0;
     if (overlap_env && dense_dev && clip_len >= 2 && n_clips_all >= 2 && n == n_clips_all * clip_len) {
         // groups of at least kSharedMinPairs pairs (the small build's threshold), at most 4 groups (VS_STAB_GROUPS): every group boundary is a host
@@ -728,6 +764,7 @@ static int stab_run(vs_stabilizer* s, const StabCall& c) {
         const std::string why = vs_last_error();             // the reset below must not hide the cause
         vsi::align_abandon(s->aligner);                      // (a next chunk's alignment may have been started)
         s->prefetched = false; s->next_n = 0;
+        s->lens_map_made = false;                            // (the launch that made the map may be what failed)
         (void)hipStreamSynchronize((hipStream_t)vs_aligner_stream(s->aligner));
         for (auto it = s->frames.begin(); it != s->frames.end();) it = it->owned ? it + 1 : s->frames.erase(it);
         (void)vs_stabilizer_reset(s);
@@ -849,6 +886,28 @@ int vs_stabilizer_get_rolling_shutter(const vs_stabilizer* s, vs_rolling_params*
     VS_ARG(s && params);
     *params = s->rolling;
     return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_set_lens(vs_stabilizer* s, const vs_lens_params* params, int w, int h) try {
+    VS_ARG(s);
+    if (params) {
+        VS_ARG(vsl::params_ok(*params) && (params->border == VS_BORDER_CLAMP || params->border == VS_BORDER_CONSTANT));
+        VS_ARG(w >= 1 && h >= 1);
+        if (w > 32767 || h > 32767) return set_error(VS_ERR_UNSUPPORTED, "lens correction: frames up to 32767 x 32767, as the remap");
+    }
+    // the map belongs to (params, w, h): dropped here, made again by the next call that needs it (no launch of an earlier call still reads
+    // it: every call ends with its stream synchronised)
+    VS_HIP(hipSetDevice(vsi::aligner_device(s->aligner)));
+    if (s->lens_map) (void)hipFree(s->lens_map);
+    s->lens_map = nullptr; s->lens_map_bytes = 0; s->lens_map_made = false;
+    s->lens_on = params && !vsl::is_identity(*params);
+    if (s->lens_on) { s->lens = *params; s->lens_w = w; s->lens_h = h; }
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_lens(const vs_stabilizer* s, vs_lens_params* params, int* w, int* h) try {
+    VS_ARG(s && params && w && h);
+    *w = s->lens_on ? s->lens_w : 0; *h = s->lens_on ? s->lens_h : 0;
+    if (s->lens_on) *params = s->lens; else vs_lens_params_default(params, 0, 0);
+    return s->lens_on ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);

@@ -68,6 +68,11 @@ public:
         const vs_rolling_params rp{readout};
         if (vs_stabilizer_set_rolling_shutter(h_, &rp) != VS_OK) throw std::runtime_error(std::string("vs_stabilizer_set_rolling_shutter: ") + vs_last_error());
     }
+    // nullptr (or the identity lens): off; else every arriving width x height frame is corrected for the lens's distortion in front of everything --
+    // the aligner and every pass see corrected frames (vs_stabilizer_set_lens; vs_lens_params_default gives the identity lens to start from)
+    void setLens(const vs_lens_params* lens, int width = 0, int height = 0) {
+        if (vs_stabilizer_set_lens(h_, lens, width, height) != VS_OK) throw std::runtime_error(std::string("vs_stabilizer_set_lens: ") + vs_last_error());
+    }
     ~VideoStabilizer() { vs_stabilizer_destroy(h_); }
     VideoStabilizer(const VideoStabilizer&) = delete;
     VideoStabilizer& operator=(const VideoStabilizer&) = delete;
