@@ -118,6 +118,23 @@ public:
         return true;
     }
 
+    // The next frame's samples as they lie in the file, unconverted (.y4m only): fmt.frame_samples() elements -- uint8_t when fmt.bits == 8, else
+    // uint16_t -- Y (w x h), then Cb, then Cr (cw() x ch() each; none for Cmono).  For callers that convert on the device
+    // (vs_stabilizer_process_batch_ycbcr).  Returns as next() does.
+    bool next_planes(void* planes_out) {
+        if (!f_) { error = "reader is not open"; return false; }
+        if (raw_) { error = "raw .bgr has no planes"; return false; }
+        char line[256];
+        if (!read_line(line, sizeof line)) {
+            if (line[0] != 0) error = "trailing bytes without a FRAME marker";
+            return false;
+        }
+        if (std::strncmp(line, "FRAME", 5) != 0) { error = "missing FRAME marker"; return false; }
+        const size_t bytes = fmt.frame_samples() * fmt.sample_bytes();
+        if (std::fread(planes_out, 1, bytes, f_) != bytes) { error = "truncated y4m frame"; return false; }
+        return true;
+    }
+
 private:
     bool read_line(char* line, size_t cap) {
         size_t n = 0;
@@ -231,6 +248,15 @@ public:
         else pack<uint16_t>(static_cast<const uint16_t*>(bgr), reinterpret_cast<uint16_t*>(buf_.data()));
         std::fputs("FRAME\n", f_);
         return std::fwrite(buf_.data(), 1, bytes, f_) == bytes;
+    }
+
+    // A frame's samples as they go into the file, unconverted (.y4m only): the layout Reader::next_planes returns.
+    bool write_planes(const void* planes) {
+        if (!f_) { error = "writer is not open"; return false; }
+        if (raw_) { error = "raw .bgr has no planes"; return false; }
+        const size_t bytes = fmt.frame_samples() * fmt.sample_bytes();
+        std::fputs("FRAME\n", f_);
+        return std::fwrite(planes, 1, bytes, f_) == bytes;
     }
 
 private:

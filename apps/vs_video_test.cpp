@@ -1,5 +1,5 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444] [--device-convert]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
@@ -13,6 +13,8 @@
 // --lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]: every frame is corrected for that lens's distortion in front of everything (the camera matrix in
 // pixels, then OpenCV's distCoeffs in their order; --lens-zoom Z scales the output camera's focal lengths, default 1; vs_stabilizer_set_lens).  Frames go to the GPU in
 // chunks of N (default 64) and through vs_stabilizer_process_batch, which is defined as N successive processFrame calls.
+// --device-convert: a .y4m clip's frames are not converted to BGR on the host: the raw planes of a chunk go to vs_stabilizer_process_batch_ycbcr and the
+// planes it returns go to the file as they are (the same bytes either way: the device restates video_io.hpp's rule).  For .bgr clips the flag does nothing.
 #include <chrono>
 #include <filesystem>
 #include <iostream>
@@ -20,9 +22,23 @@
 
 namespace fs = std::filesystem;
 
+// the planes of frame 0 of a chunk of raw y4m frames at `base`, frames back to back in the file's layout (Y, then Cb, then Cr)
+static vs_ycbcr_planes planes_of(const vsio::Format& f, void* base) {
+    const size_t esz = f.sample_bytes();
+    vs_ycbcr_planes p{};
+    p.y = base; p.y_stride = f.w; p.c_step = 1;
+    p.y_frame_stride = p.c_frame_stride = f.frame_samples();
+    if (f.chroma == vsio::Chroma::Mono) return p;
+    p.cb = (char*)base + (size_t)f.w * f.h * esz;
+    p.cr = (char*)p.cb + (size_t)f.cw() * f.ch() * esz;
+    p.c_stride = f.cw();
+    p.sub_x = f.chroma == vsio::Chroma::C444 ? 0 : 1; p.sub_y = f.chroma == vsio::Chroma::C420 ? 1 : 0;
+    return p;
+}
+
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom) {
+                         int deflicker_step, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom, bool device_convert) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -37,7 +53,8 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
     std::cout << "Writing processed video to: " << out_path << std::endl;
 
     const size_t esz = fin.bits > 8 ? 2 : 1;
-    const size_t in_elems = fin.bgr_elems(), out_elems = fout.bgr_elems();
+    const bool planes = device_convert && vsio::ends_with(in_path, ".y4m");      // raw planes in and out, converted on the device
+    const size_t in_elems = planes ? fin.frame_samples() : fin.bgr_elems(), out_elems = planes ? fout.frame_samples() : fout.bgr_elems();
     std::vector<uint8_t> h_in((size_t)chunk * in_elems * esz), h_out((size_t)chunk * out_elems * esz);
     vsh::DeviceBuffer d_in(h_in.size()), d_out(h_out.size());
     std::vector<int32_t> has_output((size_t)chunk);
@@ -109,8 +126,20 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
     bool ok = true;
     for (;;) {
         int n = 0;
-        while (n < chunk && reader.next(h_in.data() + (size_t)n * in_elems * esz)) n++;
+        while (n < chunk && (planes ? reader.next_planes(h_in.data() + (size_t)n * in_elems * esz) : reader.next(h_in.data() + (size_t)n * in_elems * esz))) n++;
         if (n == 0) break;
+        if (planes) {
+            int ow = 0, oh = 0;
+            const vs_ycbcr_planes pin = planes_of(fin, h_in.data()), pout = planes_of(fout, h_out.data());
+            const int r = vs_stabilizer_process_batch_ycbcr(stab, &pin, n, fin.w, fin.h, vsh::vs_format_of(fin), VS_MEM_HOST, &pout, has_output.data(), &ow, &oh);
+            if (r < 0) { std::cerr << "Error: vs_stabilizer_process_batch_ycbcr: " << vs_last_error() << std::endl; ok = false; break; }
+            for (int i = 0; i < n; i++)
+                if (has_output[i]) { writer.write_planes(h_out.data() + (size_t)i * out_elems * esz); written++; }
+            frame_count += n;
+            while (frame_count >= next_report) { std::cout << "Processed " << next_report << " frames..." << std::endl; next_report += 100; }
+            if (n < chunk) break;
+            continue;
+        }
         vsh::hip_check(hipMemcpy(d_in.ptr, h_in.data(), (size_t)n * in_elems * esz, hipMemcpyHostToDevice), "hipMemcpy H2D");
         int ow = 0, oh = 0;
         const int r = vs_stabilizer_process_batch(stab, d_in.ptr, in_elems, n, fin.w, fin.h, fin.w * 3, vsh::vs_format_of(fin), VS_MEM_DEVICE,
@@ -136,7 +165,7 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
 int main(int argc, char** argv) {
     std::string input_dir = "../recordings", output_dir = "output";   // video_test.cpp:12-13
     int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, denoise = 0, denoise_strength = 0, deflicker = 0, deflicker_step = 0, positional = 0;
-    bool bilinear = false, lanczos2 = false, force444 = false;
+    bool bilinear = false, lanczos2 = false, force444 = false, device_convert = false;
     vs_fill_blend_params blend{0, 0};
     bool inpaint = false;
     double rolling = 0.0, lens_zoom = 1.0;
@@ -171,9 +200,10 @@ int main(int argc, char** argv) {
         else if (a == "--bilinear") bilinear = true;
         else if (a == "--lanczos2") lanczos2 = true;
         else if (a == "--444") force444 = true;
+        else if (a == "--device-convert") device_convert = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444] [--device-convert]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -199,7 +229,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint, rolling, lens, lens_zoom)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, inpaint, rolling, lens, lens_zoom, device_convert)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

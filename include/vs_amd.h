@@ -471,6 +471,59 @@ int vs_bgr_remap_batch(const void* src, size_t src_frame_stride, int n, int w, i
 typedef struct vs_lens_params { double fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, zoom; int border; } vs_lens_params;
 void vs_lens_params_default(vs_lens_params* p, int w, int h);
 int  vs_lens_map(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride, int mem, void* stream);
+/* YCbCr FRAMES: decoders, cameras and encoders speak planar or semi-planar YCbCr, mostly 4:2:0; every other entry point of this library takes
+ * interleaved BGR.  The two calls below convert on the device, in front of and behind everything else, under an exact integer rule:
+ * BT.601 limited range in 8.8 fixed point, chroma replicated towards BGR and box-averaged towards YCbCr -- bit for bit what the harness
+ * programs' apps/video_io.hpp does on the host (vsio::ycbcr_to_bgr, vsio::bgr_to_ycbcr, Reader::unpack, Writer::pack).
+ * THE RULE (written once for host and device: video_stabilizer_amd/csrc/vs_ycbcr.hpp).  bits = vs_format_bits(format), sh = bits - 8,
+ * maxv = vs_format_max_value(format); every `>> 8` is an arithmetic shift, a floor.
+ *
+ * To BGR, pixel (x, y):
+ * - c = Y[y][x] - (16 << sh), d = Cb - (128 << sh), e = Cr - (128 << sh).
+ * - Cb and Cr are read at (x >> sub_x, y >> sub_y).  Without chroma planes both are 128 << sh.
+ * - r = clamp((298 c + 409 e + 128) >> 8, 0, maxv)
+ * - g = clamp((298 c - 100 d - 208 e + 128) >> 8, 0, maxv)
+ * - b = clamp((298 c + 516 d + 128) >> 8, 0, maxv)
+ * - Every container value is legal input; all sums stay inside int32 at 16 bits.
+ *
+ * To YCbCr:
+ * - Every BGR sample is first cut to min(sample, maxv).
+ * - y  = clamp(((66 r + 129 g + 25 b + 128) >> 8) + (16 << sh), 0, maxv)
+ * - cb = clamp(((-38 r - 74 g + 112 b + 128) >> 8) + (128 << sh), 0, maxv)
+ * - cr = clamp(((112 r - 94 g - 18 b + 128) >> 8) + (128 << sh), 0, maxv)
+ * - Chroma cell (cx, cy) averages the bx x by per-pixel values, bx = 1 << sub_x, by = 1 << sub_y, of the pixels
+ *   (min(cx bx + dx, w - 1), min(cy by + dy, h - 1)): (sum + cnt / 2) / cnt with cnt = bx by.
+ * - Chroma planes are (w + sub_x) >> sub_x by (h + sub_y) >> sub_y.
+ *
+ * Hence
+ *
+ * - (a) Gray BGR (b == g == r) gives neutral chroma, 128 << sh, exactly.
+ * - (b) With no chroma planes, to-BGR gives b == g == r.
+ * - (c) Every output is defined for every input.
+ * - (d) Both directions equal apps/video_io.hpp on every input.
+ *
+ * THE DESCRIPTOR.  I420, YV12, NV12, NV21, I422, I444 and luma-only frames are all instances of one struct; there is no enum of layouts.
+ * Elements are uint8_t at 8 bits and uint16_t above, with the samples in the LOW bits (y4m's layout, and VS_FMT_BGR10 / 12's).  P010's
+ * high-bit alignment is out of scope, as are BT.709 and full-range matrices and sited chroma filters: each is a rule of its own.
+ * With c_step == 2 the two chroma pointers are one element apart and a row of the pair is one run of 2 * chroma-width elements. */
+typedef struct vs_ycbcr_planes {
+    void *y, *cb, *cr;          /* frame 0's first samples; cb == cr == NULL: luma only (y4m "mono") */
+    int y_stride, c_stride;     /* elements between rows */
+    int c_step;                 /* elements between chroma samples of a row: 1 planar, 2 interleaved (NV12: cr == cb + 1, NV21: cb == cr + 1) */
+    int sub_x, sub_y;           /* log2 subsampling, 0 or 1 each: (1,1) 4:2:0, (1,0) 4:2:2, (0,0) 4:4:4 */
+    size_t y_frame_stride, c_frame_stride;   /* elements between frames */
+} vs_ycbcr_planes;
+/* n frames of w x h, w, h in 1 .. 32767 (VS_ERR_UNSUPPORTED beyond, as the remap); format: a VS_FMT_BGR* (VS_FMT_GRAY8: VS_ERR_ARG).
+ * VS_ERR_ARG also for a c_step that is not 1 or 2 (or 2 with chroma pointers that are not neighbours), a sub_* that is not 0 or 1, exactly
+ * one of cb / cr being NULL, and strides shorter than a row (frame strides shorter than a frame, for n > 1).  VS_MEM_DEVICE only enqueues;
+ * VS_MEM_HOST stages every plane's span as one dense copy (an interleaved pair is one span) and synchronises.  Destination bytes outside
+ * the rows' own samples are never written; with NULL chroma no chroma is written.  Where w is a multiple of 4 and every row of every
+ * plane and of the BGR side starts on a dword, a lane takes four columns with dword accesses; anything else takes one chroma cell per
+ * lane, element by element, with the same result. */
+int vs_ycbcr_to_bgr_batch(const vs_ycbcr_planes* src, int n, int w, int h, int format,
+                          void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+int vs_bgr_to_ycbcr_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
+                          const vs_ycbcr_planes* dst, int mem, void* stream);
 /* DEFLICKER: a frame's exposure is pulled to the average exposure of a window of frames, the exposure ratio of two frames being measured
  * at the same scene points through their measured motions (a pan changes a whole-frame sum because the content changes).  Interleaved
  * BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as in the fill); s = bits - 8.  The rule:
@@ -740,6 +793,18 @@ int  vs_stabilizer_process(vs_stabilizer* s, const void* frame, int w, int h, in
 int  vs_stabilizer_process_batch(vs_stabilizer* s, const void* frames, size_t frame_stride, int n, int w, int h, int stride,
                                  int format, int mem, void* out, size_t out_frame_stride, int32_t* has_output,
                                  int* out_w, int* out_h);
+/* The batched form on YCbCr frames (the descriptor and the rule: see vs_ycbcr_to_bgr_batch).  The result is, bit for bit,
+ * vs_ycbcr_to_bgr_batch(frames) -> vs_stabilizer_process_batch -> vs_bgr_to_ycbcr_batch of the frames that have an output: output frame i
+ * goes to index i of `out`, at out_w x out_h; `out` carries its own subsampling and layout; planes of frames without an output are not
+ * written.  A wrapper, not another engine: the planes are converted into a BGR buffer the handle keeps, the batch call runs on it in
+ * device memory, ordered on the handle's stream, and every contiguous run of output frames is converted back -- straight into device
+ * planes, or through staged spans for host callers.  The handle's two BGR buffers are grown on demand, freed by vs_stabilizer_destroy and
+ * never allocated unless this entry point is called: a handle that never calls it is the handle it was.  Every setting (lens, fill,
+ * deblur, denoise, rolling shutter, deflicker, inpaint), every error and the state protocol are the inner call's.  A failure before the
+ * inner call (an argument, an allocation, the conversion) leaves the stabilizer's state untouched; one behind it ends the running
+ * sequence like a failure of the inner call itself, and the handle stays usable.  Returns the number of output frames, or <0. */
+int  vs_stabilizer_process_batch_ycbcr(vs_stabilizer* s, const vs_ycbcr_planes* frames, int n, int w, int h, int format, int mem,
+                                       const vs_ycbcr_planes* out, int32_t* has_output, int* out_w, int* out_h);
 /* Many independent clips at once: n_clips clips of frames_per_clip frames back to back (clip c, frame k at index
  * c*frames_per_clip + k, outputs at the same index).  Results = every clip through its own fresh VideoStabilizer, with the
  * alignment and the warps of all clips batched together.  The handle is reset before the first and after the last clip. */

@@ -118,6 +118,15 @@ _vp, _i32, _f32, _f64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_siz
 _TP = C.POINTER(Transform)
 _IP = C.POINTER(C.c_int)
 
+
+class YcbcrPlanes(C.Structure):
+    """vs_ycbcr_planes: frame 0's first samples, strides in elements; cb == cr == None: luma only"""
+    _fields_ = [("y", _vp), ("cb", _vp), ("cr", _vp), ("y_stride", _i32), ("c_stride", _i32), ("c_step", _i32), ("sub_x", _i32), ("sub_y", _i32),
+                ("y_frame_stride", _sz), ("c_frame_stride", _sz)]
+
+
+_YP = C.POINTER(YcbcrPlanes)
+
 # name -> (restype, argtypes).  This table is also what tests/test_capi_symbols.py checks
 # against include/vs_amd.h.
 SIGNATURES = {
@@ -185,6 +194,9 @@ SIGNATURES = {
     "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(RollingParams),
                                     _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_remap_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_ycbcr_to_bgr_batch": (_i32, [_YP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_to_ycbcr_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _YP, _i32, _vp]),
+    "vs_stabilizer_process_batch_ycbcr": (_i32, [_vp, _YP, _i32, _i32, _i32, _i32, _i32, _YP, C.POINTER(C.c_int32), _IP, _IP]),
     "vs_lens_params_default": (None, [C.POINTER(LensParams), _i32, _i32]),
     "vs_lens_map": (_i32, [C.POINTER(LensParams), _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_deflicker_params_default": (None, [C.POINTER(DeflickerParams)]),
@@ -906,6 +918,107 @@ def remap_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, map_ptr, map_s
                                     MEM_DEVICE, C.c_void_p(stream) if stream else None))
 
 
+# ---- YCbCr frames (include/vs_amd.h: vs_ycbcr_to_bgr_batch; the rule: csrc/vs_ycbcr.hpp) ----
+def chroma_shape(w, h, sub):
+    """(cw, ch) of a w x h frame's chroma planes under sub = (sub_x, sub_y)"""
+    return (w + sub[0]) >> sub[0], (h + sub[1]) >> sub[1]
+
+
+def ycbcr_planes(y, cb, cr, y_stride, c_stride, c_step, sub, y_frame_stride, c_frame_stride):
+    """a vs_ycbcr_planes from raw addresses (ints; cb = cr = None: luma only), strides in elements"""
+    vp = (lambda a: None if a is None else C.c_void_p(int(a)))
+    return YcbcrPlanes(vp(y), vp(cb), vp(cr), int(y_stride), int(c_stride), int(c_step), int(sub[0]), int(sub[1]), int(y_frame_stride), int(c_frame_stride))
+
+
+class _HostPlanes:
+    """the planes of n frames in host buffers of their own, as the host forms below lay them out: Y rows of y_stride elements; chroma planar
+    (two buffers, rows of c_stride) or, interleaved = "nv12" (Cb first) / "nv21" (Cr first), one buffer of pairs.  Every buffer has two guard
+    rows in front and two behind; `fill` is what buffers and padding start with.  desc: the vs_ycbcr_planes of it"""
+
+    def __init__(self, n, w, h, dtype, sub, interleaved, mono, y_stride, c_stride, fill):
+        cw, ch = chroma_shape(w, h, sub)
+        self.n, self.w, self.h, self.cw, self.ch, self.sub, self.interleaved, self.mono = n, w, h, cw, ch, sub, interleaved, mono
+        step = 2 if interleaved else 1
+        self.ys = w if y_stride is None else y_stride
+        self.cs = cw * step if c_stride is None else c_stride
+        self.ybuf = np.full((n * h + 4, self.ys), fill, dtype)
+        self.cbufs = [] if mono else [np.full((n * ch + 4, self.cs), fill, dtype) for _ in range(1 if interleaved else 2)]
+        esz = np.dtype(dtype).itemsize
+        ya = self.ybuf[2:].ctypes.data
+        if mono:
+            ca = ra = None
+        elif interleaved:
+            base = self.cbufs[0][2:].ctypes.data
+            ca, ra = (base, base + esz) if interleaved == "nv12" else (base + esz, base)
+        else:
+            ca, ra = self.cbufs[0][2:].ctypes.data, self.cbufs[1][2:].ctypes.data
+        self.desc = ycbcr_planes(ya, ca, ra, self.ys, self.cs, step, sub, h * self.ys, ch * self.cs)
+
+    def _views(self):
+        n, w, h, cw, ch = self.n, self.w, self.h, self.cw, self.ch
+        yv = self.ybuf[2:2 + n * h].reshape(n, h, self.ys)[:, :, :w]
+        if self.mono:
+            return yv, None, None
+        if self.interleaved:
+            pairs = self.cbufs[0][2:2 + n * ch].reshape(n, ch, self.cs)[:, :, :2 * cw]
+            first, second = pairs[:, :, 0::2], pairs[:, :, 1::2]
+            return (yv, first, second) if self.interleaved == "nv12" else (yv, second, first)
+        return (yv,) + tuple(b[2:2 + n * ch].reshape(n, ch, self.cs)[:, :, :cw] for b in self.cbufs)
+
+    def put(self, y, cb, cr):
+        yv, cbv, crv = self._views()
+        yv[...] = y
+        if not self.mono:
+            cbv[...] = cb
+            crv[...] = cr
+
+    def get(self):
+        return tuple(None if v is None else np.ascontiguousarray(v) for v in self._views())
+
+    def buffers(self):
+        return [self.ybuf] + self.cbufs
+
+
+def ycbcr_to_bgr_batch(y, cb=None, cr=None, sub=(1, 1), fmt=None, interleaved=None, y_stride=None, c_stride=None, dst_stride=None, guard=None):
+    """YCbCr planes -> interleaved BGR (include/vs_amd.h: vs_ycbcr_to_bgr_batch).  y (n,h,w) numpy; cb, cr (n,ch,cw) or both None (luma only);
+    sub = (sub_x, sub_y): log2 subsampling; interleaved: None (planar), "nv12" or "nv21" (the chroma travels as one plane of pairs) -> (n,h,w,3).
+    y_stride / c_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with
+    first; the padded buffer is returned as well"""
+    y = np.ascontiguousarray(y)
+    n, h, w = y.shape
+    fmt = _fmt_of(y.dtype, 3) if fmt is None else fmt
+    hp = _HostPlanes(n, w, h, y.dtype, sub, interleaved, cb is None, y_stride, c_stride, 0)
+    hp.put(y, cb, cr)
+    ds = 3 * w if dst_stride is None else dst_stride
+    out = np.full((n, h, ds), 0 if guard is None else guard, y.dtype)
+    _check(lib().vs_ycbcr_to_bgr_batch(C.byref(hp.desc), n, w, h, fmt, _p(out), h * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:, :, :3 * w]).reshape(n, h, w, 3)
+    return (res, out) if guard is not None else res
+
+
+def ycbcr_to_bgr_batch_device(planes, n, w, h, fmt, dst_ptr, dst_fs, dst_stride, stream=None):
+    """device-resident form: planes is a YcbcrPlanes of device addresses (ycbcr_planes), strides in elements, enqueue only"""
+    _check(lib().vs_ycbcr_to_bgr_batch(C.byref(planes), n, w, h, fmt, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
+def bgr_to_ycbcr_batch(src, sub=(1, 1), fmt=None, interleaved=None, mono=False, src_stride=None, y_stride=None, c_stride=None, guard=None):
+    """interleaved BGR -> YCbCr planes (include/vs_amd.h: vs_bgr_to_ycbcr_batch).  src (n,h,w,3) numpy -> (y (n,h,w), cb, cr (n,ch,cw)); mono:
+    luma only, cb and cr come back None.  Strides in elements: the call is made on pitched buffers.  guard: a value the destination buffers --
+    two rows in front, two behind and the padding -- are filled with first; the whole buffers are returned as well, as a list"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    hp = _HostPlanes(n, w, h, src.dtype, sub, interleaved, mono, y_stride, c_stride, 0 if guard is None else guard)
+    _check(lib().vs_bgr_to_ycbcr_batch(_p(_pitched(src, ss)), h * ss, n, w, h, ss, fmt, C.byref(hp.desc), MEM_HOST, None))
+    return (hp.get(), hp.buffers()) if guard is not None else hp.get()
+
+
+def bgr_to_ycbcr_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, planes, stream=None):
+    """device-resident form: frames and planes (a YcbcrPlanes of device addresses) in device memory, strides in elements, enqueue only"""
+    _check(lib().vs_bgr_to_ycbcr_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, C.byref(planes), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
 def deflicker_params(**kw):
     p = DeflickerParams()
     lib().vs_deflicker_params_default(C.byref(p))
@@ -1357,6 +1470,32 @@ class Stabilizer:
         r = _check(lib().vs_stabilizer_process_batch(self.h, _p(ptr), h * w * 3, n, w, h, w * 3, fmt, MEM_DEVICE, _p(out_ptr),
                                                      (h - 2 * c) * (w - 2 * c) * 3, has, C.byref(ow), C.byref(oh)))
         return r, list(has)
+
+    def process_batch_ycbcr(self, y, cb=None, cr=None, sub=(1, 1), fmt=None, interleaved=None, out_sub=None, out_interleaved="same", out_mono=None,
+                            guard=None):
+        """the batched form on YCbCr planes in host memory (vs_stabilizer_process_batch_ycbcr): y (n,h,w), cb, cr (n,ch,cw) or None (luma
+        only), laid out as in ycbcr_to_bgr_batch.  out_sub / out_interleaved / out_mono: the layout of the output planes (default: the
+        input's).  -> ((y, cb, cr) at the output size, has_output list); frames without an output keep `guard` (default 0)"""
+        y = np.ascontiguousarray(y)
+        n, hh, ww = y.shape
+        fmt = _fmt_of(y.dtype, 3) if fmt is None else fmt
+        c = max(self.params.crop_pixels, 0)
+        src = _HostPlanes(n, ww, hh, y.dtype, sub, interleaved, cb is None, None, None, 0)
+        src.put(y, cb, cr)
+        dst = _HostPlanes(n, ww - 2 * c, hh - 2 * c, y.dtype, sub if out_sub is None else out_sub, interleaved if out_interleaved == "same" else out_interleaved,
+                          (cb is None) if out_mono is None else out_mono, None, None, 0 if guard is None else guard)
+        has = (C.c_int32 * n)()
+        ow, oh = C.c_int(), C.c_int()
+        _check(lib().vs_stabilizer_process_batch_ycbcr(self.h, C.byref(src.desc), n, ww, hh, fmt, MEM_HOST, C.byref(dst.desc), has, C.byref(ow), C.byref(oh)))
+        assert (ow.value, oh.value) == (ww - 2 * c, hh - 2 * c)
+        return dst.get(), list(has)
+
+    def process_batch_ycbcr_device(self, planes, n, w, h, fmt, out_planes):
+        """device-resident form: planes / out_planes are YcbcrPlanes of device addresses (ycbcr_planes) -> (outputs, has_output, out_w, out_h)"""
+        has = (C.c_int32 * n)()
+        ow, oh = C.c_int(), C.c_int()
+        r = _check(lib().vs_stabilizer_process_batch_ycbcr(self.h, C.byref(planes), n, w, h, fmt, MEM_DEVICE, C.byref(out_planes), has, C.byref(ow), C.byref(oh)))
+        return r, list(has), ow.value, oh.value
 
     def process_clips(self, frames, n_clips, fmt=None):
         """frames (n_clips*fpc, h, w, 3) numpy: every clip through a fresh stabilizer, batched together"""

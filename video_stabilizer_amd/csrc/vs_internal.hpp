@@ -173,6 +173,13 @@ int fill_coverage_ptrs(int n_out, int w, int h, int n_cand, const void* const* c
                        int roi_h, uint8_t* cov, size_t cov_fs, int cov_stride, uint32_t* open_count, hipStream_t s, const char* fn);
 
 bool device_ready();   // true when a HIP device is usable (sets last error otherwise)
+// What vs_stabilizer_process_batch_ycbcr (vs_capi_ycbcr.hip), a wrapper around vs_stabilizer_process_batch, needs of a handle (vs_stabilizer.hip):
+// the two BGR buffers the handle keeps for it -- [0] the converted input batch, [1] the inner call's outputs; grown on demand, never allocated
+// unless that entry point is called, freed by vs_stabilizer_destroy -- the crop in force and the handle's device.
+struct YcbcrHold { void* buf[2] = {nullptr, nullptr}; size_t bytes[2] = {0, 0}; };
+YcbcrHold* stab_ycbcr_hold(vs_stabilizer* s);
+int stab_crop(const vs_stabilizer* s);      // max(crop_pixels, 0)
+int stab_device(const vs_stabilizer* s);
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the
 // standard 31 KB window does (with the CU's slack), the COMPACT six-wave instantiation's 26 KB does not (c5: 20.3 k -> 18.4 k frames/s with it).  Thread-local:

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 struct vs_lens_params;      // include/vs_amd.h
+struct vs_ycbcr_planes;
 
 namespace vsk {
 
@@ -113,6 +114,12 @@ constexpr int kRemapSlice = 8;
 hipError_t bgr_remap(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const int32_t* map,
                      int map_stride, int ow, int oh, int border, void* dst, size_t dst_fs, int dst_stride, int slice, hipStream_t s);
 hipError_t lens_map(const vs_lens_params& p, int w, int h, int32_t* map, int map_stride, hipStream_t s);
+// YCbCr frames to interleaved BGR and back (vs_ycbcr.hip: the kernels; vs_ycbcr.hpp: the rule).  The descriptor holds device pointers; bits:
+// vs_format_bits (8, 10, 12, 16), max_value: vs_format_max_value; w, h in 1 .. 32767 and a descriptor vsy::layout_ok accepts, hipErrorNotSupported
+// otherwise.  Four columns per lane with dword accesses where w % 4 == 0 and every row of every plane and of the BGR side starts on a dword,
+// one chroma cell per lane otherwise: the same bits.
+hipError_t ycbcr_to_bgr(const vs_ycbcr_planes& src, int n_frames, int w, int h, int bits, int max_value, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
+hipError_t bgr_to_ycbcr(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const vs_ycbcr_planes& dst, hipStream_t s);
 // Deflicker (vs_deflicker.hip: the rule and the kernels).  exposure_stats: cands_dev = n_frames x n_cand entries in device memory (entry 0 of a
 // frame is the target, a null frame ends the list); stats = n_frames x n_cand x 8 words in device memory, zeroed on `s` first.  exposure_gains:
 // gains[4 o + {0..2: G_c, 3: m}] from the statistics.  bgr_gain: frame i scaled by gains[4 i ..] (clamped to 16384 .. 65536); dst may be src.

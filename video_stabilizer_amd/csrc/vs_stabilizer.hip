@@ -91,6 +91,7 @@ struct vs_stabilizer {
     vs_transform accum{0, 0, 0, 0}, last_meas{0, 0, 0, 0};
     int last_success = 0;
     int w = 0, h = 0, fmt = -1;
+    vsi::YcbcrHold ycbcr;          // vs_stabilizer_process_batch_ycbcr's two BGR buffers (vs_capi_ycbcr.hip); empty unless that entry point is called
 };
 
 static void sharp_unhold(vs_stabilizer* s, vs_stabilizer::Held& f) {
@@ -140,6 +141,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     if (s->lens_map) (void)hipFree(s->lens_map);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
+    for (void* q : s->ycbcr.buf) if (q) (void)hipFree(q);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
@@ -155,6 +157,12 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
 }
 
 }  // extern "C"
+
+namespace vsi {
+YcbcrHold* stab_ycbcr_hold(vs_stabilizer* s) { return &s->ycbcr; }
+int stab_crop(const vs_stabilizer* s) { return s->params.crop_pixels > 0 ? s->params.crop_pixels : 0; }
+int stab_device(const vs_stabilizer* s) { return aligner_device(s->aligner); }
+}  // namespace vsi
 
 // One vs_stabilizer_process_batch / _clips call, or a run of its frames; strides in elements.  clip_len > 0: the n frames are n / clip_len
 // independent clips, each run through a fresh stabilizer (reset before every clip and after the last), all of them aligned and warped together.
