@@ -30,6 +30,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -183,7 +185,9 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur(const vsk::Debl
     bool any = false;                                                     // uniform: the ratios are the same for every wave of the frame
     for (int c = 1; c < n_cand; c++) any = any || r2s[c] >= 0.0f;
     if (!any) {
-        // no sharper candidate: a copy.  Rows whose both ends allow it move as dwords (the strip's first byte is 192 * sizeof(T) * txi into its row)
+        // no sharper candidate: a copy.  Rows whose both ends allow it move as dwords (the strip's first byte is 192 * sizeof(T) * txi into its row).
+        // vs_cv_sample.hpp's strip_copy, written out: called from here it changes what the compiler makes of the candidate loop below
+        // (profiles/lookahead_shared_sampler.md)
         const size_t row_bytes = (size_t)nx * 3 * sizeof(T);
         const bool wide = (((uintptr_t)tgt | (uintptr_t)dst | ((size_t)src_stride * sizeof(T)) | ((size_t)dst_stride * sizeof(T))) & 3) == 0;
         for (int y = y0; y < y1; y++) {
@@ -275,8 +279,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
         float a[12], W[4];
         int gk[4];
 #pragma unroll
-        for (int k = 0; k < 12; k++)
-            a[k] = (float)(sizeof(T) == 1 ? (d[k / 4] >> (8 * (k % 4))) & 255u : (d[k / 2] >> (16 * (k % 2))) & 65535u);
+        for (int k = 0; k < 12; k++) a[k] = (float)px_get<T>(d, k);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t g = (((uint32_t)a[3 * i] * 3735u + (uint32_t)a[3 * i + 1] * 19235u + (uint32_t)a[3 * i + 2] * 9798u + 16384u) >> 15) >> shift;
@@ -310,7 +313,7 @@ __global__ __launch_bounds__(64 * DB_WAVES) void vs_k_bgr_deblur_x4(const vsk::D
 #pragma unroll
         for (int k = 0; k < 12; k++) {
             const uint32_t v = (uint32_t)min(max((int)floorf(a[k] / W[k / 3] + 0.5f), 0), maxv);
-            if (sizeof(T) == 1) o[k / 4] |= v << (8 * (k % 4)); else o[k / 2] |= v << (16 * (k % 2));
+            px_put<T>(o, k, v);
         }
         uint32_t* const op = (uint32_t*)(dst + VS_IDX((size_t)y * (size_t)dst_stride, (long long)(h - 1) * dst_stride + 1, 516) + VS_IDX((size_t)x * 3, 3LL * w - 11, 516));
 #pragma unroll
@@ -330,11 +333,10 @@ hipError_t bgr_sharpness(const void* src, int w, int h, int src_stride, int bits
     hipError_t e = hipMemsetAsync(out, 0, (size_t)n_frames * sizeof(unsigned long long), s);
     if (e != hipSuccess || w < 3 || h < 3) return e;
     const size_t esz = (size_t)bits / 8;
-    const bool x4 = w % 4 == 0 && (((uintptr_t)src | ((size_t)src_stride * esz) | (n_frames > 1 ? src_fs * esz : 0)) & 3) == 0;
+    const bool x4 = w % 4 == 0 && rows_on_dwords(src, src_stride, src_fs, n_frames, esz);
     const int cols = x4 ? SV_COLS : SH_COLS;
     const int tiles_x = (w - 2 + cols - 1) / cols, tiles_y = (h - 2 + SH_ROWS * SH_WAVES - 1) / (SH_ROWS * SH_WAVES);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * SH_WAVES);
         const char* sp = (const char*)src + (size_t)f0 * src_fs * esz;
         if (x4 && bits == 16)
@@ -345,23 +347,21 @@ hipError_t bgr_sharpness(const void* src, int w, int h, int src_stride, int bits
             hipLaunchKernelGGL(vs_k_bgr_sharpness<uint16_t>, grid, block, 0, s, (const uint16_t*)sp, w, h, src_stride, shift_to_8, src_fs, out + f0, tiles_x);
         else
             hipLaunchKernelGGL(vs_k_bgr_sharpness<uint8_t>, grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, shift_to_8, src_fs, out + f0, tiles_x);
-    }
+    });
     return hipGetLastError();
 }
 
 hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value,
                       float sensitivity, float max_ratio, void* dst, int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (shift_to_8 < 0 || shift_to_8 > 8 || n_cand < 1 || n_frames < 1 || w < 1 || h < 1) return hipErrorNotSupported;
     hipLaunchKernelGGL(vs_k_deblur_ratio, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), 0, s, cands_dev, n_cand, n_frames, max_ratio, r2_dev);
     const size_t esz = (size_t)bits / 8;
     // four pixels per lane with dword accesses where every target row and every destination row starts on a dword
-    const bool x4 = targets_aligned && w % 4 == 0 && (((size_t)src_stride * esz) & 3) == 0 &&
-                    (((uintptr_t)dst | ((size_t)dst_stride * esz) | (n_frames > 1 ? dst_fs * esz : 0)) & 3) == 0;
+    const bool x4 = targets_aligned && w % 4 == 0 && rows_on_dwords(nullptr, src_stride, 0, 1, esz) && rows_on_dwords(dst, dst_stride, dst_fs, n_frames, esz);
     const int tw = x4 ? 4 * DB_W : DB_W;
     const int tiles_x = (w + tw - 1) / tw, tiles_y = (h + DB_ROWS * DB_WAVES - 1) / (DB_ROWS * DB_WAVES);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * DB_WAVES);
         const DeblurCand* cp = cands_dev + (size_t)f0 * (size_t)n_cand;
         const float* rp = r2_dev + (size_t)f0 * (size_t)n_cand;
@@ -378,7 +378,7 @@ hipError_t bgr_deblur(const DeblurCand* cands_dev, float* r2_dev, int n_cand, in
         else
             hipLaunchKernelGGL(vs_k_bgr_deblur<uint8_t>, grid, block, 0, s, cp, rp, n_cand, w, h, src_stride, shift_to_8, max_value, sensitivity, (uint8_t*)dp,
                                dst_stride, dst_fs, tiles_x);
-    }
+    });
     return hipGetLastError();
 }
 

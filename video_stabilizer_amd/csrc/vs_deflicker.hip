@@ -47,6 +47,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -180,10 +182,10 @@ __global__ __launch_bounds__(64 * GN_WAVES) void vs_k_bgr_gain(const T* src, int
             uint32_t e[3] = {0u, 0u, 0u};
             if (sizeof(T) == 1) {
 #pragma unroll
-                for (int k = 0; k < 12; k++) e[k / 4] |= gn_apply((d[k / 4] >> (8 * (k % 4))) & 255u, g[k % 3], lim) << (8 * (k % 4));
+                for (int k = 0; k < 12; k++) px_put<T>(e, k, gn_apply(px_get<T>(d, k), g[k % 3], lim));
             } else {
 #pragma unroll
-                for (int k = 0; k < 6; k++) e[k / 2] |= gn_apply((d[k / 2] >> (16 * (k % 2))) & 65535u, g[k % 3], lim) << (16 * (k % 2));
+                for (int k = 0; k < 6; k++) px_put<T>(e, k, gn_apply(px_get<T>(d, k), g[k % 3], lim));
             }
             op[0] = e[0]; op[1] = e[1]; op[2] = e[2];
         } else {
@@ -243,16 +245,14 @@ hipError_t exposure_gains(const unsigned long long* stats, int n_out, int n_cand
 
 hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int max_value, const uint32_t* gains, void* dst, int dst_stride, int n_frames,
                     size_t src_fs, size_t dst_fs, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (w < 1 || h < 1 || n_frames < 1) return hipErrorNotSupported;
     const size_t esz = (size_t)bits / 8;
     // dword accesses where every row of every frame starts on a dword, in the source and in the destination
-    const bool x4 = (((uintptr_t)src | (uintptr_t)dst | ((size_t)src_stride * esz) | ((size_t)dst_stride * esz) |
-                      (n_frames > 1 ? (src_fs * esz) | (dst_fs * esz) : 0)) & 3) == 0;
+    const bool x4 = rows_on_dwords(src, src_stride, src_fs, n_frames, esz) && rows_on_dwords(dst, dst_stride, dst_fs, n_frames, esz);
     const int g = x4 ? (bits == 16 ? 2 : 4) : 1;
     const int tiles_x = (w + 64 * g - 1) / (64 * g), tiles_y = (h + GN_ROWS * GN_WAVES - 1) / (GN_ROWS * GN_WAVES);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * GN_WAVES);
         const char* sp = (const char*)src + (size_t)f0 * src_fs * esz;
         char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
@@ -265,7 +265,7 @@ hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int
             hipLaunchKernelGGL((vs_k_bgr_gain<uint16_t, false>), grid, block, 0, s, (const uint16_t*)sp, w, h, src_stride, src_fs, gp, max_value, (uint16_t*)dp, dst_stride, dst_fs, tiles_x);
         else
             hipLaunchKernelGGL((vs_k_bgr_gain<uint8_t, false>), grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, src_fs, gp, max_value, (uint8_t*)dp, dst_stride, dst_fs, tiles_x);
-    }
+    });
     return hipGetLastError();
 }
 

@@ -39,6 +39,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -48,30 +50,9 @@ constexpr int DN_W = 64, DN_WAVES = 4;                    // a wave's strip is 6
 constexpr int DN_ROWS = 8, DN_ROWS_X4 = 4;                // rows of a strip: per-sample kernel / four-pixel kernel
 
 // The bounds build (-DVS_DEBUG_BOUNDS, vs_device.hpp) checks every gather and every store of this file, sites 531-544: an element offset within
-// a frame, the access's last sample included, lies below (h - 1) * stride + 3 w (531-534 the copy; 535 / 541 the per-sample kernel's target row
+// a frame, the access's last sample included, lies below (h - 1) * stride + 3 w (531-534 the copy, strip_copy<T, 531> of vs_cv_sample.hpp; 535 / 541 the per-sample kernel's target row
 // and column offsets, 536 its gathers, 537 / 542 its store's row and column offsets; 538 / 543, 539, 540 / 544 likewise in the four-pixel kernel).
 // The extents are written inside the macros' arguments, which the regular build drops.
-
-// VS_WARP_BILINEAR_CV's value at a position whose four taps lie inside the frame (vs_fill.hip's cv_sample_inside, operation for operation).
-// r0: the first tap
-__device__ __forceinline__ void cv_blend(GPtr<uint8_t> r0, int stride, CvPos p, int, uint32_t q[3]) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    GPtr<uint8_t> r1 = r0 + stride;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        q[c] = (uint32_t)(((int)r0[c] * (a0 * b0) + (int)r0[c + 3] * (a1 * b0) + (int)r1[c] * (a0 * b1) + (int)r1[c + 3] * (a1 * b1) + 512) >> 10);
-}
-__device__ __forceinline__ void cv_blend(GPtr<uint16_t> r0, int stride, CvPos p, int maxv, uint32_t q[3]) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    GPtr<uint16_t> r1 = r0 + stride;
-    const float k = 1.0f / 1024.0f;
-    const float w00 = (float)(a0 * b0) * k, w01 = (float)(a1 * b0) * k, w10 = (float)(a0 * b1) * k, w11 = (float)(a1 * b1) * k;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float sum = (float)r0[c] * w00 + (float)r0[c + 3] * w01 + (float)r1[c] * w10 + (float)r1[c + 3] * w11;
-        q[c] = (uint32_t)min(max((int)rintf(sum), 0), maxv);
-    }
-}
 
 // one candidate at one pixel: p (the target's samples), acc / W (the sums so far)
 template <typename T>
@@ -80,7 +61,7 @@ __device__ __forceinline__ void dn_take(GPtr<T> cs, int w, int h, int stride, Cv
     if (!cv_covers(pos, w, h)) return;
     uint32_t q[3];
     // (the four taps' last sample lies stride + 5 behind the first)
-    cv_blend(cs + VS_IDX((size_t)(pos.Y >> 5) * (size_t)stride + (size_t)(pos.X >> 5) * 3, (long long)(h - 2) * stride + 3LL * w - 5, site), stride, pos, maxv, q);
+    cv_sample_inside<T>(cs + VS_IDX((size_t)(pos.Y >> 5) * (size_t)stride + (size_t)(pos.X >> 5) * 3, (long long)(h - 2) * stride + 3LL * w - 5, site), stride, pos, maxv, q);
     uint32_t d = 0;
 #pragma unroll
     for (int c = 0; c < 3; c++) d = max(d, (uint32_t)abs((int)p[c] - (int)q[c]));
@@ -109,27 +90,6 @@ __device__ __forceinline__ void dn_finish(const uint32_t p[3], const uint32_t ac
     for (int c = 0; c < 3; c++) out[c] = W == t ? p[c] : min(dn_div(2u * acc[c] + W, 2u * W, rd), maxv);
 }
 
-// a frame without candidates: the wave's nx x (y1 - y0) strip at (x0, y0) is copied, as dwords where both rows allow it
-template <typename T>
-__device__ __forceinline__ void dn_copy(const T* __restrict__ tgt, T* __restrict__ dst, int w, int h, int src_stride, int dst_stride, int x0, int nx, int y0,
-                                        int y1, int lane) {
-    const size_t row_bytes = (size_t)nx * 3 * sizeof(T);
-    const bool wide = (((uintptr_t)tgt | (uintptr_t)dst | ((size_t)src_stride * sizeof(T)) | ((size_t)dst_stride * sizeof(T)) | ((size_t)x0 * 3 * sizeof(T))) & 3) == 0;
-    for (int y = y0; y < y1; y++) {
-        const uint8_t* const sp = (const uint8_t*)(tgt + (size_t)y * (size_t)src_stride + (size_t)x0 * 3);
-        uint8_t* const dp = (uint8_t*)(dst + (size_t)y * (size_t)dst_stride + (size_t)x0 * 3);
-        size_t done = 0;
-        if (wide) {
-            const size_t nd = row_bytes / 4;
-            for (size_t i = lane; i < nd; i += 64)
-                ((uint32_t*)dp)[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 531)] = ((const uint32_t*)sp)[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 532)];
-            done = nd * 4;
-        }
-        for (size_t i = done + lane; i < row_bytes; i += 64)
-            dp[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T), 533)] = sp[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T), 534)];
-    }
-}
-
 // cands: n_cand entries per output frame (gridDim.y frames); entry 0 = the target frame (its matrix is not read), a null frame ends the list
 template <typename T>
 __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise(const vsk::FillCand* __restrict__ cands, int n_cand, int w, int h, int src_stride, int shift,
@@ -144,7 +104,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise(const vsk::Fil
     dst += (size_t)blockIdx.y * dst_fs;
     const T* const tgt = (const T*)cands[0].src;
     if (n_cand < 2 || cands[1].src == nullptr) {                          // uniform: only the frame itself
-        dn_copy(tgt, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
+        strip_copy<T, 531>(tgt, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
         return;
     }
     const int x = min(x0 + lane, w - 1);                                  // (lanes past the row compute on its last column and store nothing)
@@ -203,7 +163,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise_x4(const vsk::
     dst += (size_t)blockIdx.y * dst_fs;
     const T* const tgt = (const T*)cands[0].src;
     if (n_cand < 2 || cands[1].src == nullptr) {                          // uniform: only the frame itself
-        dn_copy(tgt, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
+        strip_copy<T, 531>(tgt, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
         return;
     }
     const int x = min(x0 + 4 * lane, w - 4);                              // (lanes past the row compute on its last group and store nothing)
@@ -217,7 +177,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise_x4(const vsk::
 #pragma unroll
         for (int k = 0; k < ND; k++) d[r][k] = tp[k];
 #pragma unroll
-        for (int k = 0; k < 12; k++) acc[r][k] = t * (sizeof(T) == 1 ? (d[r][k / 4] >> (8 * (k % 4))) & 255u : (d[r][k / 2] >> (16 * (k % 2))) & 65535u);
+        for (int k = 0; k < 12; k++) acc[r][k] = t * px_get<T>(d[r], k);
 #pragma unroll
         for (int i = 0; i < 4; i++) W[r][i] = t;
     }
@@ -240,8 +200,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise_x4(const vsk::
                 for (int i = 0; i < 4; i++) {
                     uint32_t p[3];
 #pragma unroll
-                    for (int k = 0; k < 3; k++)
-                        p[k] = sizeof(T) == 1 ? (d[r][(3 * i + k) / 4] >> (8 * ((3 * i + k) % 4))) & 255u : (d[r][(3 * i + k) / 2] >> (16 * ((3 * i + k) % 2))) & 65535u;
+                    for (int k = 0; k < 3; k++) p[k] = px_get<T>(d[r], 3 * i + k);
                     dn_take(cs, w, h, src_stride, cv_pos(X0, Y0, ad[i], bd[i]), maxv, shift, t, 539, p, &acc[r][3 * i], W[r][i]);
                 }
             }
@@ -258,14 +217,10 @@ __global__ __launch_bounds__(64 * DN_WAVES) void vs_k_bgr_denoise_x4(const vsk::
         for (int i = 0; i < 4; i++) {
             uint32_t p[3], v[3];
 #pragma unroll
-            for (int k = 0; k < 3; k++)
-                p[k] = sizeof(T) == 1 ? (d[r][(3 * i + k) / 4] >> (8 * ((3 * i + k) % 4))) & 255u : (d[r][(3 * i + k) / 2] >> (16 * ((3 * i + k) % 2))) & 65535u;
+            for (int k = 0; k < 3; k++) p[k] = px_get<T>(d[r], 3 * i + k);
             dn_finish(p, &acc[r][3 * i], W[r][i], t, (uint32_t)maxv, v);
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int j = 3 * i + k;
-                if (sizeof(T) == 1) o[j / 4] |= v[k] << (8 * (j % 4)); else o[j / 2] |= v[k] << (16 * (j % 2));
-            }
+            for (int k = 0; k < 3; k++) px_put<T>(o, 3 * i + k, v[k]);
         }
         uint32_t* const op = (uint32_t*)(dst + VS_IDX((size_t)(y0 + r) * (size_t)dst_stride, (long long)(h - 1) * dst_stride + 1, 540) + VS_IDX((size_t)x * 3, 3LL * w - 11, 544));
 #pragma unroll
@@ -281,17 +236,15 @@ namespace vsk {
 
 hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int strength, void* dst,
                        int dst_stride, int n_frames, size_t dst_fs, bool targets_aligned, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (shift_to_8 < 0 || shift_to_8 > 8 || n_cand < 1 || n_cand > 16 || n_frames < 1 || w < 1 || h < 1 || w > 32767 || h > 32767) return hipErrorNotSupported;
     if (strength < 1 || strength > 255) return hipErrorNotSupported;
     const size_t esz = (size_t)bits / 8;
     // four pixels per lane with dword accesses where every target row and every destination row starts on a dword
-    const bool x4 = targets_aligned && w % 4 == 0 && (((size_t)src_stride * esz) & 3) == 0 &&
-                    (((uintptr_t)dst | ((size_t)dst_stride * esz) | (n_frames > 1 ? dst_fs * esz : 0)) & 3) == 0;
+    const bool x4 = targets_aligned && w % 4 == 0 && rows_on_dwords(nullptr, src_stride, 0, 1, esz) && rows_on_dwords(dst, dst_stride, dst_fs, n_frames, esz);
     const int tw = x4 ? 4 * DN_W : DN_W, th = (x4 ? DN_ROWS_X4 : DN_ROWS) * DN_WAVES;
     const int tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * DN_WAVES);
         const FillCand* cp = cands_dev + (size_t)f0 * (size_t)n_cand;
         char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
@@ -307,7 +260,7 @@ hipError_t bgr_denoise(const FillCand* cands_dev, int n_cand, int w, int h, int 
         else
             hipLaunchKernelGGL(vs_k_bgr_denoise<uint8_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, shift_to_8, max_value, strength, (uint8_t*)dp,
                                dst_stride, dst_fs, tiles_x);
-    }
+    });
     return hipGetLastError();
 }
 

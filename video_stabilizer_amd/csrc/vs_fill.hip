@@ -33,7 +33,9 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
 #include "vs_cover.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -41,26 +43,12 @@ namespace {
 
 // (the strip and block constants FL_* and cv_covers_rect: vs_cover.hpp, shared with the coverage index of vs_inpaint.hip)
 
-// one output pixel of a candidate that covers it: all four taps inside the frame
-__device__ __forceinline__ void cv_sample_inside(const uint8_t* __restrict__ src, int stride, CvPos p, int, uint8_t* __restrict__ out) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    const uint8_t* r0 = src + (size_t)(p.Y >> 5) * (size_t)stride + (size_t)(p.X >> 5) * 3;
-    const uint8_t* r1 = r0 + stride;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        out[c] = (uint8_t)(((int)r0[c] * (a0 * b0) + (int)r0[c + 3] * (a1 * b0) + (int)r1[c] * (a0 * b1) + (int)r1[c + 3] * (a1 * b1) + 512) >> 10);
-}
-__device__ __forceinline__ void cv_sample_inside(const uint16_t* __restrict__ src, int stride, CvPos p, int maxv, uint16_t* __restrict__ out) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    const uint16_t* r0 = src + (size_t)(p.Y >> 5) * (size_t)stride + (size_t)(p.X >> 5) * 3;
-    const uint16_t* r1 = r0 + stride;
-    const float k = 1.0f / 1024.0f;
-    const float w00 = (float)(a0 * b0) * k, w01 = (float)(a1 * b0) * k, w10 = (float)(a0 * b1) * k, w11 = (float)(a1 * b1) * k;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float sum = (float)r0[c] * w00 + (float)r0[c + 3] * w01 + (float)r1[c] * w10 + (float)r1[c + 3] * w11;
-        out[c] = (uint16_t)min(max((int)rintf(sum), 0), maxv);
-    }
+// one output pixel of a candidate that covers it, all four taps inside the frame: vs_cv_sample.hpp's cv_sample_inside on the first tap
+template <typename T>
+__device__ __forceinline__ void fill_sample(const T* __restrict__ src, int stride, CvPos p, int maxv, T* __restrict__ out) {
+    uint32_t q[3];
+    cv_sample_inside<T>(src + (size_t)(p.Y >> 5) * (size_t)stride + (size_t)(p.X >> 5) * 3, stride, p, maxv, q);
+    out[0] = (T)q[0]; out[1] = (T)q[1]; out[2] = (T)q[2];
 }
 
 // cands: n_cand entries per output frame (gridDim.y frames); entry 0 = the frame itself (its matrix only), a null frame ends the list
@@ -107,10 +95,10 @@ __global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_c3(const 
                     // the bounds build (vs_device.hpp), sites 521 / 522: the 2 x 2 taps' last sample, at stride + 5 from the first, lies inside the source
                     // frame's (h - 1) * stride + 3 w elements -- else pixel (0, 0) is sampled; the store's last sample lies inside the output window
                     const bool taps_in = vsd::bounds_ok((long long)(p.Y >> 5) * src_stride + 3LL * (p.X >> 5) + src_stride + 5, (long long)(h - 1) * src_stride + 3LL * w, 521);
-                    cv_sample_inside(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, o);
+                    fill_sample(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, o);
                     if (!vsd::bounds_ok((long long)y * dst_stride + 3LL * x + 2, (long long)(roi.h - 1) * dst_stride + 3LL * roi.w, 522)) continue;
 #else
-                    cv_sample_inside(cs, src_stride, p, maxv, o);
+                    fill_sample(cs, src_stride, p, maxv, o);
 #endif
                     px[0] = o[0]; px[1] = o[1]; px[2] = o[2];
                     open = false;
@@ -286,10 +274,10 @@ __global__ __launch_bounds__(64 * FL_WAVES) void vs_k_bgr_warp_cv_fill_blend_c3(
                     // the bounds build (vs_device.hpp), sites 523 / 524 / 525: the taps as in the fill kernel; the read-back and the store's last
                     // sample lie inside the output window
                     const bool taps_in = vsd::bounds_ok((long long)(p.Y >> 5) * src_stride + 3LL * (p.X >> 5) + src_stride + 5, (long long)(h - 1) * src_stride + 3LL * w, 523);
-                    cv_sample_inside(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, q);
+                    fill_sample(cs, src_stride, taps_in ? p : CvPos{0, 0}, maxv, q);
                     if (!vsd::bounds_ok((long long)y * dst_stride + 3LL * x + 2, (long long)(roi.h - 1) * dst_stride + 3LL * roi.w, cov0 ? 524 : 525)) continue;
 #else
-                    cv_sample_inside(cs, src_stride, p, maxv, q);
+                    fill_sample(cs, src_stride, p, maxv, q);
 #endif
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++) {
@@ -314,12 +302,11 @@ namespace vsk {
 
 hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, void* dst, int dst_stride,
                                int n_frames, size_t dst_fs, Roi roi, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (w > 32767 || h > 32767 || n_cand < 1) return hipErrorNotSupported;
     const int blocks_x = (roi.w + FL_BLOCK - 1) / FL_BLOCK, blocks_y = (roi.h + FL_BLOCK - 1) / FL_BLOCK;
     const size_t esz = (size_t)bits / 8;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(blocks_x * blocks_y), (unsigned)nf), block(64 * FL_WAVES);
         const FillCand* cp = cands_dev + (size_t)f0 * (size_t)n_cand;
         char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
@@ -327,7 +314,7 @@ hipError_t bgr_warp_cv_fill_c3(const FillCand* cands_dev, int n_cand, int w, int
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_c3<uint16_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, (uint16_t*)dp, dst_stride, dst_fs, roi, blocks_x);
         else
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_c3<uint8_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, (uint8_t*)dp, dst_stride, dst_fs, roi, blocks_x);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -338,12 +325,10 @@ hipError_t bgr_channel_sums(const void* src, int w, int h, int src_stride, int b
     hipError_t e = hipMemsetAsync(out, 0, (size_t)n_frames * 3 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     const size_t esz = (size_t)bits / 8;
-    // dword loads where every row of every frame starts on a dword
-    const bool x4 = (((uintptr_t)src | ((size_t)src_stride * esz) | (n_frames > 1 ? src_fs * esz : 0)) & 3) == 0;
+    const bool x4 = rows_on_dwords(src, src_stride, src_fs, n_frames, esz);      // dword loads
     const int g = x4 ? (bits == 16 ? 2 : 4) : 1;
     const int tiles_x = (w + 64 * g - 1) / (64 * g), tiles_y = (h + CS_ROWS * CS_WAVES - 1) / (CS_ROWS * CS_WAVES);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * CS_WAVES);
         const char* sp = (const char*)src + (size_t)f0 * src_fs * esz;
         unsigned long long* op = out + (size_t)f0 * 3;
@@ -355,19 +340,18 @@ hipError_t bgr_channel_sums(const void* src, int w, int h, int src_stride, int b
             hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint16_t, false>), grid, block, 0, s, (const uint16_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
         else
             hipLaunchKernelGGL((vs_k_bgr_channel_sums<uint8_t, false>), grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, src_fs, op, tiles_x);
-    }
+    });
     return hipGetLastError();
 }
 
 hipError_t bgr_warp_cv_fill_blend_c3(FillCand* cands_dev, int n_cand, int w, int h, int src_stride, int bits, int max_value, int feather, bool match, void* dst,
                                      int dst_stride, int n_frames, size_t dst_fs, Roi roi, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (w > 32767 || h > 32767 || n_cand < 1 || feather < 0 || feather > 6) return hipErrorNotSupported;
     if (match) hipLaunchKernelGGL(vs_k_fill_gains, dim3((unsigned)((n_frames + 63) / 64)), dim3(64), 0, s, cands_dev, n_cand, n_frames);
     const int blocks_x = (roi.w + FL_BLOCK - 1) / FL_BLOCK, blocks_y = (roi.h + FL_BLOCK - 1) / FL_BLOCK;
     const size_t esz = (size_t)bits / 8;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(blocks_x * blocks_y), (unsigned)nf), block(64 * FL_WAVES);
         const FillCand* cp = cands_dev + (size_t)f0 * (size_t)n_cand;
         char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
@@ -375,7 +359,7 @@ hipError_t bgr_warp_cv_fill_blend_c3(FillCand* cands_dev, int n_cand, int w, int
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_blend_c3<uint16_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, feather, (uint16_t*)dp, dst_stride, dst_fs, roi, blocks_x);
         else
             hipLaunchKernelGGL(vs_k_bgr_warp_cv_fill_blend_c3<uint8_t>, grid, block, 0, s, cp, n_cand, w, h, src_stride, max_value, feather, (uint8_t*)dp, dst_stride, dst_fs, roi, blocks_x);
-    }
+    });
     return hipGetLastError();
 }
 

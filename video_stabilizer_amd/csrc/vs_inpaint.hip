@@ -38,6 +38,7 @@
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
 #include "vs_cover.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -346,8 +347,8 @@ hipError_t inpaint_launch(T* img, size_t img_fs, int n, int w, int h, int stride
     const Plan p = make_plan(w, h);
     const unsigned int total = (unsigned int)((size_t)w * h);
     auto blocks = [](int W, int H) { return (unsigned)(((size_t)W * H + IP_THREADS - 1) / IP_THREADS); };
-    for (int f0 = 0; f0 < n; f0 += 65535) {                  // gridDim.y limit
-        const unsigned nf = (unsigned)std::min(n - f0, 65535);
+    vsk::for_frame_chunks(n, [&](int f0, int count) {
+        const unsigned nf = (unsigned)count;
         T* const ip = img + (size_t)f0 * img_fs;
         const uint8_t* const mp = mask + (size_t)f0 * mask_fs;
         Tex<T>* const pp = pyr + (size_t)f0 * p.texels;
@@ -372,7 +373,7 @@ hipError_t inpaint_launch(T* img, size_t img_fs, int n, int w, int h, int stride
                 hipLaunchKernelGGL((vs_k_inpaint_pull<T, false>), grid, dim3(IP_THREADS), 0, s, (T*)nullptr, 0, (size_t)0, (const uint8_t*)nullptr, 0, (size_t)0, pp + p.off[l],
                                    (const Tex<T>*)(pp + p.off[l + 1]), p.texels, p.W[l], p.H[l], cp, total);
         }
-    }
+    });
     return hipGetLastError();
 }
 
@@ -387,16 +388,15 @@ hipError_t fill_coverage(const FillCand* cands_dev, int n_cand, int w, int h, ui
     if (w > 32767 || h > 32767 || n_cand < 1 || roi.w < 1 || roi.h < 1) return hipErrorNotSupported;
     const int blocks_x = (roi.w + FL_BLOCK - 1) / FL_BLOCK, blocks_y = (roi.h + FL_BLOCK - 1) / FL_BLOCK;
     // dword stores where every row of every frame's index starts on a dword
-    const int wide = (((uintptr_t)cov | (size_t)cov_stride | (n_frames > 1 ? cov_fs : 0)) & 3) == 0;
+    const int wide = rows_on_dwords(cov, cov_stride, cov_fs, n_frames, 1);
     if (open_count) {
         const hipError_t e = hipMemsetAsync(open_count, 0, (size_t)n_frames * sizeof(unsigned int), s);
         if (e != hipSuccess) return e;
     }
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         hipLaunchKernelGGL(vs_k_fill_coverage, dim3((unsigned)(blocks_x * blocks_y), (unsigned)nf), dim3(64 * FL_WAVES), 0, s, cands_dev + (size_t)f0 * (size_t)n_cand, n_cand,
                            w, h, cov + (size_t)f0 * cov_fs, cov_stride, cov_fs, roi, blocks_x, wide, open_count ? open_count + f0 : nullptr);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -408,11 +408,10 @@ hipError_t mask_open_count(const uint8_t* mask, int w, int h, int mask_stride, s
     if (w < 1 || h < 1 || n_frames < 1) return hipErrorNotSupported;
     const hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_frames * sizeof(unsigned int), s);
     if (e != hipSuccess) return e;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         hipLaunchKernelGGL(vs_k_mask_open_count, dim3((unsigned)((h + 15) / 16), (unsigned)nf), dim3(IP_THREADS), 0, s, mask + (size_t)f0 * mask_fs, w, h, mask_stride, mask_fs,
                            counts + f0);
-    }
+    });
     return hipGetLastError();
 }
 

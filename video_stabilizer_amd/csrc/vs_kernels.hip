@@ -8,6 +8,7 @@
 
 #include <utility>
 #include "vs_device.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -1055,8 +1056,7 @@ hipError_t ingest_pyr(const void* src, int w, int h, int src_stride, int bits, i
     const int chunk = (int)((tpf + 7) / 8);
     const uint32_t magic = (uint32_t)(0x100000000ULL / (uint32_t)tiles_x) + 1u;    // tiles_x >= 2; the kernel special-cases 1
     const size_t esz = bits == 8 ? 1 : 2;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {          // gridDim.y limit
-        const int nf = std::min(65535, n_frames - f0);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(chunk * 8), (unsigned)nf);
         const uint8_t* sp = (const uint8_t*)src + (size_t)f0 * src_fs * esz;
         if (bits == 8)
@@ -1065,7 +1065,7 @@ hipError_t ingest_pyr(const void* src, int w, int h, int src_stride, int bits, i
         else
             hipLaunchKernelGGL(vs_k_ingest_pyr<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)sp, w, h, src_stride, shift_to_8,
                                g0 + (size_t)f0 * pyr_fs, g1 + (size_t)f0 * pyr_fs, ow, oh, src_fs, pyr_fs, tiles_x, magic, (int)tpf, chunk);
-    }
+    });
     return hipGetLastError();
 }
 

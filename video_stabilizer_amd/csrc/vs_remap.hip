@@ -14,7 +14,7 @@
 // `w, h, ow, oh` in 1 .. 32767, `VS_ERR_UNSUPPORTED` beyond, as the rolling-shutter pass does.
 //
 // - Taps sit at `(X >> 5, Y >> 5)` and the three neighbours to the right and below. Fractions are `X & 31`, `Y & 31`.
-// - The blend is `VS_WARP_BILINEAR_CV`'s, operation for operation (`rs_blend` in `vs_rolling.hip`).
+// - The blend is `VS_WARP_BILINEAR_CV`'s (`cv_blend` in `vs_cv_sample.hpp`).
 //   - 8-bit containers: integer weights, `(sum + 512) >> 10`.
 //   - 16-bit containers: fp32 weights `a * b / 1024`, `rintf`, saturated to `vs_format_max_value(format)`.
 // - `VS_BORDER_CLAMP`: each tap's column is clamped to `0 .. w - 1` and its row to `0 .. h - 1`, with weights unchanged. This is the
@@ -40,6 +40,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 #include "vs_lens.hpp"
 
 using namespace vsd;
@@ -54,15 +56,13 @@ constexpr int RM_W = 64, RM_WAVES = 4, RM_ROWS = 8;       // a wave's strip is 6
 // build drops.
 
 struct __attribute__((packed, aligned(4))) rm_pos { int32_t X, Y; };                  // a map entry: a dwordx2 on a dword boundary
-struct __attribute__((packed)) rm_u64 { uint64_t v; };
-struct __attribute__((packed, aligned(2))) rm_u128 { uint64_t lo, hi; };
 
 // What a pixel keeps across the frames of a slice.  o0, o1: element offsets, from the frame's first sample, of the loads of rows sy and sy + 1
 // (WIDE: the start of the eight-element load, pulled back from the row's end so that every byte read lies inside the row; else tap c0's first
 // sample); sh: WIDE, the bits that put tap c0 at the bottom; d1: the second tap's distance from the first in samples, 3 or (the clamp folded
 // them) 0; wt: the four weight products a0 b0, a1 b0, a0 b1, a1 b1 (8-bit containers: int; 16-bit: the products times 1 / 1024 in fp32).
-template <typename T> struct Weight { typedef int type; };
-template <> struct Weight<uint16_t> { typedef float type; };
+// The loads and their unpacking are vs_cv_sample.hpp's row_fetch and row_unpack, used apart: a lane has the loads of all its pixels in flight
+// before it unpacks the first (with a load and its unpack back to back the kernel waited out a memory latency per frame row).
 template <typename T>
 struct Plan {
     long long o0, o1;
@@ -88,86 +88,28 @@ __device__ __forceinline__ Plan<T> rm_plan(CvPos p, int w, int h, int stride, in
     pl.d1 = (c1 - c0) * 3;
     pl.o0 = (long long)VS_IDX((size_t)r0 * (size_t)stride, (long long)(h - 1) * stride + 1, 593) + col;
     pl.o1 = (long long)VS_IDX((size_t)r1 * (size_t)stride, (long long)(h - 1) * stride + 1, 594) + col;
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    int m[4] = {a0 * b0, a1 * b0, a0 * b1, a1 * b1};
+    int m[4];
+    cv_products(p, m);
     if (border != VS_BORDER_CLAMP) {                      // constant border: a tap outside the frame counts as 0
         const bool x0in = sx == c0, x1in = sx + 1 == c1, y0in = sy == r0, y1in = sy + 1 == r1;
         m[0] = x0in && y0in ? m[0] : 0; m[1] = x1in && y0in ? m[1] : 0; m[2] = x0in && y1in ? m[2] : 0; m[3] = x1in && y1in ? m[3] : 0;
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (sizeof(T) == 1) pl.wt[k] = (typename Weight<T>::type)m[k];
-        else pl.wt[k] = (typename Weight<T>::type)((float)m[k] * (1.0f / 1024.0f));
-    }
+    cv_weights<T>(m, pl.wt);
     return pl;
 }
 
-// The two taps of one frame row (vs_rolling.hip's rs_row_taps with the offsets made beforehand), in two steps: rm_fetch issues the load and
-// keeps what came as it came, rm_taps shifts and unpacks it into a[3], b[3].  Apart, so that a lane has the loads of all its pixels in flight
-// before it unpacks the first: with a load and its unpack back to back the kernel waited out a memory latency per frame row.
-template <typename T, bool WIDE> struct Raw { uint32_t s[6]; };
-template <> struct Raw<uint8_t, true> { uint64_t q; };
-template <> struct Raw<uint16_t, true> { uint64_t lo, hi; };
-__device__ __forceinline__ Raw<uint8_t, true> rm_fetch(GPtr<uint8_t> p, int, Raw<uint8_t, true>*) {
-    return Raw<uint8_t, true>{((const __attribute__((address_space(1))) rm_u64*)p)->v};
-}
-__device__ __forceinline__ Raw<uint16_t, true> rm_fetch(GPtr<uint16_t> p, int, Raw<uint16_t, true>*) {
-    const __attribute__((address_space(1))) rm_u128* const q = (const __attribute__((address_space(1))) rm_u128*)p;
-    return Raw<uint16_t, true>{q->lo, q->hi};
-}
-template <typename T>
-__device__ __forceinline__ Raw<T, false> rm_fetch(GPtr<T> p, int d1, Raw<T, false>*) {
-    Raw<T, false> r;
-#pragma unroll
-    for (int c = 0; c < 3; c++) { r.s[c] = p[c]; r.s[3 + c] = p[d1 + c]; }
-    return r;
-}
-__device__ __forceinline__ void rm_taps(const Raw<uint8_t, true>& r, int sh, int d1, uint32_t a[3], uint32_t b[3]) {
-    const uint64_t q = r.q >> sh;
-    const uint64_t q1 = d1 ? q >> 24 : q;                 // (d1 == 3: sh <= 16, the second tap ends at byte 7 at the most)
-#pragma unroll
-    for (int c = 0; c < 3; c++) { a[c] = (uint32_t)(q >> (8 * c)) & 255u; b[c] = (uint32_t)(q1 >> (8 * c)) & 255u; }
-}
-__device__ __forceinline__ void rm_taps(const Raw<uint16_t, true>& r, int sh, int d1, uint32_t a[3], uint32_t b[3]) {
-    const uint64_t lo = r.lo, hi = r.hi;                  // sh: 0 .. 80 bits
-    // (lo, hi) >> sh, the low 96 bits
-    const uint64_t m0 = sh >= 64 ? hi >> (sh - 64) : (sh ? (lo >> sh) | (hi << (64 - sh)) : lo);
-    const uint64_t m1 = sh >= 64 ? 0 : hi >> sh;
-    const uint64_t ta = m0, tb = d1 ? (m0 >> 48) | (m1 << 16) : m0;                   // (d1 == 3: sh <= 32, nothing above bit 127 is asked for)
-#pragma unroll
-    for (int c = 0; c < 3; c++) { a[c] = (uint32_t)(ta >> (16 * c)) & 65535u; b[c] = (uint32_t)(tb >> (16 * c)) & 65535u; }
-}
-template <typename T>
-__device__ __forceinline__ void rm_taps(const Raw<T, false>& r, int, int, uint32_t a[3], uint32_t b[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) { a[c] = r.s[c]; b[c] = r.s[3 + c]; }
-}
 // a frame's loads for a lane's PX pixels: rows sy and sy + 1 of each
 template <typename T, int PX, bool WIDE>
-__device__ __forceinline__ void rm_fetch_frame(GPtr<T> fs, const Plan<T> pl[PX], Raw<T, WIDE> raw[PX][2]) {
+__device__ __forceinline__ void rm_fetch_frame(GPtr<T> fs, const Plan<T> pl[PX], RowRaw<T, WIDE> raw[PX][2]) {
 #pragma unroll
     for (int i = 0; i < PX; i++) {
-        raw[i][0] = rm_fetch(fs + pl[i].o0, pl[i].d1, (Raw<T, WIDE>*)nullptr);
-        raw[i][1] = rm_fetch(fs + pl[i].o1, pl[i].d1, (Raw<T, WIDE>*)nullptr);
+        raw[i][0] = row_fetch(fs + pl[i].o0, pl[i].d1, (RowRaw<T, WIDE>*)nullptr);
+        raw[i][1] = row_fetch(fs + pl[i].o1, pl[i].d1, (RowRaw<T, WIDE>*)nullptr);
     }
 }
-// VS_WARP_BILINEAR_CV's blend (vs_rolling.hip's rs_blend, operation for operation) with the weight products made beforehand
-__device__ __forceinline__ void rm_blend(const uint32_t t[4][3], const int wt[4], int, uint32_t q[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        q[c] = (uint32_t)(((int)t[0][c] * wt[0] + (int)t[1][c] * wt[1] + (int)t[2][c] * wt[2] + (int)t[3][c] * wt[3] + 512) >> 10);
-}
-__device__ __forceinline__ void rm_blend(const uint32_t t[4][3], const float wt[4], int maxv, uint32_t q[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float sum = (float)t[0][c] * wt[0] + (float)t[1][c] * wt[1] + (float)t[2][c] * wt[2] + (float)t[3][c] * wt[3];
-        q[c] = (uint32_t)min(max((int)rintf(sum), 0), maxv);
-    }
-}
-
 // a lane's PX pixels of one frame from what rm_fetch_frame brought: unpack, blend, store (PX == 4: three or six dwords)
 template <typename T, int PX, bool WIDE>
-__device__ __forceinline__ void rm_emit(const Raw<T, WIDE> raw[PX][2], const Plan<T> pl[PX], int maxv, T* op) {
+__device__ __forceinline__ void rm_emit(const RowRaw<T, WIDE> raw[PX][2], const Plan<T> pl[PX], int maxv, T* op) {
     constexpr int ND = PX * 3 * (int)sizeof(T) / 4;                       // dwords of a lane's four pixels (PX == 4)
     uint32_t o[ND > 0 ? ND : 1];
 #pragma unroll
@@ -175,17 +117,14 @@ __device__ __forceinline__ void rm_emit(const Raw<T, WIDE> raw[PX][2], const Pla
 #pragma unroll
     for (int i = 0; i < PX; i++) {
         uint32_t t[4][3], q[3];
-        rm_taps(raw[i][0], pl[i].sh, pl[i].d1, t[0], t[1]);
-        rm_taps(raw[i][1], pl[i].sh, pl[i].d1, t[2], t[3]);
-        rm_blend(t, pl[i].wt, maxv, q);
+        row_unpack(raw[i][0], pl[i].sh, pl[i].d1, t[0], t[1]);
+        row_unpack(raw[i][1], pl[i].sh, pl[i].d1, t[2], t[3]);
+        cv_blend(t, pl[i].wt, maxv, q);
         if (PX == 1) {
             op[0] = (T)q[0]; op[1] = (T)q[1]; op[2] = (T)q[2];
         } else {
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int j = 3 * i + k;
-                if (sizeof(T) == 1) o[j / 4] |= q[k] << (8 * (j % 4)); else o[j / 2] |= q[k] << (16 * (j % 2));
-            }
+            for (int k = 0; k < 3; k++) px_put<T>(o, 3 * i + k, q[k]);
         }
     }
     if (PX > 1) {
@@ -221,7 +160,7 @@ __global__ __launch_bounds__(64 * RM_WAVES) void vs_k_bgr_remap(const T* __restr
         // the unpack would wait for everything, stores included.  (Two sets of loads in turn, and two frames per iteration, took more registers
         // and no less time: DESIGN.md "Lens-distortion correction".)
         auto frame = [&](int f) { return (GPtr<T>)(src + (size_t)VS_IDX(min(f, f1 - 1), n, 597) * src_fs); };
-        Raw<T, WIDE> raw[PX][2];
+        RowRaw<T, WIDE> raw[PX][2];
         rm_fetch_frame<T, PX, WIDE>(frame(f0), pl, raw);
         for (int f = f0; f < f1; f++) {
             rm_emit<T, PX, WIDE>(raw, pl, maxv, dst + (size_t)f * dst_fs + oo);
@@ -248,17 +187,16 @@ namespace vsk {
 
 hipError_t bgr_remap(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const int32_t* map,
                      int map_stride, int ow, int oh, int border, void* dst, size_t dst_fs, int dst_stride, int slice, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (n_frames < 1 || w < 1 || h < 1 || w > 32767 || h > 32767 || ow < 1 || oh < 1 || ow > 32767 || oh > 32767 || slice < 1) return hipErrorNotSupported;
     if (border != VS_BORDER_CLAMP && border != VS_BORDER_CONSTANT) return hipErrorNotSupported;
     const size_t esz = (size_t)bits / 8;
     // four pixels per lane with dword stores where every destination row starts on a dword
-    const bool x4 = ow % 4 == 0 && (((uintptr_t)dst | ((size_t)dst_stride * esz) | (n_frames > 1 ? dst_fs * esz : 0)) & 3) == 0;
+    const bool x4 = ow % 4 == 0 && rows_on_dwords(dst, dst_stride, dst_fs, n_frames, esz);
     const int tw = x4 ? 4 * RM_W : RM_W, th = RM_ROWS * RM_WAVES;
     const int tiles_x = (ow + tw - 1) / tw, tiles_y = (oh + th - 1) / th;
     const int groups = (n_frames + slice - 1) / slice;
-    for (int g0 = 0; g0 < groups; g0 += 65535) {           // gridDim.y limit
-        const int ng = std::min(groups - g0, 65535);
+    for_frame_chunks(groups, [&](int g0, int ng) {         // (chunks of frame groups: gridDim.y counts slices)
         const size_t f0 = (size_t)g0 * slice;
         const int nf = (int)std::min<size_t>((size_t)n_frames - f0, (size_t)ng * slice);
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)ng), block(64 * RM_WAVES);
@@ -272,7 +210,7 @@ hipError_t bgr_remap(const void* src, size_t src_fs, int n_frames, int w, int h,
         else if (bits == 16) VS_RM_LAUNCH(uint16_t, 1, true);
         else VS_RM_LAUNCH(uint8_t, 1, true);
 #undef VS_RM_LAUNCH
-    }
+    });
     return hipGetLastError();
 }
 

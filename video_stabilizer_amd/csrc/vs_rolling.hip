@@ -63,7 +63,7 @@
 // the strip's row r once, and the wave reads them with v_readlane (uniform values).  What is new: r0 and r3 depend on the row, so the two column
 // cvRounds (fp64: two multiplies, rint, clamp, convert) are per pixel, not per strip; the rest per pixel is int32 -- position, clamped taps,
 // fraction, blend -- plus the fp32 blend the 16-bit warp is defined by.  The frame and the matrix are scalar loads from the frame's two 64-byte
-// entries (vsk::FillCand); the four taps are two GPtr gathers (global_load), one unaligned load of eight elements per frame row (rs_row_taps).  PX = 1: one pixel per
+// entries (vsk::FillCand); the four taps are two GPtr gathers (global_load), one unaligned load of eight elements per frame row (row_fetch).  PX = 1: one pixel per
 // lane, any width and pitch, a wave owns 64 columns x 8 rows.  PX = 4: a lane owns four consecutive pixels and stores them as three (u8) or six
 // (u16) dwords, a wave owns 256 columns x 8 rows; for widths that are multiples of 4 with every destination row on a dword (the source is only
 // gathered from: it needs no alignment).  A frame without motion is a copy, as dwords where both rows allow it.  No LDS, no barrier, no scratch.
@@ -76,6 +76,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 
 using namespace vsd;
 
@@ -84,44 +86,20 @@ namespace {
 constexpr int RS_W = 64, RS_WAVES = 4, RS_ROWS = 8;       // a wave's strip is 64 lanes wide and 8 rows high; four strips stacked make a workgroup's tile
 
 // The bounds build (-DVS_DEBUG_BOUNDS, vs_device.hpp) checks every gather and every store of this file, sites 581-590: an element offset within
-// a frame, the access's last sample included, lies below (h - 1) * stride + 3 w (581-584 the copy; 585 / 586 a gather's two row offsets, 587 / 588
+// a frame, the access's last sample included, lies below (h - 1) * stride + 3 w (581-584 the copy, strip_copy<T, 581> of vs_cv_sample.hpp; 585 / 586 a gather's two row offsets, 587 / 588
 // its two column offsets; 589 / 590 the store's row and column offsets).  The extents are written inside the macros' arguments, which the
 // regular build drops.
 
-// The two taps of one frame row: columns c0 and c1 (c1 == c0 + 1, or c1 == c0 where the clamp folded them) -> a[3], b[3].  A byte gather per
-// sample is twelve loads per pixel, and the pass is then bound by the rate at which a CU takes gather instructions; the six samples of a row's
-// two taps are neighbours, so (WIDE: the row holds at least eight elements, w >= 3) they come as ONE unaligned load of eight elements whose start
-// is pulled back from the row's end, and a shift puts tap c0 at the bottom.  Every byte read lies inside the row.
-struct __attribute__((packed)) rs_u64 { uint64_t v; };
-struct __attribute__((packed, aligned(2))) rs_u128 { uint64_t lo, hi; };
-template <bool WIDE>
-__device__ __forceinline__ void rs_row_taps(GPtr<uint8_t> row, int w, int c0, int c1, uint32_t a[3], uint32_t b[3]) {
-    if (WIDE) {
-        const int e0 = c0 * 3, base = min(e0, 3 * w - 8);
-        const uint64_t q = ((const __attribute__((address_space(1))) rs_u64*)(row + VS_IDX(base, 3LL * w - 7, 587)))->v >> (8 * (e0 - base));
-        const uint64_t q1 = c1 != c0 ? q >> 24 : q;          // (c1 == c0 + 1: e0 - base <= 2, the second tap ends at byte 7 at the most)
-#pragma unroll
-        for (int c = 0; c < 3; c++) { a[c] = (uint32_t)(q >> (8 * c)) & 255u; b[c] = (uint32_t)(q1 >> (8 * c)) & 255u; }
+// The two taps of one frame row: columns c0 and c1 (c1 == c0 + 1, or c1 == c0 where the clamp folded them) -> a[3], b[3].  WIDE: vs_cv_sample.hpp's
+// row_fetch and row_unpack back to back, one unaligned load of eight elements pulled back from the row's end.  A row of fewer than eight
+// elements is read sample by sample from its two taps' own addresses (the header's form with d1 costs this kernel two more subtractions).
+template <bool WIDE, typename T>
+__device__ __forceinline__ void rs_row_taps(GPtr<T> row, int w, int c0, int c1, uint32_t a[3], uint32_t b[3]) {
+    if constexpr (WIDE) {
+        const int e0 = c0 * 3, base = VS_IDX(min(e0, 3 * w - 8), 3LL * w - 7, 587), d1 = (c1 - c0) * 3;
+        row_unpack(row_fetch(row + base, d1, (RowRaw<T, true>*)nullptr), 8 * (int)sizeof(T) * (e0 - base), d1, a, b);
     } else {
-        GPtr<uint8_t> pa = row + VS_IDX(c0 * 3, 3LL * w - 2, 587), pb = row + VS_IDX(c1 * 3, 3LL * w - 2, 588);
-#pragma unroll
-        for (int c = 0; c < 3; c++) { a[c] = pa[c]; b[c] = pb[c]; }
-    }
-}
-template <bool WIDE>
-__device__ __forceinline__ void rs_row_taps(GPtr<uint16_t> row, int w, int c0, int c1, uint32_t a[3], uint32_t b[3]) {
-    if (WIDE) {
-        const int e0 = c0 * 3, base = min(e0, 3 * w - 8), sh = 16 * (e0 - base);      // sh: 0 .. 80 bits
-        const __attribute__((address_space(1))) rs_u128* const p = (const __attribute__((address_space(1))) rs_u128*)(row + VS_IDX(base, 3LL * w - 7, 587));
-        const uint64_t lo = p->lo, hi = p->hi;
-        // (lo, hi) >> sh, the low 96 bits: three 32-bit pieces
-        const uint64_t m0 = sh >= 64 ? hi >> (sh - 64) : (sh ? (lo >> sh) | (hi << (64 - sh)) : lo);
-        const uint64_t m1 = sh >= 64 ? 0 : hi >> sh;
-        const uint64_t ta = m0, tb = c1 != c0 ? (m0 >> 48) | (m1 << 16) : m0;          // (c1 == c0 + 1: sh <= 32, nothing above bit 127 is asked for)
-#pragma unroll
-        for (int c = 0; c < 3; c++) { a[c] = (uint32_t)(ta >> (16 * c)) & 65535u; b[c] = (uint32_t)(tb >> (16 * c)) & 65535u; }
-    } else {
-        GPtr<uint16_t> pa = row + VS_IDX(c0 * 3, 3LL * w - 2, 587), pb = row + VS_IDX(c1 * 3, 3LL * w - 2, 588);
+        GPtr<T> pa = row + VS_IDX(c0 * 3, 3LL * w - 2, 587), pb = row + VS_IDX(c1 * 3, 3LL * w - 2, 588);
 #pragma unroll
         for (int c = 0; c < 3; c++) { a[c] = pa[c]; b[c] = pb[c]; }
     }
@@ -137,43 +115,12 @@ __device__ __forceinline__ Taps rs_taps(GPtr<T> fs, int w, int h, int stride, Cv
     rs_row_taps<WIDE>(fs + VS_IDX((size_t)clampi(sy + 1, 0, h - 1) * (size_t)stride, (long long)(h - 1) * stride + 1, 586), w, c0, c1, t.v[2], t.v[3]);
     return t;
 }
-// VS_WARP_BILINEAR_CV's blend (vs_fill.hip's cv_sample_inside, operation for operation) on those taps
-__device__ __forceinline__ void rs_blend(uint8_t, const Taps& t, CvPos p, int, uint32_t q[3]) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        q[c] = (uint32_t)(((int)t.v[0][c] * (a0 * b0) + (int)t.v[1][c] * (a1 * b0) + (int)t.v[2][c] * (a0 * b1) + (int)t.v[3][c] * (a1 * b1) + 512) >> 10);
-}
-__device__ __forceinline__ void rs_blend(uint16_t, const Taps& t, CvPos p, int maxv, uint32_t q[3]) {
-    const int a1 = p.X & 31, b1 = p.Y & 31, a0 = 32 - a1, b0 = 32 - b1;
-    const float k = 1.0f / 1024.0f;
-    const float w00 = (float)(a0 * b0) * k, w01 = (float)(a1 * b0) * k, w10 = (float)(a0 * b1) * k, w11 = (float)(a1 * b1) * k;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float sum = (float)t.v[0][c] * w00 + (float)t.v[1][c] * w01 + (float)t.v[2][c] * w10 + (float)t.v[3][c] * w11;
-        q[c] = (uint32_t)min(max((int)rintf(sum), 0), maxv);
-    }
-}
-
-// a frame without motion: the wave's nx x (y1 - y0) strip at (x0, y0) is copied, as dwords where both rows allow it
+// VS_WARP_BILINEAR_CV's blend (vs_cv_sample.hpp) on those taps
 template <typename T>
-__device__ __forceinline__ void rs_copy(const T* __restrict__ src, T* __restrict__ dst, int w, int h, int src_stride, int dst_stride, int x0, int nx, int y0,
-                                        int y1, int lane) {
-    const size_t row_bytes = (size_t)nx * 3 * sizeof(T);
-    const bool wide = (((uintptr_t)src | (uintptr_t)dst | ((size_t)src_stride * sizeof(T)) | ((size_t)dst_stride * sizeof(T)) | ((size_t)x0 * 3 * sizeof(T))) & 3) == 0;
-    for (int y = y0; y < y1; y++) {
-        const uint8_t* const sp = (const uint8_t*)(src + (size_t)y * (size_t)src_stride + (size_t)x0 * 3);
-        uint8_t* const dp = (uint8_t*)(dst + (size_t)y * (size_t)dst_stride + (size_t)x0 * 3);
-        size_t done = 0;
-        if (wide) {
-            const size_t nd = row_bytes / 4;
-            for (size_t i = lane; i < nd; i += 64)
-                ((uint32_t*)dp)[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 581)] = ((const uint32_t*)sp)[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T) / 4, 582)];
-            done = nd * 4;
-        }
-        for (size_t i = done + lane; i < row_bytes; i += 64)
-            dp[VS_IDX(i, ((long long)(h - 1) * dst_stride + 3LL * w - ((long long)y * dst_stride + 3LL * x0)) * (long long)sizeof(T), 583)] = sp[VS_IDX(i, ((long long)(h - 1) * src_stride + 3LL * w - ((long long)y * src_stride + 3LL * x0)) * (long long)sizeof(T), 584)];
-    }
+__device__ __forceinline__ void rs_blend(const Taps& t, CvPos p, int maxv, uint32_t q[3]) {
+    typename Weight<T>::type wt[4];
+    cv_weights<T>(p, wt);
+    cv_blend(t.v, wt, maxv, q);
 }
 
 // cands: two entries per output frame (gridDim.y frames); entry 0 = the frame (its matrix is not read), entry 1 = the motion's output -> source
@@ -191,7 +138,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void vs_k_bgr_rolling(const vsk::Fil
     cands += (size_t)blockIdx.y * 2;
     dst += (size_t)blockIdx.y * dst_fs;
     if (cands[1].src == nullptr) {                                        // uniform: no motion known
-        rs_copy((const T*)cands[0].src, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
+        strip_copy<T, 581>((const T*)cands[0].src, dst, w, h, src_stride, dst_stride, x0, nx, y0, y1, lane);
         return;
     }
     const GPtr<T> fs = (GPtr<T>)cands[0].src;
@@ -213,7 +160,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void vs_k_bgr_rolling(const vsk::Fil
         if (PX == 1) {
             const CvPos pos = cv_pos(X0, Y0, cv_delta(r0, x), cv_delta(r3, x));
             uint32_t q[3];
-            rs_blend(T(), rs_taps<WIDE>(fs, w, h, src_stride, pos), pos, maxv, q);
+            rs_blend<T>(rs_taps<WIDE>(fs, w, h, src_stride, pos), pos, maxv, q);
             T* const op = orow + VS_IDX((size_t)x * 3, 3LL * w - 2, 590);
             op[0] = (T)q[0]; op[1] = (T)q[1]; op[2] = (T)q[2];
         } else {
@@ -224,12 +171,9 @@ __global__ __launch_bounds__(64 * RS_WAVES) void vs_k_bgr_rolling(const vsk::Fil
             for (int i = 0; i < PX; i++) {
                 const CvPos pos = cv_pos(X0, Y0, cv_delta(r0, x + i), cv_delta(r3, x + i));
                 uint32_t q[3];
-                rs_blend(T(), rs_taps<WIDE>(fs, w, h, src_stride, pos), pos, maxv, q);
+                rs_blend<T>(rs_taps<WIDE>(fs, w, h, src_stride, pos), pos, maxv, q);
 #pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const int j = 3 * i + k;
-                    if (sizeof(T) == 1) o[j / 4] |= q[k] << (8 * (j % 4)); else o[j / 2] |= q[k] << (16 * (j % 2));
-                }
+                for (int k = 0; k < 3; k++) px_put<T>(o, 3 * i + k, q[k]);
             }
             uint32_t* const op = (uint32_t*)(orow + VS_IDX((size_t)x * 3, 3LL * w - (3 * PX - 1), 590));      // (3 PX samples)
 #pragma unroll
@@ -246,15 +190,14 @@ namespace vsk {
 
 hipError_t bgr_rolling(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int max_value, double readout, void* dst, int dst_stride,
                        int n_frames, size_t dst_fs, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;
     if (n_frames < 1 || w < 1 || h < 1 || w > 32767 || h > 32767 || !(readout >= -1.0 && readout <= 1.0)) return hipErrorNotSupported;
     const size_t esz = (size_t)bits / 8;
     // four pixels per lane with dword stores where every destination row starts on a dword
-    const bool x4 = w % 4 == 0 && (((uintptr_t)dst | ((size_t)dst_stride * esz) | (n_frames > 1 ? dst_fs * esz : 0)) & 3) == 0;
+    const bool x4 = w % 4 == 0 && rows_on_dwords(dst, dst_stride, dst_fs, n_frames, esz);
     const int tw = x4 ? 4 * RS_W : RS_W, th = RS_ROWS * RS_WAVES;
     const int tiles_x = (w + tw - 1) / tw, tiles_y = (h + th - 1) / th;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)nf), block(64 * RS_WAVES);
         const FillCand* cp = cands_dev + (size_t)f0 * 2;
         char* dp = (char*)dst + (size_t)f0 * dst_fs * esz;
@@ -266,7 +209,7 @@ hipError_t bgr_rolling(const FillCand* cands_dev, int w, int h, int src_stride, 
         else if (bits == 16) VS_RS_LAUNCH(uint16_t, 1, true);
         else VS_RS_LAUNCH(uint8_t, 1, true);
 #undef VS_RS_LAUNCH
-    }
+    });
     return hipGetLastError();
 }
 

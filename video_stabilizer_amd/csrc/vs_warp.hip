@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <cmath>
 #include "vs_device.hpp"
+#include "vs_launch.hpp"
 #include "vs_cv_window.hpp"
 #include "vs_c3_window.hpp"
 
@@ -1514,8 +1515,7 @@ static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const fl
     const int chunk = (int)((tpf + 7) / 8);
     // tl / tiles_x == (tl * magic) >> 32 for every tl with tl * tiles_x < 2^32 (tiles_x >= 2; the kernel special-cases 1)
     const uint32_t magic = (uint32_t)(0x100000000ULL / (uint32_t)tiles_x) + 1u;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = n_frames - f0 < 65535 ? n_frames - f0 : 65535;
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const T* sp = src + (size_t)f0 * src_fs;
         T* dp = dst + (size_t)f0 * dst_fs;
         const float4* pp = params_dev + f0;
@@ -1552,7 +1552,7 @@ static hipError_t launch_c3(const T* src, int w, int h, int src_stride, const fl
         else if (mode == 3) VS_LAUNCH(3, 1);
         else if (border == 0) VS_LAUNCH(1, 0);
         else VS_LAUNCH(1, 1);
-    }
+    });
 #undef VS_LAUNCH
 #undef VS_LAUNCH_C
     return hipGetLastError();
@@ -1591,7 +1591,7 @@ size_t bgr_warp_cv_table_ints(int bits, Roi roi) {
 
 hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bits, const double* minv_dev, const double* minv_host, int* tab_dev, int border, int max_value,
                           void* dst, int dst_stride, int n_frames, size_t src_fs, size_t dst_fs, Roi roi, hipStream_t s) {
-    if (bits == 16 ? (max_value < 0 || max_value > 65535) : (bits != 8 || max_value != 255)) return hipErrorNotSupported;   // (8-bit results never exceed 255: the weights sum to 1024)
+    if (!container_ok(bits, max_value)) return hipErrorNotSupported;   // (8-bit results never exceed 255: the weights sum to 1024)
     const int th = bits == 16 ? CV16_TH : CV_TH;
     const int tiles_x = (roi.w + WT_W - 1) / WT_W, tiles_y = (roi.h + th - 1) / th;
     const long long tpf = (long long)tiles_x * tiles_y;
@@ -1600,15 +1600,15 @@ hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bit
     const uint32_t magic = (uint32_t)(0x100000000ULL / (uint32_t)tiles_x) + 1u;
     const int tab_w = tiles_x * WT_W, tab_h = tiles_y * th;
     const size_t per = 2 * ((size_t)tab_w + (size_t)tab_h), esz = (size_t)bits / 8;
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {         // gridDim.y limit
-        const int nf = n_frames - f0 < 65535 ? n_frames - f0 : 65535;
+    const bool inline_m = minv_host && n_frames <= kCvInlineFrames;       // the matrices travel in the launch
+    if (n_frames > 0 && !inline_m && !minv_dev) return hipErrorInvalidValue;
+    for_frame_chunks(n_frames, [&](int f0, int nf) {
         const int* tp = tab_dev + (size_t)f0 * per;
-        if (minv_host && n_frames <= kCvInlineFrames) {
+        if (inline_m) {
             CvMatrices inl{};
             for (int k = 0; k < 6 * n_frames; k++) inl.m[k] = minv_host[k];
             hipLaunchKernelGGL(vs_k_cv_tables<true>, dim3((unsigned)((per + 255) / 256), (unsigned)nf), dim3(256), 0, s, (const double*)nullptr, inl, tab_dev, tab_w, tab_h, roi);
         } else {
-            if (!minv_dev) return hipErrorInvalidValue;
             hipLaunchKernelGGL(vs_k_cv_tables<false>, dim3((unsigned)((per + 255) / 256), (unsigned)nf), dim3(256), 0, s, minv_dev + 6 * (size_t)f0, CvMatrices{},
                                tab_dev + (size_t)f0 * per, tab_w, tab_h, roi);
         }
@@ -1630,7 +1630,7 @@ hipError_t bgr_warp_cv_c3(const void* src, int w, int h, int src_stride, int bit
                 hipLaunchKernelGGL((vs_k_bgr_warp_cv_c3<1>), grid, block, 0, s, (const uint8_t*)sp, w, h, src_stride, tp, tab_w, tab_h, (uint8_t*)dp, dst_stride, src_fs, dst_fs,
                                    tiles_x, magic, (int)tpf, chunk, roi);
         }
-    }
+    });
     return hipGetLastError();
 }
 

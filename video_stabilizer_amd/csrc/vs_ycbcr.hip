@@ -19,6 +19,8 @@
 
 #include "vs_kernels.hpp"
 #include "vs_device.hpp"
+#include "vs_cv_sample.hpp"
+#include "vs_launch.hpp"
 #include "vs_ycbcr.hpp"
 
 using namespace vsd;
@@ -61,14 +63,14 @@ struct Run {
                *(yc_dw<ND>*)p = q; }
     }
     __device__ __forceinline__ int get(int k) const {
-        return sizeof(T) == 1 ? (int)((v[k / 4] >> (8 * (k % 4))) & 255u) : (int)((v[k / 2] >> (16 * (k % 2))) & 65535u);
+        return (int)px_get<T>(v, k);
     }
     __device__ __forceinline__ void clear() {
 #pragma unroll
         for (int k = 0; k < ND; k++) v[k] = 0;
     }
     __device__ __forceinline__ void put(int k, int s) {        // (after clear(); s inside T's range)
-        if (sizeof(T) == 1) v[k / 4] |= (uint32_t)s << (8 * (k % 4)); else v[k / 2] |= (uint32_t)s << (16 * (k % 2));
+        px_put<T>(v, k, (uint32_t)s);
     }
 };
 
@@ -247,12 +249,12 @@ Planes<P> planes_of(const vs_ycbcr_planes& pl) {
 }
 // every row of every plane and of the BGR side starts on a dword, and w is a multiple of 4
 bool wide_ok(const vs_ycbcr_planes& pl, int n, int w, size_t esz, const void* bgr, size_t bgr_fs, int bgr_stride) {
-    uintptr_t m = (uintptr_t)bgr | ((size_t)bgr_stride * esz) | (n > 1 ? bgr_fs * esz : 0) | (uintptr_t)pl.y | ((size_t)pl.y_stride * esz) | (n > 1 ? pl.y_frame_stride * esz : 0);
-    if (pl.cb) {
-        const uintptr_t lo = std::min((uintptr_t)pl.cb, (uintptr_t)pl.cr), hi = std::max((uintptr_t)pl.cb, (uintptr_t)pl.cr);
-        m |= lo | (pl.c_step == 1 ? hi : 0) | ((size_t)pl.c_stride * esz) | (n > 1 ? pl.c_frame_stride * esz : 0);
+    bool ok = vsk::rows_on_dwords(bgr, bgr_stride, bgr_fs, n, esz) && vsk::rows_on_dwords(pl.y, pl.y_stride, pl.y_frame_stride, n, esz);
+    if (pl.cb) {                                          // two planes, or one of pairs that starts at the lower of the two pointers
+        if (pl.c_step == 1) ok = ok && vsk::rows_on_dwords(pl.cb, pl.c_stride, pl.c_frame_stride, n, esz) && vsk::rows_on_dwords(pl.cr, pl.c_stride, pl.c_frame_stride, n, esz);
+        else ok = ok && vsk::rows_on_dwords((uintptr_t)pl.cb < (uintptr_t)pl.cr ? pl.cb : pl.cr, pl.c_stride, pl.c_frame_stride, n, esz);
     }
-    return w % 4 == 0 && (m & 3) == 0;
+    return w % 4 == 0 && ok;
 }
 // frame f0's descriptor
 vs_ycbcr_planes at_frame(vs_ycbcr_planes pl, size_t f0, size_t esz) {
@@ -300,12 +302,11 @@ hipError_t ycbcr_to_bgr(const vs_ycbcr_planes& src, int n_frames, int w, int h, 
     const Shape sp = shape_of(src, n_frames, w, h, bits, max_value);
     if (!sp.ok || !dst || dst_stride < 3 * w) return hipErrorNotSupported;
     const bool wide = wide_ok(src, n_frames, w, sp.esz, dst, dst_fs, dst_stride);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {          // gridDim.y limit
-        const int nf = std::min(n_frames - f0, 65535);
+    vsk::for_frame_chunks(n_frames, [&](int f0, int nf) {
         char* const dp = (char*)dst + (size_t)f0 * dst_fs * sp.esz;
         if (sp.esz == 2) launch_to_bgr<uint16_t>(at_frame(src, (size_t)f0, sp.esz), nf, w, h, sp.sh, max_value, dp, dst_fs, dst_stride, wide, s);
         else launch_to_bgr<uint8_t>(at_frame(src, (size_t)f0, sp.esz), nf, w, h, sp.sh, max_value, dp, dst_fs, dst_stride, wide, s);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -313,12 +314,11 @@ hipError_t bgr_to_ycbcr(const void* src, size_t src_fs, int n_frames, int w, int
     const Shape sp = shape_of(dst, n_frames, w, h, bits, max_value);
     if (!sp.ok || !src || src_stride < 3 * w) return hipErrorNotSupported;
     const bool wide = wide_ok(dst, n_frames, w, sp.esz, src, src_fs, src_stride);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {
-        const int nf = std::min(n_frames - f0, 65535);
+    vsk::for_frame_chunks(n_frames, [&](int f0, int nf) {
         const char* const sp0 = (const char*)src + (size_t)f0 * src_fs * sp.esz;
         if (sp.esz == 2) launch_to_ycbcr<uint16_t>(sp0, src_fs, src_stride, nf, w, h, sp.sh, max_value, at_frame(dst, (size_t)f0, sp.esz), wide, s);
         else launch_to_ycbcr<uint8_t>(sp0, src_fs, src_stride, nf, w, h, sp.sh, max_value, at_frame(dst, (size_t)f0, sp.esz), wide, s);
-    }
+    });
     return hipGetLastError();
 }
 
