@@ -568,6 +568,42 @@ int vs_exposure_gains_batch(const uint64_t* stats, int n_out, int n_cand, int w,
  * any device work; gains in device memory are never seen by the host: the kernel clamps them to that range. */
 int vs_bgr_gain_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
                       const uint32_t* gains, void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
+/* SCENE-CUT DETECTION: the frame difference of two consecutive frames taken through their measured motion.  The aligner is no cut detector:
+ * across a hard cut it often converges to some small similarity and reports success.  Inside a scene the difference through the measured
+ * motion is close to zero however hard the camera shakes; across a cut it is large whatever the aligner made of it.
+ *
+ * THE SCENE-CUT RULE (also vs_scene.hip).
+ * Interleaved BGR, every VS_FMT_BGR*, frames up to 32767 a side; s = bits - 8.
+ *   - PARAMETERS.  step is 1 .. 64 (default 4, the deflicker's lattice); threshold is 1 .. 255, in 8-bit levels (default 32: above a 20 % exposure
+ *     jump and below every cut of the synthetic clips it was measured on -- a starting value, not a calibrated one).
+ *   - PAIR AND LATTICE.  A pair is (target frame, candidate frame, forward transform t in VS_WARP_BILINEAR_CV's convention): what a deflicker or
+ *     denoise candidate list gives for candidate 1.  The lattice pixels are those with x % step == 0 && y % step == 0;
+ *     L = ceil(w / step) * ceil(h / step).
+ *   - POSITION.  With M = vs_cv_inverse_matrix(t) lattice pixel (x, y) lies in the candidate at qx = rint((M0 x + M1 y) + M2),
+ *     qy = rint((M3 x + M4 y) + M5): doubles, that order, no fma, ties to even -- the deflicker's and deblur's nearest-sample position.  The
+ *     lattice pixel COUNTS iff qx, qy are finite, 0 <= qx <= w - 1 and 0 <= qy <= h - 1.  There is no level test: black and clipped samples count.
+ *   - STATISTIC.  With v' = min(v, max_value) >> s, each pair yields two uint64: count, and sad = the sum over the counted lattice pixels of
+ *     sum_c |p'_c - q'_c| (p the target at (x, y), q the candidate at (qx, qy)).  count < 2^30 and sad < 3 * 255 * 2^30; integer sums: the
+ *     order of the reduction cannot matter.  A NaN or infinite map counts nothing.
+ *   - DECISION.  Unsigned 64-bit: the pair is a CUT iff count < max(1, L / 16) or sad > 3 * threshold * count.  The inequality is strict:
+ *     equality is no cut.  Too little overlap is a cut: nothing shows that the frames are one scene, and nothing could be borrowed from the
+ *     candidate anyway.
+ *   - HENCE (a) identical frames under the identity give sad == 0; (b) a frame and its copy shifted by whole pixels, under that shift, give
+ *     sad == 0 and count = the overlap's lattice count; (c) constant frames of 100 and 130 give sad == 90 * count.
+ * The default threshold, 32, comes from SYNTHETIC clips (within a scene at most 1.8 levels, a 20 % exposure jump 25,
+ * cuts 48 and more) and is a starting value: footage with flashes or hard exposure steps may want it higher, low-contrast footage lower.
+ * A step outside 1 .. 64 or a threshold outside 1 .. 255 is VS_ERR_ARG, before any device work. */
+typedef struct vs_scene_params { int step; int threshold; } vs_scene_params;
+void vs_scene_params_default(vs_scene_params* p);   /* {4, 32}: a starting value, see above */
+/* stats[2*i + {0: count, 1: sad}] of pair i = (frame pair_frames[2*i] of the batch as the target, frame pair_frames[2*i + 1] as the
+ * candidate, pair_t[i]); `stats` lives in `mem`; pair_frames and pair_t are host arrays.  A pair may name a frame twice and pairs may come
+ * in any order.  n_pairs == 0 is VS_OK and launches nothing; a frame index outside 0 .. n_src-1 is VS_ERR_ARG.  VS_MEM_DEVICE only
+ * enqueues. */
+int vs_bgr_scene_stats_batch(const void* src, size_t src_frame_stride, int n_src, int w, int h, int src_stride, int format,
+                             int n_pairs, const int32_t* pair_frames /* 2 per pair: target, candidate */, const vs_transform* pair_t,
+                             const vs_scene_params* params /* NULL = defaults */, uint64_t* stats /* 2 per pair */, int mem, void* stream);
+/* The rule's decision, on the host (no device needed): cut[i] = 1 iff pair i is a cut.  stats and cut are host arrays. */
+int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_scene_params* params /* NULL = defaults */, uint8_t* cut);
 /* ---- Inpaint of what the border fill leaves open: a coverage index and an exact-integer push-pull over the output window ----
  * THE RULE.  VS_WARP_BILINEAR_CV conventions, 3 channels, 8- and 16-bit containers, every VS_FMT_BGR*, windows up to 32767 a side.
  *   - COVERAGE INDEX.  Output frame o has n_cand (1 .. 16) candidates exactly as in vs_bgr_image_warp_fill_batch: each a forward
@@ -901,6 +937,24 @@ int   vs_stabilizer_get_deflicker(const vs_stabilizer* s);
  * VS_WARP_BILINEAR_CV; VS_ERR_ARG for a value other than 0 or 1.  Takes effect with the next output frame.  get returns the switch. */
 int   vs_stabilizer_set_inpaint(vs_stabilizer* s, int on);
 int   vs_stabilizer_get_inpaint(const vs_stabilizer* s);
+/* Scene-cut detection (the rule: see vs_bgr_scene_stats_batch).  NULL (default): off -- the handle as it is without this call, launch for
+ * launch and allocation for allocation.  On: every arriving frame that has a predecessor in the same clip is compared with it through the
+ * motion the aligner has just measured (one statistics launch and one download of two words per frame and call).  A frame whose pair is a
+ * cut (a) enters the smoother and the queue with the identity as its measurement, (b) counts as a failed alignment for every look-ahead
+ * pass: border fill, fill blend, deblur, denoise, deflicker, rolling shutter and the inpaint's coverage all end their candidate lists in
+ * front of it, so nothing of the new scene reaches the old one's frames, (c) leaves the accumulated correction alone on arrival (the
+ * frames of the old scene that are still queued finish as they would have) and, when it is itself finalised, gets the identity as its
+ * correction and resets the accumulated correction: the new scene starts from a clean path.  vs_stabilizer_state reports the identity and
+ * last_success == 0 for a cut frame.  With the lens correction on the statistic sees corrected frames.  vs_stabilizer_reset, a size or
+ * format change and every clip start of vs_stabilizer_process_clips forget the predecessor and the cut list.  Takes effect with the next
+ * frame.  Not detected: fades and dissolves; a flash frame is two cuts; an exposure jump above about 25 % at mid-grey crosses the default
+ * threshold.  VS_ERR_ARG for a step outside 1 .. 64 or a threshold outside 1 .. 255.
+ * get_scene_cut: returns 1 (on: *params in force) or 0 (off: *params = the defaults).
+ * get_scene_cuts: returns the number of cuts since the last reset and writes, in ascending order, the 0-based indices (counted from that
+ * reset) of the most recent min(total, cap, 256) cut frames; frames may be NULL with cap == 0. */
+int   vs_stabilizer_set_scene_cut(vs_stabilizer* s, const vs_scene_params* params /* NULL = off */);
+int   vs_stabilizer_get_scene_cut(const vs_stabilizer* s, vs_scene_params* params);
+int   vs_stabilizer_get_scene_cuts(const vs_stabilizer* s, int64_t* frames, int cap);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

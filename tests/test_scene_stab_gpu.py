@@ -1,0 +1,338 @@
+"""Scene-cut detection in the stabilizer (include/vs_amd.h: vs_stabilizer_set_scene_cut) on 160 x 128 clips of 12 + 12 frames from two synthetic
+scenes (the clips of tests/test_scene_cpu.py's premise): off is the handle as it was; a cut is detected, reported and resets the path; nothing of
+the next scene reaches the previous one's frames, whatever passes are on; chunking, scheduling, memory, lag, warp and format cannot change a
+byte; clips are independent; state changes do what the header says.  Bit for bit throughout."""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _scene_ref as R
+from test_deblur_gpu import _frame_by_frame, _walk
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H, N = 160, 128, 12
+# (the clips shake by up to 16 px from frame to frame: the aligner's displacement limit is raised so that it follows them, as a caller with
+# such footage would)
+KW = dict(device=0, lag=6, crop_pixels=8, max_displacement=40.0)
+
+
+def _scene(seed, n=N, bits=8, calm=False):
+    """the shaky clips of tests/test_scene_cpu.py's premise; calm: a hand-held camera the aligner follows at every step"""
+    from video_stabilizer_amd import synth
+    kw = dict(pan=1.0, jitter_t=2.0) if calm else dict(pan=4.0, jitter_t=6.0)
+    return synth.make_clip(W, H, n, seed=seed, channels=3, bits=bits, **kw)[0]
+
+
+@pytest.fixture(scope="module")
+def clips():
+    """scene A (seed 3) with scene B (seed 4) behind it, and one 24-frame take of scene A: made once, left unchanged"""
+    a, b = _scene(3), _scene(4)
+    return {"ab": np.concatenate([a, b]), "long": _scene(3, 2 * N)}
+
+
+def _run(st, frames, chunks=None):
+    """-> {input frame index: output} through process (chunks None) or process_batch in chunks of the given sizes, cyclically"""
+    if chunks is None:
+        return _frame_by_frame(st, frames)
+    out, i, k = {}, 0, 0
+    while i < len(frames):
+        m = min(chunks[k % len(chunks)], len(frames) - i)
+        o, has = st.process_batch(frames[i:i + m])
+        for j in range(m):
+            if has[j]:
+                out[i + j - st.params.lag] = o[j].copy()
+        i, k = i + m, k + 1
+    return out
+
+
+def _same(a, b):
+    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_off_is_the_plain_stabilizer(gpu_vs, clips):
+    vs = gpu_vs
+    frames = clips["long"]
+    never, null, on = vs.Stabilizer(**KW), vs.Stabilizer(**KW), vs.Stabilizer(scene_cut=True, **KW)
+    null.set_scene_cut(vs.scene_params())
+    null.set_scene_cut(None)
+    assert never.get_scene_cut() is None and null.get_scene_cut() is None
+    p = on.get_scene_cut()
+    assert (p.step, p.threshold) == (4, 32)
+    s0, s1, s2 = [], [], []
+    o0, o1, o2 = _frame_by_frame(never, frames, s0), _frame_by_frame(null, frames, s1), _frame_by_frame(on, frames, s2)
+    assert len(o0) == 2 * N - KW["lag"] and _same(o0, o1) and _same(o0, o2)
+    assert s0 == s1 == s2
+    followed = sum(1 for s in s0[1:] if s[2])
+    print("the aligner follows %d of the shaky clip's %d steps" % (followed, len(s0) - 1))
+    assert followed >= N, "the aligner no longer follows the shaky clip: the test input has to change"
+    assert on.scene_cuts() == (0, []) and never.scene_cuts() == (0, [])
+    # the cut clip too: a handle that had detection switched on and off again is one that never had it
+    null.reset()
+    assert _same(_frame_by_frame(vs.Stabilizer(**KW), clips["ab"]), _frame_by_frame(null, clips["ab"]))
+    assert null.scene_cuts() == (0, [])
+
+
+def _expected(vs, frames, fmt, kw, params):
+    """the engine's outputs rebuilt outside it: the measurements of a capi.Aligner on the same frames, the cut flags from the rule's restatement on
+    those measurements, the corrections from the Python step, the frames from the kernel-level warp"""
+    n, h, w, _ = frames.shape
+    lag, crop = kw["lag"], kw["crop_pixels"]
+    bits = 8 if frames.dtype == np.uint8 else 10
+    mode = kw.get("warp_mode", vs.WARP_BILINEAR_CV)
+    status, meas = vs.Aligner(device=0, select_mode=vs.SELECT_DEVICE, max_displacement=kw["max_displacement"]).align_batch(frames, fmt=fmt)
+    rows = [R.pair_stats(vs, frames[j - 1], frames[j], R.pair_transform(vs, meas[j]), bits, params.step) for j in range(1, n)]
+    cut = [False] + [R.is_cut(c, s, w, h, params.step, params.threshold) for c, s in rows]
+    step = R.Step(vs, vs.stabilizer_params(**{k: v for k, v in kw.items() if k != "device"}), w, h)
+    roi = (crop, crop, w - 2 * crop, h - 2 * crop)
+    outs = {}
+    for i in range(n):
+        corr = step.step(meas[i], bool(status[i]), cut[i])
+        if corr is None:
+            continue
+        t = corr if mode == vs.WARP_BILINEAR_CV else vs.t_inverse(corr)
+        outs[i - lag] = vs.bgr_image_warp_roi_batch(frames[i - lag][None], [t], roi, mode=mode, border=vs.BORDER_CONSTANT, max_value=(1 << bits) - 1)[0]
+    return outs, cut, rows, status, [m.tup() for m in meas]
+
+
+@pytest.mark.parametrize("case", ["cv", "lanczos2", "cv_10bit", "lag0", "lag1"])
+def test_a_cut_is_detected_and_resets_the_path(gpu_vs, clips, case):
+    vs = gpu_vs
+    kw = dict(KW)
+    frames, fmt = clips["ab"], vs.FMT_BGR8
+    if case == "lanczos2":
+        kw["warp_mode"] = vs.WARP_LANCZOS2
+    if case == "cv_10bit":
+        frames, fmt = np.concatenate([_scene(3, bits=10), _scene(4, bits=10)]), vs.FMT_BGR10
+    if case in ("lag0", "lag1"):
+        kw["lag"] = int(case[3])
+    p = vs.scene_params()
+    want, cut, rows, status, meas = _expected(vs, frames, fmt, kw, p)
+    levels = [R.mean_level(r) for r in rows]
+    print(case, "status at the cut", status[N], "levels within %.2f, at the cut %.2f" % (max(levels[:N - 1] + levels[N:]), levels[N - 1]))
+    assert [i for i, c in enumerate(cut) if c] == [N]                    # premise: the rule on the aligner's own measurements names frame 12 alone
+    st = vs.Stabilizer(scene_cut=p, **kw)
+    states = []
+    got = {}
+    for i, f in enumerate(frames):
+        o = st.process(f, fmt=fmt)
+        m, a, s = st.state()
+        states.append((m.tup(), s))
+        if o is not None:
+            got[i - kw["lag"]] = o
+    assert st.scene_cuts() == (1, [N])
+    assert status[N] == 1, "the aligner no longer converges across the cut: the test input has to change"
+    assert states[N] == ((0.0, 0.0, 0.0, 0.0), False)                     # the cut frame: the identity, last_success 0
+    assert all(states[i] == (meas_tup, bool(ok)) for i, (meas_tup, ok) in enumerate(zip(meas, status)) if i != N)
+    c = kw["crop_pixels"]
+    if case != "lanczos2":                                               # (the fixed-point warp under the identity is the copy)
+        assert np.array_equal(got[N], frames[N][c:H - c, c:W - c])
+    assert _same(got, want)
+    # the batched forms: frame by frame, batches of 5, 12 and 13 (the cut last, first and second in its chunk), host memory
+    for chunks in ([5], [12], [13], [1, 24]):
+        s2 = vs.Stabilizer(scene_cut=p, **kw)
+        assert _same(_run(s2, frames, chunks), want), (case, chunks)
+        assert s2.scene_cuts() == (1, [N])
+
+
+def test_device_memory_gives_the_same_bytes(gpu_vs, clips):
+    import torch
+    vs = gpu_vs
+    frames = clips["ab"]
+    c, lag = KW["crop_pixels"], KW["lag"]
+    want = _frame_by_frame(vs.Stabilizer(scene_cut=True, **KW), frames)
+    dev = torch.from_numpy(frames).cuda()
+    for chunk in (24, 13, 5):
+        st = vs.Stabilizer(scene_cut=True, **KW)
+        out = torch.zeros((len(frames), H - 2 * c, W - 2 * c, 3), dtype=torch.uint8, device="cuda")
+        has = []
+        for i in range(0, len(frames), chunk):
+            m = min(chunk, len(frames) - i)
+            _, hh = st.process_batch_device(dev[i].data_ptr(), m, W, H, vs.FMT_BGR8, out[i].data_ptr())
+            has += hh
+        torch.cuda.synchronize()
+        o = out.cpu().numpy()
+        got = {i - lag: o[i] for i in range(len(frames)) if has[i]}
+        assert _same(got, want), chunk
+        assert st.scene_cuts() == (1, [N])
+
+
+PASSES = dict(border_fill=4, fill_blend=(3, 1), denoise=3, deblur=3, deflicker=4)
+
+
+def test_the_leak_is_closed(gpu_vs, clips):
+    """With fill, fill blend, denoise, deblur and deflicker on, the outputs of scene A's 12 frames must not depend on which scene follows.
+    Premise, asserted: without detection they do -- this is the test that fails without the feature."""
+    vs = gpu_vs
+    # The smoother is off here: a frame's smoothed path is computed from the MEASUREMENTS of the `lag` frames that follow it, those of the next
+    # scene among them (never their pixels), so with it on the tail of scene A moves a little differently when B' has another camera path than
+    # B -- the second half of the test pins how far that reaches.  What this half is about is pixels: every pass that borrows them is on.
+    kw = dict(KW, crop_pixels=0, enable_smoother=0, **PASSES)
+    # (calm clips: a failed alignment resets the accumulated correction when it ARRIVES -- the reference's rule -- and so moves the queued frames
+    # of the scene before; that is no leak of this feature's, and these clips keep it out: every alignment succeeds, the one across the cut too)
+    # B and B': the first two seeds from 4 up whose clip the aligner follows at every step behind scene A, the cut included (across most cuts
+    # the aligner does fail, which is the case that needs no detection)
+    ca, found = _scene(3, calm=True), []
+    for seed in range(4, 64):
+        seq = np.concatenate([ca, _scene(seed, calm=True)])
+        status, _ = vs.Aligner(device=0, select_mode=vs.SELECT_DEVICE, max_displacement=KW["max_displacement"]).align_batch(seq)
+        if all(status[1:]):
+            found.append((seed, seq))
+        if len(found) == 2:
+            break
+    assert len(found) == 2, "the aligner no longer follows two of the calm clips: the test input has to change"
+    print("scene A is followed by seeds", [f[0] for f in found])
+    clips = {"ab": found[0][1], "ab2": found[1][1]}
+    off_b, off_b2 = _frame_by_frame(vs.Stabilizer(**kw), clips["ab"]), _frame_by_frame(vs.Stabilizer(**kw), clips["ab2"])
+    leaked = [k for k in range(N) if not np.array_equal(off_b[k], off_b2[k])]
+    print("without detection the following scene changes frames", leaked)
+    assert leaked, "the following scene no longer reaches scene A's frames without detection: the test input has to change"
+    on_b, on_b2 = vs.Stabilizer(scene_cut=True, **kw), vs.Stabilizer(scene_cut=True, **kw)
+    got_b, got_b2 = _frame_by_frame(on_b, clips["ab"]), _frame_by_frame(on_b2, clips["ab2"])
+    assert on_b.scene_cuts() == (1, [N]) and on_b2.scene_cuts() == (1, [N])
+    assert all(np.array_equal(got_b[k], got_b2[k]) for k in range(N))
+    # ... and they are what scene A alone gives for the frames that finish before the cut frame arrives
+    alone = _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"][:N])
+    assert all(np.array_equal(got_b[k], alone[k]) for k in alone)
+    # in batches too
+    assert _same(_run(vs.Stabilizer(scene_cut=True, **kw), clips["ab"], [13]), got_b)
+    # With the smoother on, frame k's correction is made when frame k + lag arrives, from the measurements up to that frame: frames 0 .. 12 - lag
+    # see nothing behind the cut frame (whose measurement is the identity whatever follows) and stay identical; the rest of scene A may move
+    # with the next scene's camera path (known limits) -- but only move: their candidate lists still end at the cut
+    kw = dict(KW, crop_pixels=0, **PASSES)
+    sm_b, sm_b2 = _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"]), _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab2"])
+    print("with the smoother on the following scene's motion reaches frames", [k for k in range(N) if not np.array_equal(sm_b[k], sm_b2[k])])
+    assert all(np.array_equal(sm_b[k], sm_b2[k]) for k in range(N + 1 - kw["lag"]))
+
+
+def test_process_clips_reports_no_cut(gpu_vs, clips):
+    vs = gpu_vs
+    frames = clips["ab"]
+    st = vs.Stabilizer(scene_cut=True, **KW)
+    out, has = st.process_clips(frames, 2)
+    assert st.scene_cuts() == (0, [])
+    plain, has0 = vs.Stabilizer(**KW).process_clips(frames, 2)
+    assert has == has0 and np.array_equal(out, plain)
+
+
+def test_state_changes(gpu_vs, clips):
+    vs = gpu_vs
+    frames = clips["ab"]
+    st = vs.Stabilizer(scene_cut=True, **KW)
+    _frame_by_frame(st, frames)
+    assert st.scene_cuts() == (1, [N]) and st.scene_cuts(cap=0) == (1, [])
+    st.reset()
+    assert st.scene_cuts() == (0, [])
+    # after the reset the first frame has no predecessor: the second scene alone shows no cut, and indices count from the reset
+    _frame_by_frame(st, frames[N:])
+    assert st.scene_cuts() == (0, [])
+    _frame_by_frame(st, frames[:N])                                      # ... scene A behind scene B, without a reset: a cut at index 12
+    assert st.scene_cuts() == (1, [N])
+    # switched on between frames 11 and 12: the cut frame is the next frame, and is detected; switched on after it: nothing to detect
+    for at, want in ((N, (1, [N])), (N + 1, (0, []))):
+        s2 = vs.Stabilizer(**KW)
+        for i, f in enumerate(frames):
+            if i == at:
+                s2.set_scene_cut(vs.scene_params())
+            s2.process(f)
+        assert s2.scene_cuts() == want, at
+    # a flash frame is two cuts; more than the list holds
+    flash = np.concatenate([frames[:5], frames[N:N + 1], frames[5:N]])
+    s3 = vs.Stabilizer(scene_cut=True, **KW)
+    _frame_by_frame(s3, flash)
+    assert s3.scene_cuts() == (2, [5, 6]) and s3.scene_cuts(cap=1) == (2, [6])
+    # the parameter boundary at the handle
+    for kw in (dict(step=0), dict(step=65), dict(threshold=0), dict(threshold=256)):
+        with pytest.raises(vs.VsError, match="error -1"):
+            s3.set_scene_cut(vs.scene_params(**kw))
+    assert s3.get_scene_cut().threshold == 32
+    s3.set_scene_cut(vs.scene_params(step=64, threshold=255))
+    assert (s3.get_scene_cut().step, s3.get_scene_cut().threshold) == (64, 255)
+
+
+def test_video_test_prints_the_cut_list(gpu_vs, clips, tmp_path):
+    vs = gpu_vs
+    frames = clips["ab"]
+    d = tmp_path / "in"
+    d.mkdir()
+    raw = d / ("cut_%dx%d.bgr" % (W, H))
+    frames.tofile(raw)
+    exe = os.path.join(ROOT, "apps", "bin", "vs_video_test")
+    r = subprocess.run([exe, str(d), str(tmp_path / "out"), "--crop", "8", "--scene-cut", "--chunk", "13"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert "Scene cuts: 1 [12]" in r.stdout, r.stdout[-2000:]
+    st = vs.Stabilizer(device=0, crop_pixels=8, scene_cut=True)          # the program's handle: the library's defaults
+    want = np.stack([o for o in (st.process(f) for f in frames) if o is not None])
+    assert st.scene_cuts() == (1, [N])
+    got = np.fromfile(tmp_path / "out" / ("processed_" + raw.name), np.uint8).reshape(-1, H - 16, W - 16, 3)
+    assert np.array_equal(got, want)
+    r = subprocess.run([exe, str(d), str(tmp_path / "out2"), "--scene-cut", "300"], capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "vs_stabilizer_set_scene_cut" in r.stderr
+
+
+@pytest.mark.parametrize("throwing", [False, True])
+def test_process_batch_survives_every_allocation_failure(gpu_vs, clips, throwing):
+    """the new allocation points: the staging block of the statistics' download, and (lag 0) the handle's copy of the call's last frame"""
+    vs = gpu_vs
+    frames = clips["ab"]
+
+    def call(s):
+        out, has = s.process_batch(frames[:16])
+        out2, has2 = s.process_batch(frames[16:])
+        return list(has), list(has2), out.tobytes(), out2.tobytes(), s.scene_cuts()
+    for lag in (0, 4):
+        kw = dict(KW, lag=lag, smoother_memory=2)
+        plain = _walk(vs, lambda: vs.Stabilizer(**kw), call, 1, throwing)
+        n = _walk(vs, lambda: vs.Stabilizer(scene_cut=True, **kw), call, plain + (1 if lag == 0 else 0), throwing)
+        print("lag %d: %d allocations failed one by one with detection (%s); %d without" % (lag, n, "throwing" if throwing else "error code", plain))
+
+
+CHILD = r'''
+import sys, hashlib, os
+sys.path.insert(0, %r)
+import numpy as np, torch
+from video_stabilizer_amd import capi, synth
+W, H, crop, n_scenes, fps = 160, 128, 8, 6, 24
+frames = np.concatenate([synth.make_clip(W, H, fps, seed=3 + s, channels=3, pan=4.0, jitter_t=6.0)[0] for s in range(n_scenes)])
+dev = torch.from_numpy(frames).cuda()
+res = []
+for kw in (dict(warp_mode=capi.WARP_LANCZOS2_FAST), dict()):
+    out = torch.zeros((len(frames), H - 2 * crop, W - 2 * crop, 3), dtype=torch.uint8, device="cuda")
+    st = capi.Stabilizer(device=0, lag=6, crop_pixels=crop, max_displacement=40.0, scene_cut=True, **kw)
+    r, has = st.process_batch_device(dev.data_ptr(), len(frames), W, H, capi.FMT_BGR8, out.data_ptr())
+    torch.cuda.synchronize()
+    res += [str(r), hashlib.sha256(out.cpu().numpy().tobytes() + bytes(has)).hexdigest(), ",".join(str(c) for c in st.scene_cuts()[1])]
+print("DIGEST", *res)
+'''
+
+
+def test_every_scheduling_switch_gives_the_same_bytes(gpu_vs):
+    """one device-resident sequence of six scenes x 24 frames, long enough for the overlapped run path to cut it in time (the Lanczos2 warp: chunks
+    of 48, the default warp: of 120, so that a cut is first in a chunk both times) -- with the warps on a second stream and the next chunk's
+    alignment prefetched the statistics run beside that alignment on a stream of their own.  Every switch tests/test_stab_modes_gpu.py walks is
+    read once per process: one child each."""
+    vs = gpu_vs
+    from video_stabilizer_amd import synth
+    crop, n_scenes, fps = 8, 6, 24
+    frames = np.concatenate([synth.make_clip(W, H, fps, seed=3 + s, channels=3, pan=4.0, jitter_t=6.0)[0] for s in range(n_scenes)])
+    want = []
+    for kw in (dict(warp_mode=vs.WARP_LANCZOS2_FAST), dict()):
+        st = vs.Stabilizer(scene_cut=True, **dict(KW, **kw))
+        outs, has = [], []
+        for f in frames:
+            o = st.process(f)
+            has.append(1 if o is not None else 0)
+            outs.append(o if o is not None else np.zeros((H - 2 * crop, W - 2 * crop, 3), np.uint8))
+        assert st.scene_cuts() == (n_scenes - 1, [fps * k for k in range(1, n_scenes)])
+        want += [str(len(frames) - 6), hashlib.sha256(np.stack(outs).tobytes() + bytes(has)).hexdigest(), ",".join(str(fps * k) for k in range(1, n_scenes))]
+    for env in ({"VS_STAB_OVERLAP": "1", "VS_STAB_PREFETCH": "1"}, {"VS_STAB_OVERLAP": "1", "VS_STAB_PREFETCH": "0"}, {"VS_STAB_OVERLAP": "0"},
+                {"VS_STAB_OVERLAP": "1", "VS_STAB_PREFETCH": "1", "VS_GN_CORESIDENT": "0"}):
+        out = subprocess.run([sys.executable, "-c", CHILD % ROOT], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = [l for l in out.stdout.splitlines() if l.startswith("DIGEST")][-1].split()[1:]
+        assert line == want, (env, line, want)

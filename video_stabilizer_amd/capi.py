@@ -105,6 +105,11 @@ class DeflickerParams(C.Structure):
     _fields_ = [("step", C.c_int)]
 
 
+class SceneParams(C.Structure):
+    """vs_scene_params: the lattice step of the scene-cut statistics, 1 .. 64; the threshold in 8-bit levels, 1 .. 255"""
+    _fields_ = [("step", C.c_int), ("threshold", C.c_int)]
+
+
 class FillBlendParams(C.Structure):
     """vs_fill_blend_params: feather 0 (off) or 1 .. 6; match 0 or 1"""
     _fields_ = [("feather", C.c_int), ("match", C.c_int)]
@@ -204,6 +209,9 @@ SIGNATURES = {
                                            _vp, _i32, _vp]),
     "vs_exposure_gains_batch": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(DeflickerParams), _vp, _i32, _vp]),
     "vs_bgr_gain_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "vs_scene_params_default": (None, [C.POINTER(SceneParams)]),
+    "vs_bgr_scene_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(SceneParams), _vp, _i32, _vp]),
+    "vs_scene_cuts": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(SceneParams), _vp]),
     "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_inpaint_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
@@ -233,6 +241,9 @@ SIGNATURES = {
     "vs_stabilizer_get_lens": (_i32, [_vp, C.POINTER(LensParams), _IP, _IP]),
     "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
     "vs_stabilizer_get_deflicker": (_i32, [_vp]),
+    "vs_stabilizer_set_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
+    "vs_stabilizer_get_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
+    "vs_stabilizer_get_scene_cuts": (_i32, [_vp, C.POINTER(C.c_int64), _i32]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_inpaint": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
@@ -1066,6 +1077,52 @@ def exposure_gains_batch_device(stats_ptr, n_out, n_cand, w, h, gains_ptr, param
                                          C.c_void_p(stream) if stream else None))
 
 
+def scene_params(**kw):
+    p = SceneParams()
+    lib().vs_scene_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _scene_pairs(pair_frames, pair_t):
+    idx = _c(pair_frames, np.int32).reshape(-1, 2)
+    n_pairs = idx.shape[0]
+    assert len(pair_t) == n_pairs
+    return idx, n_pairs, (Transform * max(n_pairs, 1))(*pair_t)
+
+
+def scene_stats_batch(src, pair_frames, pair_t, params=None, fmt=None, src_stride=None):
+    """the scene-cut pair statistics (include/vs_amd.h: vs_bgr_scene_stats_batch).  src (n_src,h,w,3) numpy; pair_frames (n_pairs, 2) ints: target,
+    candidate; pair_t: n_pairs Transforms.  -> (n_pairs, 2) uint64: count, sad.  src_stride (elements): the call is made on pitched copies of the
+    frames"""
+    src = np.ascontiguousarray(src)
+    n_src, h, w, c = src.shape
+    idx, n_pairs, arr = _scene_pairs(pair_frames, pair_t)
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = w * c if src_stride is None else src_stride
+    out = np.full((max(n_pairs, 1), 2), 0xA5A5A5A5, np.uint64)
+    _check(lib().vs_bgr_scene_stats_batch(_p(_pitched(src, ss)), h * ss, n_src, w, h, ss, fmt, n_pairs, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                          C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    return out[:n_pairs]
+
+
+def scene_stats_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, pair_frames, pair_t, stats_ptr, params=None, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    idx, n_pairs, arr = _scene_pairs(pair_frames, pair_t)
+    _check(lib().vs_bgr_scene_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_pairs, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
+                                          C.byref(params) if params is not None else None, _p(stats_ptr), MEM_DEVICE,
+                                          C.c_void_p(stream) if stream else None))
+
+
+def scene_cuts(stats, w, h, params=None):
+    """the scene-cut rule's decision, on the host (include/vs_amd.h: vs_scene_cuts).  stats (n_pairs, 2) uint64 -> (n_pairs,) uint8"""
+    st = _c(stats, np.uint64).reshape(-1, 2)
+    out = np.full((max(st.shape[0], 1),), 0xA5, np.uint8)
+    _check(lib().vs_scene_cuts(_p(st), st.shape[0], w, h, C.byref(params) if params is not None else None, _p(out)))
+    return out[:st.shape[0]]
+
+
 def bgr_gain_batch(src, gains, fmt=None, src_stride=None, dst_stride=None, guard=None):
     """the deflicker's point-wise pass (include/vs_amd.h: vs_bgr_gain_batch).  src (n,h,w,3) numpy; gains (n,4) uint32 -> (n,h,w,3).  src_stride /
     dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
@@ -1330,7 +1387,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1353,6 +1410,24 @@ class Stabilizer:
             self.set_rolling_shutter(rolling_shutter)
         if lens is not None:
             self.set_lens(*lens)
+        if scene_cut is not None:
+            self.set_scene_cut(scene_params() if scene_cut is True else scene_cut)
+
+    def set_scene_cut(self, params):
+        """None: off; a SceneParams (scene_params()): every arriving frame is compared with its predecessor through the measured motion, and a
+        frame that shows another scene ends every candidate list in front of it and starts a clean path"""
+        _check(lib().vs_stabilizer_set_scene_cut(self.h, C.byref(params) if params is not None else None))
+
+    def get_scene_cut(self):
+        """None (off) or the SceneParams in force"""
+        p = SceneParams()
+        return p if _check(lib().vs_stabilizer_get_scene_cut(self.h, C.byref(p))) else None
+
+    def scene_cuts(self, cap=256):
+        """(the number of cuts since the last reset, the 0-based indices since that reset of the most recent min(total, cap, 256) cut frames)"""
+        buf = (C.c_int64 * max(cap, 1))()
+        total = _check(lib().vs_stabilizer_get_scene_cuts(self.h, buf, int(cap)))
+        return total, [int(buf[k]) for k in range(min(total, cap, 256))]
 
     def set_lens(self, params, w=0, h=0):
         """None (or the identity lens): off; else every arriving w x h frame is remapped through the lens map of `params` (LensParams) in front of

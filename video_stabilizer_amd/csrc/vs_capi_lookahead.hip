@@ -1,5 +1,5 @@
 // vs_capi_lookahead.hip -- the look-ahead passes of the C ABI (include/vs_amd.h) next to the border fill (vs_capi_warp.hip): channel sums,
-// sharpness and deblur, denoise, rolling-shutter correction, remap and lens map, exposure statistics / gains / gain, coverage index and inpaint.  Each pass that takes candidate lists is a
+// sharpness and deblur, denoise, rolling-shutter correction, remap and lens map, exposure statistics / gains / gain, scene-cut statistics, coverage index and inpaint.  Each pass that takes candidate lists is a
 // *_ptrs function in vsi (device-resident frames, enqueue only: the engine's form) and an index-based *_batch wrapper over it; what brings a
 // list to a kernel is cand_groups (vs_capi.hpp).
 #include "vs_capi.hpp"
@@ -170,6 +170,38 @@ int vsi::exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format
         FrameIsEntry0{cand_src, n_cand, __func__}, no_side_word,
         [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
             VS_HIP(vsk::exposure_stats(cdev, n_cand, w, h, src_stride, (int)esz * 8, bits - 8, p.step, (unsigned long long*)stats + (size_t)f0 * n_cand * 8, nf, s));
+            return VS_OK;
+        });
+}
+
+// ---- scene-cut detection (vs_scene.hip) ----
+namespace {
+int scene_params_ok(const vs_scene_params* params, vs_scene_params* p) {
+    if (params) *p = *params; else vs_scene_params_default(p);
+    VS_ARG(p->step >= 1 && p->step <= 64 && p->threshold >= 1 && p->threshold <= 255);
+    return VS_OK;
+}
+}  // namespace
+
+// The statistics pass on device-resident frames (vs_internal.hpp); two entries per pair, in the denoise's groups.
+int vsi::scene_stats_ptrs(int n_pairs, int w, int h, int src_stride, int format, const void* const* pair_src, const vs_transform* pair_t,
+                          const vs_scene_params* params, uint64_t* stats, hipStream_t s) {
+    const int bits = vs_format_bits(format);
+    VS_TRY(pass_args_ok(__func__, "scene cut", kAsTheFill, w, h, format, 2, pair_src && pair_t && stats, n_pairs, src_stride, nullptr));
+    vs_scene_params p;
+    VS_TRY(scene_params_ok(params, &p));
+    for (int i = 0; i < n_pairs; i++) VS_ARG(pair_src[2 * (size_t)i] && pair_src[2 * (size_t)i + 1]);
+    ParamRing* ring = param_ring();
+    if (!ring) return no_ring();
+    const size_t esz = plan::elem_size(bits);
+    std::vector<vs_transform> t2((size_t)n_pairs * 2, vs_transform{0, 0, 0, 0});      // (entry 0's transform is not read)
+    for (int i = 0; i < n_pairs; i++) t2[2 * (size_t)i + 1] = pair_t[i];
+    std::vector<vsk::FillCand> pc;
+    return cand_groups(ring, 0, n_pairs, plan::frames_per_group_entries(2, 4), 2, pair_src, t2.data(), w, h, false, true, s, pc,
+        FrameIsEntry0{pair_src, 2, __func__}, no_side_word,
+        [&](vsk::FillCand* cdev, float*, int f0, int nf) -> int {
+            VS_HIP(vsk::scene_stats(cdev, w, h, src_stride, (int)esz * 8, bits - 8, vs_format_max_value(format), p.step,
+                                    (unsigned long long*)stats + (size_t)f0 * 2, nf, s));
             return VS_OK;
         });
 }
@@ -355,6 +387,29 @@ int vs_bgr_exposure_stats_batch(const void* src, size_t src_fs, int n_src, int w
     VS_TRY(o.out(stats, (size_t)n_out * n_cand * 8 * sizeof(uint64_t), mem));
     const std::vector<const void*> ptrs = idx.pointers<void>(a.dev, src_fs * in.esz());
     VS_TRY(exposure_stats_ptrs(n_out, w, h, src_stride, format, n_cand, ptrs.data(), cand_t, &p, o.as<uint64_t>(), s));
+    return finish_outputs(mem, s, {&o});
+} VS_CATCH_ALL
+
+int vs_bgr_scene_stats_batch(const void* src, size_t src_fs, int n_src, int w, int h, int src_stride, int format, int n_pairs, const int32_t* pair_frames,
+                             const vs_transform* pair_t, const vs_scene_params* params, uint64_t* stats, int mem, void* stream) try {
+    const int bits = vs_format_bits(format);
+    const plan::Batch in{src, src_fs, n_src, w, h, src_stride, 3, bits};
+    VS_ARG(n_pairs >= 0);
+    VS_TRY(pass_args_ok(__func__, "scene cut", kAsTheFill, w, h, format, 2, src != nullptr, 1, src_stride, nullptr));
+    VS_ARG(n_src >= 1 && in.strides_ok());
+    vs_scene_params p;
+    VS_TRY(scene_params_ok(params, &p));
+    if (n_pairs == 0) return VS_OK;                                     // nothing to measure, nothing launched
+    VS_ARG(pair_frames && pair_t && stats);
+    for (size_t i = 0; i < 2 * (size_t)n_pairs; i++) VS_ARG(pair_frames[i] >= 0 && pair_frames[i] < n_src);
+    if (!device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    Staged a, o;
+    VS_TRY(stage_in(a, in, mem, s));
+    VS_TRY(o.out(stats, (size_t)n_pairs * 2 * sizeof(uint64_t), mem));
+    std::vector<const void*> ptrs(2 * (size_t)n_pairs);
+    for (size_t i = 0; i < ptrs.size(); i++) ptrs[i] = (const char*)a.dev + (size_t)pair_frames[i] * src_fs * in.esz();
+    VS_TRY(scene_stats_ptrs(n_pairs, w, h, src_stride, format, ptrs.data(), pair_t, &p, o.as<uint64_t>(), s));
     return finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 

@@ -114,6 +114,27 @@ void vs_lens_params_default(vs_lens_params* p, int w, int h) {
 void vs_deflicker_params_default(vs_deflicker_params* p) {
     p->step = 4;
 }
+// vs_scene.hip (DESIGN.md "Scene-cut detection": the deflicker's lattice; 32 levels lies above a 20 % exposure jump and below every cut of the
+// synthetic clips -- a starting value, not a calibrated one)
+void vs_scene_params_default(vs_scene_params* p) {
+    p->step = 4;
+    p->threshold = 32;
+}
+// the scene-cut rule's decision (vs_scene.hip), unsigned 64-bit throughout
+int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_scene_params* params, uint8_t* cut) try {
+    vs_scene_params p;
+    if (params) p = *params; else vs_scene_params_default(&p);
+    if (n_pairs < 0 || w < 1 || h < 1 || w > 65535 || h > 65535 || p.step < 1 || p.step > 64 || p.threshold < 1 || p.threshold > 255 ||
+        (n_pairs > 0 && (!stats || !cut)))
+        return vsi::set_error(VS_ERR_ARG, "bad argument: n_pairs >= 0, w, h in 1 .. 65535, step in 1 .. 64, threshold in 1 .. 255, stats and cut (vs_scene_cuts)");
+    const uint64_t L = (uint64_t)((w + p.step - 1) / p.step) * (uint64_t)((h + p.step - 1) / p.step);
+    const uint64_t need = std::max<uint64_t>(1, L / 16);
+    for (int i = 0; i < n_pairs; i++) {
+        const uint64_t count = stats[2 * (size_t)i], sad = stats[2 * (size_t)i + 1];
+        cut[i] = (count < need || sad > 3ull * (uint64_t)p.threshold * count) ? 1 : 0;
+    }
+    return VS_OK;
+} VS_CATCH_ALL
 
 // imgproc.cpp:333-359
 vs_transform vs_transform_inverse(const vs_transform* t) {

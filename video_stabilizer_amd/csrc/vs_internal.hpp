@@ -164,6 +164,12 @@ int bgr_rolling_ptrs(int n_out, int w, int h, int src_stride, int format, const 
 int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int n_cand, const void* const* cand_src, const vs_transform* cand_t,
                         const vs_deflicker_params* params, uint64_t* stats, hipStream_t s);
 
+// The scene-cut statistics (the rule: vs_scene.hip) on device-resident frames; vs_bgr_scene_stats_batch is the index-based wrapper over it.  Pair
+// i: the target frame at pair_src[2 i] and the candidate frame at pair_src[2 i + 1] (any device pointers, w x h, rows of src_stride elements) under
+// pair_t[i].  stats: n_pairs x 2 words of device memory, zeroed on `s` first.  Host arrays; enqueue only.
+int scene_stats_ptrs(int n_pairs, int w, int h, int src_stride, int format, const void* const* pair_src, const vs_transform* pair_t,
+                     const vs_scene_params* params, uint64_t* stats, hipStream_t s);
+
 // The inpaint's coverage index (the rule: vs_inpaint.hip) on the device; vs_bgr_fill_coverage_batch is the index-based wrapper over it.  The
 // candidates of output frame o as bgr_warp_fill_ptrs takes them -- cand_t[o * n_cand + c], a null cand_src entry ends the list, entry 0 is the
 // frame itself; no frame is read.  cov: n_out indices of roi_h rows of cov_stride bytes, cov_fs bytes apart, in device memory; open_count (may

@@ -129,6 +129,11 @@ hipError_t exposure_stats(const FillCand* cands_dev, int n_cand, int w, int h, i
 hipError_t exposure_gains(const unsigned long long* stats, int n_out, int n_cand, int w, int h, int step, uint32_t* gains, hipStream_t s);
 hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int max_value, const uint32_t* gains, void* dst, int dst_stride, int n_frames,
                     size_t src_fs, size_t dst_fs, hipStream_t s);
+// Scene-cut detection (vs_scene.hip: the rule and the kernel).  cands_dev = n_pairs x 2 entries in device memory: entry 0 of a pair is the target
+// frame (its matrix is not read), entry 1 the candidate frame with vs_cv_inverse_matrix of the pair's transform; a null frame on either side
+// leaves the pair's words zero.  stats = n_pairs x 2 words (count, sad) in device memory, zeroed on `s` first.
+hipError_t scene_stats(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int step, unsigned long long* stats,
+                       int n_pairs, hipStream_t s);
 // Inpaint of what the fill leaves open (vs_inpaint.hip: the rule and the kernels).  fill_coverage: cands_dev as the fill takes them (entry 0's
 // matrix; a null frame ends a list; no frame is read); cov[frame][y * cov_stride + x] = 1 + the first covering candidate, 0 for none;
 // open_count (device, may be null): zeroed on `s`, then the frame's number of zeros.  mask_open_count: the same count from a mask.

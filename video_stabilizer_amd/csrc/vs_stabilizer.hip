@@ -1,5 +1,5 @@
 // vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
-// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_remap, vs_deflicker).
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_remap, vs_deflicker, vs_scene).
 //
 // Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
 // then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
@@ -56,6 +56,16 @@ struct vs_stabilizer {
     int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
     vs_deflicker_params deflicker_params{4};
     void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
+    // scene-cut detection (vs_scene.hip)
+    bool scene_on = false;         // vs_stabilizer_set_scene_cut: NULL: off
+    vs_scene_params scene_params{4, 32};
+    std::deque<int> meas_cut;      // the cut flag of every entry of `measurements` (vs_stab_step.hpp: stab_step_cut); all zero while detection is off
+    void* scene_prev = nullptr; size_t scene_prev_bytes = 0;   // lag == 0: nothing is queued, so the last frame of a call waits here for the next call's first pair
+    bool scene_prev_valid = false;
+    hipStream_t scene_stream = nullptr;   // overlapped runs: the statistics and their download go beside the next chunk's alignment, which is already
+    hipEvent_t scene_ev = nullptr;        // enqueued on the handle's stream; scene_ev: everything on that stream in front of it
+    long long cut_total = 0;       // cuts since the last reset
+    std::deque<int64_t> cut_list;  // ... the most recent 256 of them: 0-based frame indices since that reset
     // inpaint (vs_inpaint.hip)
     int inpaint = 0;               // vs_stabilizer_set_inpaint: what no candidate covers in the output window is inpainted (0: off)
     void* inpaint_buf = nullptr; size_t inpaint_bytes = 0;   // one group of frames: their open counts, their coverage indices, their pyramids
@@ -141,6 +151,9 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     if (s->lens_map) (void)hipFree(s->lens_map);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
+    if (s->scene_prev) (void)hipFree(s->scene_prev);
+    if (s->scene_stream) { (void)vsi::retire_stream(s->scene_stream); (void)hipStreamDestroy(s->scene_stream); }
+    if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     for (void* q : s->ycbcr.buf) if (q) (void)hipFree(q);
     if (s->batch_in) (void)hipFree(s->batch_in);
     for (void* q : s->batch_out) if (q) (void)hipFree(q);
@@ -254,6 +267,8 @@ struct Chunk {
                                        // sharpness); denoise; deflicker (candidate 0 stays the ORIGINAL frame whatever deblur and denoise do)
     Ahead rs{};                        // rolling shutter: depth min(1, lag) -- the motion to the frame that follows (that frame's pixels are not read)
     uint32_t* fk_gains = nullptr;  // deflicker: four words per job, in flicker_buf
+    std::vector<uint8_t> cuts;     // scene-cut detection: frame i of the chunk shows another scene than its predecessor (all zero while it is off)
+    hipStream_t cut_stream = st;   // ... where its statistics run: scene_stream once the next chunk's alignment has been enqueued on `st`
 
     // stabilizer.cpp:15: a private dense copy of every input frame, in device memory
     // With the lens correction on the frames land there corrected: the remap reads device frames in place, whatever their pitch, and host frames
@@ -340,10 +355,66 @@ struct Chunk {
         else VS_TRY(start(cur, dense, c.n, false));
         VS_TRY(vsi::align_finish(a));
         if (s->next_n > 0 && already_dense) {
+            if (s->scene_on) {                              // detect_cuts works beside the alignment started here, behind what `st` holds now
+                if (!s->scene_stream) VS_HIP(hipStreamCreateWithFlags(&s->scene_stream, hipStreamNonBlocking));
+                if (!s->scene_ev) VS_HIP(hipEventCreateWithFlags(&s->scene_ev, hipEventDisableTiming));
+                VS_HIP(hipEventRecord(s->scene_ev, st));
+                VS_HIP(hipStreamWaitEvent(s->scene_stream, s->scene_ev, 0));
+                cut_stream = s->scene_stream;
+            }
             VS_TRY(start(cur ^ 1, s->next_frames, s->next_n, true));
             s->prefetched = true;
             s->tb = cur ^ 1;
         }
+        return VS_OK;
+    }
+
+    // Scene-cut detection (vs_scene.hip): every frame of the call that has a predecessor in the same clip is compared with
+    // it through the motion just measured -- the pair (frame j-1, frame j, t), t from lookahead_transforms over the single measurement T_j, so
+    // that its direction is the look-ahead passes' by construction.  One statistics launch, one download of two words per pair through the
+    // pinned staging of the kernel-level calls, the decision on the host.  The predecessor of the call's first frame is the back of the queue
+    // (lag == 0: the handle's copy of the previous call's last frame).  Off: nothing is launched and nothing allocated.
+    int detect_cuts() {
+        cuts.assign((size_t)c.n, 0);
+        if (!s->scene_on) return VS_OK;
+        std::vector<const void*> src;
+        std::vector<vs_transform> t;
+        std::vector<int> at;
+        const int one = 1;
+        for (int i = 0; i < c.n; i++) {
+            const void* prev = nullptr;
+            if (c.clip_len > 0 ? i % c.clip_len != 0 : i > 0) prev = dense + (size_t)(i - 1) * fbytes;
+            else if (c.clip_len > 0) continue;              // a clip's first frame
+            else if (!s->frames.empty()) prev = s->frames.back().ptr;
+            else if (s->scene_prev_valid) prev = s->scene_prev;
+            if (!prev) continue;
+            vs_transform tr;
+            (void)vsi::lookahead_transforms(&s->t_buf[cur][i], &one, 1, 1, nullptr, &tr);
+            src.push_back(prev);
+            src.push_back(dense + (size_t)i * fbytes);
+            t.push_back(tr);
+            at.push_back(i);
+        }
+        if (at.empty()) return VS_OK;
+        const int np = (int)at.size();
+        std::vector<uint64_t> stats(2 * (size_t)np);
+        {
+            vsi::Staged o;
+            VS_TRY(o.out(stats.data(), stats.size() * sizeof(uint64_t), VS_MEM_HOST));
+            VS_TRY(vsi::scene_stats_ptrs(np, w, h, w * 3, c.format, src.data(), t.data(), &s->scene_params, o.as<uint64_t>(), cut_stream));
+            VS_TRY(vsi::finish_outputs(VS_MEM_HOST, cut_stream, {&o}));
+        }
+        std::vector<uint8_t> flag((size_t)np);
+        VS_TRY(vs_scene_cuts(stats.data(), np, w, h, &s->scene_params, flag.data()));
+        for (int k = 0; k < np; k++) cuts[(size_t)at[k]] = flag[(size_t)k];
+        return VS_OK;
+    }
+    // lag == 0: the call's last frame waits in a buffer of the handle's for the next call's first pair
+    int keep_last_frame() {
+        if (!s->scene_on || s->params.lag > 0 || c.clip_len > 0) return VS_OK;
+        VS_HIP(grow(&s->scene_prev, &s->scene_prev_bytes, fbytes));   // (its one reader, detect_cuts, has synchronised)
+        VS_HIP(hipMemcpyAsync(s->scene_prev, dense + (size_t)(c.n - 1) * fbytes, fbytes, hipMemcpyDeviceToDevice, st));
+        s->scene_prev_valid = true;
         return VS_OK;
     }
 
@@ -384,12 +455,18 @@ struct Chunk {
                                      mblk ? mblk->dev + 3 * (size_t)i : nullptr});
             if (sblk) ++sblk->refs;
             if (mblk) ++mblk->refs;
-            const vs_transform meas = s->t_buf[cur][i];
+            const bool cut = cuts[(size_t)i] != 0;
+            const vs_transform meas = cut ? vs_transform{0, 0, 0, 0} : s->t_buf[cur][i];
             const bool success = s->st_buf[cur][i] == 1;
-            s->last_meas = meas; s->last_success = success ? 1 : 0;
+            s->last_meas = meas; s->last_success = success && !cut ? 1 : 0;
+            if (cut) {
+                ++s->cut_total;
+                if (s->cut_list.size() == 256) s->cut_list.pop_front();
+                s->cut_list.push_back((int64_t)s->frame_index - 1);
+            }
             c.has_output[i] = 0;
             vs_transform correction;
-            if (!vsi::stab_step(meas, success, w, h, s->params, s->smoother, s->measurements, s->meas_ok, s->accum, &correction)) continue;
+            if (!vsi::stab_step_cut(meas, success, cut, w, h, s->params, s->smoother, s->measurements, s->meas_ok, s->meas_cut, s->accum, &correction)) continue;
             if (s->frames.empty()) continue;
             const Held src = s->frames.front();
             s->frames.pop_front();
@@ -611,6 +688,7 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
     VS_TRY(k.make_dense());
     VS_TRY(k.measure_side_values());
     VS_TRY(k.align());
+    VS_TRY(k.detect_cuts());
     VS_TRY(k.frame_loop());
     if (!k.jobs.empty()) {
         VS_TRY(k.passes());
@@ -621,6 +699,7 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
     if (!warps_apart) sharp_settle(s);                    // (readers and the next writer share this stream)
     if (c.clip_len > 0) VS_TRY(vs_stabilizer_reset(s));   // nothing carries over from the last clip
     VS_TRY(k.own_queued());
+    VS_TRY(k.keep_last_frame());
     if (!s->prefetched) VS_HIP(hipStreamSynchronize(st));   // (with the next chunk's alignment in flight its completion is the next call's wait)
     return std::accumulate(c.has_output, c.has_output + c.n, 0);
 }
@@ -917,6 +996,25 @@ int vs_stabilizer_get_lens(const vs_stabilizer* s, vs_lens_params* params, int* 
     if (s->lens_on) *params = s->lens; else vs_lens_params_default(params, 0, 0);
     return s->lens_on ? 1 : 0;
 } VS_CATCH_ALL
+int vs_stabilizer_set_scene_cut(vs_stabilizer* s, const vs_scene_params* params) try {
+    VS_ARG(s);
+    if (params) VS_ARG(params->step >= 1 && params->step <= 64 && params->threshold >= 1 && params->threshold <= 255);
+    s->scene_on = params != nullptr;
+    if (params) s->scene_params = *params;
+    else s->scene_prev_valid = false;                                 // (off: no frame is kept; switched on again, a lag-0 handle starts with the frame after next)
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_scene_cut(const vs_stabilizer* s, vs_scene_params* params) try {
+    VS_ARG(s && params);
+    if (s->scene_on) *params = s->scene_params; else vs_scene_params_default(params);
+    return s->scene_on ? 1 : 0;
+} VS_CATCH_ALL
+int vs_stabilizer_get_scene_cuts(const vs_stabilizer* s, int64_t* frames, int cap) try {
+    VS_ARG(s && cap >= 0 && (frames || cap == 0));
+    const size_t m = std::min(s->cut_list.size(), (size_t)cap);
+    for (size_t k = 0; k < m; k++) frames[k] = s->cut_list[s->cut_list.size() - m + k];
+    return (int)std::min<long long>(s->cut_total, 0x7fffffff);
+} VS_CATCH_ALL
 int vs_stabilizer_wait_stream(vs_stabilizer* s, void* producer_stream) try {
     VS_ARG(s && s->aligner);
     return vs_aligner_wait_stream(s->aligner, producer_stream);
@@ -930,6 +1028,10 @@ int vs_stabilizer_reset(vs_stabilizer* s) try {
     s->frames.clear();
     s->measurements.clear();
     s->meas_ok.clear();
+    s->meas_cut.clear();
+    s->scene_prev_valid = false;
+    s->cut_total = 0;
+    s->cut_list.clear();
     // (make the new smoother first: if that fails the handle keeps a valid, if stale, one -- never a null pointer for the next call to walk into)
     vs_smoother* fresh = vs_smoother_create(s->params.lag, s->params.smoother_memory, s->params.lambda);
     if (!fresh) return VS_ERR_NOMEM;
