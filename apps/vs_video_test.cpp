@@ -1,5 +1,5 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444] [--device-convert]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444] [--device-convert]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
@@ -10,7 +10,8 @@
 // output frame's exposure is pulled to the mean exposure of itself and the next N input frames (vs_stabilizer_set_deflicker; --deflicker-step S: the lattice
 // step of the exposure statistics, 1 .. 64, default 4).  --scene-cut [T]: consecutive frames are compared through their measured motion and a frame that shows
 // another scene ends every look-ahead list in front of it and starts a clean path (vs_stabilizer_set_scene_cut; T: the threshold in 8-bit levels, 1 .. 255,
-// default 32); the clip's cut list is printed.  --rolling-shutter R: every frame is corrected for a rolling shutter whose readout takes the
+// default 32); the clip's cut list is printed.  --sharpen [S]: every output window is sharpened behind the warp by the sub-pixel phase of its own
+// correction, which evens out the bilinear warp's phase-dependent blur (vs_stabilizer_set_sharpen; S: the strength in sixteenths, 1 .. 32, default 16).  --rolling-shutter R: every frame is corrected for a rolling shutter whose readout takes the
 // share R (-1 .. 1, negative: bottom-up) of the frame period, by the motion to the following frame (vs_stabilizer_set_rolling_shutter).
 // --lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]: every frame is corrected for that lens's distortion in front of everything (the camera matrix in
 // pixels, then OpenCV's distCoeffs in their order; --lens-zoom Z scales the output camera's focal lengths, default 1; vs_stabilizer_set_lens).  Frames go to the GPU in
@@ -40,7 +41,7 @@ static vs_ycbcr_planes planes_of(const vsio::Format& f, void* base) {
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step, int scene_cut, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom, bool device_convert) {
+                         int deflicker_step, int scene_cut, int sharpen, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom, bool device_convert) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -108,6 +109,16 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
         if (scene_cut != 0) sp.threshold = scene_cut;
         if (vs_stabilizer_set_scene_cut(stab, &sp) != VS_OK) {
             std::cerr << "Error: vs_stabilizer_set_scene_cut: " << vs_last_error() << std::endl;
+            vs_stabilizer_destroy(stab);
+            return false;
+        }
+    }
+    if (sharpen >= 0) {
+        vs_sharpen_params hp;
+        vs_sharpen_params_default(&hp);
+        if (sharpen != 0) hp.strength = sharpen;
+        if (vs_stabilizer_set_sharpen(stab, &hp) != VS_OK) {
+            std::cerr << "Error: vs_stabilizer_set_sharpen: " << vs_last_error() << std::endl;
             vs_stabilizer_destroy(stab);
             return false;
         }
@@ -183,7 +194,7 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
 
 int main(int argc, char** argv) {
     std::string input_dir = "../recordings", output_dir = "output";   // video_test.cpp:12-13
-    int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, denoise = 0, denoise_strength = 0, deflicker = 0, deflicker_step = 0, scene_cut = -1, positional = 0;
+    int chunk = 64, device = 0, crop = 0, fill = 0, deblur = 0, denoise = 0, denoise_strength = 0, deflicker = 0, deflicker_step = 0, scene_cut = -1, sharpen = -1, positional = 0;
     bool bilinear = false, lanczos2 = false, force444 = false, device_convert = false;
     vs_fill_blend_params blend{0, 0};
     bool inpaint = false;
@@ -210,6 +221,13 @@ int main(int argc, char** argv) {
                 if (scene_cut == 0) scene_cut = 256;           // (0 is not a threshold: refused by the library like any value outside 1 .. 255)
             }
         }
+        else if (a == "--sharpen") {                            // (-1: off, 0: the default strength)
+            sharpen = 0;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos) {
+                sharpen = std::atoi(argv[++i]);
+                if (sharpen == 0) sharpen = 33;                // (0 is not a strength: refused by the library like any value outside 1 .. 32)
+            }
+        }
         else if (a == "--rolling-shutter" && i + 1 < argc) rolling = std::atof(argv[++i]);
         else if (a == "--lens" && i + 1 < argc) {
             lens.clear();
@@ -229,7 +247,7 @@ int main(int argc, char** argv) {
         else if (a == "--device-convert") device_convert = true;
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444] [--device-convert]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444] [--device-convert]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -255,7 +273,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, scene_cut, inpaint, rolling, lens, lens_zoom, device_convert)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, scene_cut, sharpen, inpaint, rolling, lens, lens_zoom, device_convert)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

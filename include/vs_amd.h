@@ -604,6 +604,43 @@ int vs_bgr_scene_stats_batch(const void* src, size_t src_frame_stride, int n_src
                              const vs_scene_params* params /* NULL = defaults */, uint64_t* stats /* 2 per pair */, int mem, void* stream);
 /* The rule's decision, on the host (no device needed): cut[i] = 1 iff pair i is a cut.  stats and cut are host arrays. */
 int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_scene_params* params /* NULL = defaults */, uint8_t* cut);
+/* PHASE-COMPENSATED SHARPENING behind VS_WARP_BILINEAR_CV.  A bilinear resample is a two-tap box filter per axis, [1 - f, f], whose blur
+ * depends on the sub-pixel phase f: none at f = 0, most at f = 1/2.  In stabilised video every pixel's phase drifts from frame to frame, so
+ * the output's sharpness pulses.  The warp's positions carry five fraction bits, a = X & 31, b = Y & 31; the filter [1 - a/32, a/32] has
+ * variance a (32 - a) / 1024 pixel^2, and its second-order inverse is identity - (variance / 2) [1, -2, 1]: a five-point stencil whose two
+ * weights are known per pixel from the warp's own matrix.
+ *
+ * THE SHARPEN RULE (also vs_sharpen.hip).
+ *   - SCOPE.  Interleaved BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as the fill).
+ *   - IMAGE AND WINDOW.  The input is an image of roi_w x roi_h pixels: the window [roi_x, roi_x + roi_w) x [roi_y, roi_y + roi_h) of a
+ *     w x h output frame that VS_WARP_BILINEAR_CV made under the forward transform t.  (x, y) below are full-frame coordinates, as in the
+ *     fill.
+ *   - POSITIONS.  X, Y (int32, five fraction bits) and sx = X >> 5, sy = Y >> 5 are the fill's, to the letter (see
+ *     vs_bgr_image_warp_fill_batch): M = vs_cv_inverse_matrix(t); cvRound saturates to int32, NaN gives 0, and + 16 and X0 + adelta wrap.
+ *     a = X & 31, b = Y & 31, va = a (32 - a), vb = b (32 - b): both lie in 0 .. 256.
+ *   - COVERED.  A pixel is covered iff all four taps lie in the frame (the fill's candidate-0 rule): 0 <= sx, sx + 1 <= w - 1, 0 <= sy,
+ *     sy + 1 <= h - 1.
+ *   - ELIGIBLE.  A pixel is eligible iff it is not on the window's outermost row or column, it is covered, and its four edge neighbours
+ *     (x +- 1, y) and (x, y +- 1) are covered.
+ *   - DELTA.  For an eligible pixel and each channel, with raw samples c, l, r, u, d (no clamp of the taps):
+ *     num = strength * (va * (2c - l - r) + vb * (2c - u - d)), delta = (num + 16384) >> 15, an arithmetic shift.
+ *   - OUTPUT.  out = c if the pixel is not eligible or delta == 0; otherwise out = clamp(c + delta, 0, max_value).
+ *   - STRENGTH.  1 .. 32 in sixteenths, default 16: the filter's own variance, the derivation above, not a tuned value.  Anything else
+ *     is VS_ERR_ARG.
+ *   - BOUND.  |num| <= 32 * 512 * 131070 = 2 147 450 880 < 2^31 - 16384: int32 is enough throughout.
+ *   - HENCE (a) under the identity or any whole-pixel shift every pixel comes back bit for bit; (b) a constant image, and an image linear
+ *     in x and y, come back bit for bit under any map; (c) pixels the frame's own source does not cover (border, fill, inpaint), and their
+ *     edge neighbours, come back bit for bit; (d) a sample above max_value is changed only where delta != 0; (e) a NaN map gives
+ *     X = Y = 16 >> 5 = 0 everywhere: every pixel is covered and va = vb = 0, so the image comes back bit for bit. */
+typedef struct vs_sharpen_params { int strength; } vs_sharpen_params;
+void vs_sharpen_params_default(vs_sharpen_params* p);   /* 16 */
+/* n images of roi_w x roi_h at src (rows of src_stride elements, src_frame_stride elements apart), image i under t[i], to dst in the same
+ * shape (dst_stride, dst_frame_stride).  n == 0 is VS_OK without a launch.  The stencil cannot run in place: a src range that overlaps the
+ * dst range is VS_ERR_ARG.  A window outside the w x h frame is VS_ERR_ARG.  t is a host array.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_sharpen_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int format,
+                         const vs_transform* t /* host, n */, const vs_sharpen_params* params /* NULL = defaults */,
+                         int roi_x, int roi_y, int roi_w, int roi_h, int src_stride,
+                         void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 /* ---- Inpaint of what the border fill leaves open: a coverage index and an exact-integer push-pull over the output window ----
  * THE RULE.  VS_WARP_BILINEAR_CV conventions, 3 channels, 8- and 16-bit containers, every VS_FMT_BGR*, windows up to 32767 a side.
  *   - COVERAGE INDEX.  Output frame o has n_cand (1 .. 16) candidates exactly as in vs_bgr_image_warp_fill_batch: each a forward
@@ -955,6 +992,16 @@ int   vs_stabilizer_get_inpaint(const vs_stabilizer* s);
 int   vs_stabilizer_set_scene_cut(vs_stabilizer* s, const vs_scene_params* params /* NULL = off */);
 int   vs_stabilizer_get_scene_cut(const vs_stabilizer* s, vs_scene_params* params);
 int   vs_stabilizer_get_scene_cuts(const vs_stabilizer* s, int64_t* frames, int cap);
+/* Phase-compensated sharpening (the rule: see vs_bgr_sharpen_batch).  NULL (default): off -- the handle as it is without this call, launch
+ * for launch and allocation for allocation.  On: the warp -- with fill, blend and inpaint as configured -- writes groups of output windows
+ * into a scratch buffer of the handle (one allocation, at most 256 MB or one window), and the sharpen writes them to where they went
+ * before, each under its own frame's correction; the deflicker's gain follows in place as before.  Fill and inpaint pixels and their edge
+ * neighbours are not sharpened, nor is the window's outer ring.  A frame whose correction puts every pixel on phase 0 comes back bit for
+ * bit; its launch is not skipped.  VS_ERR_UNSUPPORTED on a handle with another warp_mode than VS_WARP_BILINEAR_CV; VS_ERR_ARG for a
+ * strength outside 1 .. 32.  Takes effect with the next output frame.
+ * get_sharpen: returns 1 (on: *params in force) or 0 (off: *params = the defaults). */
+int   vs_stabilizer_set_sharpen(vs_stabilizer* s, const vs_sharpen_params* params /* NULL = off */);
+int   vs_stabilizer_get_sharpen(const vs_stabilizer* s, vs_sharpen_params* params);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -110,6 +110,11 @@ class SceneParams(C.Structure):
     _fields_ = [("step", C.c_int), ("threshold", C.c_int)]
 
 
+class SharpenParams(C.Structure):
+    """vs_sharpen_params: the strength in sixteenths of the two-tap filter's own variance, 1 .. 32"""
+    _fields_ = [("strength", C.c_int)]
+
+
 class FillBlendParams(C.Structure):
     """vs_fill_blend_params: feather 0 (off) or 1 .. 6; match 0 or 1"""
     _fields_ = [("feather", C.c_int), ("match", C.c_int)]
@@ -213,6 +218,8 @@ SIGNATURES = {
     "vs_bgr_scene_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(SceneParams), _vp, _i32, _vp]),
     "vs_scene_cuts": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(SceneParams), _vp]),
     "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_sharpen_params_default": (None, [C.POINTER(SharpenParams)]),
+    "vs_bgr_sharpen_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _TP, C.POINTER(SharpenParams), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_inpaint_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
@@ -244,6 +251,8 @@ SIGNATURES = {
     "vs_stabilizer_set_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
     "vs_stabilizer_get_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
     "vs_stabilizer_get_scene_cuts": (_i32, [_vp, C.POINTER(C.c_int64), _i32]),
+    "vs_stabilizer_set_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
+    "vs_stabilizer_get_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_inpaint": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
@@ -1123,6 +1132,40 @@ def scene_cuts(stats, w, h, params=None):
     return out[:st.shape[0]]
 
 
+def sharpen_params(**kw):
+    p = SharpenParams()
+    lib().vs_sharpen_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def sharpen_batch(src, ts, w, h, roi_x=0, roi_y=0, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """phase-compensated sharpening behind VS_WARP_BILINEAR_CV (include/vs_amd.h: vs_bgr_sharpen_batch).  src (n, roi_h, roi_w, 3) numpy: the
+    window at (roi_x, roi_y) of w x h output frames warped under the forward Transforms ts (n of them) -> (n, roi_h, roi_w, 3).  src_stride /
+    dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
+    buffer is returned as well"""
+    src = np.ascontiguousarray(src)
+    n, rh, rw, c = src.shape
+    assert len(ts) == n
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = rw * c if src_stride is None else src_stride
+    ds = rw * c if dst_stride is None else dst_stride
+    arr = (Transform * max(n, 1))(*ts)
+    out = np.full((max(n, 1), rh, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_sharpen_batch(_p(_pitched(src, ss)) if n else None, rh * ss, n, w, h, fmt, arr, C.byref(params) if params is not None else None,
+                                      roi_x, roi_y, rw, rh, ss, _p(out), rh * ds, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:n, :, :rw * c]).reshape(n, rh, rw, c)
+    return (res, out) if guard is not None else res
+
+
+def sharpen_batch_device(src_ptr, src_fs, n, w, h, fmt, ts, roi_x, roi_y, roi_w, roi_h, src_stride, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    arr = (Transform * max(n, 1))(*ts)
+    _check(lib().vs_bgr_sharpen_batch(_p(src_ptr), src_fs, n, w, h, fmt, arr, C.byref(params) if params is not None else None, roi_x, roi_y, roi_w, roi_h,
+                                      src_stride, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
 def bgr_gain_batch(src, gains, fmt=None, src_stride=None, dst_stride=None, guard=None):
     """the deflicker's point-wise pass (include/vs_amd.h: vs_bgr_gain_batch).  src (n,h,w,3) numpy; gains (n,4) uint32 -> (n,h,w,3).  src_stride /
     dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
@@ -1387,7 +1430,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, sharpen=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1412,6 +1455,18 @@ class Stabilizer:
             self.set_lens(*lens)
         if scene_cut is not None:
             self.set_scene_cut(scene_params() if scene_cut is True else scene_cut)
+        if sharpen is not None:
+            self.set_sharpen(sharpen_params() if sharpen is True else sharpen)
+
+    def set_sharpen(self, params):
+        """None: off; a SharpenParams (sharpen_params()): every output window is sharpened behind the warp by the phase of its own correction
+        (VS_WARP_BILINEAR_CV handles)"""
+        _check(lib().vs_stabilizer_set_sharpen(self.h, C.byref(params) if params is not None else None))
+
+    def get_sharpen(self):
+        """None (off) or the SharpenParams in force"""
+        p = SharpenParams()
+        return p if _check(lib().vs_stabilizer_get_sharpen(self.h, C.byref(p))) else None
 
     def set_scene_cut(self, params):
         """None: off; a SceneParams (scene_params()): every arriving frame is compared with its predecessor through the measured motion, and a

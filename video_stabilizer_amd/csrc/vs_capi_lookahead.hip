@@ -1,5 +1,5 @@
 // vs_capi_lookahead.hip -- the look-ahead passes of the C ABI (include/vs_amd.h) next to the border fill (vs_capi_warp.hip): channel sums,
-// sharpness and deblur, denoise, rolling-shutter correction, remap and lens map, exposure statistics / gains / gain, scene-cut statistics, coverage index and inpaint.  Each pass that takes candidate lists is a
+// sharpness and deblur, denoise, rolling-shutter correction, remap and lens map, exposure statistics / gains / gain, scene-cut statistics, sharpen, coverage index and inpaint.  Each pass that takes candidate lists is a
 // *_ptrs function in vsi (device-resident frames, enqueue only: the engine's form) and an index-based *_batch wrapper over it; what brings a
 // list to a kernel is cand_groups (vs_capi.hpp).
 #include "vs_capi.hpp"
@@ -237,6 +237,56 @@ int vsi::fill_coverage_ptrs(int n_out, int w, int h, int n_cand, const void* con
             VS_HIP(vsk::fill_coverage(cdev, n_cand, w, h, cov + (size_t)f0 * cov_fs, cov_stride, nf, cov_fs, roi, open_count ? open_count + f0 : nullptr, s));
             return VS_OK;
         });
+}
+
+// ---- phase-compensated sharpening (vs_sharpen.hip) ----
+namespace {
+int sharpen_params_ok(const vs_sharpen_params* params, vs_sharpen_params* p) {
+    if (params) *p = *params; else vs_sharpen_params_default(p);
+    VS_ARG(p->strength >= 1 && p->strength <= 32);
+    return VS_OK;
+}
+// the sharpen's argument rule, for the function on the device and its staging wrapper alike; none of it needs a device
+int sharpen_args_ok(const char* fn, const plan::Batch& in, const plan::Batch& out, int w, int h, int format, const vs_transform* t, int roi_x, int roi_y) {
+    VS_ARG_AS(w > 0 && h > 0 && w <= 65535 && h <= 65535 && in.n >= 0, fn);
+    VS_TRY(bgr_format_ok(format));
+    VS_TRY(lookahead_args_ok("sharpen", kAsTheFill, w, h, 1));
+    VS_ARG_AS(plan::window_ok(roi_x, roi_y, in.w, in.h, w, h), fn);
+    if (in.n == 0) return VS_OK;
+    VS_ARG_AS(in.p && out.p && t, fn);
+    VS_ARG_AS(in.strides_ok() && out.strides_ok(), fn);
+    // the stencil cannot run in place
+    const char *a0 = (const char*)in.p, *a1 = a0 + in.bytes(), *b0 = (const char*)out.p, *b1 = b0 + out.bytes();
+    VS_ARG_AS(a1 <= b0 || b1 <= a0, fn);
+    return VS_OK;
+}
+}  // namespace
+
+// The sharpen pass on device-resident windows (vs_internal.hpp).  The frames' matrices travel through the parameter ring, three slots a frame, in
+// the plain warp's groups.
+int vsi::bgr_sharpen_ptrs(const void* src, size_t src_fs, int n, int w, int h, int format, const vs_transform* t, const vs_sharpen_params* params, int roi_x,
+                          int roi_y, int roi_w, int roi_h, int src_stride, void* dst, size_t dst_fs, int dst_stride, hipStream_t s) {
+    const int bits = vs_format_bits(format);
+    const plan::Batch in{src, src_fs, n, roi_w, roi_h, src_stride, 3, bits}, out{dst, dst_fs, n, roi_w, roi_h, dst_stride, 3, bits};
+    VS_TRY(sharpen_args_ok(__func__, in, out, w, h, format, t, roi_x, roi_y));
+    vs_sharpen_params p;
+    VS_TRY(sharpen_params_ok(params, &p));
+    if (n == 0) return VS_OK;
+    ParamRing* ring = param_ring();
+    if (!ring) return no_ring();
+    const size_t esz = in.esz();
+    const int per_call = plan::frames_per_group_matrices();
+    std::vector<double> Mv((size_t)std::min(n, per_call) * 6);
+    for (int f0 = 0; f0 < n; f0 += per_call) {
+        const int nf = std::min(per_call, n - f0);
+        for (int i = 0; i < nf; i++) vs_cv_inverse_matrix(&t[f0 + i], w, h, &Mv[(size_t)i * 6]);
+        float4* mdev = nullptr;
+        VS_TRY(send_slots(ring, Mv.data(), (size_t)nf * 3, s, &mdev));             // (six doubles: three 16-byte slots)
+        VS_HIP(vsk::bgr_sharpen((const char*)src + (size_t)f0 * src_fs * esz, src_fs, nf, w, h, src_stride, (int)esz * 8, vs_format_max_value(format),
+                                (const double*)mdev, p.strength, vsk::Roi{roi_x, roi_y, roi_w, roi_h}, (char*)dst + (size_t)f0 * dst_fs * esz, dst_fs, dst_stride, s));
+        VS_TRY(ring->fence(mdev, s));
+    }
+    return VS_OK;
 }
 
 extern "C" {
@@ -498,6 +548,24 @@ int vs_bgr_inpaint_batch(void* img, size_t frame_stride, int n, int w, int h, in
     const int r = finish_outputs(mem, s, {&o});
     if (mem != VS_MEM_HOST) VS_HIP(hipStreamSynchronize(s));             // (the scratch is released on return)
     return r;
+} VS_CATCH_ALL
+
+int vs_bgr_sharpen_batch(const void* src, size_t src_fs, int n, int w, int h, int format, const vs_transform* t, const vs_sharpen_params* params, int roi_x,
+                         int roi_y, int roi_w, int roi_h, int src_stride, void* dst, size_t dst_fs, int dst_stride, int mem, void* stream) try {
+    const int bits = vs_format_bits(format);
+    const plan::Batch in{src, src_fs, n, roi_w, roi_h, src_stride, 3, bits}, out{dst, dst_fs, n, roi_w, roi_h, dst_stride, 3, bits};
+    VS_ARG(mem == VS_MEM_HOST || mem == VS_MEM_DEVICE);
+    VS_TRY(sharpen_args_ok(__func__, in, out, w, h, format, t, roi_x, roi_y));
+    vs_sharpen_params p;
+    VS_TRY(sharpen_params_ok(params, &p));
+    if (n == 0) return VS_OK;                                           // nothing to sharpen, nothing launched
+    if (!device_ready()) return VS_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    Staged a, o;
+    VS_TRY(stage_in(a, in, mem, s));
+    VS_TRY(stage_out(o, out, mem, out.esz()));
+    VS_TRY(bgr_sharpen_ptrs(a.dev, src_fs, n, w, h, format, t, &p, roi_x, roi_y, roi_w, roi_h, src_stride, o.dev, dst_fs, dst_stride, s));
+    return finish_outputs(mem, s, {&o});
 } VS_CATCH_ALL
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// vs_cv_sample.hpp -- the device side that the look-ahead passes share (fill, deblur, denoise, deflicker, rolling shutter, lens remap, YCbCr):
+// vs_cv_sample.hpp -- the device side that the look-ahead passes share (fill, deblur, denoise, deflicker, rolling shutter, lens remap, YCbCr, sharpen):
 // VS_WARP_BILINEAR_CV's weights and blend, the two taps of a frame row in one unaligned load, sample j of a lane's packed dwords, and the wave's
 // strip copy for a frame with nothing to do.  The sampler is the numerics contract of all those passes ("device side"): it
 // is written here once, and a pass keeps only its own walk, pipeline and rule.  Everything is __forceinline__: a kernel's code is what it was

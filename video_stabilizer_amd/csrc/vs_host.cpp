@@ -120,6 +120,10 @@ void vs_scene_params_default(vs_scene_params* p) {
     p->step = 4;
     p->threshold = 32;
 }
+// vs_sharpen.hip (sixteen sixteenths, the two-tap filter's own variance)
+void vs_sharpen_params_default(vs_sharpen_params* p) {
+    p->strength = 16;
+}
 // the scene-cut rule's decision (vs_scene.hip), unsigned 64-bit throughout
 int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_scene_params* params, uint8_t* cut) try {
     vs_scene_params p;

@@ -170,6 +170,12 @@ int exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format, int
 int scene_stats_ptrs(int n_pairs, int w, int h, int src_stride, int format, const void* const* pair_src, const vs_transform* pair_t,
                      const vs_scene_params* params, uint64_t* stats, hipStream_t s);
 
+// The sharpen pass (the rule: vs_sharpen.hip) on device-resident windows; vs_bgr_sharpen_batch is the staging wrapper over it.  Image i: the
+// roi_w x roi_h window at src + i * src_fs elements (rows of src_stride elements) of a w x h output frame warped under t[i]; dst likewise.  The
+// two ranges must not overlap.  Host array; enqueue only.
+int bgr_sharpen_ptrs(const void* src, size_t src_fs, int n, int w, int h, int format, const vs_transform* t, const vs_sharpen_params* params, int roi_x,
+                     int roi_y, int roi_w, int roi_h, int src_stride, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
+
 // The inpaint's coverage index (the rule: vs_inpaint.hip) on the device; vs_bgr_fill_coverage_batch is the index-based wrapper over it.  The
 // candidates of output frame o as bgr_warp_fill_ptrs takes them -- cand_t[o * n_cand + c], a null cand_src entry ends the list, entry 0 is the
 // frame itself; no frame is read.  cov: n_out indices of roi_h rows of cov_stride bytes, cov_fs bytes apart, in device memory; open_count (may

@@ -134,6 +134,11 @@ hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int
 // leaves the pair's words zero.  stats = n_pairs x 2 words (count, sad) in device memory, zeroed on `s` first.
 hipError_t scene_stats(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int step, unsigned long long* stats,
                        int n_pairs, hipStream_t s);
+// Phase-compensated sharpening behind VS_WARP_BILINEAR_CV (vs_sharpen.hip: the rule and the kernels).  n_frames images of roi.w x roi.h, the
+// window `roi` of w x h output frames; minv_dev = n_frames x 6 doubles in device memory, the output -> source matrix of each frame
+// (vs_cv_inverse_matrix); strength: 1 .. 32.  Out of place: src and dst must not overlap.
+hipError_t bgr_sharpen(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const double* minv_dev,
+                       int strength, Roi roi, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
 // Inpaint of what the fill leaves open (vs_inpaint.hip: the rule and the kernels).  fill_coverage: cands_dev as the fill takes them (entry 0's
 // matrix; a null frame ends a list; no frame is read); cov[frame][y * cov_stride + x] = 1 + the first covering candidate, 0 for none;
 // open_count (device, may be null): zeroed on `s`, then the frame's number of zeros.  mask_open_count: the same count from a mask.

@@ -1,5 +1,5 @@
 // vs_stabilizer.hip -- VideoStabilizer (stabilizer.cpp:3-117) on top of the aligner (vs_engine.hip): scalar bookkeeping on the host, frames stay in
-// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_remap, vs_deflicker, vs_scene).
+// HBM.  Host code only: every kernel it needs is launched by the files it calls (vs_kernels, vs_warp, vs_fill, vs_inpaint, vs_deblur, vs_denoise, vs_rolling, vs_remap, vs_deflicker, vs_scene, vs_sharpen).
 //
 // Design (DESIGN.md "Engine"): a process call of n frames is one batched alignment, the reference's bookkeeping frame by frame (vs_stab_step.hpp),
 // then batched warps of every frame that became due -- stab_chunk, a sequence of named steps.  Around it stab_run picks how a call is cut: host
@@ -69,6 +69,10 @@ struct vs_stabilizer {
     // inpaint (vs_inpaint.hip)
     int inpaint = 0;               // vs_stabilizer_set_inpaint: what no candidate covers in the output window is inpainted (0: off)
     void* inpaint_buf = nullptr; size_t inpaint_bytes = 0;   // one group of frames: their open counts, their coverage indices, their pyramids
+    // phase-compensated sharpening (vs_sharpen.hip), behind the warp
+    bool sharpen_on = false;       // vs_stabilizer_set_sharpen: NULL: off
+    vs_sharpen_params sharpen{16};
+    void* sharpen_buf = nullptr; size_t sharpen_bytes = 0;   // one group of output windows as the warp (fill, inpaint) leaves them: the sharpen's source
     struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
                   SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
@@ -151,6 +155,7 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     if (s->lens_map) (void)hipFree(s->lens_map);
     if (s->flicker_buf) (void)hipFree(s->flicker_buf);
     if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
+    if (s->sharpen_buf) (void)hipFree(s->sharpen_buf);
     if (s->scene_prev) (void)hipFree(s->scene_prev);
     if (s->scene_stream) { (void)vsi::retire_stream(s->scene_stream); (void)hipStreamDestroy(s->scene_stream); }
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
@@ -591,6 +596,19 @@ struct Chunk {
         // Lanczos2 warp keeps its standard window: see vsi::warp_keeps_solver_slot)
         struct SlotHint { bool& f; bool old; SlotHint(bool on) : f(vsi::warp_keeps_solver_slot()), old(f) { f = on; } ~SlotHint() { f = old; } } hint(s->overlap_warps);
         std::vector<vs_transform> ts;
+        // Sharpen on: a run goes in groups whose windows, as the warp (fill, inpaint) leaves them, lie dense in the handle's scratch; the sharpen
+        // writes them to where the warp wrote them before, each under its own frame's correction.  The scratch holds kSharpenScratch bytes or
+        // one window, whichever is more, and no more than the call's due frames need: one allocation for all runs of the call (sync in grow:
+        // an earlier call's sharpen may still read the block).  256 MB: forty-three 1080p or ten 4K 8-bit windows -- launches that long are
+        // bound by bytes, not by their count.
+        size_t max_group = jobs.size();
+        if (s->sharpen_on && !jobs.empty()) {
+            // (test hook, read at every call: VS_TEST_SHARPEN_SCRATCH_BYTES in place of the budget, so that clips of a few frames run in several groups)
+            const char* const hook = vsi::test_env("VS_TEST_SHARPEN_SCRATCH_BYTES");
+            const size_t budget = hook ? (size_t)strtoull(hook, nullptr, 0) : kSharpenScratch;
+            max_group = std::min(max_group, std::max<size_t>(1, budget / obytes));
+            VS_HIP(grow(&s->sharpen_buf, &s->sharpen_bytes, max_group * obytes, ws, true));
+        }
         for (size_t j = 0, e; j < jobs.size(); j = e) {
             e = j + 1;
             while (e < jobs.size() && (const uint8_t*)jobs[e].src == (const uint8_t*)jobs[e - 1].src + fbytes && jobs[e].i == jobs[e - 1].i + 1) e++;
@@ -598,20 +616,32 @@ struct Chunk {
             for (size_t q = j; q < e; q++) ts.push_back(jobs[q].sampling);
             void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot] + j * obytes) : (void*)c.out_frame(jobs[j].i);
             const size_t dst_fs = to_host ? (size_t)ow * oh * 3 : c.out_frame_stride;
-            if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
-                VS_TRY(vsi::bgr_warp_fill_ptrs(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, bits, 1 + nfill, &fill.src[j * (1 + nfill)],
-                                               &fill.t[j * (1 + nfill)], s->params.warp_border, max_value, crop, crop, ow, oh, dst, dst_fs, ow * 3, ws,
-                                               want_sums ? &fill.side[j * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr));
-            else
-                VS_TRY(vs_bgr_image_warp_roi_batch(jobs[j].src, (size_t)w * h * 3, (int)(e - j), w, h, w * 3, 3, bits, ts.data(), s->params.warp_mode,
-                                                   s->params.warp_border, max_value, crop, crop, ow, oh, dst, dst_fs, ow * 3, VS_MEM_DEVICE, ws));
-            if (s->inpaint) VS_TRY(inpaint_run(j, e, dst, dst_fs));
-            // deflicker: the run's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
-            if (fk.n > 0)
-                VS_HIP(vsk::bgr_gain(dst, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * j, dst, ow * 3, (int)(e - j), dst_fs, dst_fs, ws));
+            // (sharpen off: one group, the run itself, written where it always went)
+            const size_t group = std::min(e - j, max_group);
+            for (size_t g = j, ge; g < e; g = ge) {
+                ge = std::min(e, g + group);
+                const int m = (int)(ge - g);
+                void* const out = (uint8_t*)dst + (g - j) * dst_fs * c.esz();
+                void* const wdst = s->sharpen_on ? s->sharpen_buf : out;
+                const size_t wfs = s->sharpen_on ? (size_t)ow * oh * 3 : dst_fs;
+                if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
+                    VS_TRY(vsi::bgr_warp_fill_ptrs(jobs[g].src, (size_t)w * h * 3, m, w, h, w * 3, bits, 1 + nfill, &fill.src[g * (1 + nfill)],
+                                                   &fill.t[g * (1 + nfill)], s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, ws,
+                                                   want_sums ? &fill.side[g * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr));
+                else
+                    VS_TRY(vs_bgr_image_warp_roi_batch(jobs[g].src, (size_t)w * h * 3, m, w, h, w * 3, 3, bits, &ts[g - j], s->params.warp_mode,
+                                                       s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, VS_MEM_DEVICE, ws));
+                if (s->inpaint) VS_TRY(inpaint_run(g, ge, wdst, wfs));
+                if (s->sharpen_on)
+                    VS_TRY(vsi::bgr_sharpen_ptrs(wdst, wfs, m, w, h, c.format, &ts[g - j], &s->sharpen, crop, crop, ow, oh, ow * 3, out, dst_fs, ow * 3, ws));
+                // deflicker: the group's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
+                if (fk.n > 0)
+                    VS_HIP(vsk::bgr_gain(out, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * g, out, ow * 3, m, dst_fs, dst_fs, ws));
+            }
         }
         return VS_OK;
     }
+    static constexpr size_t kSharpenScratch = (size_t)256 << 20;
 
     // the buffers of ours that the jobs' frames lay in are free again: read on warp_stream and refilled on st, they wait for that stream's
     // synchronisation; else they are reused only by later work on this stream
@@ -922,6 +952,19 @@ int vs_stabilizer_set_inpaint(vs_stabilizer* s, int on) try {
 int vs_stabilizer_get_inpaint(const vs_stabilizer* s) try {
     VS_ARG(s);
     return s->inpaint;
+} VS_CATCH_ALL
+int vs_stabilizer_set_sharpen(vs_stabilizer* s, const vs_sharpen_params* params) try {
+    VS_ARG(s);
+    if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "sharpen: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
+    if (params) VS_ARG(params->strength >= 1 && params->strength <= 32);
+    s->sharpen_on = params != nullptr;
+    if (params) s->sharpen = *params;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_sharpen(const vs_stabilizer* s, vs_sharpen_params* params) try {
+    VS_ARG(s && params);
+    if (s->sharpen_on) *params = s->sharpen; else vs_sharpen_params_default(params);
+    return s->sharpen_on ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
