@@ -187,7 +187,7 @@ static void sizing_tests() {
                         if (hw > (size_t)m) hw = (size_t)m;
                         int hc = (int)hw;
                         if (clip_len > 0) hc = hc / clip_len * clip_len < clip_len ? clip_len : hc / clip_len * clip_len;
-                        const int host = host_chunk_frames(m, ingest, step, clip_len);
+                        const int host = vsi::host_chunk_frames(m, ingest, step, clip_len);
                         expect(host == hc && host >= 1, "host_chunk restated", (long)step, (long)ingest, host);
                         expect(host <= m, "an upload fits a chunk", host, m);
                     }
@@ -195,7 +195,7 @@ static void sizing_tests() {
                 // the chunks of a call (chunk_count / chunk_span: what both cutting loops of vs_engine.hip walk) tile [0, n) whatever n
                 // is; a call of whole clips (the API takes no other: n = n_clips * clip_len) gets whole clips in every chunk
                 for (int total : {n, clip_len > 0 ? (n + clip_len - 1) / clip_len * clip_len : n})
-                    for (int step : {m, host_chunk_frames(m, (size_t)3 * 9216, 9216, clip_len)}) {
+                    for (int step : {m, vsi::host_chunk_frames(m, (size_t)3 * 9216, 9216, clip_len)}) {
                         const bool whole = clip_len == 0 || total % clip_len == 0;
                         int covered = 0;
                         for (int k = 0; k < chunk_count(total, step); k++) {

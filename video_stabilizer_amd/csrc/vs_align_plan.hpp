@@ -85,12 +85,8 @@ inline int max_chunk_frames(size_t pyr_frame, int clip_len, int* max_chunk) {
     *max_chunk = m;
     return VS_OK;
 }
-// Frames per upload of a host-resident batch: about ingest_bytes (vsi::ingest_chunk_bytes()), at least 4, whole clips, within max_chunk.
-inline int host_chunk_frames(int max_chunk, size_t ingest_bytes, size_t step_bytes, int clip_len) {
-    int c = (int)std::min<size_t>((size_t)max_chunk, std::max<size_t>(4, ingest_bytes / std::max<size_t>(1, step_bytes)));
-    if (clip_len > 0) c = std::max(clip_len, c - c % clip_len);
-    return c;
-}
+// Frames per upload of a host-resident batch: vs_internal.hpp's rule, the stabilizer's too (vs_stab_plan.hpp)
+using vsi::host_chunk_frames;
 // An n-frame call in chunks of m frames: chunk k of chunk_count(n, m) covers the frames [off, off + len).
 struct ChunkSpan { int off, len; };
 inline int chunk_count(int n, int m) { return (n + m - 1) / m; }

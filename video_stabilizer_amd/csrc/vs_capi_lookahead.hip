@@ -44,17 +44,17 @@ int deblur_params_ok(const vs_deblur_params* params, vs_deblur_params* p) {
 }
 int denoise_params_ok(const vs_denoise_params* params, vs_denoise_params* p) {
     if (params) *p = *params; else vs_denoise_params_default(p);
-    VS_ARG(p->strength >= 1 && p->strength <= 255);
+    VS_ARG(denoise_params_valid(*p));
     return VS_OK;
 }
 int rolling_params_ok(const vs_rolling_params* params, vs_rolling_params* p) {
     if (params) *p = *params; else vs_rolling_params_default(p);
-    VS_ARG(p->readout >= -1.0 && p->readout <= 1.0);                 // (a NaN fails both)
+    VS_ARG(rolling_params_valid(*p));
     return VS_OK;
 }
 int deflicker_params_ok(const vs_deflicker_params* params, vs_deflicker_params* p) {
     if (params) *p = *params; else vs_deflicker_params_default(p);
-    VS_ARG(p->step >= 1 && p->step <= 64);
+    VS_ARG(deflicker_params_valid(*p));
     return VS_OK;
 }
 
@@ -178,7 +178,7 @@ int vsi::exposure_stats_ptrs(int n_out, int w, int h, int src_stride, int format
 namespace {
 int scene_params_ok(const vs_scene_params* params, vs_scene_params* p) {
     if (params) *p = *params; else vs_scene_params_default(p);
-    VS_ARG(p->step >= 1 && p->step <= 64 && p->threshold >= 1 && p->threshold <= 255);
+    VS_ARG(scene_params_valid(*p));
     return VS_OK;
 }
 }  // namespace
@@ -243,7 +243,7 @@ int vsi::fill_coverage_ptrs(int n_out, int w, int h, int n_cand, const void* con
 namespace {
 int sharpen_params_ok(const vs_sharpen_params* params, vs_sharpen_params* p) {
     if (params) *p = *params; else vs_sharpen_params_default(p);
-    VS_ARG(p->strength >= 1 && p->strength <= 32);
+    VS_ARG(sharpen_params_valid(*p));
     return VS_OK;
 }
 // the sharpen's argument rule, for the function on the device and its staging wrapper alike; none of it needs a device

@@ -177,7 +177,7 @@ int bgr_warp_common(const void* src, size_t src_fs, int n_frames, int w, int h, 
 
 int fill_blend_params_ok(const vs_fill_blend_params* params, vs_fill_blend_params* p) {
     *p = params ? *params : vs_fill_blend_params{0, 0};
-    VS_ARG(p->feather >= 0 && p->feather <= 6 && (p->match == 0 || p->match == 1));
+    VS_ARG(fill_blend_params_valid(*p));
     return VS_OK;
 }
 }  // namespace

@@ -5,6 +5,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <initializer_list>
 
 namespace vsi {
@@ -25,6 +26,21 @@ inline bool deblur_params_finite(float sensitivity, float max_ratio) {
     if (!(sensitivity > 0.0f && sensitivity <= 3.0e38f && max_ratio > 0.0f && max_ratio <= 1.0e18f)) return false;
     const double r = (double)max_ratio < 9007199254740992.0 ? (double)max_ratio : 9007199254740992.0;
     return r * r <= (double)sensitivity * 0x1p100;
+}
+// The other passes' parameter ranges (include/vs_amd.h), each written once: the kernel-level entry points (vs_capi_lookahead.hip,
+// vs_capi_warp.hip) and the stabilizer's setters (vs_stabilizer.hip) ask these.  What a NULL pointer means stays with the caller.
+inline bool denoise_params_valid(const vs_denoise_params& p) { return p.strength >= 1 && p.strength <= 255; }
+inline bool rolling_params_valid(const vs_rolling_params& p) { return p.readout >= -1.0 && p.readout <= 1.0; }   // (a NaN fails both)
+inline bool deflicker_params_valid(const vs_deflicker_params& p) { return p.step >= 1 && p.step <= 64; }
+inline bool scene_params_valid(const vs_scene_params& p) { return p.step >= 1 && p.step <= 64 && p.threshold >= 1 && p.threshold <= 255; }
+inline bool sharpen_params_valid(const vs_sharpen_params& p) { return p.strength >= 1 && p.strength <= 32; }
+inline bool fill_blend_params_valid(const vs_fill_blend_params& p) { return p.feather >= 0 && p.feather <= 6 && (p.match == 0 || p.match == 1); }
+// Frames per upload of a host-resident batch, for the aligner and the stabilizer alike: about ingest_bytes (vsi::ingest_chunk_bytes()), at
+// least 4, whole clips, within max_chunk.
+inline int host_chunk_frames(int max_chunk, size_t ingest_bytes, size_t step_bytes, int clip_len) {
+    int c = (int)std::min<size_t>((size_t)max_chunk, std::max<size_t>(4, ingest_bytes / std::max<size_t>(1, step_bytes)));
+    if (clip_len > 0) c = std::max(clip_len, c - c % clip_len);
+    return c;
 }
 // vs_lens_map with VS_MEM_HOST (vs_host.cpp; the rule: vs_lens.hpp): checks its arguments, needs no device
 int lens_map_host(const vs_lens_params* p, int w, int h, int32_t* map, int map_stride);
@@ -65,6 +81,13 @@ inline hipError_t grow(void** buf, size_t* bytes, size_t need, hipStream_t ws = 
     if (e == hipSuccess) *bytes = need;
     return e;
 }
+// One scratch buffer of a handle and its size, under grow's protocol; drop: the handle holds no buffer again.
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipError_t grow(size_t need, hipStream_t ws = nullptr, bool sync = false) { return vsi::grow(&p, &bytes, need, ws, sync); }
+    void drop() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+};
 
 // RAII device allocation used by the host-staged (VS_MEM_HOST) form of the kernel-level calls.
 struct DevBuf {

@@ -7,11 +7,13 @@
 // sub-batches whose warps run under the next sub-batch's alignment (stab_run_overlapped).
 #include "vs_engine.hpp"
 #include "vs_lookahead.hpp"
+#include "vs_stab_plan.hpp"
 #include "vs_stab_step.hpp"
 #include "vs_kernels.hpp"
 #include "vs_lens.hpp"
 
 #include <algorithm>
+#include <array>
 #include <deque>
 #include <numeric>
 #include <string>
@@ -20,6 +22,8 @@
 using vsi::set_error;
 using vsi::run_async;
 using vsi::grow;
+using vsi::Scratch;
+using namespace vsi::stab;
 
 struct vs_stabilizer {
     vs_stabilizer_params params;
@@ -28,67 +32,48 @@ struct vs_stabilizer {
     int frame_index = 0;
     std::deque<vs_transform> measurements;
     std::deque<int> meas_ok;       // the success flag of every entry of `measurements` (border fill: a failed alignment ends a candidate list)
-    int border_fill = 0;           // vs_stabilizer_set_border_fill: candidates per output frame beyond the frame itself (0: off)
-    vs_fill_blend_params fill_blend{0, 0};   // vs_stabilizer_set_fill_blend.  With match on, the three channel sums of every queued frame lie in device
-                                   // memory like the sharpness below: in blocks of the same pool, under the same reference protocol (Held::mb / sums)
+    PassConfig cfg;                // what the vs_stabilizer_set_* calls set (vs_stab_plan.hpp)
+    // Fill blend with match on: the three channel sums of every queued frame lie in device memory like the sharpness below: in blocks of the
+    // same pool, under the same reference protocol (Held::mb / sums).
     // deblur (vs_deblur.hip): the sharpness of every queued frame lies in device memory, one value per frame in a block taken per call; a block is
     // free again when no queued frame and no launch in flight refers to it (refs; sharp_pending: references given up, counted down at the next point
     // where every reader has been ordered before whatever may refill the block)
     struct SharpBlock { unsigned long long* dev; size_t cap; int refs; };
     std::vector<SharpBlock*> sharp_blocks, sharp_pending;
-    int deblur = 0;                // vs_stabilizer_set_deblur: following frames a frame is deblurred from (0: off)
-    vs_deblur_params deblur_params{2.0f, 4.0f};
-    void* deblur_buf = nullptr; size_t deblur_bytes = 0;     // the deblurred frames of the current call: the source of its warps
-    // temporal denoise (vs_denoise.hip)
-    int denoise = 0;               // vs_stabilizer_set_denoise: following frames a frame is averaged with (0: off)
-    vs_denoise_params denoise_params{24};
-    void* denoise_buf = nullptr; size_t denoise_bytes = 0;   // the denoised frames of the current call: the source of its warps
-    // rolling-shutter correction (vs_rolling.hip)
-    vs_rolling_params rolling{0.0};   // vs_stabilizer_set_rolling_shutter: readout 0: off
-    void* rolling_buf = nullptr; size_t rolling_bytes = 0;   // the corrected frames of the current call: the source of its warps
-    // lens-distortion correction (vs_remap.hip), in front of everything: the chunk's frames land, corrected, in batch_in
-    bool lens_on = false;          // vs_stabilizer_set_lens: NULL or the identity lens: off
-    vs_lens_params lens{};
-    int lens_w = 0, lens_h = 0;    // the frame size the lens was calibrated for; frames of another size are refused while the pass is on
-    void* lens_map = nullptr; size_t lens_map_bytes = 0;     // the map, made once per (params, w, h) on the device
+    // The scratch of the passes, each grown on demand (Scratch::grow) and freed by vs_stabilizer_destroy (scratch()).
+    Scratch deblur_buf, denoise_buf, rolling_buf;   // the deblurred / denoised / rolling-shutter-corrected frames of the current call: the source of its warps
+    Scratch lens_map;              // lens-distortion correction (vs_remap.hip), in front of everything: the map, made once per (params, w, h) on the device
     bool lens_map_made = false;
-    // deflicker (vs_deflicker.hip)
-    int deflicker = 0;             // vs_stabilizer_set_deflicker: following frames in a frame's exposure window (0: off)
-    vs_deflicker_params deflicker_params{4};
-    void* flicker_buf = nullptr; size_t flicker_bytes = 0;   // the pair statistics and, behind them, the gains of the current call's output frames
-    // scene-cut detection (vs_scene.hip)
-    bool scene_on = false;         // vs_stabilizer_set_scene_cut: NULL: off
-    vs_scene_params scene_params{4, 32};
-    std::deque<int> meas_cut;      // the cut flag of every entry of `measurements` (vs_stab_step.hpp: stab_step_cut); all zero while detection is off
-    void* scene_prev = nullptr; size_t scene_prev_bytes = 0;   // lag == 0: nothing is queued, so the last frame of a call waits here for the next call's first pair
+    Scratch flicker_buf;           // deflicker: the pair statistics and, behind them, the gains of the current call's output frames
+    Scratch inpaint_buf;           // one group of frames: their open counts, their coverage indices, their pyramids
+    Scratch sharpen_buf;           // one group of output windows as the warp (fill, inpaint) leaves them: the sharpen's source
+    Scratch scene_prev;            // scene cuts, lag == 0: nothing is queued, so the last frame of a call waits here for the next call's first pair
     bool scene_prev_valid = false;
+    Scratch batch_in;              // dense device copy of the current batch (lens correction on: the chunk's frames land there corrected)
+    // host callers: cropped outputs of the current chunk on their way down.  Two areas, used alternately by the chunks of a
+    // pipelined batch; a downloader thread drains area k on down_stream while the next chunk is computed into area k^1.
+    Scratch batch_out[2];
+    // PITCHED host frames travel as ONE linear copy of their whole span (gaps included) into a device area and are made dense by device-to-device
+    // 2-D copies: the HIP runtime never gets a 2-D copy out of pageable caller memory (profiles/r06_flake.md); dense frames: one linear copy as ever
+    Scratch span_in[2];
+    std::array<Scratch*, 13> scratch() {
+        return {&deblur_buf, &denoise_buf, &rolling_buf, &lens_map, &flicker_buf, &inpaint_buf, &sharpen_buf, &scene_prev, &batch_in, &batch_out[0],
+                &batch_out[1], &span_in[0], &span_in[1]};
+    }
+    std::deque<int> meas_cut;      // the cut flag of every entry of `measurements` (vs_stab_step.hpp: stab_step_cut); all zero while detection is off
     hipStream_t scene_stream = nullptr;   // overlapped runs: the statistics and their download go beside the next chunk's alignment, which is already
     hipEvent_t scene_ev = nullptr;        // enqueued on the handle's stream; scene_ev: everything on that stream in front of it
     long long cut_total = 0;       // cuts since the last reset
     std::deque<int64_t> cut_list;  // ... the most recent 256 of them: 0-based frame indices since that reset
-    // inpaint (vs_inpaint.hip)
-    int inpaint = 0;               // vs_stabilizer_set_inpaint: what no candidate covers in the output window is inpainted (0: off)
-    void* inpaint_buf = nullptr; size_t inpaint_bytes = 0;   // one group of frames: their open counts, their coverage indices, their pyramids
-    // phase-compensated sharpening (vs_sharpen.hip), behind the warp
-    bool sharpen_on = false;       // vs_stabilizer_set_sharpen: NULL: off
-    vs_sharpen_params sharpen{16};
-    void* sharpen_buf = nullptr; size_t sharpen_bytes = 0;   // one group of output windows as the warp (fill, inpaint) leaves them: the sharpen's source
     struct Held { void* ptr; bool owned; SharpBlock* sb = nullptr; const unsigned long long* sharp = nullptr;
                   SharpBlock* mb = nullptr; const unsigned long long* sums = nullptr; };   // owned: a buffer of ours; else a frame of the batch being processed
     std::deque<Held> frames;       // the buffered input frames (stabilizer.cpp:15), dense, in device memory
     std::vector<void*> pool;       // recycled frame buffers
     size_t frame_bytes = 0;
-    void* batch_in = nullptr; size_t batch_in_bytes = 0;     // dense device copy of the current batch
-    // host callers: cropped outputs of the current chunk on their way down.  Two areas, used alternately by the chunks of a
-    // pipelined batch; a downloader thread drains area k on down_stream while the next chunk is computed into area k^1.
-    void* batch_out[2] = {nullptr, nullptr}; size_t batch_out_bytes[2] = {0, 0};
     std::future<hipError_t> down[2];
     hipEvent_t down_ev[2] = {nullptr, nullptr};
     hipStream_t down_stream = nullptr, up_stream = nullptr;
-    void* pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_bytes = 0;     // upload areas of a pipelined host batch
-    // PITCHED host frames travel as ONE linear copy of their whole span (gaps included) into a device area and are made dense by device-to-device
-    // 2-D copies: the HIP runtime never gets a 2-D copy out of pageable caller memory (profiles/r06_flake.md); dense frames: one linear copy as ever
-    void* span_in[2] = {nullptr, nullptr}; size_t span_in_bytes[2] = {0, 0};
+    void* pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_bytes = 0;     // upload areas of a pipelined host batch (two halves, one size: vsi::grow)
     // device-resident batches: the warps of sub-batch g run on warp_stream under the alignment of sub-batch g + 1 (stab_run_overlapped)
     hipStream_t warp_stream = nullptr;
     hipEvent_t warp_ev = nullptr;
@@ -149,21 +134,11 @@ void vs_stabilizer_destroy(vs_stabilizer* s) {
     stab_drop_frames(s);
     for (auto& f : s->down) if (f.valid()) (void)f.get();
     for (auto* b : s->sharp_blocks) { (void)hipFree(b->dev); delete b; }
-    if (s->deblur_buf) (void)hipFree(s->deblur_buf);
-    if (s->denoise_buf) (void)hipFree(s->denoise_buf);
-    if (s->rolling_buf) (void)hipFree(s->rolling_buf);
-    if (s->lens_map) (void)hipFree(s->lens_map);
-    if (s->flicker_buf) (void)hipFree(s->flicker_buf);
-    if (s->inpaint_buf) (void)hipFree(s->inpaint_buf);
-    if (s->sharpen_buf) (void)hipFree(s->sharpen_buf);
-    if (s->scene_prev) (void)hipFree(s->scene_prev);
+    for (Scratch* b : s->scratch()) b->drop();
     if (s->scene_stream) { (void)vsi::retire_stream(s->scene_stream); (void)hipStreamDestroy(s->scene_stream); }
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     for (void* q : s->ycbcr.buf) if (q) (void)hipFree(q);
-    if (s->batch_in) (void)hipFree(s->batch_in);
-    for (void* q : s->batch_out) if (q) (void)hipFree(q);
     for (void* q : s->pipe_in) if (q) (void)hipFree(q);
-    for (void* q : s->span_in) if (q) (void)hipFree(q);
     for (hipEvent_t e : s->down_ev) if (e) (void)hipEventDestroy(e);
     if (s->warp_stream) { (void)vsi::retire_stream(s->warp_stream); (void)hipStreamDestroy(s->warp_stream); }
     if (s->warp_ev) (void)hipEventDestroy(s->warp_ev);
@@ -208,9 +183,9 @@ static hipError_t make_dense(vs_stabilizer* s, const StabCall& c, bool dense, in
     hipError_t e = hipSuccess;
     if (c.mem == VS_MEM_HOST) {
         const size_t span = c.span_bytes();
-        e = grow(&s->span_in[area], &s->span_in_bytes[area], span);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->span_in[area], c.frames, span, hipMemcpyHostToDevice, st);
-        from = (const uint8_t*)s->span_in[area];
+        e = s->span_in[area].grow(span);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->span_in[area].p, c.frames, span, hipMemcpyHostToDevice, st);
+        from = (const uint8_t*)s->span_in[area].p;
     }
     for (int i = 0; e == hipSuccess && i < c.n; i++)
         e = hipMemcpy2DAsync((uint8_t*)dst + (size_t)i * fbytes, row, from + (size_t)i * c.frame_stride * esz, (size_t)c.stride * esz, row, c.h,
@@ -235,7 +210,6 @@ static hipError_t copy_outputs_down(const StabCall& c, const std::vector<int>& i
 // ---- one chunk: n successive VideoStabilizer::processFrame calls (stabilizer.cpp:9-117) as one batch ---------------------------------------
 using Held = vs_stabilizer::Held;
 using SharpBlock = vs_stabilizer::SharpBlock;
-struct Job { const void* src; vs_transform sampling; int i; void* release; };   // frame i of the chunk is due: warp `src`, then `release` is free
 // The look-ahead passes (DESIGN.md "Look-ahead passes: the shared path"): per job 1 + n candidates -- the frame itself, then the frames
 // that follow it in the queue; null frames and zero transforms behind the end of a list.  `side`: where each candidate's side value lies.
 struct Ahead { int n; std::vector<const void*> src; std::vector<vs_transform> t; std::vector<const uint64_t*> side; };
@@ -251,6 +225,13 @@ static int take_block(vs_stabilizer* s, size_t need, SharpBlock* keep, SharpBloc
     *out = new SharpBlock{(unsigned long long*)q, need, 0};
     s->sharp_blocks.push_back(*out);
     return VS_OK;
+}
+
+// The byte budget of a pass's scratch groups (vs_stab_plan.hpp: scratch_group).  (hook_name: a test hook, read at every call, in place of the
+// budget, so that clips of a few frames run in several groups)
+static size_t scratch_budget(const char* hook_name, size_t default_bytes) {
+    const char* const hook = vsi::test_env(hook_name);
+    return hook ? (size_t)strtoull(hook, nullptr, 0) : default_bytes;
 }
 
 // One chunk in flight: what its steps share, and the steps in the order stab_chunk runs them.
@@ -280,32 +261,32 @@ struct Chunk {
     // from span_in[0], where their whole span travels as one linear copy; the aligner, the side values, the queue and every pass then see
     // corrected frames only.  (already_dense stays false: no next chunk's alignment is started on the caller's uncorrected frames.)
     int make_dense() {
-        if (s->lens_on) return make_dense_corrected();
+        if (s->cfg.lens_on) return make_dense_corrected();
         already_dense = c.mem == VS_MEM_DEVICE && c.dense();
         dense = (const uint8_t*)c.frames;                  // read in place during this call; the tail is copied out by own_queued
         if (already_dense) return VS_OK;
-        VS_HIP(grow(&s->batch_in, &s->batch_in_bytes, fbytes * c.n));
-        VS_HIP(::make_dense(s, c, c.dense(), 0, s->batch_in, st));
-        dense = (const uint8_t*)s->batch_in;
+        VS_HIP(s->batch_in.grow(fbytes * c.n));
+        VS_HIP(::make_dense(s, c, c.dense(), 0, s->batch_in.p, st));
+        dense = (const uint8_t*)s->batch_in.p;
         return VS_OK;
     }
 
     int make_dense_corrected() {
         if (!s->lens_map_made) {                           // once per (params, w, h): vs_stabilizer_set_lens drops it
-            VS_HIP(grow(&s->lens_map, &s->lens_map_bytes, (size_t)w * h * 2 * sizeof(int32_t)));
-            VS_HIP(vsk::lens_map(s->lens, w, h, (int32_t*)s->lens_map, 2 * w, st));
+            VS_HIP(s->lens_map.grow((size_t)w * h * 2 * sizeof(int32_t)));
+            VS_HIP(vsk::lens_map(s->cfg.lens, w, h, (int32_t*)s->lens_map.p, 2 * w, st));
             s->lens_map_made = true;
         }
         const void* from = c.frames;
         if (c.mem == VS_MEM_HOST) {
-            VS_HIP(grow(&s->span_in[0], &s->span_in_bytes[0], c.span_bytes()));
-            VS_HIP(hipMemcpyAsync(s->span_in[0], c.frames, c.span_bytes(), hipMemcpyHostToDevice, st));
-            from = s->span_in[0];
+            VS_HIP(s->span_in[0].grow(c.span_bytes()));
+            VS_HIP(hipMemcpyAsync(s->span_in[0].p, c.frames, c.span_bytes(), hipMemcpyHostToDevice, st));
+            from = s->span_in[0].p;
         }
-        VS_HIP(grow(&s->batch_in, &s->batch_in_bytes, fbytes * c.n));
-        VS_HIP(vsk::bgr_remap(from, c.frame_stride, c.n, w, h, c.stride, bits, vs_format_max_value(c.format), (const int32_t*)s->lens_map, 2 * w, w, h,
-                              s->lens.border, s->batch_in, (size_t)w * h * 3, w * 3, vsk::kRemapSlice, st));
-        dense = (const uint8_t*)s->batch_in;
+        VS_HIP(s->batch_in.grow(fbytes * c.n));
+        VS_HIP(vsk::bgr_remap(from, c.frame_stride, c.n, w, h, c.stride, bits, vs_format_max_value(c.format), (const int32_t*)s->lens_map.p, 2 * w, w, h,
+                              s->cfg.lens.border, s->batch_in.p, (size_t)w * h * 3, w * 3, vsk::kRemapSlice, st));
+        dense = (const uint8_t*)s->batch_in.p;
         return VS_OK;
     }
 
@@ -360,7 +341,7 @@ struct Chunk {
         else VS_TRY(start(cur, dense, c.n, false));
         VS_TRY(vsi::align_finish(a));
         if (s->next_n > 0 && already_dense) {
-            if (s->scene_on) {                              // detect_cuts works beside the alignment started here, behind what `st` holds now
+            if (s->cfg.scene_on) {                              // detect_cuts works beside the alignment started here, behind what `st` holds now
                 if (!s->scene_stream) VS_HIP(hipStreamCreateWithFlags(&s->scene_stream, hipStreamNonBlocking));
                 if (!s->scene_ev) VS_HIP(hipEventCreateWithFlags(&s->scene_ev, hipEventDisableTiming));
                 VS_HIP(hipEventRecord(s->scene_ev, st));
@@ -381,7 +362,7 @@ struct Chunk {
     // (lag == 0: the handle's copy of the previous call's last frame).  Off: nothing is launched and nothing allocated.
     int detect_cuts() {
         cuts.assign((size_t)c.n, 0);
-        if (!s->scene_on) return VS_OK;
+        if (!s->cfg.scene_on) return VS_OK;
         std::vector<const void*> src;
         std::vector<vs_transform> t;
         std::vector<int> at;
@@ -391,7 +372,7 @@ struct Chunk {
             if (c.clip_len > 0 ? i % c.clip_len != 0 : i > 0) prev = dense + (size_t)(i - 1) * fbytes;
             else if (c.clip_len > 0) continue;              // a clip's first frame
             else if (!s->frames.empty()) prev = s->frames.back().ptr;
-            else if (s->scene_prev_valid) prev = s->scene_prev;
+            else if (s->scene_prev_valid) prev = s->scene_prev.p;
             if (!prev) continue;
             vs_transform tr;
             (void)vsi::lookahead_transforms(&s->t_buf[cur][i], &one, 1, 1, nullptr, &tr);
@@ -406,19 +387,19 @@ struct Chunk {
         {
             vsi::Staged o;
             VS_TRY(o.out(stats.data(), stats.size() * sizeof(uint64_t), VS_MEM_HOST));
-            VS_TRY(vsi::scene_stats_ptrs(np, w, h, w * 3, c.format, src.data(), t.data(), &s->scene_params, o.as<uint64_t>(), cut_stream));
+            VS_TRY(vsi::scene_stats_ptrs(np, w, h, w * 3, c.format, src.data(), t.data(), &s->cfg.scene_params, o.as<uint64_t>(), cut_stream));
             VS_TRY(vsi::finish_outputs(VS_MEM_HOST, cut_stream, {&o}));
         }
         std::vector<uint8_t> flag((size_t)np);
-        VS_TRY(vs_scene_cuts(stats.data(), np, w, h, &s->scene_params, flag.data()));
+        VS_TRY(vs_scene_cuts(stats.data(), np, w, h, &s->cfg.scene_params, flag.data()));
         for (int k = 0; k < np; k++) cuts[(size_t)at[k]] = flag[(size_t)k];
         return VS_OK;
     }
     // lag == 0: the call's last frame waits in a buffer of the handle's for the next call's first pair
     int keep_last_frame() {
-        if (!s->scene_on || s->params.lag > 0 || c.clip_len > 0) return VS_OK;
-        VS_HIP(grow(&s->scene_prev, &s->scene_prev_bytes, fbytes));   // (its one reader, detect_cuts, has synchronised)
-        VS_HIP(hipMemcpyAsync(s->scene_prev, dense + (size_t)(c.n - 1) * fbytes, fbytes, hipMemcpyDeviceToDevice, st));
+        if (!s->cfg.scene_on || s->params.lag > 0 || c.clip_len > 0) return VS_OK;
+        VS_HIP(s->scene_prev.grow(fbytes));   // (its one reader, detect_cuts, has synchronised)
+        VS_HIP(hipMemcpyAsync(s->scene_prev.p, dense + (size_t)(c.n - 1) * fbytes, fbytes, hipMemcpyDeviceToDevice, st));
         s->scene_prev_valid = true;
         return VS_OK;
     }
@@ -488,54 +469,53 @@ struct Chunk {
         return VS_OK;
     }
 
+    // One pass that rewrites every due frame (`a` on): its scratch grows, candidate 0 of every list is the job's current source (the deblur,
+    // first in line, finds it there already), launch(to) writes the frames to the scratch one after the other, and there the warps (and the
+    // fill's candidate 0) read them from now on.
+    template <typename Launch>
+    int rewrite(Ahead& a, Scratch& buf, Launch launch) {
+        if (a.n <= 0) return VS_OK;
+        VS_HIP(buf.grow(fbytes * jobs.size(), ws, true));
+        for (size_t j = 0; j < jobs.size(); j++) a.src[j * (1 + a.n)] = jobs[j].src;
+        VS_TRY(launch(buf.p));
+        for (size_t j = 0; j < jobs.size(); j++) {
+            jobs[j].src = (const uint8_t*)buf.p + j * fbytes;
+            if (fill.n > 0) fill.src[j * (1 + fill.n)] = jobs[j].src;
+        }
+        return VS_OK;
+    }
     // The look-ahead passes that run in front of the warps, on their stream, one launch each over every due frame.  The candidates are read
     // before their own jobs release them: releases follow the warps.  (sync in grow: warps / gain passes of an earlier chunk may still read the
     // area.)  Host callers first: the staging area's previous user has been drained (through down[slot]), and the area holds the jobs' outputs.
     int passes() {
-        const int nj = (int)jobs.size(), nfill = fill.n;
+        const int nj = (int)jobs.size();
         if (to_host) {
             if (s->down[slot].valid()) {
                 const hipError_t de = s->down[slot].get();
                 if (de != hipSuccess) return set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
             }
-            VS_HIP(grow(&s->batch_out[slot], &s->batch_out_bytes[slot], obytes * jobs.size()));
+            VS_HIP(s->batch_out[slot].grow(obytes * jobs.size()));
         }
-        // the jobs' frames now lie in `buf`, one after the other: the warps (and the fill's candidate 0) read them there
-        auto sources = [&](const void* buf) {
-            for (size_t j = 0; j < jobs.size(); j++) {
-                jobs[j].src = (const uint8_t*)buf + j * fbytes;
-                if (nfill > 0) fill.src[j * (1 + nfill)] = jobs[j].src;
-            }
-        };
-        if (db.n > 0) {     // every due frame is deblurred into a scratch frame of its own
-            VS_HIP(grow(&s->deblur_buf, &s->deblur_bytes, fbytes * jobs.size(), ws, true));
-            VS_TRY(vsi::bgr_deblur_ptrs(nj, w, h, w * 3, c.format, 1 + db.n, db.src.data(), db.side.data(), db.t.data(), &s->deblur_params, s->deblur_buf,
-                                        (size_t)w * h * 3, w * 3, ws));
-            sources(s->deblur_buf);
-        }
-        if (dn.n > 0) {     // ... (deblurred, if that pass is on) denoised into a scratch frame of its own; the candidates are the original input frames
-            VS_HIP(grow(&s->denoise_buf, &s->denoise_bytes, fbytes * jobs.size(), ws, true));
-            for (size_t j = 0; j < jobs.size(); j++) dn.src[j * (1 + dn.n)] = jobs[j].src;
-            VS_TRY(vsi::bgr_denoise_ptrs(nj, w, h, w * 3, c.format, 1 + dn.n, dn.src.data(), dn.t.data(), &s->denoise_params, s->denoise_buf,
-                                         (size_t)w * h * 3, w * 3, ws));
-            sources(s->denoise_buf);
-        }
-        if (rs.n > 0) {     // ... (deblurred, denoised) corrected for the rolling shutter into a scratch frame of its own, by the motion to the next input frame
-            VS_HIP(grow(&s->rolling_buf, &s->rolling_bytes, fbytes * jobs.size(), ws, true));
-            for (size_t j = 0; j < jobs.size(); j++) rs.src[j * 2] = jobs[j].src;
-            VS_TRY(vsi::bgr_rolling_ptrs(nj, w, h, w * 3, c.format, rs.src.data(), rs.t.data(), &s->rolling, s->rolling_buf, (size_t)w * h * 3, w * 3, ws));
-            sources(s->rolling_buf);
-        }
+        const size_t fs = (size_t)w * h * 3;
+        // every due frame is deblurred into a scratch frame of its own
+        VS_TRY(rewrite(db, s->deblur_buf, [&](void* to) {
+            return vsi::bgr_deblur_ptrs(nj, w, h, w * 3, c.format, 1 + db.n, db.src.data(), db.side.data(), db.t.data(), &s->cfg.deblur_params, to, fs, w * 3, ws); }));
+        // ... (deblurred, if that pass is on) denoised into a scratch frame of its own; the candidates are the original input frames
+        VS_TRY(rewrite(dn, s->denoise_buf, [&](void* to) {
+            return vsi::bgr_denoise_ptrs(nj, w, h, w * 3, c.format, 1 + dn.n, dn.src.data(), dn.t.data(), &s->cfg.denoise_params, to, fs, w * 3, ws); }));
+        // ... (deblurred, denoised) corrected for the rolling shutter into a scratch frame of its own, by the motion to the next input frame
+        VS_TRY(rewrite(rs, s->rolling_buf, [&](void* to) {
+            return vsi::bgr_rolling_ptrs(nj, w, h, w * 3, c.format, rs.src.data(), rs.t.data(), &s->cfg.rolling, to, fs, w * 3, ws); }));
         if (fk.n > 0) {
             // the exposure statistics of every due frame against the frames that follow it -- the original input frames on both sides -- and
             // its three gains: one statistics launch and one gains launch.  Nothing of it reaches the host; the gain pass behind each run's
             // warp (and fill) reads the gains there.
             const size_t sbytes = jobs.size() * (size_t)(1 + fk.n) * 8 * sizeof(uint64_t), need = sbytes + jobs.size() * 4 * sizeof(uint32_t);
-            VS_HIP(grow(&s->flicker_buf, &s->flicker_bytes, need, ws, true));
-            fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf + sbytes);
-            VS_TRY(vsi::exposure_stats_ptrs(nj, w, h, w * 3, c.format, 1 + fk.n, fk.src.data(), fk.t.data(), &s->deflicker_params,
-                                            (uint64_t*)s->flicker_buf, ws));
-            VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf, nj, 1 + fk.n, w, h, s->deflicker_params.step, fk_gains, ws));
+            VS_HIP(s->flicker_buf.grow(need, ws, true));
+            fk_gains = (uint32_t*)((uint8_t*)s->flicker_buf.p + sbytes);
+            VS_TRY(vsi::exposure_stats_ptrs(nj, w, h, w * 3, c.format, 1 + fk.n, fk.src.data(), fk.t.data(), &s->cfg.deflicker_params,
+                                            (uint64_t*)s->flicker_buf.p, ws));
+            VS_HIP(vsk::exposure_gains((const unsigned long long*)s->flicker_buf.p, nj, 1 + fk.n, w, h, s->cfg.deflicker_params.step, fk_gains, ws));
         }
         return VS_OK;
     }
@@ -570,14 +550,11 @@ struct Chunk {
         if (all_covered) return VS_OK;
         const int ms = (ow + 3) & ~3;
         const size_t mfs = (size_t)ms * oh, pbytes = (vsk::inpaint_pyramid_bytes(ow, oh, bits) + 15) & ~(size_t)15;
-        // (test hook, read at every call: VS_TEST_INPAINT_SCRATCH_BYTES in place of the budget, so that clips of a few frames run in several groups)
-        const char* const hook = vsi::test_env("VS_TEST_INPAINT_SCRATCH_BYTES");
-        const size_t budget = hook ? (size_t)strtoull(hook, nullptr, 0) : kInpaintScratch;
-        const size_t group = std::min(e - j, std::max<size_t>(1, budget / (mfs + pbytes + sizeof(uint32_t))));
+        const size_t group = scratch_group(e - j, scratch_budget("VS_TEST_INPAINT_SCRATCH_BYTES", kInpaintScratch), mfs + pbytes + sizeof(uint32_t));
         const size_t cbytes = (group * sizeof(uint32_t) + 255) & ~(size_t)255;
-        VS_HIP(grow(&s->inpaint_buf, &s->inpaint_bytes, cbytes + group * (mfs + pbytes), ws, true));   // (an earlier run's kernels may still read the block)
-        uint32_t* const counts = (uint32_t*)s->inpaint_buf;
-        uint8_t* const cov = (uint8_t*)s->inpaint_buf + cbytes;
+        VS_HIP(s->inpaint_buf.grow(cbytes + group * (mfs + pbytes), ws, true));   // (an earlier run's kernels may still read the block)
+        uint32_t* const counts = (uint32_t*)s->inpaint_buf.p;
+        uint8_t* const cov = (uint8_t*)s->inpaint_buf.p + cbytes;
         void* const pyr = cov + group * mfs;
         for (size_t g = j; g < e; g += group) {
             const int m = (int)std::min(group, e - g);
@@ -602,19 +579,15 @@ struct Chunk {
         // an earlier call's sharpen may still read the block).  256 MB: forty-three 1080p or ten 4K 8-bit windows -- launches that long are
         // bound by bytes, not by their count.
         size_t max_group = jobs.size();
-        if (s->sharpen_on && !jobs.empty()) {
-            // (test hook, read at every call: VS_TEST_SHARPEN_SCRATCH_BYTES in place of the budget, so that clips of a few frames run in several groups)
-            const char* const hook = vsi::test_env("VS_TEST_SHARPEN_SCRATCH_BYTES");
-            const size_t budget = hook ? (size_t)strtoull(hook, nullptr, 0) : kSharpenScratch;
-            max_group = std::min(max_group, std::max<size_t>(1, budget / obytes));
-            VS_HIP(grow(&s->sharpen_buf, &s->sharpen_bytes, max_group * obytes, ws, true));
+        if (s->cfg.sharpen_on && !jobs.empty()) {
+            max_group = scratch_group(max_group, scratch_budget("VS_TEST_SHARPEN_SCRATCH_BYTES", kSharpenScratch), obytes);
+            VS_HIP(s->sharpen_buf.grow(max_group * obytes, ws, true));
         }
         for (size_t j = 0, e; j < jobs.size(); j = e) {
-            e = j + 1;
-            while (e < jobs.size() && (const uint8_t*)jobs[e].src == (const uint8_t*)jobs[e - 1].src + fbytes && jobs[e].i == jobs[e - 1].i + 1) e++;
+            e = run_end(jobs, j, fbytes);
             ts.clear();
             for (size_t q = j; q < e; q++) ts.push_back(jobs[q].sampling);
-            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot] + j * obytes) : (void*)c.out_frame(jobs[j].i);
+            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot].p + j * obytes) : (void*)c.out_frame(jobs[j].i);
             const size_t dst_fs = to_host ? (size_t)ow * oh * 3 : c.out_frame_stride;
             // (sharpen off: one group, the run itself, written where it always went)
             const size_t group = std::min(e - j, max_group);
@@ -622,18 +595,18 @@ struct Chunk {
                 ge = std::min(e, g + group);
                 const int m = (int)(ge - g);
                 void* const out = (uint8_t*)dst + (g - j) * dst_fs * c.esz();
-                void* const wdst = s->sharpen_on ? s->sharpen_buf : out;
-                const size_t wfs = s->sharpen_on ? (size_t)ow * oh * 3 : dst_fs;
+                void* const wdst = s->cfg.sharpen_on ? s->sharpen_buf.p : out;
+                const size_t wfs = s->cfg.sharpen_on ? (size_t)ow * oh * 3 : dst_fs;
                 if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
                     VS_TRY(vsi::bgr_warp_fill_ptrs(jobs[g].src, (size_t)w * h * 3, m, w, h, w * 3, bits, 1 + nfill, &fill.src[g * (1 + nfill)],
                                                    &fill.t[g * (1 + nfill)], s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, ws,
-                                                   want_sums ? &fill.side[g * (1 + nfill)] : nullptr, blend_on ? &s->fill_blend : nullptr));
+                                                   want_sums ? &fill.side[g * (1 + nfill)] : nullptr, blend_on ? &s->cfg.fill_blend : nullptr));
                 else
                     VS_TRY(vs_bgr_image_warp_roi_batch(jobs[g].src, (size_t)w * h * 3, m, w, h, w * 3, 3, bits, &ts[g - j], s->params.warp_mode,
                                                        s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, VS_MEM_DEVICE, ws));
-                if (s->inpaint) VS_TRY(inpaint_run(g, ge, wdst, wfs));
-                if (s->sharpen_on)
-                    VS_TRY(vsi::bgr_sharpen_ptrs(wdst, wfs, m, w, h, c.format, &ts[g - j], &s->sharpen, crop, crop, ow, oh, ow * 3, out, dst_fs, ow * 3, ws));
+                if (s->cfg.inpaint) VS_TRY(inpaint_run(g, ge, wdst, wfs));
+                if (s->cfg.sharpen_on)
+                    VS_TRY(vsi::bgr_sharpen_ptrs(wdst, wfs, m, w, h, c.format, &ts[g - j], &s->cfg.sharpen, crop, crop, ow, oh, ow * 3, out, dst_fs, ow * 3, ws));
                 // deflicker: the group's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
                 if (fk.n > 0)
                     VS_HIP(vsk::bgr_gain(out, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * g, out, ow * 3, m, dst_fs, dst_fs, ws));
@@ -655,7 +628,7 @@ struct Chunk {
         if (!to_host) return VS_OK;
         std::vector<int> idx(jobs.size());
         for (size_t j = 0; j < jobs.size(); j++) idx[j] = jobs[j].i;
-        const uint8_t* area = (const uint8_t*)s->batch_out[slot];
+        const uint8_t* area = (const uint8_t*)s->batch_out[slot].p;
         if (!threaded_download) { VS_HIP(copy_outputs_down(c, idx, area, obytes, st)); return VS_OK; }
         if (!s->down_stream) VS_HIP(hipStreamCreateWithFlags(&s->down_stream, hipStreamNonBlocking));
         if (!s->down_ev[slot]) VS_HIP(hipEventCreateWithFlags(&s->down_ev[slot], hipEventDisableTiming));
@@ -709,11 +682,9 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
     const bool to_host = out_mem == VS_MEM_HOST, warps_apart = s->overlap_warps && !to_host;
     hipStream_t st = (hipStream_t)vs_aligner_stream(s->aligner);
     Chunk k{s, c, std::max(slot_arg, 0), slot_arg >= 0, to_host, warps_apart, st, warps_apart ? s->warp_stream : st, crop, ow, oh};
-    k.fill.n = s->params.warp_mode == VS_WARP_BILINEAR_CV ? std::min(s->border_fill, lag) : 0;
-    k.db.n = std::min(s->deblur, lag); k.dn.n = std::min(s->denoise, lag); k.fk.n = std::min(s->deflicker, lag);
-    k.rs.n = s->rolling.readout != 0.0 ? std::min(1, lag) : 0;
-    k.blend_on = k.fill.n > 0 && (s->fill_blend.feather > 0 || s->fill_blend.match != 0);
-    k.want_sums = k.fill.n > 0 && s->fill_blend.match != 0;
+    const PassPlan pp = plan_passes(s->cfg, lag, s->params.warp_mode);
+    k.fill.n = pp.fill; k.db.n = pp.deblur; k.dn.n = pp.denoise; k.fk.n = pp.deflicker; k.rs.n = pp.rolling;
+    k.blend_on = pp.blend_on; k.want_sums = pp.want_sums;
 
     VS_TRY(k.make_dense());
     VS_TRY(k.measure_side_values());
@@ -817,67 +788,25 @@ static int stab_run_overlapped(vs_stabilizer* s, const StabCall& c, int step, bo
 // warp -- must not leave such an entry behind for the next call to warp from: the stabilizer is reset to a clean
 // "new clip" state (and the stream drained, so nothing still reads the caller's frames), and the error is passed on.
 static int stab_run(vs_stabilizer* s, const StabCall& c) {
-    const int n = c.n, clip_len = c.clip_len;
+    if (!s) return stab_run_impl(s, c, c.mem, -1);           // (refused there)
     // the lens was calibrated for one frame size: another one is refused before any work, and leaves the handle as it is
-    if (s && s->lens_on && (c.w != s->lens_w || c.h != s->lens_h))
-        return set_error(VS_ERR_ARG, "bad argument: lens correction is set for %d x %d frames, this call brings %d x %d (vs_stabilizer_set_lens)", s->lens_w, s->lens_h, c.w, c.h);
-    // host-resident batches longer than one upload chunk run as a three-stage pipeline: upload / compute / download
-    int chunk = 0;
-    if (s && c.mem == VS_MEM_HOST && n > 1 && c.w > 0 && c.h > 0) {
-        chunk = (int)std::max<size_t>(4, vsi::ingest_chunk_bytes() / std::max<size_t>(1, c.fbytes()));
-        if (clip_len > 0) chunk = std::max(clip_len, chunk - chunk % clip_len);
-    }
-    // Device-resident clip batches (vs_stabilizer_process_clips, VS_MEM_DEVICE, dense frames): the clips are cut into groups and the
-    // warps of group g go to a stream of their own, so that they run under the alignment of group g + 1 -- which then takes the
-    // small-footprint solver build (VS_BATCH_SHARED: it shares CUs with the warp grid).  Every group goes through stab_run_impl
-    // exactly as a process_clips call of its own would (clips are independent: stabilizer.cpp keeps no state across a reset), so
-    // the grouping cannot change results.  VS_STAB_OVERLAP=0 turns it off.
-    static const bool overlap_env = []() { const char* e = getenv("VS_STAB_OVERLAP"); return e ? atoi(e) != 0 : true; }();
-    static const bool prefetch_env = []() { const char* e = getenv("VS_STAB_PREFETCH"); return e ? atoi(e) != 0 : true; }();
-    // (the solver build under the overlapped warps: the small-footprint one beside a Lanczos2 warp, which fills the CUs for longer than the
-    // alignment pass takes; beside the fixed-point bilinear warp -- a quarter of the alignment pass -- the exclusive 512-thread build, whose
-    // shorter solver chain is worth more than the shared CUs: 1080p x 480 frames 101 k -> 120 k frames/s, 4K x 240 21.1 k -> 34.3 k
-    // (profiles/r05_stab_cv_solver.txt; VS_STAB_CV_SOLVER=1 selects the small build for an A/B))
-    static const int cv_solver_env = []() { const char* e = getenv("VS_STAB_CV_SOLVER"); return e && atoi(e) == VS_BATCH_SHARED ? VS_BATCH_SHARED : VS_BATCH_EXCLUSIVE; }();
-    const int overlap_mode = s && s->params.warp_mode == VS_WARP_BILINEAR_CV ? cv_solver_env : VS_BATCH_SHARED;
-    const int n_clips_all = clip_len > 0 ? n / clip_len : 0;
-    // (lens correction on: the plain route.  The overlapped routes align s->next_frames, the caller's uncorrected frames, ahead of time, and their
-    // deferred queue entries would point into batch_in, which the next sub-batch's corrected frames overwrite)
-    const bool dense_dev = s && !s->lens_on && c.mem == VS_MEM_DEVICE && c.w > 0 && n > 1 && c.dense();
-    int group_clips = 0;
-    if (overlap_env && dense_dev && clip_len >= 2 && n_clips_all >= 2 && n == n_clips_all * clip_len) {
-        // groups of at least kSharedMinPairs pairs (the small build's threshold), at most 4 groups (VS_STAB_GROUPS): every group boundary is a host
-        // synchronisation and a latency-bound solver launch -- c5 (8 clips x 60 x 4K 10-bit) 17.3-18.1 k frames/s with 8 groups, 18.9-19.5 k with 4
-        group_clips = std::max(1, (vsi::kSharedMinPairs + clip_len - 2) / (clip_len - 1));
-        // (beside the fixed-point bilinear warp, with the exclusive solver build: 2 groups -- c5 27.8 k frames/s with 4 groups, 28.9 k with 2, 24.8 k with 8)
-        static const int groups_env = []() { const char* e = getenv("VS_STAB_GROUPS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 0; }();
-        const int max_groups = groups_env ? groups_env : (overlap_mode == VS_BATCH_EXCLUSIVE ? 2 : 4);
-        group_clips = std::max(group_clips, (n_clips_all + max_groups - 1) / max_groups);
-        if (group_clips >= n_clips_all) group_clips = 0;
-    }
-    // ONE long device-resident clip: cut in time.  The batched form is n successive process calls, so the chunks are the same calls in the same
-    // order.  Time chunks of >= 48 frames (the small solver build's threshold with room to spare), at most 4 of them (VS_STAB_TIME_CHUNKS:
-    // 1080p x480 64 k frames/s with 8 chunks, 70 k with 6, 72 k with 4 or 3, 69-71 k with 2; profiles/r04_stab_long_clip.txt)
-    int time_chunk = 0;
-    static const int max_time_chunks = []() { const char* e = getenv("VS_STAB_TIME_CHUNKS"); const int v = e ? atoi(e) : 0; return v >= 1 ? v : 4; }();
-    // (with the exclusive solver build a chunk is a latency-bound chain of its own: chunks of >= 120 frames -- 4K x240 34.2 k frames/s in 4 chunks, 35.8 k in 2)
-    if (overlap_env && dense_dev && clip_len == 0 && n >= 96)
-        time_chunk = std::max(overlap_mode == VS_BATCH_EXCLUSIVE ? 120 : 48, (n + max_time_chunks - 1) / max_time_chunks);
-    if (time_chunk >= n) time_chunk = 0;
+    if (s->cfg.lens_on && (c.w != s->cfg.lens_w || c.h != s->cfg.lens_h))
+        return set_error(VS_ERR_ARG, "bad argument: lens correction is set for %d x %d frames, this call brings %d x %d (vs_stabilizer_set_lens)", s->cfg.lens_w, s->cfg.lens_h, c.w, c.h);
+    // how the call is cut, its thresholds and the numbers they were measured with: pick_route (vs_stab_plan.hpp)
+    const StabRoute route = pick_route(RouteIn{c.mem, c.n, c.clip_len, c.w, c.h, c.fbytes(), c.dense(), s->cfg.lens_on, s->params.warp_mode, vsi::ingest_chunk_bytes()},
+                                       stab_knobs());
     int r;
-    if (chunk > 0 && n > chunk)
-        r = vsi::guarded([&] { return stab_run_host_pipelined(s, c, chunk); });
-    else if (group_clips > 0)
-        r = stab_run_overlapped(s, c, group_clips * clip_len, false, overlap_mode, prefetch_env);
-    else if (time_chunk > 0)
-        r = stab_run_overlapped(s, c, time_chunk, true, overlap_mode, prefetch_env);
-    else
-        r = stab_run_impl(s, c, c.mem, -1);
-    if (s) for (auto& f : s->down) if (f.valid()) {          // every download has landed before the call returns
+    switch (route.kind) {
+    case StabRoute::HostPipelined: r = vsi::guarded([&] { return stab_run_host_pipelined(s, c, route.step); }); break;
+    case StabRoute::ClipGroups:
+    case StabRoute::TimeChunks: r = stab_run_overlapped(s, c, route.step, route.defer, route.solver_mode, route.prefetch); break;
+    default: r = stab_run_impl(s, c, c.mem, -1);
+    }
+    for (auto& f : s->down) if (f.valid()) {                 // every download has landed before the call returns
         const hipError_t de = f.get();
         if (de != hipSuccess && r >= 0) r = set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
     }
-    if (r < 0 && s && s->aligner) {
+    if (r < 0 && s->aligner) {
         const std::string why = vs_last_error();             // the reset below must not hide the cause
         vsi::align_abandon(s->aligner);                      // (a next chunk's alignment may have been started)
         s->prefetched = false; s->next_n = 0;
@@ -923,98 +852,98 @@ int vs_stabilizer_set_border_fill(vs_stabilizer* s, int ahead) try {
     VS_ARG(s && ahead >= 0);
     if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "border fill: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
     VS_ARG(ahead <= s->params.lag);
-    s->border_fill = ahead;
+    s->cfg.border_fill = ahead;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_border_fill(const vs_stabilizer* s) try {
     VS_ARG(s);
-    return s->border_fill;
+    return s->cfg.border_fill;
 } VS_CATCH_ALL
 int vs_stabilizer_set_fill_blend(vs_stabilizer* s, const vs_fill_blend_params* params) try {
     VS_ARG(s);
     if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "fill blend: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
     const vs_fill_blend_params p = params ? *params : vs_fill_blend_params{0, 0};
-    VS_ARG(p.feather >= 0 && p.feather <= 6 && (p.match == 0 || p.match == 1));
-    s->fill_blend = p;
+    VS_ARG(vsi::fill_blend_params_valid(p));
+    s->cfg.fill_blend = p;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_fill_blend(const vs_stabilizer* s, vs_fill_blend_params* params) try {
     VS_ARG(s && params);
-    *params = s->fill_blend;
+    *params = s->cfg.fill_blend;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_set_inpaint(vs_stabilizer* s, int on) try {
     VS_ARG(s && (on == 0 || on == 1));
     if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "inpaint: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
-    s->inpaint = on;
+    s->cfg.inpaint = on;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_inpaint(const vs_stabilizer* s) try {
     VS_ARG(s);
-    return s->inpaint;
+    return s->cfg.inpaint;
 } VS_CATCH_ALL
 int vs_stabilizer_set_sharpen(vs_stabilizer* s, const vs_sharpen_params* params) try {
     VS_ARG(s);
     if (s->params.warp_mode != VS_WARP_BILINEAR_CV) return set_error(VS_ERR_UNSUPPORTED, "sharpen: VS_WARP_BILINEAR_CV handles only (this one has warp_mode %d)", s->params.warp_mode);
-    if (params) VS_ARG(params->strength >= 1 && params->strength <= 32);
-    s->sharpen_on = params != nullptr;
-    if (params) s->sharpen = *params;
+    if (params) VS_ARG(vsi::sharpen_params_valid(*params));
+    s->cfg.sharpen_on = params != nullptr;
+    if (params) s->cfg.sharpen = *params;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_sharpen(const vs_stabilizer* s, vs_sharpen_params* params) try {
     VS_ARG(s && params);
-    if (s->sharpen_on) *params = s->sharpen; else vs_sharpen_params_default(params);
-    return s->sharpen_on ? 1 : 0;
+    if (s->cfg.sharpen_on) *params = s->cfg.sharpen; else vs_sharpen_params_default(params);
+    return s->cfg.sharpen_on ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_set_deblur(vs_stabilizer* s, int ahead, const vs_deblur_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
     vs_deblur_params p;
     if (params) p = *params; else vs_deblur_params_default(&p);
     VS_ARG(vsi::deblur_params_finite(p.sensitivity, p.max_ratio));
-    s->deblur = ahead;
-    s->deblur_params = p;
+    s->cfg.deblur = ahead;
+    s->cfg.deblur_params = p;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_deblur(const vs_stabilizer* s) try {
     VS_ARG(s);
-    return s->deblur;
+    return s->cfg.deblur;
 } VS_CATCH_ALL
 int vs_stabilizer_set_denoise(vs_stabilizer* s, int ahead, const vs_denoise_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
     vs_denoise_params p;
     if (params) p = *params; else vs_denoise_params_default(&p);
-    VS_ARG(p.strength >= 1 && p.strength <= 255);
-    s->denoise = ahead;
-    s->denoise_params = p;
+    VS_ARG(vsi::denoise_params_valid(p));
+    s->cfg.denoise = ahead;
+    s->cfg.denoise_params = p;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_set_deflicker(vs_stabilizer* s, int ahead, const vs_deflicker_params* params) try {
     VS_ARG(s && ahead >= 0 && ahead <= s->params.lag);
     vs_deflicker_params p;
     if (params) p = *params; else vs_deflicker_params_default(&p);
-    VS_ARG(p.step >= 1 && p.step <= 64);
-    s->deflicker = ahead;
-    s->deflicker_params = p;
+    VS_ARG(vsi::deflicker_params_valid(p));
+    s->cfg.deflicker = ahead;
+    s->cfg.deflicker_params = p;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_deflicker(const vs_stabilizer* s) try {
     VS_ARG(s);
-    return s->deflicker;
+    return s->cfg.deflicker;
 } VS_CATCH_ALL
 int vs_stabilizer_get_denoise(const vs_stabilizer* s) try {
     VS_ARG(s);
-    return s->denoise;
+    return s->cfg.denoise;
 } VS_CATCH_ALL
 int vs_stabilizer_set_rolling_shutter(vs_stabilizer* s, const vs_rolling_params* params) try {
     VS_ARG(s);
     const vs_rolling_params p = params ? *params : vs_rolling_params{0.0};
-    VS_ARG(p.readout >= -1.0 && p.readout <= 1.0);                   // (a NaN fails both)
-    s->rolling = p;
+    VS_ARG(vsi::rolling_params_valid(p));
+    s->cfg.rolling = p;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_rolling_shutter(const vs_stabilizer* s, vs_rolling_params* params) try {
     VS_ARG(s && params);
-    *params = s->rolling;
+    *params = s->cfg.rolling;
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_set_lens(vs_stabilizer* s, const vs_lens_params* params, int w, int h) try {
@@ -1027,30 +956,30 @@ int vs_stabilizer_set_lens(vs_stabilizer* s, const vs_lens_params* params, int w
     // the map belongs to (params, w, h): dropped here, made again by the next call that needs it (no launch of an earlier call still reads
     // it: every call ends with its stream synchronised)
     VS_HIP(hipSetDevice(vsi::aligner_device(s->aligner)));
-    if (s->lens_map) (void)hipFree(s->lens_map);
-    s->lens_map = nullptr; s->lens_map_bytes = 0; s->lens_map_made = false;
-    s->lens_on = params && !vsl::is_identity(*params);
-    if (s->lens_on) { s->lens = *params; s->lens_w = w; s->lens_h = h; }
+    s->lens_map.drop();
+    s->lens_map_made = false;
+    s->cfg.lens_on = params && !vsl::is_identity(*params);
+    if (s->cfg.lens_on) { s->cfg.lens = *params; s->cfg.lens_w = w; s->cfg.lens_h = h; }
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_lens(const vs_stabilizer* s, vs_lens_params* params, int* w, int* h) try {
     VS_ARG(s && params && w && h);
-    *w = s->lens_on ? s->lens_w : 0; *h = s->lens_on ? s->lens_h : 0;
-    if (s->lens_on) *params = s->lens; else vs_lens_params_default(params, 0, 0);
-    return s->lens_on ? 1 : 0;
+    *w = s->cfg.lens_on ? s->cfg.lens_w : 0; *h = s->cfg.lens_on ? s->cfg.lens_h : 0;
+    if (s->cfg.lens_on) *params = s->cfg.lens; else vs_lens_params_default(params, 0, 0);
+    return s->cfg.lens_on ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_set_scene_cut(vs_stabilizer* s, const vs_scene_params* params) try {
     VS_ARG(s);
-    if (params) VS_ARG(params->step >= 1 && params->step <= 64 && params->threshold >= 1 && params->threshold <= 255);
-    s->scene_on = params != nullptr;
-    if (params) s->scene_params = *params;
+    if (params) VS_ARG(vsi::scene_params_valid(*params));
+    s->cfg.scene_on = params != nullptr;
+    if (params) s->cfg.scene_params = *params;
     else s->scene_prev_valid = false;                                 // (off: no frame is kept; switched on again, a lag-0 handle starts with the frame after next)
     return VS_OK;
 } VS_CATCH_ALL
 int vs_stabilizer_get_scene_cut(const vs_stabilizer* s, vs_scene_params* params) try {
     VS_ARG(s && params);
-    if (s->scene_on) *params = s->scene_params; else vs_scene_params_default(params);
-    return s->scene_on ? 1 : 0;
+    if (s->cfg.scene_on) *params = s->cfg.scene_params; else vs_scene_params_default(params);
+    return s->cfg.scene_on ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_get_scene_cuts(const vs_stabilizer* s, int64_t* frames, int cap) try {
     VS_ARG(s && cap >= 0 && (frames || cap == 0));
