@@ -604,6 +604,49 @@ int vs_bgr_scene_stats_batch(const void* src, size_t src_frame_stride, int n_src
                              const vs_scene_params* params /* NULL = defaults */, uint64_t* stats /* 2 per pair */, int mem, void* stream);
 /* The rule's decision, on the host (no device needed): cut[i] = 1 iff pair i is a cut.  stats and cut are host arrays. */
 int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_scene_params* params /* NULL = defaults */, uint8_t* cut);
+/* FIDELITY STATISTICS of image pairs: the squared error per channel and on gray, and an integer SSIM over 8 x 8 windows.  What the stabilization
+ * literature scores a clip by -- ITF, the mean PSNR between consecutive output frames -- and what denoise and deblur work reports against a
+ * reference clip, PSNR and SSIM, are all integer sums over two frames that already lie in device memory: one pass that reads each image once.
+ *
+ * THE FIDELITY RULE (also vs_fidelity.hip).
+ *   - SCOPE.  Interleaved BGR, every VS_FMT_BGR*, images of 1 .. 32767 pixels a side; s = bits - 8.  Every sample is first v' = min(v, max_value).
+ *   - PAIR.  A pair is (image a, image b), both w x h.  Each side has its own row stride and frame stride.  An image may be a window of a larger
+ *     frame: pass its origin pointer with the frame's strides.  Row starts may therefore fall on any byte (8-bit) or any element (16-bit).
+ *   - GRAY.  g = min(((B' * 3735 + G' * 19235 + R' * 9798 + 16384) >> 15) >> s, 255), in unsigned 32-bit arithmetic: vs_bgr_to_gray's weights.  The
+ *     largest value is 65535 * 32768 + 16384 < 2^32.
+ *   - WORDS.  Each pair gives six uint64: words 0 .. 2 sse_b, sse_g, sse_r = the sum over all pixels of (a'_c - b'_c)^2, at the format's own
+ *     precision; word 3 sse_y = the same sum on g; word 4 n_win; word 5 ssim_sum, an int64 in two's complement.
+ *   - WINDOWS.  8 x 8 at a stride of 4: nwx = w >= 8 ? (w - 8) / 4 + 1 : 0, nwy likewise from h, n_win = nwx * nwy.  Window (i, j) covers x in
+ *     4i .. 4i + 7 and y in 4j .. 4j + 7.  Pixels right of, or below, the last window belong to no window; they still count in the four SSE words.
+ *   - PER WINDOW.  All on g, all in int32.  s1 = sum g_a, s2 = sum g_b, ss = sum (g_a^2 + g_b^2), s12 = sum g_a g_b;
+ *       vars = 64 ss - s1^2 - s2^2,  cov = 64 s12 - s1 s2;  c1 = 26634, c2 = 239708 ((0.01 * 255)^2 * 64^2 and (0.03 * 255)^2 * 64^2, rounded);
+ *       A = 2 s1 s2 + c1,  B = 2 cov + c2,  C = s1^2 + s2^2 + c1,  D = vars + c2;
+ *       q = rint(((double)(int64)(A * B) / (double)(int64)(C * D)) * 65536.0): the conversions and the division correctly rounded, no fma, ties to
+ *       even.  ssim_sum = sum q.
+ *   - BOUNDS.  s1, s2 <= 16320 and ss <= 8 323 200; each of vars, |cov|, A, |B|, C, D is at most 532 924 508 < 2^31 and the products stay below
+ *     2^59; C >= c1 and D >= c2, so both are positive; |q| <= 65536, because 2 s1 s2 <= s1^2 + s2^2 and 2 |cov| <= vars.
+ *     sse_c <= 65535^2 * 2^30 < 2^62, n_win < 2^26, |ssim_sum| < 2^42.
+ *   - HENCE (a) a == b gives zero SSE words and ssim_sum = 65536 * n_win; (b) 8-bit constant images of 100 and 130 give 900 w h in each SSE word and
+ *     q = 63344 in every window; (c) all-0 against all-maximum gives max_value^2 * w h per channel, 65025 w h for sse_y and q = 7; (d) an 8-bit
+ *     checkerboard of 0 / 255 against its inverse gives q = -65300; (e) exchanging a and b changes no word.
+ *   - Integer sums only: the order of the reduction cannot matter, so results are identical from run to run.
+ * THE SCORES (vs_fidelity_scores, on the host).  With peak = max_value and N = (double)w * (double)h:
+ *     psnr_c = 10.0 * log10((peak * peak * N) / (double)sse_c);  psnr pools the three channels: 3 N and sse_b + sse_g + sse_r;  psnr_y uses a peak
+ *     of 255 and sse_y;  a zero SSE gives HUGE_VAL;  ssim = (double)ssim_sum / (65536.0 * n_win), and NaN when n_win == 0.
+ * The constants come from the usual SSIM derivation with population variances over 64 samples; they are this build's specification.  Values are
+ * close to, but not equal to, what other tools print: those scale c1 differently, weight the window with a Gaussian and finish in fp32. */
+typedef struct vs_fidelity_score { double psnr_b, psnr_g, psnr_r, psnr, psnr_y, ssim; } vs_fidelity_score;
+/* stats[6*i ..] of pair i = (image pair_frames[2*i] of the batch at `a`, image pair_frames[2*i + 1] of the batch at `b`).  Both batches hold w x h
+ * images in `format`, n_a / n_b of them, frame strides and row strides in elements; `b` may be the batch at `a` (a host batch is then staged
+ * once).  `stats` lives in `mem`; pair_frames is a host array.  Pairs may repeat, may come in any order and may name one image twice.
+ * n_pairs == 0 is VS_OK and launches nothing.  An index outside its batch, a stride below 3 w, VS_FMT_GRAY8 or a size outside 1 .. 32767 is
+ * VS_ERR_ARG, before any device work.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_fidelity_batch(const void* a, size_t a_frame_stride, int n_a, int a_stride,
+                          const void* b, size_t b_frame_stride, int n_b, int b_stride,
+                          int w, int h, int format, int n_pairs, const int32_t* pair_frames /* 2 per pair: into a, into b */,
+                          uint64_t* stats /* 6 per pair, in mem */, int mem, void* stream);
+/* The rule's scores, on the host (no device needed): stats and scores are host arrays. */
+int vs_fidelity_scores(const uint64_t* stats, int n_pairs, int w, int h, int format, vs_fidelity_score* scores);
 /* PHASE-COMPENSATED SHARPENING behind VS_WARP_BILINEAR_CV.  A bilinear resample is a two-tap box filter per axis, [1 - f, f], whose blur
  * depends on the sub-pixel phase f: none at f = 0, most at f = 1/2.  In stabilised video every pixel's phase drifts from frame to frame, so
  * the output's sharpness pulses.  The warp's positions carry five fraction bits, a = X & 31, b = Y & 31; the filter [1 - a/32, a/32] has

@@ -110,6 +110,14 @@ class SceneParams(C.Structure):
     _fields_ = [("step", C.c_int), ("threshold", C.c_int)]
 
 
+class FidelityScore(C.Structure):
+    """vs_fidelity_score: PSNR per channel, pooled and on gray, in dB (inf for identical images); the mean SSIM (NaN without a window)"""
+    _fields_ = [(k, C.c_double) for k in ("psnr_b", "psnr_g", "psnr_r", "psnr", "psnr_y", "ssim")]
+
+    def tup(self):
+        return tuple(getattr(self, k) for k, _ in self._fields_)
+
+
 class SharpenParams(C.Structure):
     """vs_sharpen_params: the strength in sixteenths of the two-tap filter's own variance, 1 .. 32"""
     _fields_ = [("strength", C.c_int)]
@@ -217,6 +225,8 @@ SIGNATURES = {
     "vs_scene_params_default": (None, [C.POINTER(SceneParams)]),
     "vs_bgr_scene_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(SceneParams), _vp, _i32, _vp]),
     "vs_scene_cuts": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(SceneParams), _vp]),
+    "vs_bgr_fidelity_batch": (_i32, [_vp, _sz, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _vp, _i32, _vp]),
+    "vs_fidelity_scores": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(FidelityScore)]),
     "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_sharpen_params_default": (None, [C.POINTER(SharpenParams)]),
     "vs_bgr_sharpen_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _TP, C.POINTER(SharpenParams), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
@@ -1130,6 +1140,54 @@ def scene_cuts(stats, w, h, params=None):
     out = np.full((max(st.shape[0], 1),), 0xA5, np.uint8)
     _check(lib().vs_scene_cuts(_p(st), st.shape[0], w, h, C.byref(params) if params is not None else None, _p(out)))
     return out[:st.shape[0]]
+
+
+def _fidelity_pairs(pair_frames):
+    idx = _c(pair_frames, np.int32).reshape(-1, 2)
+    return idx, idx.shape[0]
+
+
+def fidelity_stats_batch(a, b, pair_frames, fmt=None, a_stride=None, b_stride=None, roi=None):
+    """the fidelity statistics of image pairs (include/vs_amd.h: vs_bgr_fidelity_batch).  a (n_a,h,w,3) and b (n_b,h,w,3) numpy of one dtype; b None
+    or a itself: the pairs lie in one batch, handed over once; pair_frames (n_pairs, 2) ints: into a, into b.  -> (n_pairs, 6) uint64: sse_b, sse_g,
+    sse_r, sse_y, n_win, ssim_sum (two's complement).  a_stride / b_stride (elements): the call is made on pitched copies of the frames.  roi
+    (x, y, rw, rh): the images are that window of the frames, handed over as its origin pointer with the frames' strides"""
+    a = np.ascontiguousarray(a)
+    one = b is None or b is a
+    b = a if one else np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.shape[1:] == b.shape[1:]
+    n_a, h, w, c = a.shape
+    idx, n_pairs = _fidelity_pairs(pair_frames)
+    fmt = _fmt_of(a.dtype, 3) if fmt is None else fmt
+    sa = w * c if a_stride is None else a_stride
+    sb = (sa if one else w * c) if b_stride is None else b_stride
+    pa = _pitched(a, sa)
+    pb = pa if one and sb == sa else _pitched(b, sb)
+    x, y, rw, rh = (0, 0, w, h) if roi is None else roi
+    assert 0 <= x and 0 <= y and rw >= 1 and rh >= 1 and x + rw <= w and y + rh <= h
+    esz = a.dtype.itemsize
+    out = np.full((max(n_pairs, 1), 6), 0xA5A5A5A5, np.uint64)
+    _check(lib().vs_bgr_fidelity_batch(C.c_void_p(pa.ctypes.data + (y * sa + x * c) * esz), h * sa, n_a, sa,
+                                       C.c_void_p(pb.ctypes.data + (y * sb + x * c) * esz), h * sb, b.shape[0], sb, rw, rh, fmt, n_pairs,
+                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _p(out), MEM_HOST, None))
+    return out[:n_pairs]
+
+
+def fidelity_stats_batch_device(a_ptr, a_fs, n_a, a_stride, b_ptr, b_fs, n_b, b_stride, w, h, fmt, pair_frames, stats_ptr, stream=None):
+    """device-resident form: frame strides and row strides in elements, enqueue only"""
+    idx, n_pairs = _fidelity_pairs(pair_frames)
+    _check(lib().vs_bgr_fidelity_batch(_p(a_ptr), a_fs, n_a, a_stride, _p(b_ptr), b_fs, n_b, b_stride, w, h, fmt, n_pairs,
+                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _p(stats_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+
+
+def fidelity_scores(stats, w, h, fmt=FMT_BGR8):
+    """the fidelity rule's scores, on the host (include/vs_amd.h: vs_fidelity_scores).  stats (n_pairs, 6) uint64 -> (n_pairs, 6) float64: psnr_b,
+    psnr_g, psnr_r, psnr, psnr_y, ssim"""
+    st = _c(stats, np.uint64).reshape(-1, 6)
+    n = st.shape[0]
+    arr = (FidelityScore * max(n, 1))()
+    _check(lib().vs_fidelity_scores(_p(st), n, w, h, fmt, arr))
+    return np.array([arr[i].tup() for i in range(n)], np.float64).reshape(n, 6)
 
 
 def sharpen_params(**kw):

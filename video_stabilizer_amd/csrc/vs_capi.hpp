@@ -1,6 +1,6 @@
 // vs_capi.hpp -- what the files of the kernel-level C ABI layer share: the argument macros, the plan (vs_call_plan.hpp), the span rings of
 // vs_runtime.hip as the entry points see them, and the look-ahead passes' shared path.  Included by vs_runtime.hip, vs_capi.hip,
-// vs_capi_warp.hip, vs_capi_lookahead.hip and vs_capi_ycbcr.hip only.
+// vs_capi_warp.hip, vs_capi_lookahead.hip, vs_capi_ycbcr.hip and vs_capi_fidelity.hip only.
 #pragma once
 
 #include "vs_internal.hpp"

@@ -140,6 +140,26 @@ int vs_scene_cuts(const uint64_t* stats, int n_pairs, int w, int h, const vs_sce
     return VS_OK;
 } VS_CATCH_ALL
 
+// the fidelity rule's scores (vs_fidelity.hip) from its statistics: doubles, as include/vs_amd.h writes them
+int vs_fidelity_scores(const uint64_t* stats, int n_pairs, int w, int h, int format, vs_fidelity_score* scores) try {
+    const int maxv = vs_format_max_value(format);
+    if (n_pairs < 0 || w < 1 || h < 1 || w > 32767 || h > 32767 || format == VS_FMT_GRAY8 || vs_format_bits(format) == 0 || (n_pairs > 0 && (!stats || !scores)))
+        return vsi::set_error(VS_ERR_ARG, "bad argument: n_pairs >= 0, w, h in 1 .. 32767, a VS_FMT_BGR* format, stats and scores (vs_fidelity_scores)");
+    const double N = (double)w * (double)h, peak = (double)maxv;
+    const auto psnr = [](double peak2n, uint64_t sse) { return sse == 0 ? HUGE_VAL : 10.0 * std::log10(peak2n / (double)sse); };
+    for (int i = 0; i < n_pairs; i++) {
+        const uint64_t* st = stats + 6 * (size_t)i;
+        vs_fidelity_score& o = scores[i];
+        o.psnr_b = psnr(peak * peak * N, st[0]);
+        o.psnr_g = psnr(peak * peak * N, st[1]);
+        o.psnr_r = psnr(peak * peak * N, st[2]);
+        o.psnr = psnr(peak * peak * (3.0 * N), st[0] + st[1] + st[2]);
+        o.psnr_y = psnr(255.0 * 255.0 * N, st[3]);
+        o.ssim = st[4] == 0 ? std::nan("") : (double)(int64_t)st[5] / (65536.0 * (double)st[4]);
+    }
+    return VS_OK;
+} VS_CATCH_ALL
+
 // imgproc.cpp:333-359
 vs_transform vs_transform_inverse(const vs_transform* t) {
     const double p = 1.0 + t->A, q = t->B;

@@ -134,6 +134,12 @@ hipError_t bgr_gain(const void* src, int w, int h, int src_stride, int bits, int
 // leaves the pair's words zero.  stats = n_pairs x 2 words (count, sad) in device memory, zeroed on `s` first.
 hipError_t scene_stats(const FillCand* cands_dev, int w, int h, int src_stride, int bits, int shift_to_8, int max_value, int step, unsigned long long* stats,
                        int n_pairs, hipStream_t s);
+// Fidelity statistics of image pairs (vs_fidelity.hip: the rule and the kernel).  pairs_dev = n_pairs entries in device memory: image a and image
+// b of the pair, both w x h, rows of a_stride / b_stride elements.  on_dwords: every row of every image named starts on a dword (rows_on_dwords of
+// both batches).  stats = n_pairs x 6 words (sse_b, sse_g, sse_r, sse_y, n_win, ssim_sum) in device memory, zeroed on `s` first.
+struct FidPair { const void* a; const void* b; };                                     // 16 bytes = one float4 slot of the parameter ring
+hipError_t bgr_fidelity(const FidPair* pairs_dev, int w, int h, int a_stride, int b_stride, int bits, int shift_to_8, int max_value, bool on_dwords,
+                        unsigned long long* stats, int n_pairs, hipStream_t s);
 // Phase-compensated sharpening behind VS_WARP_BILINEAR_CV (vs_sharpen.hip: the rule and the kernels).  n_frames images of roi.w x roi.h, the
 // window `roi` of w x h output frames; minv_dev = n_frames x 6 doubles in device memory, the output -> source matrix of each frame
 // (vs_cv_inverse_matrix); strength: 1 .. 32.  Out of place: src and dst must not overlap.
