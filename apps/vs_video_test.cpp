@@ -1,5 +1,5 @@
 // vs_video_test -- stabilize every clip of a directory (the role of the reference's video_test.cpp:10-128).
-//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444] [--device-convert]
+//   vs_video_test [input_dir=../recordings] [output_dir=output] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear | --lanczos2] [--444] [--device-convert] [--out-size WxH | source] [--out-filter linear|area]
 // For each .y4m / .bgr clip writes output_dir/processed_<name>.  Like the reference's driver it runs the default
 // VideoStabilizerParams with crop_pixels = 0 (video_test.cpp:54-55) unless --crop is given.  --fill N: what the corrected frame
 // does not cover is filled from the next N input frames (vs_stabilizer_set_border_fill); --fill-feather N (1 .. 6) cross-fades the fill into the
@@ -13,6 +13,8 @@
 // default 32); the clip's cut list is printed.  --sharpen [S]: every output window is sharpened behind the warp by the sub-pixel phase of its own
 // correction, which evens out the bilinear warp's phase-dependent blur (vs_stabilizer_set_sharpen; S: the strength in sixteenths, 1 .. 32, default 16).  --rolling-shutter R: every frame is corrected for a rolling shutter whose readout takes the
 // share R (-1 .. 1, negative: bottom-up) of the frame period, by the motion to the following frame (vs_stabilizer_set_rolling_shutter).
+// --out-size WxH | source: the crop window is resized to that size, or to the source frame's, behind every other pass and the writer takes that
+// size (vs_stabilizer_set_output_size); --out-filter linear|area: the filter, by default area where an axis shrinks by more than 2:1 and linear otherwise.
 // --lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]: every frame is corrected for that lens's distortion in front of everything (the camera matrix in
 // pixels, then OpenCV's distCoeffs in their order; --lens-zoom Z scales the output camera's focal lengths, default 1; vs_stabilizer_set_lens).  Frames go to the GPU in
 // chunks of N (default 64) and through vs_stabilizer_process_batch, which is defined as N successive processFrame calls.
@@ -24,6 +26,9 @@
 #include "harness.hpp"
 
 namespace fs = std::filesystem;
+
+// --out-size: w == 0: off (the crop window is written); w == -1: the source frame's size; filter -1: chosen from the sizes
+struct OutSize { int w = 0, h = 0, filter = -1; };
 
 // the planes of frame 0 of a chunk of raw y4m frames at `base`, frames back to back in the file's layout (Y, then Cb, then Cr)
 static vs_ycbcr_planes planes_of(const vsio::Format& f, void* base) {
@@ -41,7 +46,7 @@ static vs_ycbcr_planes planes_of(const vsio::Format& f, void* base) {
 
 static bool process_clip(const std::string& in_path, const std::string& out_path, vs_stabilizer_params params, int device, int chunk,
                          bool force444, int fill, vs_fill_blend_params blend, int deblur, int denoise, int denoise_strength, int deflicker,
-                         int deflicker_step, int scene_cut, int sharpen, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom, bool device_convert) {
+                         int deflicker_step, int scene_cut, int sharpen, bool inpaint, double rolling, const std::vector<double>& lens, double lens_zoom, bool device_convert, OutSize out_size) {
     vsio::Reader reader;
     if (!reader.open(in_path)) { std::cerr << "Error: " << reader.error << std::endl; return false; }
     const vsio::Format fin = reader.fmt;
@@ -50,6 +55,14 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
     fout.w = fin.w - 2 * crop; fout.h = fin.h - 2 * crop;             // video_test.cpp:74-76
     if (force444 || fin.chroma == vsio::Chroma::Mono) fout.chroma = vsio::Chroma::C444;
     if (fout.w <= 0 || fout.h <= 0) { std::cerr << "Error: crop larger than the frame" << std::endl; return false; }
+    if (out_size.w != 0) {                                              // the writer takes the delivered size (vs_stabilizer_set_output_size)
+        const int win_w = fout.w, win_h = fout.h;
+        fout.w = out_size.w < 0 ? fin.w : out_size.w; fout.h = out_size.h < 0 ? fin.h : out_size.h;
+        // the default filter: area where an axis shrinks by more than 2:1 (and area can take both axes there), linear otherwise
+        if (out_size.filter < 0)
+            out_size.filter = (win_w > 2 * fout.w || win_h > 2 * fout.h) && fout.w <= win_w && win_w <= 8 * fout.w && fout.h <= win_h && win_h <= 8 * fout.h
+                                  ? VS_RESIZE_AREA : VS_RESIZE_LINEAR;
+    }
     vsio::Writer writer;
     if (!writer.open(out_path, fout)) { std::cerr << "Error: " << writer.error << std::endl; return false; }
     std::cout << "Input FPS: " << (double)fin.fps_num / fin.fps_den << " | Frame Size: " << fout.w << "x" << fout.h << std::endl;
@@ -122,6 +135,11 @@ static bool process_clip(const std::string& in_path, const std::string& out_path
             vs_stabilizer_destroy(stab);
             return false;
         }
+    }
+    if (out_size.w != 0 && vs_stabilizer_set_output_size(stab, out_size.w, out_size.h, out_size.filter) != VS_OK) {
+        std::cerr << "Error: vs_stabilizer_set_output_size: " << vs_last_error() << std::endl;
+        vs_stabilizer_destroy(stab);
+        return false;
     }
     if (rolling != 0.0) {
         const vs_rolling_params rp{rolling};
@@ -200,6 +218,7 @@ int main(int argc, char** argv) {
     bool inpaint = false;
     double rolling = 0.0, lens_zoom = 1.0;
     std::vector<double> lens;                              // --lens: 8, 9 or 12 numbers
+    OutSize out_size;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--chunk" && i + 1 < argc) chunk = std::max(1, std::atoi(argv[++i]));
@@ -245,9 +264,23 @@ int main(int argc, char** argv) {
         else if (a == "--lanczos2") lanczos2 = true;
         else if (a == "--444") force444 = true;
         else if (a == "--device-convert") device_convert = true;
+        else if (a == "--out-size" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            char x = 0;
+            if (v == "source") out_size.w = out_size.h = -1;
+            else if (std::sscanf(v.c_str(), "%d%c%d", &out_size.w, &x, &out_size.h) != 3 || x != 'x' || out_size.w < 1 || out_size.h < 1) {
+                std::cerr << "Error: --out-size takes WxH or source\n"; return EXIT_FAILURE;
+            }
+        }
+        else if (a == "--out-filter" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            if (v == "linear") out_size.filter = VS_RESIZE_LINEAR;
+            else if (v == "area") out_size.filter = VS_RESIZE_AREA;
+            else { std::cerr << "Error: --out-filter takes linear or area\n"; return EXIT_FAILURE; }
+        }
         else if (positional == 0) { input_dir = a; positional++; }
         else if (positional == 1) { output_dir = a; positional++; }
-        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444] [--device-convert]\n"; return EXIT_FAILURE; }
+        else { std::cerr << "Usage: " << argv[0] << " [input_dir] [output_dir] [--chunk N] [--device D] [--crop N] [--fill N] [--fill-feather N] [--fill-match] [--inpaint] [--deblur N] [--denoise N] [--denoise-strength T] [--deflicker N] [--deflicker-step S] [--scene-cut [T]] [--sharpen [S]] [--rolling-shutter R] [--lens fx,fy,cx,cy,k1,k2,p1,p2[,k3[,k4,k5,k6]]] [--lens-zoom Z] [--bilinear] [--444] [--device-convert] [--out-size WxH | source] [--out-filter linear|area]\n"; return EXIT_FAILURE; }
     }
     try {
         if (!fs::exists(output_dir)) {
@@ -273,7 +306,7 @@ int main(int argc, char** argv) {
         for (const auto& name : clips) {
             const std::string in_path = (fs::path(input_dir) / name).string();
             std::cout << "\nProcessing video: " << in_path << std::endl;
-            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, scene_cut, sharpen, inpaint, rolling, lens, lens_zoom, device_convert)) failed++;
+            if (!process_clip(in_path, (fs::path(output_dir) / ("processed_" + name)).string(), params, device, chunk, force444, fill, blend, deblur, denoise, denoise_strength, deflicker, deflicker_step, scene_cut, sharpen, inpaint, rolling, lens, lens_zoom, device_convert, out_size)) failed++;
         }
         if (failed) { std::cerr << "\n" << failed << " clip(s) failed." << std::endl; return EXIT_FAILURE; }
         std::cout << "\nAll videos have been processed successfully." << std::endl;

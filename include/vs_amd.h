@@ -524,6 +524,62 @@ int vs_ycbcr_to_bgr_batch(const vs_ycbcr_planes* src, int n, int w, int h, int f
                           void* dst, size_t dst_frame_stride, int dst_stride, int mem, void* stream);
 int vs_bgr_to_ycbcr_batch(const void* src, size_t src_frame_stride, int n, int w, int h, int src_stride, int format,
                           const vs_ycbcr_planes* dst, int mem, void* stream);
+/* RESIZE: frames from one size to another, a pass of its own behind everything (the delivery size of a transcode).
+ *
+ * THE RESIZE RULE.  This build's specification; it is not OpenCV's `cv::resize` binary (its 8-bit linear path rounds twice, its 16-bit path
+ * is float).
+ *
+ * - It applies to interleaved BGR, every `VS_FMT_BGR*`.
+ * - Source is `sw x sh`, destination `dw x dh`, each 1 .. 32767.
+ * - It is separable. Each axis gets a TAP TABLE from integers only, so host and device agree by construction.
+ * - A table entry is a first index `i0[d]`, a count `n[d] >= 1` and weights `wt[d][k] >= 0` with `sum_k wt[d][k] == 4096` exactly.
+ * - The filter is chosen per call: `VS_RESIZE_LINEAR` or `VS_RESIZE_AREA`.
+ *
+ * LINEAR, any ratio.
+ *
+ * - With 64-bit integers, `num = (2 d + 1) s - dn` and `p = floor(num * 4096 / (2 dn))`, floor towards minus infinity.
+ * - `p` is clamped to `[0, (s - 1) * 4096]`. `i = p >> 12`, `f = p & 4095`.
+ * - The taps are `(i, 4096 - f)` and `(min(i + 1, s - 1), f)`. The table lists the second tap only where `f != 0`.
+ * - Here `s` is the source extent and `dn` the destination extent of that axis.
+ *
+ * AREA, only where `dn <= s <= 8 dn` on that axis; otherwise `VS_ERR_UNSUPPORTED`.
+ *
+ * - In units of `1 / dn` source pixels, destination cell `d` covers `[d s, (d + 1) s)`.
+ * - Its taps are the source pixels `k = floor(d s / dn) .. floor(((d + 1) s - 1) / dn)`.
+ * - `cum_k = min((k + 1) dn, (d + 1) s) - d s`.
+ * - `C_k = floor((cum_k * 4096 + floor(s / 2)) / s)`.
+ * - `wt_k = C_k - C_(k-1)`, with `C = 0` before the first tap.
+ * - Hence the weights sum to 4096 and `n <= floor(s / dn) + 2 <= 10`.
+ *
+ * SAMPLE.
+ *
+ * - `v' = min(v, max_value)`.
+ * - Per channel, `H(y, d) = sum_k wx[d][k] * v'(y, ix0[d] + k)`. This is exact and below 2^28.
+ * - `V = sum_j wy[e][j] * H(iy0[e] + j, d)`. This is exact. It fits unsigned 32 bits for 8-bit frames including the rounding term:
+ *   `4096 * 4096 * 255 + 2^23 < 2^32`. Deeper frames take 64 bits.
+ * - `out = (V + 2^23) >> 24`. There is one rounding per sample and it happens here.
+ *
+ * Hence
+ *
+ * - (a) `dw == sw && dh == sh` is the identity, bit for bit, under both filters (for samples up to the format's maximum).
+ * - (b) A constant frame stays constant.
+ * - (c) Every output lies within the min .. max of its taps, so no sample exceeds `max_value`.
+ * - (d) AREA at an integer factor `k` gives equal weights when `4096 % k == 0`. Factor 2 gives `(a + b + c + d + 2) >> 2`.
+ * - (e) LINEAR at `sw == 2 dw` equals AREA there.
+ * - (f) LINEAR 4 -> 8 has weights `4096 | 3072,1024 | 1024,3072 | ... | 4096`.
+ * - (g) AREA 7 -> 3 has the tables `(0: 1755,1756,585) (2: 1170,1756,1170) (4: 585,1756,1755)`. */
+#define VS_RESIZE_LINEAR 0
+#define VS_RESIZE_AREA 1
+/* One axis' table as the kernels use it, on the host (no device needed): `i0[d]`, `n[d]` and `wt[d * 10 + k]`, `k < n[d]`, for
+ * every destination index of the axis `s -> d`; weights past `n[d]` are written as 0.  `VS_ERR_ARG` for NULL arrays, an extent outside 1 .. 32767 or an unknown
+ * filter; `VS_ERR_UNSUPPORTED` for AREA outside `d <= s <= 8 d`. */
+int vs_resize_taps(int s, int d, int filter, int32_t* i0, int32_t* n, uint16_t* wt /* d x 10 */);
+/* n frames of sw x sh -> n frames of dw x dh.  Argument checks, staging and VS_MEM_* as vs_bgr_gain_batch and vs_bgr_remap_batch.
+ * n == 0 is VS_OK without a launch.  src == dst is VS_ERR_ARG (out of place; overlapping ranges are the caller's to avoid).  An extent
+ * above 32767, or AREA outside its range (the message names the axis), is VS_ERR_UNSUPPORTED before any work.  Both axes' tables are built
+ * once per call on the device and shared by the call's frames.  VS_MEM_DEVICE only enqueues. */
+int vs_bgr_resize_batch(const void* src, size_t src_frame_stride, int n, int sw, int sh, int src_stride, int format, int filter,
+                        void* dst, size_t dst_frame_stride, int dw, int dh, int dst_stride, int mem, void* stream);
 /* DEFLICKER: a frame's exposure is pulled to the average exposure of a window of frames, the exposure ratio of two frames being measured
  * at the same scene points through their measured motions (a pan changes a whole-frame sum because the content changes).  Interleaved
  * BGR, every VS_FMT_BGR*, frames up to 32767 a side (VS_ERR_UNSUPPORTED beyond, as in the fill); s = bits - 8.  The rule:
@@ -1045,6 +1101,19 @@ int   vs_stabilizer_get_scene_cuts(const vs_stabilizer* s, int64_t* frames, int 
  * get_sharpen: returns 1 (on: *params in force) or 0 (off: *params = the defaults). */
 int   vs_stabilizer_set_sharpen(vs_stabilizer* s, const vs_sharpen_params* params /* NULL = off */);
 int   vs_stabilizer_get_sharpen(const vs_stabilizer* s, vs_sharpen_params* params);
+/* Output size (the rule: THE RESIZE RULE, see vs_bgr_resize_batch).  (0, 0) (default): off -- the crop window (w - 2 crop) x (h - 2 crop) is
+ * delivered, and the handle is the one it is without this call, launch for launch and allocation for allocation.  (-1, -1): every frame is
+ * delivered at the source frame's size ("zoom to fill").  (dw, dh), each 1 .. 32767: that size.  On: the warp -- with fill, inpaint,
+ * sharpen and the deflicker's gain as configured -- writes groups of output windows into a scratch buffer of the handle (one allocation, at
+ * most 256 MB or one window), and the resize, last on the run's stream, writes the delivered frames to where the windows went before:
+ * what a handle with the pass off returns, put through vs_bgr_resize_batch, bit for bit.  out_w, out_h, out_frame_stride and the output
+ * planes of vs_stabilizer_process_batch_ycbcr then take the delivered size.  A call whose window already has the requested size launches
+ * and allocates nothing for this pass.  A call whose window VS_RESIZE_AREA cannot take to the size (delivered <= window <= 8 delivered on
+ * each axis) returns VS_ERR_UNSUPPORTED before any work and leaves the handle's state as it was; so does set_output_size for a size above
+ * 32767.  VS_ERR_ARG for another filter or any other pair of sizes.  Takes effect with the next call.
+ * get_output_size: the three values as set; returns 1 (a size is set) or 0 (off). */
+int   vs_stabilizer_set_output_size(vs_stabilizer* s, int dw, int dh, int filter /* VS_RESIZE_* */);
+int   vs_stabilizer_get_output_size(const vs_stabilizer* s, int* dw, int* dh, int* filter);
 void vs_stabilizer_state(const vs_stabilizer* s, vs_transform* last_meas, vs_transform* accum, int* last_success);
 
 #ifdef __cplusplus

@@ -7,7 +7,7 @@
 set -euo pipefail
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 CS="$ROOT/video_stabilizer_amd/csrc"
-if [ "$1" = "bounds" ] && [ $# -eq 1 ]; then set -- bounds "-DVS_DEBUG_BOUNDS" vs_engine.hip vs_warp.hip vs_fill.hip vs_inpaint.hip vs_deblur.hip vs_denoise.hip vs_rolling.hip vs_remap.hip vs_ycbcr.hip vs_deflicker.hip vs_scene.hip vs_fidelity.hip vs_sharpen.hip vs_phase.hip vs_flow.hip vs_capi.hip; fi
+if [ "$1" = "bounds" ] && [ $# -eq 1 ]; then set -- bounds "-DVS_DEBUG_BOUNDS" vs_engine.hip vs_warp.hip vs_fill.hip vs_inpaint.hip vs_deblur.hip vs_denoise.hip vs_rolling.hip vs_remap.hip vs_ycbcr.hip vs_resize.hip vs_deflicker.hip vs_scene.hip vs_fidelity.hip vs_sharpen.hip vs_phase.hip vs_flow.hip vs_capi.hip; fi
 NAME="$1"; FLAGS="$2"; shift 2
 FILES="${*:-vs_warp.hip}"
 OUTD="$ROOT/video_stabilizer_amd/variants"; BD="$CS/build/variant_$NAME"

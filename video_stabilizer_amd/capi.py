@@ -19,6 +19,7 @@ FMT_GRAY8, FMT_BGR8 = 0, 1
 FMT_BGR10, FMT_BGR12, FMT_BGR16_FULL = 2, 3, 4      # u16 containers: bits the samples use
 WARP_LANCZOS2, WARP_BILINEAR, WARP_LANCZOS2_FAST, WARP_LANCZOS2_SEP, WARP_BILINEAR_CV = 0, 1, 2, 3, 4
 BORDER_CLAMP, BORDER_CONSTANT = 0, 1
+RESIZE_LINEAR, RESIZE_AREA = 0, 1
 SELECT_STL_HOST, SELECT_DEVICE, SELECT_STABLE = 0, 1, 2
 BATCH_EXCLUSIVE, BATCH_SHARED = 0, 1
 ABI_VERSION = 5                                     # VS_ABI_VERSION of include/vs_amd.h
@@ -212,6 +213,8 @@ SIGNATURES = {
     "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(RollingParams),
                                     _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_remap_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_resize_taps": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "vs_bgr_resize_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _i32, _vp]),
     "vs_ycbcr_to_bgr_batch": (_i32, [_YP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_to_ycbcr_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _YP, _i32, _vp]),
     "vs_stabilizer_process_batch_ycbcr": (_i32, [_vp, _YP, _i32, _i32, _i32, _i32, _i32, _YP, C.POINTER(C.c_int32), _IP, _IP]),
@@ -263,6 +266,8 @@ SIGNATURES = {
     "vs_stabilizer_get_scene_cuts": (_i32, [_vp, C.POINTER(C.c_int64), _i32]),
     "vs_stabilizer_set_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
     "vs_stabilizer_get_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
+    "vs_stabilizer_set_output_size": (_i32, [_vp, _i32, _i32, _i32]),
+    "vs_stabilizer_get_output_size": (_i32, [_vp, _IP, _IP, _IP]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_inpaint": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
@@ -948,6 +953,35 @@ def remap_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, map_ptr, map_s
                                     MEM_DEVICE, C.c_void_p(stream) if stream else None))
 
 
+# ---- resize (include/vs_amd.h: THE RESIZE RULE; the tables: csrc/vs_resize.hpp) ----
+def resize_taps(s, d, filter=RESIZE_LINEAR):
+    """one axis' tap table on the host (include/vs_amd.h: vs_resize_taps, no device needed) -> (i0 (d,), n (d,), wt (d, 10) uint16)"""
+    i0, n, wt = np.zeros(max(d, 1), np.int32), np.zeros(max(d, 1), np.int32), np.zeros((max(d, 1), 10), np.uint16)
+    _check(lib().vs_resize_taps(int(s), int(d), int(filter), _p(i0), _p(n), _p(wt)))
+    return i0, n, wt
+
+
+def resize_batch(src, dw, dh, filter=RESIZE_LINEAR, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """resize by THE RESIZE RULE (include/vs_amd.h: vs_bgr_resize_batch).  src (n,sh,sw,3) numpy -> (n, dh, dw, 3).  src_stride / dst_stride
+    (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer is
+    returned as well"""
+    src = np.ascontiguousarray(src)
+    n, sh, sw, c = src.shape
+    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
+    ss = sw * c if src_stride is None else src_stride
+    ds = dw * c if dst_stride is None else dst_stride
+    out = np.full((n, dh, ds), 0 if guard is None else guard, src.dtype)
+    _check(lib().vs_bgr_resize_batch(_p(_pitched(src, ss)), sh * ss, n, sw, sh, ss, fmt, int(filter), _p(out), dh * ds, dw, dh, ds, MEM_HOST, None))
+    res = np.ascontiguousarray(out[:, :, :dw * c]).reshape(n, dh, dw, c)
+    return (res, out) if guard is not None else res
+
+
+def resize_batch_device(src_ptr, src_fs, n, sw, sh, src_stride, fmt, filter, dst_ptr, dst_fs, dw, dh, dst_stride, stream=None):
+    """device-resident form: frames in device memory, frame strides and row strides in elements, enqueue only"""
+    _check(lib().vs_bgr_resize_batch(_p(src_ptr), src_fs, n, sw, sh, src_stride, fmt, int(filter), _p(dst_ptr), dst_fs, dw, dh, dst_stride, MEM_DEVICE,
+                                     C.c_void_p(stream) if stream else None))
+
+
 # ---- YCbCr frames (include/vs_amd.h: vs_ycbcr_to_bgr_batch; the rule: csrc/vs_ycbcr.hpp) ----
 def chroma_shape(w, h, sub):
     """(cw, ch) of a w x h frame's chroma planes under sub = (sub_x, sub_y)"""
@@ -1488,7 +1522,7 @@ class Stabilizer:
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
-                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, sharpen=None, **params):
+                 deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, sharpen=None, output_size=None, **params):
         self.params = stabilizer_params(**params)
         self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
         if not self.h:
@@ -1515,6 +1549,27 @@ class Stabilizer:
             self.set_scene_cut(scene_params() if scene_cut is True else scene_cut)
         if sharpen is not None:
             self.set_sharpen(sharpen_params() if sharpen is True else sharpen)
+        if output_size is not None:
+            self.set_output_size(*output_size)
+
+    def set_output_size(self, dw, dh, filter=RESIZE_LINEAR):
+        """(0, 0): off, the crop window is delivered; (-1, -1): every frame is delivered at the source frame's size; (dw, dh): at that size --
+        the window resized by THE RESIZE RULE behind every other pass (filter: RESIZE_LINEAR / RESIZE_AREA)"""
+        _check(lib().vs_stabilizer_set_output_size(self.h, int(dw), int(dh), int(filter)))
+
+    def get_output_size(self):
+        """None (off) or (dw, dh, filter) as set"""
+        dw, dh, f = C.c_int(), C.c_int(), C.c_int()
+        on = _check(lib().vs_stabilizer_get_output_size(self.h, C.byref(dw), C.byref(dh), C.byref(f)))
+        return (dw.value, dh.value, f.value) if on else None
+
+    def delivered_size(self, w, h):
+        """(width, height) of what a call with w x h frames delivers: the crop window, or the output size where one is set"""
+        c = max(self.params.crop_pixels, 0)
+        size = self.get_output_size()
+        if size is None:
+            return w - 2 * c, h - 2 * c
+        return (w, h) if size[0] < 0 else (size[0], size[1])
 
     def set_sharpen(self, params):
         """None: off; a SharpenParams (sharpen_params()): every output window is sharpened behind the warp by the phase of its own correction
@@ -1622,8 +1677,8 @@ class Stabilizer:
         frame = np.ascontiguousarray(frame)
         fmt = _fmt_of(frame.dtype, frame.ndim) if fmt is None else fmt
         hh, ww = frame.shape[:2]
-        c = max(self.params.crop_pixels, 0)
-        out = np.empty((hh - 2 * c, ww - 2 * c, 3), frame.dtype)
+        dw, dh = self.delivered_size(ww, hh)
+        out = np.empty((dh, dw, 3), frame.dtype)
         ow, oh = C.c_int(), C.c_int()
         r = _check(lib().vs_stabilizer_process(self.h, _p(frame), ww, hh, ww * 3, fmt, MEM_HOST, _p(out), C.byref(ow), C.byref(oh)))
         return out if r == 1 else None
@@ -1640,10 +1695,10 @@ class Stabilizer:
         frames = np.ascontiguousarray(frames)
         n, hh, ww = frames.shape[:3]
         fmt = _fmt_of(frames.dtype, 3) if fmt is None else fmt
-        c = max(self.params.crop_pixels, 0)
+        dw, dh = self.delivered_size(ww, hh)
         if out is None:
-            out = np.zeros((n, hh - 2 * c, ww - 2 * c, 3), frames.dtype)
-        assert out.shape == (n, hh - 2 * c, ww - 2 * c, 3) and out.dtype == frames.dtype and out.flags.c_contiguous
+            out = np.zeros((n, dh, dw, 3), frames.dtype)
+        assert out.shape == (n, dh, dw, 3) and out.dtype == frames.dtype and out.flags.c_contiguous
         has = (C.c_int32 * n)()
         ow, oh = C.c_int(), C.c_int()
         _check(lib().vs_stabilizer_process_batch(self.h, _p(frames), hh * ww * 3, n, ww, hh, ww * 3, fmt, MEM_HOST, _p(out),
@@ -1651,12 +1706,12 @@ class Stabilizer:
         return out, list(has)
 
     def process_batch_device(self, ptr, n, w, h, fmt, out_ptr):
-        """dense device-resident frames in, dense cropped frames out (raw device pointers)"""
-        c = max(self.params.crop_pixels, 0)
+        """dense device-resident frames in, dense delivered frames out (raw device pointers)"""
+        dw, dh = self.delivered_size(w, h)
         has = (C.c_int32 * n)()
         ow, oh = C.c_int(), C.c_int()
         r = _check(lib().vs_stabilizer_process_batch(self.h, _p(ptr), h * w * 3, n, w, h, w * 3, fmt, MEM_DEVICE, _p(out_ptr),
-                                                     (h - 2 * c) * (w - 2 * c) * 3, has, C.byref(ow), C.byref(oh)))
+                                                     dh * dw * 3, has, C.byref(ow), C.byref(oh)))
         return r, list(has)
 
     def process_batch_ycbcr(self, y, cb=None, cr=None, sub=(1, 1), fmt=None, interleaved=None, out_sub=None, out_interleaved="same", out_mono=None,
@@ -1667,15 +1722,15 @@ class Stabilizer:
         y = np.ascontiguousarray(y)
         n, hh, ww = y.shape
         fmt = _fmt_of(y.dtype, 3) if fmt is None else fmt
-        c = max(self.params.crop_pixels, 0)
+        dw, dh = self.delivered_size(ww, hh)
         src = _HostPlanes(n, ww, hh, y.dtype, sub, interleaved, cb is None, None, None, 0)
         src.put(y, cb, cr)
-        dst = _HostPlanes(n, ww - 2 * c, hh - 2 * c, y.dtype, sub if out_sub is None else out_sub, interleaved if out_interleaved == "same" else out_interleaved,
+        dst = _HostPlanes(n, dw, dh, y.dtype, sub if out_sub is None else out_sub, interleaved if out_interleaved == "same" else out_interleaved,
                           (cb is None) if out_mono is None else out_mono, None, None, 0 if guard is None else guard)
         has = (C.c_int32 * n)()
         ow, oh = C.c_int(), C.c_int()
         _check(lib().vs_stabilizer_process_batch_ycbcr(self.h, C.byref(src.desc), n, ww, hh, fmt, MEM_HOST, C.byref(dst.desc), has, C.byref(ow), C.byref(oh)))
-        assert (ow.value, oh.value) == (ww - 2 * c, hh - 2 * c)
+        assert (ow.value, oh.value) == (dw, dh)
         return dst.get(), list(has)
 
     def process_batch_ycbcr_device(self, planes, n, w, h, fmt, out_planes):
@@ -1690,8 +1745,8 @@ class Stabilizer:
         frames = np.ascontiguousarray(frames)
         n, hh, ww = frames.shape[:3]
         fmt = _fmt_of(frames.dtype, 3) if fmt is None else fmt
-        c = max(self.params.crop_pixels, 0)
-        out = np.zeros((n, hh - 2 * c, ww - 2 * c, 3), frames.dtype)
+        dw, dh = self.delivered_size(ww, hh)
+        out = np.zeros((n, dh, dw, 3), frames.dtype)
         has = (C.c_int32 * n)()
         ow, oh = C.c_int(), C.c_int()
         _check(lib().vs_stabilizer_process_clips(self.h, _p(frames), hh * ww * 3, n_clips, n // n_clips, ww, hh, ww * 3, fmt, MEM_HOST,
@@ -1699,12 +1754,12 @@ class Stabilizer:
         return out, list(has)
 
     def process_clips_device(self, ptr, n_clips, frames_per_clip, w, h, fmt, out_ptr):
-        c = max(self.params.crop_pixels, 0)
+        dw, dh = self.delivered_size(w, h)
         n = n_clips * frames_per_clip
         has = (C.c_int32 * n)()
         ow, oh = C.c_int(), C.c_int()
         r = _check(lib().vs_stabilizer_process_clips(self.h, _p(ptr), h * w * 3, n_clips, frames_per_clip, w, h, w * 3, fmt, MEM_DEVICE,
-                                                     _p(out_ptr), (h - 2 * c) * (w - 2 * c) * 3, has, C.byref(ow), C.byref(oh)))
+                                                     _p(out_ptr), dh * dw * 3, has, C.byref(ow), C.byref(oh)))
         return r, list(has)
 
     def state(self):

@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../libvs_amd.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 ${VS_EXTRA_FLAGS:-} -O3 ${VS_RESOURCE_REPORT:+-Rpass-analysis=kernel-resource-usage} -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result"
-SRCS="vs_kernels.hip vs_warp.hip vs_fill.hip vs_inpaint.hip vs_deblur.hip vs_denoise.hip vs_rolling.hip vs_remap.hip vs_ycbcr.hip vs_deflicker.hip vs_scene.hip vs_fidelity.hip vs_sharpen.hip vs_phase.hip vs_flow.hip vs_runtime.hip vs_capi.hip vs_capi_warp.hip vs_capi_lookahead.hip vs_capi_ycbcr.hip vs_capi_fidelity.hip vs_engine.hip vs_stabilizer.hip vs_host.cpp"
+SRCS="vs_kernels.hip vs_warp.hip vs_fill.hip vs_inpaint.hip vs_deblur.hip vs_denoise.hip vs_rolling.hip vs_remap.hip vs_ycbcr.hip vs_resize.hip vs_deflicker.hip vs_scene.hip vs_fidelity.hip vs_sharpen.hip vs_phase.hip vs_flow.hip vs_runtime.hip vs_capi.hip vs_capi_warp.hip vs_capi_lookahead.hip vs_capi_ycbcr.hip vs_capi_resize.hip vs_capi_fidelity.hip vs_engine.hip vs_stabilizer.hip vs_host.cpp"
 mkdir -p "$HERE/build"
 objs=""
 pids=""

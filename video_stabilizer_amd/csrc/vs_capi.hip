@@ -31,6 +31,7 @@ extern "C" int vs_bounds_fetch_sharpen(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_rolling(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_remap(unsigned out[8], int reset);
 extern "C" int vs_bounds_fetch_ycbcr(unsigned out[8], int reset);
+extern "C" int vs_bounds_fetch_resize(unsigned out[8], int reset);
 VS_BOUNDS_TU(vs_bounds_fetch_capi)
 namespace {
 // the checker checked: element 11 of an 8-element LDS array through a Span -- reported under site 900, executed on element 0
@@ -45,7 +46,7 @@ __global__ void vs_k_bounds_selftest(int* out) {
 const struct { int (*fetch)(unsigned*, int); const char* name; } kBoundsUnits[] = {
     {vs_bounds_fetch_engine, "vs_engine.hip"}, {vs_bounds_fetch_warp, "vs_warp.hip"}, {vs_bounds_fetch_phase, "vs_phase.hip"}, {vs_bounds_fetch_flow, "vs_flow.hip"},
     {vs_bounds_fetch_fill, "vs_fill.hip"}, {vs_bounds_fetch_deblur, "vs_deblur.hip"}, {vs_bounds_fetch_denoise, "vs_denoise.hip"},
-    {vs_bounds_fetch_deflicker, "vs_deflicker.hip"}, {vs_bounds_fetch_scene, "vs_scene.hip"}, {vs_bounds_fetch_fidelity, "vs_fidelity.hip"}, {vs_bounds_fetch_sharpen, "vs_sharpen.hip"}, {vs_bounds_fetch_rolling, "vs_rolling.hip"}, {vs_bounds_fetch_remap, "vs_remap.hip"}, {vs_bounds_fetch_ycbcr, "vs_ycbcr.hip"}, {vs_bounds_fetch_inpaint, "vs_inpaint.hip"}, {vs_bounds_fetch_capi, "vs_capi.hip"}};
+    {vs_bounds_fetch_deflicker, "vs_deflicker.hip"}, {vs_bounds_fetch_scene, "vs_scene.hip"}, {vs_bounds_fetch_fidelity, "vs_fidelity.hip"}, {vs_bounds_fetch_sharpen, "vs_sharpen.hip"}, {vs_bounds_fetch_rolling, "vs_rolling.hip"}, {vs_bounds_fetch_remap, "vs_remap.hip"}, {vs_bounds_fetch_ycbcr, "vs_ycbcr.hip"}, {vs_bounds_fetch_resize, "vs_resize.hip"}, {vs_bounds_fetch_inpaint, "vs_inpaint.hip"}, {vs_bounds_fetch_capi, "vs_capi.hip"}};
 }  // namespace
 #endif
 

@@ -125,7 +125,9 @@ int vs_stabilizer_process_batch_ycbcr(vs_stabilizer* s, const vs_ycbcr_planes* f
     VS_TRY(mem_ok(__func__, mem));
     const int crop = stab_crop(s);
     VS_ARG(w > 2 * crop && h > 2 * crop);
-    const int ow = w - 2 * crop, oh = h - 2 * crop;
+    int ow = 0, oh = 0;                                    // the delivered size: the crop window, or the handle's output size
+    stab_delivered_size(s, w, h, &ow, &oh);
+    VS_ARG(ow >= 1 && oh >= 1);
     VS_TRY(ycbcr_args_ok(__func__, out, n, ow, oh, format));
     if (!device_ready()) return VS_ERR_HIP;
     VS_HIP(hipSetDevice(stab_device(s)));

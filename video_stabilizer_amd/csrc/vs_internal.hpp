@@ -215,6 +215,7 @@ struct YcbcrHold { void* buf[2] = {nullptr, nullptr}; size_t bytes[2] = {0, 0}; 
 YcbcrHold* stab_ycbcr_hold(vs_stabilizer* s);
 int stab_crop(const vs_stabilizer* s);      // max(crop_pixels, 0)
 int stab_device(const vs_stabilizer* s);
+void stab_delivered_size(const vs_stabilizer* s, int w, int h, int* dw, int* dh);   // what a call with w x h frames delivers (vs_stabilizer_set_output_size)
 // Set by the engine around warp launches that run beside the NEXT group's alignment (vs_stabilizer_process_batch / _clips, overlapped): the small-footprint
 // solver build moves into a CU as soon as ONE warp workgroup leaves it, which needs the warp's workgroup to hold at least the solver's 35 KB of LDS -- the
 // standard 31 KB window does (with the CU's slack), the COMPACT six-wave instantiation's 26 KB does not (c5: 20.3 k -> 18.4 k frames/s with it).  Thread-local:

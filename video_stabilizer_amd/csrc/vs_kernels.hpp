@@ -120,6 +120,15 @@ hipError_t lens_map(const vs_lens_params& p, int w, int h, int32_t* map, int map
 // one chroma cell per lane otherwise: the same bits.
 hipError_t ycbcr_to_bgr(const vs_ycbcr_planes& src, int n_frames, int w, int h, int bits, int max_value, void* dst, size_t dst_fs, int dst_stride, hipStream_t s);
 hipError_t bgr_to_ycbcr(const void* src, size_t src_fs, int n_frames, int w, int h, int src_stride, int bits, int max_value, const vs_ycbcr_planes& dst, hipStream_t s);
+// Resize by THE RESIZE RULE (vs_resize.hip: the sample rule and the kernels; vs_resize.hpp: the tap tables).  n_frames sw x sh frames -> n_frames
+// dw x dh frames; filter: VS_RESIZE_*; tables: resize_table_ints(dw, dh) ints of device scratch, written on `s` in front of the frames' launch
+// and read by it.  form: which kernel -- both give the same bits; kResizeAuto: the tiled form where the frame grows in height (dh > sh: destination
+// rows share source rows, which the tile forms H of once), the direct form otherwise (measured both ways: DESIGN.md section 30).  A shape
+// vsr::resize_params_valid refuses: hipErrorNotSupported.
+constexpr int kResizeAuto = -1, kResizeTiled = 0, kResizeDirect = 1;
+size_t resize_table_ints(int dw, int dh);
+hipError_t bgr_resize(const void* src, size_t src_fs, int n_frames, int sw, int sh, int src_stride, int bits, int max_value, int filter, int* tables,
+                      void* dst, size_t dst_fs, int dw, int dh, int dst_stride, int form, hipStream_t s);
 // Deflicker (vs_deflicker.hip: the rule and the kernels).  exposure_stats: cands_dev = n_frames x n_cand entries in device memory (entry 0 of a
 // frame is the target, a null frame ends the list); stats = n_frames x n_cand x 8 words in device memory, zeroed on `s` first.  exposure_gains:
 // gains[4 o + {0..2: G_c, 3: m}] from the statistics.  bgr_gain: frame i scaled by gains[4 i ..] (clamped to 16384 .. 65536); dst may be src.

@@ -106,7 +106,18 @@ struct PassConfig {
     bool lens_on = false;          // vs_stabilizer_set_lens: NULL or the identity lens: off
     vs_lens_params lens{};
     int lens_w = 0, lens_h = 0;    // the frame size the lens was calibrated for; frames of another size are refused while the pass is on
+    int out_w = 0, out_h = 0;      // vs_stabilizer_set_output_size: (0, 0) off -- the window is delivered; (-1, -1) the source frame's size; else the size
+    int out_filter = VS_RESIZE_LINEAR;   // ... and the resize's filter
 };
+// What a call delivers: the crop window (w - 2 crop) x (h - 2 crop) as it is, or resized (vs_resize.hip) to the size the handle was given.
+// resize: the pass runs -- a window that already has the requested size is delivered as it is, launch for launch the handle with the pass off.
+struct Delivery { int w, h; bool resize; };
+inline Delivery delivered_size(int w, int h, int crop, const PassConfig& c) {
+    const int ow = w - 2 * crop, oh = h - 2 * crop;
+    if (c.out_w == 0 && c.out_h == 0) return Delivery{ow, oh, false};
+    const int dw = c.out_w < 0 ? w : c.out_w, dh = c.out_h < 0 ? h : c.out_h;
+    return Delivery{dw, dh, dw != ow || dh != oh};
+}
 // The candidates of each look-ahead list beyond the frame itself, for a handle of this lag and warp mode.  blend_on: the fill's blend rule
 // runs; want_sums: the frames' channel sums are measured and travel with the fill's candidates.
 struct PassPlan { int fill, deblur, denoise, deflicker, rolling; bool blend_on, want_sums; };

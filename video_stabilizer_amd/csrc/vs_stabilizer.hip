@@ -11,6 +11,7 @@
 #include "vs_stab_step.hpp"
 #include "vs_kernels.hpp"
 #include "vs_lens.hpp"
+#include "vs_resize.hpp"
 
 #include <algorithm>
 #include <array>
@@ -47,6 +48,7 @@ struct vs_stabilizer {
     Scratch flicker_buf;           // deflicker: the pair statistics and, behind them, the gains of the current call's output frames
     Scratch inpaint_buf;           // one group of frames: their open counts, their coverage indices, their pyramids
     Scratch sharpen_buf;           // one group of output windows as the warp (fill, inpaint) leaves them: the sharpen's source
+    Scratch resize_buf;            // output size set: one group of output windows as the passes leave them, the resize's source
     Scratch scene_prev;            // scene cuts, lag == 0: nothing is queued, so the last frame of a call waits here for the next call's first pair
     bool scene_prev_valid = false;
     Scratch batch_in;              // dense device copy of the current batch (lens correction on: the chunk's frames land there corrected)
@@ -56,8 +58,8 @@ struct vs_stabilizer {
     // PITCHED host frames travel as ONE linear copy of their whole span (gaps included) into a device area and are made dense by device-to-device
     // 2-D copies: the HIP runtime never gets a 2-D copy out of pageable caller memory (profiles/r06_flake.md); dense frames: one linear copy as ever
     Scratch span_in[2];
-    std::array<Scratch*, 13> scratch() {
-        return {&deblur_buf, &denoise_buf, &rolling_buf, &lens_map, &flicker_buf, &inpaint_buf, &sharpen_buf, &scene_prev, &batch_in, &batch_out[0],
+    std::array<Scratch*, 14> scratch() {
+        return {&deblur_buf, &denoise_buf, &rolling_buf, &lens_map, &flicker_buf, &inpaint_buf, &sharpen_buf, &resize_buf, &scene_prev, &batch_in, &batch_out[0],
                 &batch_out[1], &span_in[0], &span_in[1]};
     }
     std::deque<int> meas_cut;      // the cut flag of every entry of `measurements` (vs_stab_step.hpp: stab_step_cut); all zero while detection is off
@@ -155,6 +157,10 @@ namespace vsi {
 YcbcrHold* stab_ycbcr_hold(vs_stabilizer* s) { return &s->ycbcr; }
 int stab_crop(const vs_stabilizer* s) { return s->params.crop_pixels > 0 ? s->params.crop_pixels : 0; }
 int stab_device(const vs_stabilizer* s) { return aligner_device(s->aligner); }
+void stab_delivered_size(const vs_stabilizer* s, int w, int h, int* dw, int* dh) {
+    const Delivery d = delivered_size(w, h, stab_crop(s), s->cfg);
+    *dw = d.w; *dh = d.h;
+}
 }  // namespace vsi
 
 // One vs_stabilizer_process_batch / _clips call, or a run of its frames; strides in elements.  clip_len > 0: the n frames are n / clip_len
@@ -193,7 +199,7 @@ static hipError_t make_dense(vs_stabilizer* s, const StabCall& c, bool dense, in
     return e;
 }
 
-// The outputs of input frames idx[0], idx[1], .. lie dense in `area`, obytes each; down to the caller's frames on `st`, runs that are contiguous on
+// The outputs of input frames idx[0], idx[1], .. lie dense in `area`, obytes (a delivered frame) each; down to the caller's frames on `st`, runs that are contiguous on
 // both sides as one copy.
 static hipError_t copy_outputs_down(const StabCall& c, const std::vector<int>& idx, const uint8_t* area, size_t obytes, hipStream_t st) {
     const bool dense_out = c.out_frame_stride * c.esz() == obytes;
@@ -242,8 +248,10 @@ struct Chunk {
     bool threaded_download;        // ... with a downloader thread of their own, under the next chunk's compute
     bool to_host, warps_apart;     // the outputs go to host memory (a chunk of the pipelined host batch too); the warps go to warp_stream
     hipStream_t st, ws;            // the handle's stream; the stream of the passes and the warps
-    int crop, ow, oh, w = c.w, h = c.h, fbits = vs_format_bits(c.format), bits = fbits > 8 ? 16 : 8;
-    size_t fbytes = c.fbytes(), obytes = (size_t)ow * oh * 3 * c.esz();
+    int crop, ow, oh;              // the crop window: what the warp, the fill, the inpaint, the sharpen and the deflicker's gain work on
+    int dw, dh; bool resize_on;    // the delivered frame (vs_stab_plan.hpp: delivered_size): the window, or the window resized behind everything
+    int w = c.w, h = c.h, fbits = vs_format_bits(c.format), bits = fbits > 8 ? 16 : 8;
+    size_t fbytes = c.fbytes(), obytes = (size_t)ow * oh * 3 * c.esz(), dbytes = (size_t)dw * dh * 3 * c.esz();
     const uint8_t* dense = nullptr; bool already_dense = false;   // the chunk's frames, dense, in device memory; ... where the caller has them
     SharpBlock *sblk = nullptr, *mblk = nullptr;   // the sharpness of the chunk's frames (deblur on); their channel sums (fill with exposure match)
     bool blend_on = false, want_sums = false;
@@ -494,7 +502,7 @@ struct Chunk {
                 const hipError_t de = s->down[slot].get();
                 if (de != hipSuccess) return set_error(VS_ERR_HIP, "output download failed: %s", hipGetErrorString(de));
             }
-            VS_HIP(s->batch_out[slot].grow(obytes * jobs.size()));
+            VS_HIP(s->batch_out[slot].grow(dbytes * jobs.size()));
         }
         const size_t fs = (size_t)w * h * 3;
         // every due frame is deblurred into a scratch frame of its own
@@ -583,20 +591,28 @@ struct Chunk {
             max_group = scratch_group(max_group, scratch_budget("VS_TEST_SHARPEN_SCRATCH_BYTES", kSharpenScratch), obytes);
             VS_HIP(s->sharpen_buf.grow(max_group * obytes, ws, true));
         }
+        // Output size set: the group's windows, as every pass above leaves them, lie dense in resize_buf, and the resize writes the delivered
+        // frames to where the windows went before -- last on the run's stream.  The same grouping rule and budget as the sharpen's scratch.
+        if (resize_on && !jobs.empty()) {
+            max_group = scratch_group(max_group, scratch_budget("VS_TEST_RESIZE_SCRATCH_BYTES", kResizeScratch), obytes);
+            VS_HIP(s->resize_buf.grow(max_group * obytes, ws, true));
+        }
         for (size_t j = 0, e; j < jobs.size(); j = e) {
             e = run_end(jobs, j, fbytes);
             ts.clear();
             for (size_t q = j; q < e; q++) ts.push_back(jobs[q].sampling);
-            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot].p + j * obytes) : (void*)c.out_frame(jobs[j].i);
-            const size_t dst_fs = to_host ? (size_t)ow * oh * 3 : c.out_frame_stride;
-            // (sharpen off: one group, the run itself, written where it always went)
+            void* dst = to_host ? (void*)((uint8_t*)s->batch_out[slot].p + j * dbytes) : (void*)c.out_frame(jobs[j].i);
+            const size_t dst_fs = to_host ? (size_t)dw * dh * 3 : c.out_frame_stride;
+            // (sharpen and resize off: one group, the run itself, written where it always went)
             const size_t group = std::min(e - j, max_group);
             for (size_t g = j, ge; g < e; g = ge) {
                 ge = std::min(e, g + group);
                 const int m = (int)(ge - g);
-                void* const out = (uint8_t*)dst + (g - j) * dst_fs * c.esz();
+                void* const delivered = (uint8_t*)dst + (g - j) * dst_fs * c.esz();
+                void* const out = resize_on ? s->resize_buf.p : delivered;          // the group's windows
+                const size_t out_fs = resize_on ? (size_t)ow * oh * 3 : dst_fs;
                 void* const wdst = s->cfg.sharpen_on ? s->sharpen_buf.p : out;
-                const size_t wfs = s->cfg.sharpen_on ? (size_t)ow * oh * 3 : dst_fs;
+                const size_t wfs = s->cfg.sharpen_on ? (size_t)ow * oh * 3 : out_fs;
                 if (nfill > 0)     // the same warp launch, then the fill pass over the uncovered rim on the same stream
                     VS_TRY(vsi::bgr_warp_fill_ptrs(jobs[g].src, (size_t)w * h * 3, m, w, h, w * 3, bits, 1 + nfill, &fill.src[g * (1 + nfill)],
                                                    &fill.t[g * (1 + nfill)], s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, ws,
@@ -606,15 +622,17 @@ struct Chunk {
                                                        s->params.warp_border, max_value, crop, crop, ow, oh, wdst, wfs, ow * 3, VS_MEM_DEVICE, ws));
                 if (s->cfg.inpaint) VS_TRY(inpaint_run(g, ge, wdst, wfs));
                 if (s->cfg.sharpen_on)
-                    VS_TRY(vsi::bgr_sharpen_ptrs(wdst, wfs, m, w, h, c.format, &ts[g - j], &s->cfg.sharpen, crop, crop, ow, oh, ow * 3, out, dst_fs, ow * 3, ws));
+                    VS_TRY(vsi::bgr_sharpen_ptrs(wdst, wfs, m, w, h, c.format, &ts[g - j], &s->cfg.sharpen, crop, crop, ow, oh, ow * 3, out, out_fs, ow * 3, ws));
                 // deflicker: the group's output windows scaled in place by their frames' gains, last on the run's stream (in front of any download)
                 if (fk.n > 0)
-                    VS_HIP(vsk::bgr_gain(out, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * g, out, ow * 3, m, dst_fs, dst_fs, ws));
+                    VS_HIP(vsk::bgr_gain(out, ow, oh, ow * 3, bits, max_value, fk_gains + 4 * g, out, ow * 3, m, out_fs, out_fs, ws));
+                if (resize_on)
+                    VS_TRY(vs_bgr_resize_batch(out, out_fs, m, ow, oh, ow * 3, c.format, s->cfg.out_filter, delivered, dst_fs, dw, dh, dw * 3, VS_MEM_DEVICE, ws));
             }
         }
         return VS_OK;
     }
-    static constexpr size_t kSharpenScratch = (size_t)256 << 20;
+    static constexpr size_t kSharpenScratch = (size_t)256 << 20, kResizeScratch = (size_t)256 << 20;
 
     // the buffers of ours that the jobs' frames lay in are free again: read on warp_stream and refilled on st, they wait for that stream's
     // synchronisation; else they are reused only by later work on this stream
@@ -629,11 +647,11 @@ struct Chunk {
         std::vector<int> idx(jobs.size());
         for (size_t j = 0; j < jobs.size(); j++) idx[j] = jobs[j].i;
         const uint8_t* area = (const uint8_t*)s->batch_out[slot].p;
-        if (!threaded_download) { VS_HIP(copy_outputs_down(c, idx, area, obytes, st)); return VS_OK; }
+        if (!threaded_download) { VS_HIP(copy_outputs_down(c, idx, area, dbytes, st)); return VS_OK; }
         if (!s->down_stream) VS_HIP(hipStreamCreateWithFlags(&s->down_stream, hipStreamNonBlocking));
         if (!s->down_ev[slot]) VS_HIP(hipEventCreateWithFlags(&s->down_ev[slot], hipEventDisableTiming));
         VS_HIP(hipEventRecord(s->down_ev[slot], st));
-        s->down[slot] = run_async([call = c, idx, area, obytes = obytes, device = vsi::aligner_device(s->aligner), ds = s->down_stream, ev = s->down_ev[slot]]() -> hipError_t {
+        s->down[slot] = run_async([call = c, idx, area, obytes = dbytes, device = vsi::aligner_device(s->aligner), ds = s->down_stream, ev = s->down_ev[slot]]() -> hipError_t {
             hipError_t e = hipSetDevice(device);
             if (e == hipSuccess) e = hipStreamWaitEvent(ds, ev, 0);
             if (e == hipSuccess) e = copy_outputs_down(call, idx, area, obytes, ds);
@@ -667,7 +685,8 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
     const int w = c.w, h = c.h, crop = s->params.crop_pixels > 0 ? s->params.crop_pixels : 0;
     VS_ARG(w > 2 * crop && h > 2 * crop);
     const int ow = w - 2 * crop, oh = h - 2 * crop, lag = s->params.lag;
-    VS_ARG(c.n == 1 || (c.frame_stride >= (size_t)(h - 1) * c.stride + (size_t)3 * w && c.out_frame_stride >= (size_t)ow * oh * 3));
+    const Delivery dl = delivered_size(w, h, crop, s->cfg);
+    VS_ARG(c.n == 1 || (c.frame_stride >= (size_t)(h - 1) * c.stride + (size_t)3 * w && c.out_frame_stride >= (size_t)dl.w * dl.h * 3));
     VS_HIP(hipSetDevice(vsi::aligner_device(s->aligner)));
     if (s->w != w || s->h != h || s->fmt != c.format) {
         // a size change restarts the aligner (alignment.cpp:155).  The reference would go on warping queued frames of the
@@ -677,11 +696,11 @@ static int stab_chunk(vs_stabilizer* s, const StabCall& c, int out_mem, int slot
         VS_TRY(vs_stabilizer_reset(s));
         s->w = w; s->h = h; s->fmt = c.format; s->frame_bytes = c.fbytes();
     }
-    *c.out_w = ow; *c.out_h = oh;
+    *c.out_w = dl.w; *c.out_h = dl.h;
 
     const bool to_host = out_mem == VS_MEM_HOST, warps_apart = s->overlap_warps && !to_host;
     hipStream_t st = (hipStream_t)vs_aligner_stream(s->aligner);
-    Chunk k{s, c, std::max(slot_arg, 0), slot_arg >= 0, to_host, warps_apart, st, warps_apart ? s->warp_stream : st, crop, ow, oh};
+    Chunk k{s, c, std::max(slot_arg, 0), slot_arg >= 0, to_host, warps_apart, st, warps_apart ? s->warp_stream : st, crop, ow, oh, dl.w, dl.h, dl.resize};
     const PassPlan pp = plan_passes(s->cfg, lag, s->params.warp_mode);
     k.fill.n = pp.fill; k.db.n = pp.deblur; k.dn.n = pp.denoise; k.fk.n = pp.deflicker; k.rs.n = pp.rolling;
     k.blend_on = pp.blend_on; k.want_sums = pp.want_sums;
@@ -792,6 +811,19 @@ static int stab_run(vs_stabilizer* s, const StabCall& c) {
     // the lens was calibrated for one frame size: another one is refused before any work, and leaves the handle as it is
     if (s->cfg.lens_on && (c.w != s->cfg.lens_w || c.h != s->cfg.lens_h))
         return set_error(VS_ERR_ARG, "bad argument: lens correction is set for %d x %d frames, this call brings %d x %d (vs_stabilizer_set_lens)", s->cfg.lens_w, s->cfg.lens_h, c.w, c.h);
+    // an output size the resize cannot reach from this call's window is refused before any work, and leaves the handle as it is
+    const int crop = vsi::stab_crop(s);
+    if (c.w > 2 * crop && c.h > 2 * crop && c.w <= 65535 && c.h <= 65535) {
+        const Delivery dl = delivered_size(c.w, c.h, crop, s->cfg);
+        const int ow = c.w - 2 * crop, oh = c.h - 2 * crop;
+        if (dl.resize && !vsr::resize_params_valid(ow, oh, dl.w, dl.h, s->cfg.out_filter)) {
+            if (dl.w > vsr::kMaxExtent || dl.h > vsr::kMaxExtent || ow > vsr::kMaxExtent || oh > vsr::kMaxExtent)
+                return set_error(VS_ERR_UNSUPPORTED, "output size: windows and delivered frames up to 32767 x 32767 (vs_stabilizer_set_output_size)");
+            const bool on_x = !vsr::resize_axis_valid(ow, dl.w, s->cfg.out_filter);
+            return set_error(VS_ERR_UNSUPPORTED, "output size: VS_RESIZE_AREA needs delivered <= window <= 8 delivered on the %s axis, the window is %d x %d, the output size %d x %d (vs_stabilizer_set_output_size)",
+                             on_x ? "x" : "y", ow, oh, dl.w, dl.h);
+        }
+    }
     // how the call is cut, its thresholds and the numbers they were measured with: pick_route (vs_stab_plan.hpp)
     const StabRoute route = pick_route(RouteIn{c.mem, c.n, c.clip_len, c.w, c.h, c.fbytes(), c.dense(), s->cfg.lens_on, s->params.warp_mode, vsi::ingest_chunk_bytes()},
                                        stab_knobs());
@@ -967,6 +999,18 @@ int vs_stabilizer_get_lens(const vs_stabilizer* s, vs_lens_params* params, int* 
     *w = s->cfg.lens_on ? s->cfg.lens_w : 0; *h = s->cfg.lens_on ? s->cfg.lens_h : 0;
     if (s->cfg.lens_on) *params = s->cfg.lens; else vs_lens_params_default(params, 0, 0);
     return s->cfg.lens_on ? 1 : 0;
+} VS_CATCH_ALL
+int vs_stabilizer_set_output_size(vs_stabilizer* s, int dw, int dh, int filter) try {
+    VS_ARG(s && (filter == VS_RESIZE_LINEAR || filter == VS_RESIZE_AREA));
+    VS_ARG((dw == 0 && dh == 0) || (dw == -1 && dh == -1) || (dw >= 1 && dh >= 1));
+    if (dw > vsr::kMaxExtent || dh > vsr::kMaxExtent) return set_error(VS_ERR_UNSUPPORTED, "output size: up to 32767 x 32767, as the resize");
+    s->cfg.out_w = dw; s->cfg.out_h = dh; s->cfg.out_filter = filter;
+    return VS_OK;
+} VS_CATCH_ALL
+int vs_stabilizer_get_output_size(const vs_stabilizer* s, int* dw, int* dh, int* filter) try {
+    VS_ARG(s && dw && dh && filter);
+    *dw = s->cfg.out_w; *dh = s->cfg.out_h; *filter = s->cfg.out_filter;
+    return s->cfg.out_w != 0 ? 1 : 0;
 } VS_CATCH_ALL
 int vs_stabilizer_set_scene_cut(vs_stabilizer* s, const vs_scene_params* params) try {
     VS_ARG(s);
