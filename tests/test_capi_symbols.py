@@ -7,6 +7,8 @@ import re
 import numpy as np
 import pytest
 
+import _capi_header as H
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -33,6 +35,21 @@ def test_library_exports_every_declared_symbol(vs):
 
 def test_ctypes_table_matches_header(vs):
     assert set(vs.SIGNATURES) == _declared()
+
+
+def test_ctypes_table_matches_header_prototypes(vs):
+    """every prototype of the header against its SIGNATURES row: the return kind, the argument count and every argument's kind (pointer, int,
+    int64, size, double, float, the two by-value structs, void); an array declarator such as `float out4[4]` is a pointer.  No exceptions"""
+    protos = H.prototypes()
+    assert set(protos) == _declared() and len(protos) >= 133
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = vs.SIGNATURES[name]
+        want = (ret, [kind for _, kind in params])
+        got = (H.ctypes_kind(res, vs), [H.ctypes_kind(a, vs) for a in args])
+        if got != want:
+            wrong.append((name, "header", want, "table", got))
+    assert not wrong, wrong
 
 
 def test_no_cpu_fallback_without_device(vs):

@@ -61,7 +61,7 @@ def test_random_stabilizer_configuration_matches_the_oracle(gpu_vs, oracle, seed
     kw = dict(lag=int(rng.integers(1, 7)), smoother_memory=int(rng.integers(0, 6)), crop_pixels=crop,
               enable_smoother=int(rng.integers(0, 2)), warp_mode=int(rng.choice([gpu_vs.WARP_LANCZOS2, gpu_vs.WARP_BILINEAR, gpu_vs.WARP_LANCZOS2_FAST, gpu_vs.WARP_LANCZOS2_SEP, gpu_vs.WARP_BILINEAR_CV])),
               warp_border=int(rng.integers(0, 2)), min_disp=float(rng.choice([0.5, 2.0])), max_disp=float(rng.choice([8.0, 40.0])))
-    kw["lambda"] = float(rng.choice([0.5, 2.0, 8.0]))
+    kw["lambda_"] = float(rng.choice([0.5, 2.0, 8.0]))       # (the field's name: as "lambda" it was a plain attribute on both structs, and the default ran)
     n = 14
     frames, _ = synth.make_clip(w, h, n, seed=300 + seed, channels=3, bits=bits, jitter_t=float(rng.choice([1.0, 4.0, 12.0])))
     if rng.random() < 0.33:                                 # the documented STL-independent selection rule on both sides

@@ -5,6 +5,10 @@ into the hand-written gfx950 kernels.  There is no fallback -- a missing library
 
 numpy arrays are passed as VS_MEM_HOST; for VS_MEM_DEVICE pass raw device pointers (ints), e.g.
 torch tensors' data_ptr().
+
+The file is ordered by pass: a pass's params constructor, host form and device form lie together.  In front of the passes
+lie the structs and the SIGNATURES table, then the helpers every wrapper marshals its arguments with -- each decision is
+made in one of them, once.
 """
 import ctypes as C
 import os
@@ -134,8 +138,6 @@ class VsError(RuntimeError):
 
 
 _vp, _i32, _f32, _f64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
-_TP = C.POINTER(Transform)
-_IP = C.POINTER(C.c_int)
 
 
 class YcbcrPlanes(C.Structure):
@@ -144,10 +146,15 @@ class YcbcrPlanes(C.Structure):
                 ("y_frame_stride", _sz), ("c_frame_stride", _sz)]
 
 
-_YP = C.POINTER(YcbcrPlanes)
+# the pointer types the table repeats: int*, int32_t*, int64_t*, double*, and a pointer to each struct of the header
+_IP, _I32P, _I64P, _F64P = C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+_TP, _YP = C.POINTER(Transform), C.POINTER(YcbcrPlanes)
+_AlignerP, _StabilizerP, _FlowP = C.POINTER(AlignerParams), C.POINTER(StabilizerParams), C.POINTER(FlowParams)
+_FillBlendP, _DeblurP, _DenoiseP, _RollingP = C.POINTER(FillBlendParams), C.POINTER(DeblurParams), C.POINTER(DenoiseParams), C.POINTER(RollingParams)
+_LensP, _DeflickerP, _SceneP, _SharpenP = C.POINTER(LensParams), C.POINTER(DeflickerParams), C.POINTER(SceneParams), C.POINTER(SharpenParams)
 
-# name -> (restype, argtypes).  This table is also what tests/test_capi_symbols.py checks
-# against include/vs_amd.h.
+# name -> (restype, argtypes).  tests/test_capi_symbols.py holds every row of this table against the prototype of the same
+# name in include/vs_amd.h: the return type, the argument count and every argument's kind.
 SIGNATURES = {
     "vs_last_error": (C.c_char_p, []),
     "vs_version": (C.c_char_p, []),
@@ -157,7 +164,7 @@ SIGNATURES = {
     "vs_debug_bounds_check": (_i32, []),
     "vs_debug_bounds_selftest": (_i32, []),
     "vs_device_count": (_i32, []),
-    "vs_shader_clock_probe": (_i32, [C.c_void_p, C.POINTER(C.c_double)]),
+    "vs_shader_clock_probe": (_i32, [_vp, _F64P]),
     "vs_stream_retire": (_i32, [_vp]),
     "vs_format_bits": (_i32, [_i32]),
     "vs_format_max_value": (_i32, [_i32]),
@@ -165,8 +172,8 @@ SIGNATURES = {
     "vs_aligner_wait_stream": (_i32, [_vp, _vp]),
     "vs_stabilizer_stream": (_vp, [_vp]),
     "vs_stabilizer_wait_stream": (_i32, [_vp, _vp]),
-    "vs_aligner_params_default": (None, [C.POINTER(AlignerParams)]),
-    "vs_stabilizer_params_default": (None, [C.POINTER(StabilizerParams)]),
+    "vs_aligner_params_default": (None, [_AlignerP]),
+    "vs_stabilizer_params_default": (None, [_StabilizerP]),
     "vs_transform_inverse": (Transform, [_TP]),
     "vs_transform_compose": (Transform, [_TP, _TP]),
     "vs_transform_warp": (Point, [_TP, Point]),
@@ -197,51 +204,51 @@ SIGNATURES = {
     "vs_bgr_image_warp_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_roi_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _i32,
                                            _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
-    "vs_bgr_image_warp_fill_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32,
+    "vs_bgr_image_warp_fill_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _i32, _i32,
                                             _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_channel_sums_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
-    "vs_bgr_image_warp_fill_blend_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _vp,
-                                                  C.POINTER(FillBlendParams), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
-    "vs_deblur_params_default": (None, [C.POINTER(DeblurParams)]),
+    "vs_bgr_image_warp_fill_blend_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _vp,
+                                                  _FillBlendP, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_deblur_params_default": (None, [_DeblurP]),
     "vs_bgr_sharpness_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
-    "vs_bgr_deblur_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeblurParams),
+    "vs_bgr_deblur_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _I32P, _TP, _DeblurP,
                                    _vp, _sz, _i32, _i32, _vp]),
-    "vs_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
-    "vs_bgr_denoise_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DenoiseParams),
+    "vs_denoise_params_default": (None, [_DenoiseP]),
+    "vs_bgr_denoise_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _DenoiseP,
                                     _vp, _sz, _i32, _i32, _vp]),
-    "vs_rolling_params_default": (None, [C.POINTER(RollingParams)]),
-    "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(RollingParams),
+    "vs_rolling_params_default": (None, [_RollingP]),
+    "vs_bgr_rolling_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _RollingP,
                                     _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_remap_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_resize_taps": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
     "vs_bgr_resize_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _i32, _vp]),
     "vs_ycbcr_to_bgr_batch": (_i32, [_YP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_to_ycbcr_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _YP, _i32, _vp]),
-    "vs_stabilizer_process_batch_ycbcr": (_i32, [_vp, _YP, _i32, _i32, _i32, _i32, _i32, _YP, C.POINTER(C.c_int32), _IP, _IP]),
-    "vs_lens_params_default": (None, [C.POINTER(LensParams), _i32, _i32]),
-    "vs_lens_map": (_i32, [C.POINTER(LensParams), _i32, _i32, _vp, _i32, _i32, _vp]),
-    "vs_deflicker_params_default": (None, [C.POINTER(DeflickerParams)]),
-    "vs_bgr_exposure_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(DeflickerParams),
+    "vs_stabilizer_process_batch_ycbcr": (_i32, [_vp, _YP, _i32, _i32, _i32, _i32, _i32, _YP, _I32P, _IP, _IP]),
+    "vs_lens_params_default": (None, [_LensP, _i32, _i32]),
+    "vs_lens_map": (_i32, [_LensP, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "vs_deflicker_params_default": (None, [_DeflickerP]),
+    "vs_bgr_exposure_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _DeflickerP,
                                            _vp, _i32, _vp]),
-    "vs_exposure_gains_batch": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(DeflickerParams), _vp, _i32, _vp]),
+    "vs_exposure_gains_batch": (_i32, [_vp, _i32, _i32, _i32, _i32, _DeflickerP, _vp, _i32, _vp]),
     "vs_bgr_gain_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _i32, _vp]),
-    "vs_scene_params_default": (None, [C.POINTER(SceneParams)]),
-    "vs_bgr_scene_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, C.POINTER(SceneParams), _vp, _i32, _vp]),
-    "vs_scene_cuts": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(SceneParams), _vp]),
-    "vs_bgr_fidelity_batch": (_i32, [_vp, _sz, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _vp, _i32, _vp]),
+    "vs_scene_params_default": (None, [_SceneP]),
+    "vs_bgr_scene_stats_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _TP, _SceneP, _vp, _i32, _vp]),
+    "vs_scene_cuts": (_i32, [_vp, _i32, _i32, _i32, _SceneP, _vp]),
+    "vs_bgr_fidelity_batch": (_i32, [_vp, _sz, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _vp, _i32, _vp]),
     "vs_fidelity_scores": (_i32, [_vp, _i32, _i32, _i32, _i32, C.POINTER(FidelityScore)]),
-    "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(C.c_int32), _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
-    "vs_sharpen_params_default": (None, [C.POINTER(SharpenParams)]),
-    "vs_bgr_sharpen_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _TP, C.POINTER(SharpenParams), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_bgr_fill_coverage_batch": (_i32, [_i32, _i32, _i32, _i32, _I32P, _TP, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "vs_sharpen_params_default": (None, [_SharpenP]),
+    "vs_bgr_sharpen_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _TP, _SharpenP, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_inpaint_batch": (_i32, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "vs_bgr_image_warp_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _TP, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vs_bgr_to_gray": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
-    "vs_flow_params_default": (None, [C.POINTER(FlowParams)]),
-    "vs_flow_create": (_vp, [C.POINTER(FlowParams), _i32]),
+    "vs_flow_params_default": (None, [_FlowP]),
+    "vs_flow_create": (_vp, [_FlowP, _i32]),
     "vs_flow_destroy": (None, [_vp]),
     "vs_flow_compute": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
-    "vs_flow_jitter": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.POINTER(C.c_double)]),
-    "vs_aligner_create": (_vp, [C.POINTER(AlignerParams), _i32]),
+    "vs_flow_jitter": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _F64P]),
+    "vs_aligner_create": (_vp, [_AlignerP, _i32]),
     "vs_aligner_destroy": (None, [_vp]),
     "vs_aligner_set_select_mode": (_i32, [_vp, _i32]),
     "vs_stabilizer_set_select_mode": (_i32, [_vp, _i32]),
@@ -249,32 +256,32 @@ SIGNATURES = {
     "vs_stabilizer_get_select_mode": (_i32, [_vp]),
     "vs_stabilizer_set_border_fill": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_border_fill": (_i32, [_vp]),
-    "vs_stabilizer_set_fill_blend": (_i32, [_vp, C.POINTER(FillBlendParams)]),
-    "vs_stabilizer_get_fill_blend": (_i32, [_vp, C.POINTER(FillBlendParams)]),
-    "vs_stabilizer_set_deblur": (_i32, [_vp, _i32, C.POINTER(DeblurParams)]),
+    "vs_stabilizer_set_fill_blend": (_i32, [_vp, _FillBlendP]),
+    "vs_stabilizer_get_fill_blend": (_i32, [_vp, _FillBlendP]),
+    "vs_stabilizer_set_deblur": (_i32, [_vp, _i32, _DeblurP]),
     "vs_stabilizer_get_deblur": (_i32, [_vp]),
-    "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, C.POINTER(DenoiseParams)]),
+    "vs_stabilizer_set_denoise": (_i32, [_vp, _i32, _DenoiseP]),
     "vs_stabilizer_get_denoise": (_i32, [_vp]),
-    "vs_stabilizer_set_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
-    "vs_stabilizer_get_rolling_shutter": (_i32, [_vp, C.POINTER(RollingParams)]),
-    "vs_stabilizer_set_lens": (_i32, [_vp, C.POINTER(LensParams), _i32, _i32]),
-    "vs_stabilizer_get_lens": (_i32, [_vp, C.POINTER(LensParams), _IP, _IP]),
-    "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, C.POINTER(DeflickerParams)]),
+    "vs_stabilizer_set_rolling_shutter": (_i32, [_vp, _RollingP]),
+    "vs_stabilizer_get_rolling_shutter": (_i32, [_vp, _RollingP]),
+    "vs_stabilizer_set_lens": (_i32, [_vp, _LensP, _i32, _i32]),
+    "vs_stabilizer_get_lens": (_i32, [_vp, _LensP, _IP, _IP]),
+    "vs_stabilizer_set_deflicker": (_i32, [_vp, _i32, _DeflickerP]),
     "vs_stabilizer_get_deflicker": (_i32, [_vp]),
-    "vs_stabilizer_set_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
-    "vs_stabilizer_get_scene_cut": (_i32, [_vp, C.POINTER(SceneParams)]),
-    "vs_stabilizer_get_scene_cuts": (_i32, [_vp, C.POINTER(C.c_int64), _i32]),
-    "vs_stabilizer_set_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
-    "vs_stabilizer_get_sharpen": (_i32, [_vp, C.POINTER(SharpenParams)]),
+    "vs_stabilizer_set_scene_cut": (_i32, [_vp, _SceneP]),
+    "vs_stabilizer_get_scene_cut": (_i32, [_vp, _SceneP]),
+    "vs_stabilizer_get_scene_cuts": (_i32, [_vp, _I64P, _i32]),
+    "vs_stabilizer_set_sharpen": (_i32, [_vp, _SharpenP]),
+    "vs_stabilizer_get_sharpen": (_i32, [_vp, _SharpenP]),
     "vs_stabilizer_set_output_size": (_i32, [_vp, _i32, _i32, _i32]),
     "vs_stabilizer_get_output_size": (_i32, [_vp, _IP, _IP, _IP]),
     "vs_stabilizer_set_inpaint": (_i32, [_vp, _i32]),
     "vs_stabilizer_get_inpaint": (_i32, [_vp]),
     "vs_aligner_set_batch_mode": (_i32, [_vp, _i32]),
     "vs_aligner_reset": (_i32, [_vp]),
-    "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP]),
-    "vs_aligner_align_batch": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP, C.POINTER(C.c_int32)]),
-    "vs_aligner_align_clips": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(AlignerParams), _TP, C.POINTER(C.c_int32)]),
+    "vs_aligner_align_next": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _AlignerP, _TP]),
+    "vs_aligner_align_batch": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _AlignerP, _TP, _I32P]),
+    "vs_aligner_align_clips": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _AlignerP, _TP, _I32P]),
     "vs_aligner_enable_timing": (_i32, [_vp, _i32]),
     "vs_aligner_get_timings": (_i32, [_vp, C.POINTER(StageTimings)]),
     "vs_aligner_get_info": (_i32, [_vp, _i32, C.POINTER(AlignInfo)]),
@@ -282,11 +289,11 @@ SIGNATURES = {
     "vs_aligner_read_level_image": (_i32, [_vp, _i32, _i32, _vp]),
     "vs_aligner_read_level_argmax": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "vs_aligner_read_level_jacobian": (_i32, [_vp, _i32, _i32, _i32, _vp]),
-    "vs_stabilizer_create": (_vp, [C.POINTER(StabilizerParams), _i32]),
+    "vs_stabilizer_create": (_vp, [_StabilizerP, _i32]),
     "vs_stabilizer_destroy": (None, [_vp]),
     "vs_stabilizer_process": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _IP, _IP]),
-    "vs_stabilizer_process_batch": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, C.POINTER(C.c_int32), _IP, _IP]),
-    "vs_stabilizer_process_clips": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, C.POINTER(C.c_int32), _IP, _IP]),
+    "vs_stabilizer_process_batch": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _I32P, _IP, _IP]),
+    "vs_stabilizer_process_clips": (_i32, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _I32P, _IP, _IP]),
     "vs_stabilizer_reset": (_i32, [_vp]),
     "vs_stabilizer_state": (None, [_vp, _TP, _TP, _IP]),
 }
@@ -324,6 +331,9 @@ def _check(r):
     return r
 
 
+# ---- marshalling: one helper per decision, used by every wrapper below -----------------------
+# Foreign-call conversion happens in these four and in _frames_in / _frames_out: a numpy array or a raw address as void*, an optional struct
+# by reference, a stream, an int32 array, a Transform array.
 def _p(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(C.c_void_p)
@@ -334,6 +344,133 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def _ref(s):
+    """an optional struct by reference: None is the library's own default (or "off")"""
+    return C.byref(s) if s is not None else None
+
+
+def _stream(s):
+    """a raw hipStream_t value; None or 0: the default stream"""
+    return C.c_void_p(s) if s else None
+
+
+def _i32p(a):
+    return a.ctypes.data_as(_I32P)
+
+
+def _transforms(ts, n):
+    """n Transforms as a ctypes array with at least one element; a ctypes array (what align_* gave with raw=True) is passed through as is, so
+    that no per-frame Python objects are made"""
+    return ts if isinstance(ts, C.Array) else (Transform * max(n, 1))(*ts)
+
+
+def _fmt_of(frame_dtype, ndim_tail):
+    if ndim_tail == 2:
+        return FMT_GRAY8
+    return FMT_BGR8 if frame_dtype == np.uint8 else FMT_BGR10      # u16 numpy frames are 10-bit unless the caller passes fmt=
+
+
+def _channels(fmt):
+    return 1 if fmt == FMT_GRAY8 else 3
+
+
+def _depth(dtype, max_value):
+    """(bits of the container, the value the warps saturate at: the container's largest unless the caller says otherwise)"""
+    bits = 8 if dtype == np.uint8 else 16
+    return bits, ((255 if bits == 8 else 65535) if max_value is None else max_value)
+
+
+def _pitched(src, stride):
+    """(n,h,w,c) -> (n,h,stride) with the rows' own elements in front (the padding is zero)"""
+    n, h, w, c = src.shape
+    if stride == w * c:
+        return src.reshape(n, h, w * c)
+    wide = np.zeros((n, h, stride), src.dtype)
+    wide[:, :, :w * c] = src.reshape(n, h, w * c)
+    return wide
+
+
+def _frames_in(src, fmt=None, src_stride=None):
+    """frames in: src (n,h,w,c) numpy -> the contiguous frames, the format (u16 frames are 10-bit unless fmt says otherwise), the row stride in
+    elements (dense unless src_stride says otherwise) and the frames as rows of that stride"""
+    src = np.ascontiguousarray(src)
+    n, h, w, c = src.shape
+    ss = w * c if src_stride is None else src_stride
+    return src, (_fmt_of(src.dtype, 3) if fmt is None else fmt), ss, _pitched(src, ss)
+
+
+def _frames_out(n, h, w, c, dtype, dst_stride=None, guard=None, fill=0):
+    """frames out: the padded destination of n frames of h rows of w * c elements -- rows of dst_stride elements (dense unless it says
+    otherwise), at least one frame so that there is an address to hand over, every element `guard`, or `fill` without one -- and its row stride"""
+    ds = w * c if dst_stride is None else dst_stride
+    return np.full((max(n, 1), h, ds), fill if guard is None else guard, dtype), ds
+
+
+def _cut(out, shape, guard):
+    """the frames of `shape` = (n, h, w[, c]) out of their padded destination; with a guard the padded buffer is returned as well, so that the
+    caller can see that the padding was left alone"""
+    res = np.ascontiguousarray(out[:shape[0], :, :int(np.prod(shape[2:]))]).reshape(shape)
+    return (res, out) if guard is not None else res
+
+
+def _window(roi, w, h):
+    return roi if roi is not None else (0, 0, w, h)
+
+
+def _candidates(cand_frame, cand_t):
+    """the candidate lists of the look-ahead passes (fill, deblur, denoise, rolling shutter, exposure statistics, coverage): cand_frame
+    (n_out, n_cand) ints, cand_t n_out lists of n_cand Transforms -> the int32 indices, n_out, n_cand, the Transform array.  The library reads
+    n_out * n_cand Transforms, so a shorter cand_t is refused here, for host and device forms alike"""
+    idx = _c(cand_frame, np.int32)
+    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
+    flat = [t for row in cand_t for t in row]
+    assert len(flat) == n_out * n_cand
+    return idx, n_out, n_cand, _transforms(flat, len(flat))
+
+
+def _pairs(pair_frames):
+    """pair_frames (n_pairs, 2) ints -> the int32 indices, n_pairs"""
+    idx = _c(pair_frames, np.int32).reshape(-1, 2)
+    return idx, idx.shape[0]
+
+
+def _params(cls, default, kw, *lead):
+    """the constructor behind every *_params(): a `cls` with the library's defaults (`default`, called with the struct and `lead`), fields
+    overridden by keyword"""
+    p = cls()
+    getattr(lib(), default)(C.byref(p), *lead)
+    _set_fields(p, kw)
+    return p
+
+
+def _set_fields(p, kw, inner=None):
+    """a name that is no field of p is one of `inner`, a struct inside p, or a TypeError: a plain attribute on a ctypes struct would be ignored
+    without a word"""
+    for k, v in kw.items():
+        if k in dict(p._fields_):
+            setattr(p, k, v)
+        elif inner is not None and k in dict(inner._fields_):
+            setattr(inner, k, v)
+        else:
+            raise TypeError("%s has no field %r" % (type(p).__name__, k))
+
+
+class _Handle:
+    """a handle of the library: made by `_create` (a null handle raises with the library's error text), destroyed with the object"""
+    _create = _destroy = None
+
+    def _open(self, *args):
+        self.h = getattr(lib(), self._create)(*args)
+        if not self.h:
+            raise VsError("%s failed: %s" % (self._create, lib().vs_last_error().decode()))
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:      # (the module may be half torn down at interpreter exit)
+            getattr(_lib, self._destroy)(self.h)
+            self.h = None
+
+
+# ---- the library itself ----------------------------------------------------------------------
 def device_count():
     return lib().vs_device_count()
 
@@ -341,40 +478,19 @@ def device_count():
 def shader_clock_probe(stream=None):
     """shader clock in MHz as a VALU-bound probe kernel on `stream` sees it (s_memtime / s_memrealtime)"""
     mhz = C.c_double(0.0)
-    _check(lib().vs_shader_clock_probe(C.c_void_p(stream) if stream else None, C.byref(mhz)))
+    _check(lib().vs_shader_clock_probe(_stream(stream), C.byref(mhz)))
     return mhz.value
 
 
 def debug_bounds_check():
     """bounds build only: violations since the last call (0 = clean); raises VsError in the regular library"""
-    r = lib().vs_debug_bounds_check()
-    if r < 0:
-        raise VsError("vs_amd error %d: %s" % (r, lib().vs_last_error().decode()))
+    r = _check(lib().vs_debug_bounds_check())
     return r, (lib().vs_last_error().decode() if r else "")
 
 
 def test_fail_alloc(k):
     """fault injection: the k-th allocation of the library from now on fails once (0 disarms); returns the allocations seen since the last call"""
     return lib().vs_test_fail_alloc(int(k))
-
-
-def aligner_params(**kw):
-    p = AlignerParams()
-    lib().vs_aligner_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def stabilizer_params(**kw):
-    p = StabilizerParams()
-    lib().vs_stabilizer_params_default(C.byref(p))
-    for k, v in kw.items():
-        if hasattr(p.aligner, k) and not hasattr(p, k):
-            setattr(p.aligner, k, v)
-        else:
-            setattr(p, k, v)
-    return p
 
 
 # ---- host-side algebra ---------------------------------------------------------------------
@@ -428,21 +544,17 @@ def tvl1_smooth(data, lam, iterations=100):
     return out
 
 
-class Smoother:
+class Smoother(_Handle):
     """L1SmootherCenter (smoother.hpp:10-30)"""
+    _create, _destroy = "vs_smoother_create", "vs_smoother_destroy"
 
     def __init__(self, lag_behind, lag_ahead, lam):
-        self.h = lib().vs_smoother_create(lag_behind, lag_ahead, lam)
+        self._open(lag_behind, lag_ahead, lam)
 
     def update(self, meas):
         out = Transform()
         ok = lib().vs_smoother_update(self.h, C.byref(meas), C.byref(out))
         return bool(ok), out
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.vs_smoother_destroy(self.h)
-            self.h = None
 
 
 # ---- kernel level (host-staged numpy convenience wrappers) ---------------------------------
@@ -596,17 +708,27 @@ def image_warp(img, t):
     return image_warp_raw(img, float(p[0]), float(p[1]), float(p[2]), float(p[3]))
 
 
+def bgr_to_gray(src, shift_to_8=None):
+    src = np.ascontiguousarray(src)
+    h, w, _ = src.shape
+    bits = 8 if src.dtype == np.uint8 else 16
+    if shift_to_8 is None:
+        shift_to_8 = 0 if bits == 8 else 2
+    out = np.empty((h, w), np.uint8)
+    _check(lib().vs_bgr_to_gray(_p(src), w, h, w * 3, bits, shift_to_8, _p(out), w, MEM_HOST, None))
+    return out
+
+
+# ---- the warps -------------------------------------------------------------------------------
 def bgr_image_warp(src, t, mode=WARP_LANCZOS2, border=BORDER_CLAMP, max_value=None, f32=False):
     src = np.ascontiguousarray(src)
     assert src.dtype in (np.uint8, np.uint16) and src.ndim == 3
     h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
+    bits, max_value = _depth(src.dtype, max_value)
     if f32:
         out = np.empty((h, w, c), np.float32)
         _check(lib().vs_bgr_image_warp_f32(_p(src), w, h, w * c, c, bits, C.byref(t), mode, border, _p(out), w * c, MEM_HOST, None))
         return out
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
     out = np.empty_like(src)
     _check(lib().vs_bgr_image_warp(_p(src), w, h, w * c, c, bits, C.byref(t), mode, border, max_value, _p(out), w * c, MEM_HOST, None))
     return out
@@ -616,84 +738,55 @@ def bgr_image_warp_batch(src, ts, mode=WARP_LANCZOS2, border=BORDER_CLAMP, max_v
     """src (n,h,w,c) numpy; ts list of Transform"""
     src = np.ascontiguousarray(src)
     n, h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
-    arr = (Transform * n)(*ts)
+    bits, max_value = _depth(src.dtype, max_value)
     out = np.empty_like(src)
-    _check(lib().vs_bgr_image_warp_batch(_p(src), h * w * c, n, w, h, w * c, c, bits, arr, mode, border, max_value,
+    _check(lib().vs_bgr_image_warp_batch(_p(src), h * w * c, n, w, h, w * c, c, bits, _transforms(ts, n), mode, border, max_value,
                                          _p(out), h * w * c, w * c, MEM_HOST, None))
     return out
+
+
+def bgr_image_warp_batch_device(src_ptr, n, w, h, c, bits, ts, dst_ptr, mode=WARP_LANCZOS2, border=BORDER_CLAMP,
+                                max_value=None, stream=None):
+    """device-resident form: dense frames, enqueue only"""
+    if max_value is None:
+        max_value = 255 if bits == 8 else 65535
+    _check(lib().vs_bgr_image_warp_batch(_p(src_ptr), h * w * c, n, w, h, w * c, c, bits, _transforms(ts, n), mode, border, max_value,
+                                         _p(dst_ptr), h * w * c, w * c, MEM_DEVICE, _stream(stream)))
 
 
 def bgr_image_warp_roi_batch(src, ts, roi, mode=WARP_LANCZOS2, border=BORDER_CLAMP, max_value=None):
     """only the window roi = (x, y, w, h) of every warped frame: (n, roi_h, roi_w, c)"""
     src = np.ascontiguousarray(src)
     n, h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
+    bits, max_value = _depth(src.dtype, max_value)
     rx, ry, rw, rh = roi
-    arr = (Transform * n)(*ts)
     out = np.empty((n, rh, rw, c), src.dtype)
-    _check(lib().vs_bgr_image_warp_roi_batch(_p(src), h * w * c, n, w, h, w * c, c, bits, arr, mode, border, max_value,
+    _check(lib().vs_bgr_image_warp_roi_batch(_p(src), h * w * c, n, w, h, w * c, c, bits, _transforms(ts, n), mode, border, max_value,
                                              rx, ry, rw, rh, _p(out), rh * rw * c, rw * c, MEM_HOST, None))
     return out
 
 
-def _pitched(src, stride):
-    """(n,h,w,c) -> (n,h,stride) with the rows' own elements in front (the padding is zero)"""
-    n, h, w, c = src.shape
-    if stride == w * c:
-        return src.reshape(n, h, w * c)
-    wide = np.zeros((n, h, stride), src.dtype)
-    wide[:, :, :w * c] = src.reshape(n, h, w * c)
-    return wide
-
-
-def _lookahead_args(src, cand_frame, cand_t, src_stride):
-    """what the host forms of the look-ahead passes (fill, deblur, denoise, exposure statistics) begin with: src (n_src,h,w,c) numpy, cand_frame
-    (n_out, n_cand) ints, cand_t n_out lists of n_cand Transforms -> the contiguous frames, the int32 indices, n_out, n_cand, the Transform
-    array, the source stride in elements and the frames as rows of that stride"""
-    src = np.ascontiguousarray(src)
-    n_src, h, w, c = src.shape
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape if idx.ndim == 2 else (0, 0)
-    flat = [t for row in cand_t for t in row]
-    assert len(flat) == n_out * n_cand
-    arr = (Transform * max(len(flat), 1))(*flat)
-    ss = w * c if src_stride is None else src_stride
-    return src, idx, n_out, n_cand, arr, ss, _pitched(src, ss)
-
-
+# ---- border fill: the fill, its seam blend (channel sums), the coverage index, the inpaint ----
 def bgr_image_warp_fill_batch(src, cand_frame, cand_t, roi=None, border=BORDER_CONSTANT, max_value=None, src_stride=None, dst_stride=None):
     """VS_WARP_BILINEAR_CV with border fill (include/vs_amd.h: vs_bgr_image_warp_fill_batch).  src (n_src,h,w,3) numpy; cand_frame
     (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w, 3).
     src_stride / dst_stride (elements): the call is made on pitched copies of the frames (the padding is not part of the result)"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, _, ss, buf = _frames_in(src, None, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     n_src, h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
-    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
-    ds = rw * c if dst_stride is None else dst_stride
-    out = np.zeros((max(n_out, 1), rh, ds), src.dtype)
-    _check(lib().vs_bgr_image_warp_fill_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+    bits, max_value = _depth(src.dtype, max_value)
+    rx, ry, rw, rh = _window(roi, w, h)
+    out, ds = _frames_out(n_out, rh, rw, c, src.dtype, dst_stride)
+    _check(lib().vs_bgr_image_warp_fill_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, _i32p(idx),
                                               arr, border, max_value, rx, ry, rw, rh, _p(out), rh * ds, ds, MEM_HOST, None))
-    return np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
+    return _cut(out, (n_out, rh, rw, c), None)
 
 
 def channel_sums_batch(src, fmt=None, src_stride=None):
     """the per-channel sample sums of every frame (include/vs_amd.h: vs_bgr_channel_sums_batch).  src (n,h,w,3) numpy -> (n,3) uint64.
     src_stride (elements): the call is made on pitched copies of the frames"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
-    buf = src.reshape(n, h, w * c) if ss == w * c else None
-    if buf is None:
-        buf = np.zeros((n, h, ss), src.dtype)
-        buf[:, :, :w * c] = src.reshape(n, h, w * c)
     out = np.zeros((n, 3), np.uint64)
     _check(lib().vs_bgr_channel_sums_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(out), MEM_HOST, None))
     return out
@@ -701,7 +794,7 @@ def channel_sums_batch(src, fmt=None, src_stride=None):
 
 def channel_sums_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, sums_ptr, stream=None):
     """device-resident form (any base address and pitch, in elements): enqueue only"""
-    _check(lib().vs_bgr_channel_sums_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(sums_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+    _check(lib().vs_bgr_channel_sums_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(sums_ptr), MEM_DEVICE, _stream(stream)))
 
 
 def bgr_image_warp_fill_blend_batch(src, cand_frame, cand_t, sums=None, feather=0, match=0, roi=None, border=BORDER_CONSTANT, max_value=None,
@@ -709,21 +802,18 @@ def bgr_image_warp_fill_blend_batch(src, cand_frame, cand_t, sums=None, feather=
     """the fill with its seams blended (include/vs_amd.h: vs_bgr_image_warp_fill_blend_batch).  Arguments as bgr_image_warp_fill_batch;
     sums (n_src,3) uint64 (None only with match == 0).  guard: a value the destination's padding is filled with first; the padded buffer
     is returned as well, so that the caller can see that the padding was left alone"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, _, ss, buf = _frames_in(src, None, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     n_src, h, w, c = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
-    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
-    ds = rw * c if dst_stride is None else dst_stride
+    bits, max_value = _depth(src.dtype, max_value)
+    rx, ry, rw, rh = _window(roi, w, h)
     sm = _c(sums, np.uint64) if sums is not None else None
     p = FillBlendParams(int(feather), int(match))
-    out = np.full((max(n_out, 1), rh, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_image_warp_fill_blend_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+    out, ds = _frames_out(n_out, rh, rw, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_image_warp_fill_blend_batch(_p(buf), h * ss, n_src, w, h, ss, c, bits, n_out, n_cand, _i32p(idx),
                                                     arr, _p(sm) if sm is not None else None, C.byref(p), border, max_value, rx, ry, rw, rh, _p(out),
                                                     rh * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n_out, :, :rw * c]).reshape(n_out, rh, rw, c)
-    return (res, out) if guard is not None else res
+    return _cut(out, (n_out, rh, rw, c), guard)
 
 
 def bgr_fill_coverage_batch(w, h, cand_frame, cand_t, roi=None, cov_stride=None, guard=None):
@@ -731,25 +821,20 @@ def bgr_fill_coverage_batch(w, h, cand_frame, cand_t, roi=None, cov_stride=None,
     list (only the sign is looked at); cand_t: n_out lists of n_cand Transforms.  -> (n_out, roi_h, roi_w) uint8: 1 + the first covering
     candidate, 0 for none.  cov_stride (bytes): the call is made on a pitched buffer.  guard: a value the padding is filled with first; the
     padded buffer is returned as well"""
-    _, idx, n_out, n_cand, arr, _, _ = _lookahead_args(np.zeros((1, 1, 1, 3), np.uint8), cand_frame, cand_t, None)
-    rx, ry, rw, rh = roi if roi is not None else (0, 0, w, h)
-    cs = rw if cov_stride is None else cov_stride
-    out = np.full((max(n_out, 1), rh, cs), 0xA5 if guard is None else guard, np.uint8)
-    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, rx, ry, rw, rh, _p(out), rh * cs, cs,
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
+    rx, ry, rw, rh = _window(roi, w, h)
+    out, cs = _frames_out(n_out, rh, rw, 1, np.uint8, cov_stride, guard, fill=0xA5)
+    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, _i32p(idx), arr, rx, ry, rw, rh, _p(out), rh * cs, cs,
                                             MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n_out, :, :rw])
-    return (res, out) if guard is not None else res
+    return _cut(out, (n_out, rh, rw), guard)
 
 
 def bgr_fill_coverage_batch_device(w, h, cand_frame, cand_t, roi, cov_ptr, cov_fs, cov_stride, stream=None):
     """device-resident form: the index goes to device memory (strides in bytes), enqueue only"""
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape
-    flat = [t for row in cand_t for t in row]
-    arr = (Transform * len(flat))(*flat)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     rx, ry, rw, rh = roi
-    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, rx, ry, rw, rh, _p(cov_ptr), cov_fs,
-                                            cov_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+    _check(lib().vs_bgr_fill_coverage_batch(w, h, n_out, n_cand, _i32p(idx), arr, rx, ry, rw, rh, _p(cov_ptr), cov_fs,
+                                            cov_stride, MEM_DEVICE, _stream(stream)))
 
 
 def bgr_inpaint_batch(img, mask, fmt=None, stride=None, mask_stride=None, guard=None):
@@ -759,42 +844,38 @@ def bgr_inpaint_batch(img, mask, fmt=None, stride=None, mask_stride=None, guard=
     img = np.ascontiguousarray(img)
     n, h, w, c = img.shape
     fmt = _fmt_of(img.dtype, 3) if fmt is None else fmt
-    st = w * c if stride is None else stride
     ms = w if mask_stride is None else mask_stride
-    buf = np.full((n, h, st), 0 if guard is None else guard, img.dtype)
-    buf[:, :, :w * c] = img.reshape(n, h, w * c)
+    buf, st = _frames_out(n, h, w, c, img.dtype, stride, guard)         # in place: the destination starts as the image
+    buf[:n, :, :w * c] = img.reshape(n, h, w * c)
     mk = np.zeros((n, h, ms), np.uint8)
     mk[:, :, :w] = _c(mask, np.uint8).reshape(n, h, w)
     _check(lib().vs_bgr_inpaint_batch(_p(buf), h * st, n, w, h, st, fmt, _p(mk), h * ms, ms, MEM_HOST, None))
-    res = np.ascontiguousarray(buf[:, :, :w * c]).reshape(n, h, w, c)
-    return (res, buf) if guard is not None else res
+    return _cut(buf, (n, h, w, c), guard)
 
 
 def bgr_inpaint_batch_device(img_ptr, frame_stride, n, w, h, stride, fmt, mask_ptr, mask_fs, mask_stride, stream=None):
     """device-resident form: in place (frame_stride, stride in elements; the mask's in bytes)"""
     _check(lib().vs_bgr_inpaint_batch(_p(img_ptr), frame_stride, n, w, h, stride, fmt, _p(mask_ptr), mask_fs, mask_stride, MEM_DEVICE,
-                                      C.c_void_p(stream) if stream else None))
+                                      _stream(stream)))
 
 
+# ---- deblur by transfer (sharpness, then the transfer) ----
 def deblur_params(**kw):
-    p = DeblurParams()
-    lib().vs_deblur_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(DeblurParams, "vs_deblur_params_default", kw)
 
 
 def sharpness_batch(src, fmt=None, src_stride=None):
     """the gradient energy S of every frame (include/vs_amd.h: vs_bgr_sharpness_batch).  src (n,h,w,3) numpy -> (n,) uint64.
     src_stride (elements): the call is made on pitched copies of the frames"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
-    buf = _pitched(src, ss)
     out = np.zeros(n, np.uint64)
     _check(lib().vs_bgr_sharpness_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(out), MEM_HOST, None))
     return out
+
+
+def sharpness_batch_device(src_ptr, n, w, h, fmt, sharp_ptr, stream=None):
+    _check(lib().vs_bgr_sharpness_batch(_p(src_ptr), h * w * 3, n, w, h, w * 3, fmt, _p(sharp_ptr), MEM_DEVICE, _stream(stream)))
 
 
 def bgr_deblur_batch(src, sharpness, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
@@ -802,35 +883,26 @@ def bgr_deblur_batch(src, sharpness, cand_frame, cand_t, params=None, fmt=None, 
     (n_out, n_cand) ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).
     src_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with
     first; the padded buffer is returned as well, so that the caller can see that the padding was left alone"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     n_src, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ds = w * c if dst_stride is None else dst_stride
     sh = _c(sharpness, np.uint64)
-    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_deblur_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, _p(sh), n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                     C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
-    return (res, out) if guard is not None else res
+    out, ds = _frames_out(n_out, h, w, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_deblur_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, _p(sh), n_out, n_cand, _i32p(idx), arr,
+                                     _ref(params), _p(out), h * ds, ds, MEM_HOST, None))
+    return _cut(out, (n_out, h, w, c), guard)
 
 
 def bgr_deblur_batch_device(src_ptr, n_src, w, h, fmt, sharp_ptr, cand_frame, cand_t, dst_ptr, params=None, stream=None):
     """device-resident form: dense frames, sharpness in device memory, enqueue only"""
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape
-    flat = [t for row in cand_t for t in row]
-    arr = (Transform * len(flat))(*flat)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     _check(lib().vs_bgr_deblur_batch(_p(src_ptr), h * w * 3, n_src, w, h, w * 3, fmt, _p(sharp_ptr), n_out, n_cand,
-                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), arr, C.byref(params) if params is not None else None,
-                                     _p(dst_ptr), h * w * 3, w * 3, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+                                     _i32p(idx), arr, _ref(params), _p(dst_ptr), h * w * 3, w * 3, MEM_DEVICE, _stream(stream)))
 
 
+# ---- motion-compensated temporal denoise ----
 def denoise_params(**kw):
-    p = DenoiseParams()
-    lib().vs_denoise_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(DenoiseParams, "vs_denoise_params_default", kw)
 
 
 def denoise_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
@@ -838,34 +910,25 @@ def denoise_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=Non
     ints, a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, h, w, 3).  src_stride / dst_stride
     (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer
     is returned as well, so that the caller can see that the padding was left alone"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     n_src, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ds = w * c if dst_stride is None else dst_stride
-    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_denoise_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                      C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
-    return (res, out) if guard is not None else res
+    out, ds = _frames_out(n_out, h, w, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_denoise_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, _i32p(idx), arr,
+                                      _ref(params), _p(out), h * ds, ds, MEM_HOST, None))
+    return _cut(out, (n_out, h, w, c), guard)
 
 
 def denoise_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape
-    flat = [t for row in cand_t for t in row]
-    arr = (Transform * len(flat))(*flat)
-    _check(lib().vs_bgr_denoise_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                      C.byref(params) if params is not None else None, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
-                                      C.c_void_p(stream) if stream else None))
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
+    _check(lib().vs_bgr_denoise_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, _i32p(idx), arr,
+                                      _ref(params), _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, _stream(stream)))
 
 
+# ---- rolling-shutter correction ----
 def rolling_params(**kw):
-    p = RollingParams()
-    lib().vs_rolling_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(RollingParams, "vs_rolling_params_default", kw)
 
 
 def rolling_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
@@ -873,42 +936,31 @@ def rolling_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=Non
     then any index >= 0 (a motion is known) or a negative one (none); cand_t: n_out lists of 2 Transforms, the second the motion to the
     following frame.  -> (n_out, h, w, 3).  src_stride / dst_stride (elements): the call is made on pitched buffers.  guard: a value the
     destination's padding is filled with first; the padded buffer is returned as well"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     assert n_cand == 2
     n_src, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ds = w * c if dst_stride is None else dst_stride
-    out = np.full((max(n_out, 1), h, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_rolling_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                      C.byref(params) if params is not None else None, _p(out), h * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n_out, :, :w * c]).reshape(n_out, h, w, c)
-    return (res, out) if guard is not None else res
+    out, ds = _frames_out(n_out, h, w, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_rolling_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, _i32p(idx), arr,
+                                      _ref(params), _p(out), h * ds, ds, MEM_HOST, None))
+    return _cut(out, (n_out, h, w, c), guard)
 
 
 def rolling_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     assert n_cand == 2
-    flat = [t for row in cand_t for t in row]
-    arr = (Transform * len(flat))(*flat)
-    _check(lib().vs_bgr_rolling_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                      C.byref(params) if params is not None else None, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
-                                      C.c_void_p(stream) if stream else None))
+    _check(lib().vs_bgr_rolling_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, _i32p(idx), arr,
+                                      _ref(params), _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, _stream(stream)))
 
 
+# ---- lens-distortion correction: the radial map, the remap through it ----
 REMAP_SLICE = 8                                     # vsk::kRemapSlice: the frames a workgroup of the remap takes a pixel through
 
 
 def lens_params(w, h, **kw):
     """the identity lens of a w x h frame (vs_lens_params_default), fields overridden by keyword"""
-    p = LensParams()
-    lib().vs_lens_params_default(C.byref(p), int(w), int(h))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError("LensParams has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(LensParams, "vs_lens_params_default", kw, int(w), int(h))
 
 
 def lens_map(params, w, h, map_stride=None, guard=None):
@@ -924,33 +976,28 @@ def lens_map(params, w, h, map_stride=None, guard=None):
 
 def lens_map_device(params, w, h, map_ptr, map_stride=None, stream=None):
     """device-resident form: the map is written at map_ptr (int32, rows of map_stride elements), enqueue only"""
-    _check(lib().vs_lens_map(C.byref(params), w, h, _p(map_ptr), 2 * w if map_stride is None else map_stride, MEM_DEVICE,
-                             C.c_void_p(stream) if stream else None))
+    _check(lib().vs_lens_map(C.byref(params), w, h, _p(map_ptr), 2 * w if map_stride is None else map_stride, MEM_DEVICE, _stream(stream)))
 
 
 def remap_batch(src, pos, border=BORDER_CLAMP, fmt=None, src_stride=None, dst_stride=None, map_stride=None, guard=None):
     """remap through a map of fixed-point positions (include/vs_amd.h: vs_bgr_remap_batch).  src (n,h,w,3) numpy; pos (oh, ow, 2) int32 (X, Y)
     with 5 fraction bits, one map for every frame -> (n, oh, ow, 3).  src_stride / dst_stride (elements), map_stride (int32 elements): the call
     is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer is returned as well"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, h, w, c = src.shape
     pos = _c(pos, np.int32)
     oh, ow, _ = pos.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
-    ds = ow * c if dst_stride is None else dst_stride
     ms = 2 * ow if map_stride is None else map_stride
     mp = _pitched(pos.reshape(1, oh, ow, 2), ms)
-    out = np.full((n, oh, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_remap_batch(_p(_pitched(src, ss)), h * ss, n, w, h, ss, fmt, _p(mp), ms, ow, oh, border, _p(out), oh * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:, :, :ow * c]).reshape(n, oh, ow, c)
-    return (res, out) if guard is not None else res
+    out, ds = _frames_out(n, oh, ow, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_remap_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(mp), ms, ow, oh, border, _p(out), oh * ds, ds, MEM_HOST, None))
+    return _cut(out, (n, oh, ow, c), guard)
 
 
 def remap_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, map_ptr, map_stride, ow, oh, dst_ptr, dst_fs, dst_stride, border=BORDER_CLAMP, stream=None):
     """device-resident form: frames and map in device memory, frame strides and row strides in elements, enqueue only"""
     _check(lib().vs_bgr_remap_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(map_ptr), map_stride, ow, oh, border, _p(dst_ptr), dst_fs, dst_stride,
-                                    MEM_DEVICE, C.c_void_p(stream) if stream else None))
+                                    MEM_DEVICE, _stream(stream)))
 
 
 # ---- resize (include/vs_amd.h: THE RESIZE RULE; the tables: csrc/vs_resize.hpp) ----
@@ -965,21 +1012,17 @@ def resize_batch(src, dw, dh, filter=RESIZE_LINEAR, fmt=None, src_stride=None, d
     """resize by THE RESIZE RULE (include/vs_amd.h: vs_bgr_resize_batch).  src (n,sh,sw,3) numpy -> (n, dh, dw, 3).  src_stride / dst_stride
     (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded buffer is
     returned as well"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, sh, sw, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = sw * c if src_stride is None else src_stride
-    ds = dw * c if dst_stride is None else dst_stride
-    out = np.full((n, dh, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_resize_batch(_p(_pitched(src, ss)), sh * ss, n, sw, sh, ss, fmt, int(filter), _p(out), dh * ds, dw, dh, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:, :, :dw * c]).reshape(n, dh, dw, c)
-    return (res, out) if guard is not None else res
+    out, ds = _frames_out(n, dh, dw, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_resize_batch(_p(buf), sh * ss, n, sw, sh, ss, fmt, int(filter), _p(out), dh * ds, dw, dh, ds, MEM_HOST, None))
+    return _cut(out, (n, dh, dw, c), guard)
 
 
 def resize_batch_device(src_ptr, src_fs, n, sw, sh, src_stride, fmt, filter, dst_ptr, dst_fs, dw, dh, dst_stride, stream=None):
     """device-resident form: frames in device memory, frame strides and row strides in elements, enqueue only"""
     _check(lib().vs_bgr_resize_batch(_p(src_ptr), src_fs, n, sw, sh, src_stride, fmt, int(filter), _p(dst_ptr), dst_fs, dw, dh, dst_stride, MEM_DEVICE,
-                                     C.c_void_p(stream) if stream else None))
+                                     _stream(stream)))
 
 
 # ---- YCbCr frames (include/vs_amd.h: vs_ycbcr_to_bgr_batch; the rule: csrc/vs_ycbcr.hpp) ----
@@ -1053,66 +1096,55 @@ def ycbcr_to_bgr_batch(y, cb=None, cr=None, sub=(1, 1), fmt=None, interleaved=No
     fmt = _fmt_of(y.dtype, 3) if fmt is None else fmt
     hp = _HostPlanes(n, w, h, y.dtype, sub, interleaved, cb is None, y_stride, c_stride, 0)
     hp.put(y, cb, cr)
-    ds = 3 * w if dst_stride is None else dst_stride
-    out = np.full((n, h, ds), 0 if guard is None else guard, y.dtype)
+    out, ds = _frames_out(n, h, w, 3, y.dtype, dst_stride, guard)
     _check(lib().vs_ycbcr_to_bgr_batch(C.byref(hp.desc), n, w, h, fmt, _p(out), h * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:, :, :3 * w]).reshape(n, h, w, 3)
-    return (res, out) if guard is not None else res
+    return _cut(out, (n, h, w, 3), guard)
 
 
 def ycbcr_to_bgr_batch_device(planes, n, w, h, fmt, dst_ptr, dst_fs, dst_stride, stream=None):
     """device-resident form: planes is a YcbcrPlanes of device addresses (ycbcr_planes), strides in elements, enqueue only"""
-    _check(lib().vs_ycbcr_to_bgr_batch(C.byref(planes), n, w, h, fmt, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
+    _check(lib().vs_ycbcr_to_bgr_batch(C.byref(planes), n, w, h, fmt, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, _stream(stream)))
 
 
 def bgr_to_ycbcr_batch(src, sub=(1, 1), fmt=None, interleaved=None, mono=False, src_stride=None, y_stride=None, c_stride=None, guard=None):
     """interleaved BGR -> YCbCr planes (include/vs_amd.h: vs_bgr_to_ycbcr_batch).  src (n,h,w,3) numpy -> (y (n,h,w), cb, cr (n,ch,cw)); mono:
     luma only, cb and cr come back None.  Strides in elements: the call is made on pitched buffers.  guard: a value the destination buffers --
     two rows in front, two behind and the padding -- are filled with first; the whole buffers are returned as well, as a list"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
     hp = _HostPlanes(n, w, h, src.dtype, sub, interleaved, mono, y_stride, c_stride, 0 if guard is None else guard)
-    _check(lib().vs_bgr_to_ycbcr_batch(_p(_pitched(src, ss)), h * ss, n, w, h, ss, fmt, C.byref(hp.desc), MEM_HOST, None))
+    _check(lib().vs_bgr_to_ycbcr_batch(_p(buf), h * ss, n, w, h, ss, fmt, C.byref(hp.desc), MEM_HOST, None))
     return (hp.get(), hp.buffers()) if guard is not None else hp.get()
 
 
 def bgr_to_ycbcr_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, planes, stream=None):
     """device-resident form: frames and planes (a YcbcrPlanes of device addresses) in device memory, strides in elements, enqueue only"""
-    _check(lib().vs_bgr_to_ycbcr_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, C.byref(planes), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+    _check(lib().vs_bgr_to_ycbcr_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, C.byref(planes), MEM_DEVICE, _stream(stream)))
 
 
+# ---- deflicker: pair statistics, gains from them, the point-wise gain pass ----
 def deflicker_params(**kw):
-    p = DeflickerParams()
-    lib().vs_deflicker_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(DeflickerParams, "vs_deflicker_params_default", kw)
 
 
 def exposure_stats_batch(src, cand_frame, cand_t, params=None, fmt=None, src_stride=None):
     """the deflicker's pair statistics (include/vs_amd.h: vs_bgr_exposure_stats_batch).  src (n_src,h,w,3) numpy; cand_frame (n_out, n_cand) ints,
     a negative index ends a list; cand_t: n_out lists of n_cand Transforms.  -> (n_out, n_cand, 8) uint64.  src_stride (elements): the call is
     made on pitched copies of the frames"""
-    src, idx, n_out, n_cand, arr, ss, buf = _lookahead_args(src, cand_frame, cand_t, src_stride)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
     n_src, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
     out = np.full((max(n_out, 1), max(n_cand, 1), 8), 0xA5A5A5A5, np.uint64)
-    _check(lib().vs_bgr_exposure_stats_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                             C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    _check(lib().vs_bgr_exposure_stats_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_out, n_cand, _i32p(idx), arr,
+                                             _ref(params), _p(out), MEM_HOST, None))
     return out
 
 
 def exposure_stats_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, cand_frame, cand_t, stats_ptr, params=None, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
-    idx = _c(cand_frame, np.int32)
-    n_out, n_cand = idx.shape
-    flat = [t for row in cand_t for t in row]
-    arr = (Transform * len(flat))(*flat)
-    _check(lib().vs_bgr_exposure_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             arr, C.byref(params) if params is not None else None, _p(stats_ptr), MEM_DEVICE,
-                                             C.c_void_p(stream) if stream else None))
+    idx, n_out, n_cand, arr = _candidates(cand_frame, cand_t)
+    _check(lib().vs_bgr_exposure_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_out, n_cand, _i32p(idx),
+                                             arr, _ref(params), _p(stats_ptr), MEM_DEVICE, _stream(stream)))
 
 
 def exposure_gains_batch(stats, w, h, params=None):
@@ -1121,97 +1153,102 @@ def exposure_gains_batch(stats, w, h, params=None):
     st = _c(stats, np.uint64)
     n_out, n_cand = st.shape[0], st.shape[1]
     out = np.full((n_out, 4), 0xA5A5A5A5, np.uint32)
-    _check(lib().vs_exposure_gains_batch(_p(st), n_out, n_cand, w, h, C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    _check(lib().vs_exposure_gains_batch(_p(st), n_out, n_cand, w, h, _ref(params), _p(out), MEM_HOST, None))
     return out
 
 
 def exposure_gains_batch_device(stats_ptr, n_out, n_cand, w, h, gains_ptr, params=None, stream=None):
-    _check(lib().vs_exposure_gains_batch(_p(stats_ptr), n_out, n_cand, w, h, C.byref(params) if params is not None else None, _p(gains_ptr), MEM_DEVICE,
-                                         C.c_void_p(stream) if stream else None))
+    _check(lib().vs_exposure_gains_batch(_p(stats_ptr), n_out, n_cand, w, h, _ref(params), _p(gains_ptr), MEM_DEVICE, _stream(stream)))
 
 
+def bgr_gain_batch(src, gains, fmt=None, src_stride=None, dst_stride=None, guard=None):
+    """the deflicker's point-wise pass (include/vs_amd.h: vs_bgr_gain_batch).  src (n,h,w,3) numpy; gains (n,4) uint32 -> (n,h,w,3).  src_stride /
+    dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
+    buffer is returned as well"""
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
+    n, h, w, c = src.shape
+    g = _c(gains, np.uint32)
+    out, ds = _frames_out(n, h, w, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_gain_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(g), _p(out), h * ds, ds, MEM_HOST, None))
+    return _cut(out, (n, h, w, c), guard)
+
+
+def bgr_gain_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, gains_ptr, dst_ptr, dst_fs, dst_stride, stream=None):
+    """device-resident form (dst_ptr may equal src_ptr): enqueue only"""
+    _check(lib().vs_bgr_gain_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(gains_ptr), _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
+                                   _stream(stream)))
+
+
+# ---- scene-cut detection: pair statistics, the rule's decision ----
 def scene_params(**kw):
-    p = SceneParams()
-    lib().vs_scene_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(SceneParams, "vs_scene_params_default", kw)
 
 
 def _scene_pairs(pair_frames, pair_t):
-    idx = _c(pair_frames, np.int32).reshape(-1, 2)
-    n_pairs = idx.shape[0]
+    """_pairs, and one Transform for every pair"""
+    idx, n_pairs = _pairs(pair_frames)
     assert len(pair_t) == n_pairs
-    return idx, n_pairs, (Transform * max(n_pairs, 1))(*pair_t)
+    return idx, n_pairs, _transforms(pair_t, n_pairs)
 
 
 def scene_stats_batch(src, pair_frames, pair_t, params=None, fmt=None, src_stride=None):
     """the scene-cut pair statistics (include/vs_amd.h: vs_bgr_scene_stats_batch).  src (n_src,h,w,3) numpy; pair_frames (n_pairs, 2) ints: target,
     candidate; pair_t: n_pairs Transforms.  -> (n_pairs, 2) uint64: count, sad.  src_stride (elements): the call is made on pitched copies of the
     frames"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n_src, h, w, c = src.shape
     idx, n_pairs, arr = _scene_pairs(pair_frames, pair_t)
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
     out = np.full((max(n_pairs, 1), 2), 0xA5A5A5A5, np.uint64)
-    _check(lib().vs_bgr_scene_stats_batch(_p(_pitched(src, ss)), h * ss, n_src, w, h, ss, fmt, n_pairs, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                          C.byref(params) if params is not None else None, _p(out), MEM_HOST, None))
+    _check(lib().vs_bgr_scene_stats_batch(_p(buf), h * ss, n_src, w, h, ss, fmt, n_pairs, _i32p(idx), arr,
+                                          _ref(params), _p(out), MEM_HOST, None))
     return out[:n_pairs]
 
 
 def scene_stats_batch_device(src_ptr, src_fs, n_src, w, h, src_stride, fmt, pair_frames, pair_t, stats_ptr, params=None, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
     idx, n_pairs, arr = _scene_pairs(pair_frames, pair_t)
-    _check(lib().vs_bgr_scene_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_pairs, idx.ctypes.data_as(C.POINTER(C.c_int32)), arr,
-                                          C.byref(params) if params is not None else None, _p(stats_ptr), MEM_DEVICE,
-                                          C.c_void_p(stream) if stream else None))
+    _check(lib().vs_bgr_scene_stats_batch(_p(src_ptr), src_fs, n_src, w, h, src_stride, fmt, n_pairs, _i32p(idx), arr,
+                                          _ref(params), _p(stats_ptr), MEM_DEVICE, _stream(stream)))
 
 
 def scene_cuts(stats, w, h, params=None):
     """the scene-cut rule's decision, on the host (include/vs_amd.h: vs_scene_cuts).  stats (n_pairs, 2) uint64 -> (n_pairs,) uint8"""
     st = _c(stats, np.uint64).reshape(-1, 2)
     out = np.full((max(st.shape[0], 1),), 0xA5, np.uint8)
-    _check(lib().vs_scene_cuts(_p(st), st.shape[0], w, h, C.byref(params) if params is not None else None, _p(out)))
+    _check(lib().vs_scene_cuts(_p(st), st.shape[0], w, h, _ref(params), _p(out)))
     return out[:st.shape[0]]
 
 
-def _fidelity_pairs(pair_frames):
-    idx = _c(pair_frames, np.int32).reshape(-1, 2)
-    return idx, idx.shape[0]
-
-
+# ---- fidelity metrics: pair statistics, the rule's scores ----
 def fidelity_stats_batch(a, b, pair_frames, fmt=None, a_stride=None, b_stride=None, roi=None):
     """the fidelity statistics of image pairs (include/vs_amd.h: vs_bgr_fidelity_batch).  a (n_a,h,w,3) and b (n_b,h,w,3) numpy of one dtype; b None
     or a itself: the pairs lie in one batch, handed over once; pair_frames (n_pairs, 2) ints: into a, into b.  -> (n_pairs, 6) uint64: sse_b, sse_g,
     sse_r, sse_y, n_win, ssim_sum (two's complement).  a_stride / b_stride (elements): the call is made on pitched copies of the frames.  roi
     (x, y, rw, rh): the images are that window of the frames, handed over as its origin pointer with the frames' strides"""
-    a = np.ascontiguousarray(a)
+    a, fmt, sa, pa = _frames_in(a, fmt, a_stride)
     one = b is None or b is a
-    b = a if one else np.ascontiguousarray(b)
+    if one and b_stride in (None, sa):
+        b, sb, pb = a, sa, pa
+    else:
+        b, _, sb, pb = _frames_in(a if one else b, fmt, b_stride)
     assert a.dtype == b.dtype and a.shape[1:] == b.shape[1:]
     n_a, h, w, c = a.shape
-    idx, n_pairs = _fidelity_pairs(pair_frames)
-    fmt = _fmt_of(a.dtype, 3) if fmt is None else fmt
-    sa = w * c if a_stride is None else a_stride
-    sb = (sa if one else w * c) if b_stride is None else b_stride
-    pa = _pitched(a, sa)
-    pb = pa if one and sb == sa else _pitched(b, sb)
-    x, y, rw, rh = (0, 0, w, h) if roi is None else roi
+    idx, n_pairs = _pairs(pair_frames)
+    x, y, rw, rh = _window(roi, w, h)
     assert 0 <= x and 0 <= y and rw >= 1 and rh >= 1 and x + rw <= w and y + rh <= h
     esz = a.dtype.itemsize
     out = np.full((max(n_pairs, 1), 6), 0xA5A5A5A5, np.uint64)
     _check(lib().vs_bgr_fidelity_batch(C.c_void_p(pa.ctypes.data + (y * sa + x * c) * esz), h * sa, n_a, sa,
                                        C.c_void_p(pb.ctypes.data + (y * sb + x * c) * esz), h * sb, b.shape[0], sb, rw, rh, fmt, n_pairs,
-                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _p(out), MEM_HOST, None))
+                                       _i32p(idx), _p(out), MEM_HOST, None))
     return out[:n_pairs]
 
 
 def fidelity_stats_batch_device(a_ptr, a_fs, n_a, a_stride, b_ptr, b_fs, n_b, b_stride, w, h, fmt, pair_frames, stats_ptr, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
-    idx, n_pairs = _fidelity_pairs(pair_frames)
+    idx, n_pairs = _pairs(pair_frames)
     _check(lib().vs_bgr_fidelity_batch(_p(a_ptr), a_fs, n_a, a_stride, _p(b_ptr), b_fs, n_b, b_stride, w, h, fmt, n_pairs,
-                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), _p(stats_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
+                                       _i32p(idx), _p(stats_ptr), MEM_DEVICE, _stream(stream)))
 
 
 def fidelity_scores(stats, w, h, fmt=FMT_BGR8):
@@ -1224,12 +1261,9 @@ def fidelity_scores(stats, w, h, fmt=FMT_BGR8):
     return np.array([arr[i].tup() for i in range(n)], np.float64).reshape(n, 6)
 
 
+# ---- phase-compensated sharpening ----
 def sharpen_params(**kw):
-    p = SharpenParams()
-    lib().vs_sharpen_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(SharpenParams, "vs_sharpen_params_default", kw)
 
 
 def sharpen_batch(src, ts, w, h, roi_x=0, roi_y=0, params=None, fmt=None, src_stride=None, dst_stride=None, guard=None):
@@ -1237,102 +1271,46 @@ def sharpen_batch(src, ts, w, h, roi_x=0, roi_y=0, params=None, fmt=None, src_st
     window at (roi_x, roi_y) of w x h output frames warped under the forward Transforms ts (n of them) -> (n, roi_h, roi_w, 3).  src_stride /
     dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
     buffer is returned as well"""
-    src = np.ascontiguousarray(src)
+    src, fmt, ss, buf = _frames_in(src, fmt, src_stride)
     n, rh, rw, c = src.shape
     assert len(ts) == n
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = rw * c if src_stride is None else src_stride
-    ds = rw * c if dst_stride is None else dst_stride
-    arr = (Transform * max(n, 1))(*ts)
-    out = np.full((max(n, 1), rh, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_sharpen_batch(_p(_pitched(src, ss)) if n else None, rh * ss, n, w, h, fmt, arr, C.byref(params) if params is not None else None,
+    out, ds = _frames_out(n, rh, rw, c, src.dtype, dst_stride, guard)
+    _check(lib().vs_bgr_sharpen_batch(_p(buf) if n else None, rh * ss, n, w, h, fmt, _transforms(ts, n), _ref(params),
                                       roi_x, roi_y, rw, rh, ss, _p(out), rh * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:n, :, :rw * c]).reshape(n, rh, rw, c)
-    return (res, out) if guard is not None else res
+    return _cut(out, (n, rh, rw, c), guard)
 
 
 def sharpen_batch_device(src_ptr, src_fs, n, w, h, fmt, ts, roi_x, roi_y, roi_w, roi_h, src_stride, dst_ptr, dst_fs, dst_stride, params=None, stream=None):
     """device-resident form: frame strides and row strides in elements, enqueue only"""
-    arr = (Transform * max(n, 1))(*ts)
-    _check(lib().vs_bgr_sharpen_batch(_p(src_ptr), src_fs, n, w, h, fmt, arr, C.byref(params) if params is not None else None, roi_x, roi_y, roi_w, roi_h,
-                                      src_stride, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, C.c_void_p(stream) if stream else None))
-
-
-def bgr_gain_batch(src, gains, fmt=None, src_stride=None, dst_stride=None, guard=None):
-    """the deflicker's point-wise pass (include/vs_amd.h: vs_bgr_gain_batch).  src (n,h,w,3) numpy; gains (n,4) uint32 -> (n,h,w,3).  src_stride /
-    dst_stride (elements): the call is made on pitched buffers.  guard: a value the destination's padding is filled with first; the padded
-    buffer is returned as well"""
-    src = np.ascontiguousarray(src)
-    n, h, w, c = src.shape
-    fmt = _fmt_of(src.dtype, 3) if fmt is None else fmt
-    ss = w * c if src_stride is None else src_stride
-    ds = w * c if dst_stride is None else dst_stride
-    buf = _pitched(src, ss)
-    g = _c(gains, np.uint32)
-    out = np.full((n, h, ds), 0 if guard is None else guard, src.dtype)
-    _check(lib().vs_bgr_gain_batch(_p(buf), h * ss, n, w, h, ss, fmt, _p(g), _p(out), h * ds, ds, MEM_HOST, None))
-    res = np.ascontiguousarray(out[:, :, :w * c]).reshape(n, h, w, c)
-    return (res, out) if guard is not None else res
-
-
-def bgr_gain_batch_device(src_ptr, src_fs, n, w, h, src_stride, fmt, gains_ptr, dst_ptr, dst_fs, dst_stride, stream=None):
-    """device-resident form (dst_ptr may equal src_ptr): enqueue only"""
-    _check(lib().vs_bgr_gain_batch(_p(src_ptr), src_fs, n, w, h, src_stride, fmt, _p(gains_ptr), _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE,
-                                   C.c_void_p(stream) if stream else None))
-
-
-def sharpness_batch_device(src_ptr, n, w, h, fmt, sharp_ptr, stream=None):
-    _check(lib().vs_bgr_sharpness_batch(_p(src_ptr), h * w * 3, n, w, h, w * 3, fmt, _p(sharp_ptr), MEM_DEVICE, C.c_void_p(stream) if stream else None))
-
-
-def bgr_image_warp_batch_device(src_ptr, n, w, h, c, bits, ts, dst_ptr, mode=WARP_LANCZOS2, border=BORDER_CLAMP,
-                                max_value=None, stream=None):
-    """device-resident form: dense frames, enqueue only"""
-    if max_value is None:
-        max_value = 255 if bits == 8 else 65535
-    arr = ts if isinstance(ts, C.Array) else (Transform * n)(*ts)     # a ctypes array from align_* is passed through as is
-    _check(lib().vs_bgr_image_warp_batch(_p(src_ptr), h * w * c, n, w, h, w * c, c, bits, arr, mode, border, max_value,
-                                         _p(dst_ptr), h * w * c, w * c, MEM_DEVICE, stream))
-
-
-def bgr_to_gray(src, shift_to_8=None):
-    src = np.ascontiguousarray(src)
-    h, w, _ = src.shape
-    bits = 8 if src.dtype == np.uint8 else 16
-    if shift_to_8 is None:
-        shift_to_8 = 0 if bits == 8 else 2
-    out = np.empty((h, w), np.uint8)
-    _check(lib().vs_bgr_to_gray(_p(src), w, h, w * 3, bits, shift_to_8, _p(out), w, MEM_HOST, None))
-    return out
+    _check(lib().vs_bgr_sharpen_batch(_p(src_ptr), src_fs, n, w, h, fmt, _transforms(ts, n), _ref(params), roi_x, roi_y, roi_w, roi_h,
+                                      src_stride, _p(dst_ptr), dst_fs, dst_stride, MEM_DEVICE, _stream(stream)))
 
 
 # ---- engine level ---------------------------------------------------------------------------
-def _fmt_of(frame_dtype, ndim_tail):
-    if ndim_tail == 2:
-        return FMT_GRAY8
-    return FMT_BGR8 if frame_dtype == np.uint8 else FMT_BGR10      # u16 numpy frames are 10-bit unless the caller passes fmt=
+def _dense(w, h, fmt, stride, frame_stride):
+    """the strides (elements) of device-resident frames: dense unless the caller says otherwise"""
+    stride = stride or w * _channels(fmt)
+    return stride, frame_stride or h * stride
+
+
+def _batch_outs(n):
+    """the out-arguments of a process_* call over n frames: has_output, out_w, out_h"""
+    return (C.c_int32 * n)(), C.c_int(), C.c_int()
 
 
 # ---- dense optical flow (this build's Farneback specification, vs_flow.hip) -------------------
 def flow_params(**kw):
     """FlowParams with the reference's defaults (0.5, 3, 15, 3, 5, 1.2, 0), fields overridden by keyword"""
-    p = FlowParams()
-    lib().vs_flow_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise TypeError("FlowParams has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params(FlowParams, "vs_flow_params_default", kw)
 
 
-class Flow:
+class Flow(_Handle):
     """a vs_flow handle: its own stream and scratch, reused by every call"""
+    _create, _destroy = "vs_flow_create", "vs_flow_destroy"
 
     def __init__(self, params=None, device=0):
         self.params = params if params is not None else flow_params()
-        self.h = lib().vs_flow_create(C.byref(self.params), device)
-        if not self.h:
-            raise VsError("vs_flow_create failed: %s" % lib().vs_last_error().decode())
+        self._open(C.byref(self.params), device)
 
     def compute(self, prev, next_):
         """(h, w, 2) float32 flow (dx, dy) from prev to next (u8 gray, or any 2-D array with row stride = its strides[0])"""
@@ -1347,33 +1325,25 @@ class Flow:
         _check(lib().vs_flow_compute(self.h, _p(a), _p(b), w, h, a.strides[0], MEM_HOST, _p(out), 2 * w))
         return out
 
+    def _jitter(self, ptr, frame_stride, n, w, h, stride, fmt, mem):
+        pm = np.zeros(max(n - 1, 0), np.float32)
+        med = C.c_double(0.0)
+        _check(lib().vs_flow_jitter(self.h, _p(ptr), frame_stride, n, w, h, stride, fmt, mem, _p(pm), C.byref(med)))
+        return med.value, pm
+
     def jitter(self, frames, fmt=None):
         """frames: numpy (n, h, w) u8 gray or (n, h, w, 3) BGR u8 / u16 (10-bit unless fmt says otherwise).
         returns (median, pair medians (n-1) float32)"""
         frames = np.ascontiguousarray(frames)
-        n = frames.shape[0]
         fmt = _fmt_of(frames.dtype, frames.ndim - 1) if fmt is None else fmt
-        hh, ww = frames.shape[1:3]
-        ch = 1 if fmt == FMT_GRAY8 else 3
-        pm = np.zeros(max(n - 1, 0), np.float32)
-        med = C.c_double(0.0)
-        _check(lib().vs_flow_jitter(self.h, _p(frames), hh * ww * ch, n, ww, hh, ww * ch, fmt, MEM_HOST, _p(pm), C.byref(med)))
-        return med.value, pm
+        n, hh, ww = frames.shape[:3]
+        ch = _channels(fmt)
+        return self._jitter(frames, hh * ww * ch, n, ww, hh, ww * ch, fmt, MEM_HOST)
 
     def jitter_device(self, ptr, n, w, h, fmt, stride=None, frame_stride=None):
         """device-resident frames (raw device pointer; strides in elements): (median, pair medians)"""
-        ch = 1 if fmt == FMT_GRAY8 else 3
-        stride = stride or w * ch
-        frame_stride = frame_stride or h * stride
-        pm = np.zeros(max(n - 1, 0), np.float32)
-        med = C.c_double(0.0)
-        _check(lib().vs_flow_jitter(self.h, _p(ptr), frame_stride, n, w, h, stride, fmt, MEM_DEVICE, _p(pm), C.byref(med)))
-        return med.value, pm
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.vs_flow_destroy(self.h)
-            self.h = None
+        stride, frame_stride = _dense(w, h, fmt, stride, frame_stride)
+        return self._jitter(ptr, frame_stride, n, w, h, stride, fmt, MEM_DEVICE)
 
 
 def dense_flow(prev, next_, params=None, device=0):
@@ -1386,14 +1356,18 @@ def flow_jitter(frames, params=None, fmt=None, device=0):
     return Flow(params, device).jitter(frames, fmt)
 
 
-class Aligner:
+# ---- the aligner -----------------------------------------------------------------------------
+def aligner_params(**kw):
+    return _params(AlignerParams, "vs_aligner_params_default", kw)
+
+
+class Aligner(_Handle):
     """VideoAligner (alignment.hpp:51-99) on the GPU engine."""
+    _create, _destroy = "vs_aligner_create", "vs_aligner_destroy"
 
     def __init__(self, device=0, select_mode=SELECT_DEVICE, **params):
         self.params = aligner_params(**params)
-        self.h = lib().vs_aligner_create(C.byref(self.params), device)
-        if not self.h:
-            raise VsError("vs_aligner_create failed: %s" % lib().vs_last_error().decode())
+        self._open(C.byref(self.params), device)
         _check(lib().vs_aligner_set_select_mode(self.h, select_mode))
 
     def set_select_mode(self, mode):
@@ -1416,34 +1390,31 @@ class Aligner:
         frame = np.ascontiguousarray(frame)
         fmt = _fmt_of(frame.dtype, frame.ndim) if fmt is None else fmt
         hh, ww = frame.shape[:2]
-        stride = ww * (1 if fmt == FMT_GRAY8 else 3)
         t = Transform()
-        r = _check(lib().vs_aligner_align_next(self.h, _p(frame), ww, hh, stride, fmt, MEM_HOST, C.byref(self.params), C.byref(t)))
+        r = _check(lib().vs_aligner_align_next(self.h, _p(frame), ww, hh, ww * _channels(fmt), fmt, MEM_HOST, C.byref(self.params), C.byref(t)))
         return bool(r), t
+
+    def _align(self, entry, n, raw, *args):
+        """one batched call: `args` lie between the handle and the parameters; -> (status, transforms), as ctypes arrays if raw"""
+        out = (Transform * n)()
+        status = (C.c_int32 * n)()
+        _check(getattr(lib(), entry)(self.h, *args, C.byref(self.params), out, status))
+        if raw:
+            return status, out       # ctypes arrays: no per-frame Python objects (bench.py hands `out` to the warp call)
+        return list(status), list(out)
 
     def align_batch(self, frames, fmt=None):
         """frames: numpy (n,h,w[,3]).  returns (status[n], [Transform]*n)"""
         frames = np.ascontiguousarray(frames)
-        n = frames.shape[0]
         fmt = _fmt_of(frames.dtype, frames.ndim - 1) if fmt is None else fmt
-        hh, ww = frames.shape[1:3]
-        ch = 1 if fmt == FMT_GRAY8 else 3
-        out = (Transform * n)()
-        status = (C.c_int32 * n)()
-        _check(lib().vs_aligner_align_batch(self.h, _p(frames), hh * ww * ch, n, ww, hh, ww * ch, fmt, MEM_HOST,
-                                            C.byref(self.params), out, status))
-        return list(status), list(out)
+        n, hh, ww = frames.shape[:3]
+        ch = _channels(fmt)
+        return self._align("vs_aligner_align_batch", n, False, _p(frames), hh * ww * ch, n, ww, hh, ww * ch, fmt, MEM_HOST)
 
     def align_batch_device(self, ptr, n, w, h, fmt, stride=None, frame_stride=None):
         """device-resident frames (raw device pointer)"""
-        ch = 1 if fmt == FMT_GRAY8 else 3
-        stride = stride or w * ch
-        frame_stride = frame_stride or h * stride
-        out = (Transform * n)()
-        status = (C.c_int32 * n)()
-        _check(lib().vs_aligner_align_batch(self.h, _p(ptr), frame_stride, n, w, h, stride, fmt, MEM_DEVICE,
-                                            C.byref(self.params), out, status))
-        return list(status), list(out)
+        stride, frame_stride = _dense(w, h, fmt, stride, frame_stride)
+        return self._align("vs_aligner_align_batch", n, False, _p(ptr), frame_stride, n, w, h, stride, fmt, MEM_DEVICE)
 
     def align_clips(self, frames, n_clips, mem_ptr=None, w=None, h=None, fmt=None, raw=False):
         """frames: numpy (n_clips*fpc, h, w[,3]) (host) -- or pass mem_ptr/w/h/fmt with frames = total frame count
@@ -1456,14 +1427,8 @@ class Aligner:
             ptr, mem = _p(frames), MEM_HOST
         else:
             n, ptr, mem = int(frames), _p(mem_ptr), MEM_DEVICE
-        ch = 1 if fmt == FMT_GRAY8 else 3
-        out = (Transform * n)()
-        status = (C.c_int32 * n)()
-        _check(lib().vs_aligner_align_clips(self.h, ptr, h * w * ch, n_clips, n // n_clips, w, h, w * ch, fmt, mem,
-                                            C.byref(self.params), out, status))
-        if raw:
-            return status, out       # ctypes arrays: no per-frame Python objects (bench.py hands `out` to the warp call)
-        return list(status), list(out)
+        ch = _channels(fmt)
+        return self._align("vs_aligner_align_clips", n, raw, ptr, h * w * ch, n_clips, n // n_clips, w, h, w * ch, fmt, mem)
 
     def reset(self):
         _check(lib().vs_aligner_reset(self.h))
@@ -1488,20 +1453,21 @@ class Aligner:
         _check(lib().vs_aligner_get_info(self.h, i, C.byref(inf)))
         return inf
 
+    def _level_dims(self, level):
+        dims = [C.c_int() for _ in range(5)]
+        _check(lib().vs_aligner_level_dims(self.h, level, *(C.byref(v) for v in dims)))
+        return dict(zip(("w", "h", "tx", "ty", "ts"), (v.value for v in dims)))
+
     def level(self, i, level):
-        w, h, tx, ty, ts = (C.c_int() for _ in range(5))
-        _check(lib().vs_aligner_level_dims(self.h, level, *(C.byref(v) for v in (w, h, tx, ty, ts))))
-        w, h, tx, ty, ts = (v.value for v in (w, h, tx, ty, ts))
-        d = {"w": w, "h": h, "tx": tx, "ty": ty, "ts": ts}
-        img = np.empty((h, w), np.uint8)
+        d = self._level_dims(level)
+        img = np.empty((d["h"], d["w"]), np.uint8)
         _check(lib().vs_aligner_read_level_image(self.h, i, level, _p(img)))
         d["img"] = img
         return d
 
     def keyframe_tables(self, i, level):
-        w, h, tx, ty, ts = (C.c_int() for _ in range(5))
-        _check(lib().vs_aligner_level_dims(self.h, level, *(C.byref(v) for v in (w, h, tx, ty, ts))))
-        tx, ty = tx.value, ty.value
+        d = self._level_dims(level)
+        tx, ty = d["tx"], d["ty"]
         out = {"argmax": [], "jac": []}
         for s in (0, 1):
             am = np.empty((2, ty, tx), np.uint16)
@@ -1512,21 +1478,23 @@ class Aligner:
             out["jac"].append(jc)
         return out
 
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.vs_aligner_destroy(self.h)
-            self.h = None
+
+# ---- the stabilizer --------------------------------------------------------------------------
+def stabilizer_params(**kw):
+    """StabilizerParams with the library's defaults; a keyword that names a field of the aligner's parameters goes to p.aligner"""
+    p = _params(StabilizerParams, "vs_stabilizer_params_default", {})
+    _set_fields(p, kw, p.aligner)
+    return p
 
 
-class Stabilizer:
+class Stabilizer(_Handle):
     """VideoStabilizer (stabilizer.hpp:32-56) on the GPU engine."""
+    _create, _destroy = "vs_stabilizer_create", "vs_stabilizer_destroy"
 
     def __init__(self, device=0, select_mode=None, border_fill=0, deblur=0, deblur_params=None, denoise=0, denoise_params=None, fill_blend=None,
                  deflicker=0, deflicker_params=None, inpaint=0, rolling_shutter=None, lens=None, scene_cut=None, sharpen=None, output_size=None, **params):
         self.params = stabilizer_params(**params)
-        self.h = lib().vs_stabilizer_create(C.byref(self.params), device)
-        if not self.h:
-            raise VsError("vs_stabilizer_create failed: %s" % lib().vs_last_error().decode())
+        self._open(C.byref(self.params), device)
         if select_mode is not None:
             self.set_select_mode(select_mode)
         if border_fill:
@@ -1574,7 +1542,7 @@ class Stabilizer:
     def set_sharpen(self, params):
         """None: off; a SharpenParams (sharpen_params()): every output window is sharpened behind the warp by the phase of its own correction
         (VS_WARP_BILINEAR_CV handles)"""
-        _check(lib().vs_stabilizer_set_sharpen(self.h, C.byref(params) if params is not None else None))
+        _check(lib().vs_stabilizer_set_sharpen(self.h, _ref(params)))
 
     def get_sharpen(self):
         """None (off) or the SharpenParams in force"""
@@ -1584,7 +1552,7 @@ class Stabilizer:
     def set_scene_cut(self, params):
         """None: off; a SceneParams (scene_params()): every arriving frame is compared with its predecessor through the measured motion, and a
         frame that shows another scene ends every candidate list in front of it and starts a clean path"""
-        _check(lib().vs_stabilizer_set_scene_cut(self.h, C.byref(params) if params is not None else None))
+        _check(lib().vs_stabilizer_set_scene_cut(self.h, _ref(params)))
 
     def get_scene_cut(self):
         """None (off) or the SceneParams in force"""
@@ -1600,7 +1568,7 @@ class Stabilizer:
     def set_lens(self, params, w=0, h=0):
         """None (or the identity lens): off; else every arriving w x h frame is remapped through the lens map of `params` (LensParams) in front of
         everything: the aligner and every pass see corrected frames"""
-        _check(lib().vs_stabilizer_set_lens(self.h, C.byref(params) if params is not None else None, int(w), int(h)))
+        _check(lib().vs_stabilizer_set_lens(self.h, _ref(params), int(w), int(h)))
 
     def get_lens(self):
         """None (off) or (LensParams, w, h)"""
@@ -1611,8 +1579,7 @@ class Stabilizer:
     def set_rolling_shutter(self, readout):
         """None or 0: off; else every frame is corrected for a rolling shutter of that readout share (-1 .. 1) by the motion to the next input
         frame, before it is warped"""
-        p = RollingParams(float(readout)) if readout is not None else None
-        _check(lib().vs_stabilizer_set_rolling_shutter(self.h, C.byref(p) if p is not None else None))
+        _check(lib().vs_stabilizer_set_rolling_shutter(self.h, _ref(RollingParams(float(readout)) if readout is not None else None)))
 
     def get_rolling_shutter(self):
         p = RollingParams()
@@ -1629,7 +1596,7 @@ class Stabilizer:
     def set_deflicker(self, ahead, params=None):
         """0: off; 1 .. lag: every output frame's exposure is pulled to the mean exposure of itself and the next `ahead` input frames
         (params: DeflickerParams, None = defaults)"""
-        _check(lib().vs_stabilizer_set_deflicker(self.h, int(ahead), C.byref(params) if params is not None else None))
+        _check(lib().vs_stabilizer_set_deflicker(self.h, int(ahead), _ref(params)))
 
     def get_deflicker(self):
         return _check(lib().vs_stabilizer_get_deflicker(self.h))
@@ -1637,14 +1604,14 @@ class Stabilizer:
     def set_denoise(self, ahead, params=None):
         """0: off; 1 .. lag: every frame is averaged with what the next `ahead` input frames show at the same scene point before it is warped
         (params: DenoiseParams, None = defaults)"""
-        _check(lib().vs_stabilizer_set_denoise(self.h, int(ahead), C.byref(params) if params is not None else None))
+        _check(lib().vs_stabilizer_set_denoise(self.h, int(ahead), _ref(params)))
 
     def get_denoise(self):
         return _check(lib().vs_stabilizer_get_denoise(self.h))
 
     def set_deblur(self, ahead, params=None):
         """0: off; 1 .. lag: every frame is deblurred from the next `ahead` input frames before it is warped (params: DeblurParams, None = defaults)"""
-        _check(lib().vs_stabilizer_set_deblur(self.h, int(ahead), C.byref(params) if params is not None else None))
+        _check(lib().vs_stabilizer_set_deblur(self.h, int(ahead), _ref(params)))
 
     def deblur(self):
         return _check(lib().vs_stabilizer_get_deblur(self.h))
@@ -1689,9 +1656,9 @@ class Stabilizer:
     def wait_stream(self, stream_handle):
         _check(lib().vs_stabilizer_wait_stream(self.h, C.c_void_p(stream_handle)))
 
-    def process_batch(self, frames, out=None, fmt=None):
-        """frames (n,h,w,3) numpy.  returns (outputs (n,oh,ow,3), has_output list).  out: a buffer of that shape to reuse
-        (frames without an output are left untouched in it)"""
+    def _host_batch(self, frames, fmt, out=None):
+        """what the host forms of process_batch / process_clips begin with: frames (n,h,w,3) numpy -> the contiguous frames, n, h, w, the format
+        and the destination at the delivered size (`out`, if the caller gave one to reuse)"""
         frames = np.ascontiguousarray(frames)
         n, hh, ww = frames.shape[:3]
         fmt = _fmt_of(frames.dtype, 3) if fmt is None else fmt
@@ -1699,8 +1666,13 @@ class Stabilizer:
         if out is None:
             out = np.zeros((n, dh, dw, 3), frames.dtype)
         assert out.shape == (n, dh, dw, 3) and out.dtype == frames.dtype and out.flags.c_contiguous
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        return frames, n, hh, ww, fmt, out
+
+    def process_batch(self, frames, out=None, fmt=None):
+        """frames (n,h,w,3) numpy.  returns (outputs (n,oh,ow,3), has_output list).  out: a buffer of that shape to reuse
+        (frames without an output are left untouched in it)"""
+        frames, n, hh, ww, fmt, out = self._host_batch(frames, fmt, out)
+        has, ow, oh = _batch_outs(n)
         _check(lib().vs_stabilizer_process_batch(self.h, _p(frames), hh * ww * 3, n, ww, hh, ww * 3, fmt, MEM_HOST, _p(out),
                                                  out[0].size, has, C.byref(ow), C.byref(oh)))
         return out, list(has)
@@ -1708,8 +1680,7 @@ class Stabilizer:
     def process_batch_device(self, ptr, n, w, h, fmt, out_ptr):
         """dense device-resident frames in, dense delivered frames out (raw device pointers)"""
         dw, dh = self.delivered_size(w, h)
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        has, ow, oh = _batch_outs(n)
         r = _check(lib().vs_stabilizer_process_batch(self.h, _p(ptr), h * w * 3, n, w, h, w * 3, fmt, MEM_DEVICE, _p(out_ptr),
                                                      dh * dw * 3, has, C.byref(ow), C.byref(oh)))
         return r, list(has)
@@ -1727,28 +1698,21 @@ class Stabilizer:
         src.put(y, cb, cr)
         dst = _HostPlanes(n, dw, dh, y.dtype, sub if out_sub is None else out_sub, interleaved if out_interleaved == "same" else out_interleaved,
                           (cb is None) if out_mono is None else out_mono, None, None, 0 if guard is None else guard)
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        has, ow, oh = _batch_outs(n)
         _check(lib().vs_stabilizer_process_batch_ycbcr(self.h, C.byref(src.desc), n, ww, hh, fmt, MEM_HOST, C.byref(dst.desc), has, C.byref(ow), C.byref(oh)))
         assert (ow.value, oh.value) == (dw, dh)
         return dst.get(), list(has)
 
     def process_batch_ycbcr_device(self, planes, n, w, h, fmt, out_planes):
         """device-resident form: planes / out_planes are YcbcrPlanes of device addresses (ycbcr_planes) -> (outputs, has_output, out_w, out_h)"""
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        has, ow, oh = _batch_outs(n)
         r = _check(lib().vs_stabilizer_process_batch_ycbcr(self.h, C.byref(planes), n, w, h, fmt, MEM_DEVICE, C.byref(out_planes), has, C.byref(ow), C.byref(oh)))
         return r, list(has), ow.value, oh.value
 
     def process_clips(self, frames, n_clips, fmt=None):
         """frames (n_clips*fpc, h, w, 3) numpy: every clip through a fresh stabilizer, batched together"""
-        frames = np.ascontiguousarray(frames)
-        n, hh, ww = frames.shape[:3]
-        fmt = _fmt_of(frames.dtype, 3) if fmt is None else fmt
-        dw, dh = self.delivered_size(ww, hh)
-        out = np.zeros((n, dh, dw, 3), frames.dtype)
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        frames, n, hh, ww, fmt, out = self._host_batch(frames, fmt)
+        has, ow, oh = _batch_outs(n)
         _check(lib().vs_stabilizer_process_clips(self.h, _p(frames), hh * ww * 3, n_clips, n // n_clips, ww, hh, ww * 3, fmt, MEM_HOST,
                                                  _p(out), out[0].size, has, C.byref(ow), C.byref(oh)))
         return out, list(has)
@@ -1756,8 +1720,7 @@ class Stabilizer:
     def process_clips_device(self, ptr, n_clips, frames_per_clip, w, h, fmt, out_ptr):
         dw, dh = self.delivered_size(w, h)
         n = n_clips * frames_per_clip
-        has = (C.c_int32 * n)()
-        ow, oh = C.c_int(), C.c_int()
+        has, ow, oh = _batch_outs(n)
         r = _check(lib().vs_stabilizer_process_clips(self.h, _p(ptr), h * w * 3, n_clips, frames_per_clip, w, h, w * 3, fmt, MEM_DEVICE,
                                                      _p(out_ptr), dh * dw * 3, has, C.byref(ow), C.byref(oh)))
         return r, list(has)
@@ -1766,8 +1729,3 @@ class Stabilizer:
         m, a, s = Transform(), Transform(), C.c_int()
         lib().vs_stabilizer_state(self.h, C.byref(m), C.byref(a), C.byref(s))
         return m, a, bool(s.value)
-
-    def __del__(self):
-        if getattr(self, "h", None) and _lib is not None:
-            _lib.vs_stabilizer_destroy(self.h)
-            self.h = None
