@@ -1,13 +1,8 @@
-"""The deblur rule (include/vs_amd.h: vs_bgr_sharpness_batch / vs_bgr_deblur_batch) in numpy, in the kernels' operation order, and the
-engine's model of it.
+"""The deblur rule (include/vs_amd.h: vs_bgr_sharpness_batch / vs_bgr_deblur_batch) in numpy, in the kernels' operation order.
 
 Kernel level: int64 sums for the sharpness, float64 maps from cv_inverse_matrix (the host algebra: no device involved), float32 weights
 and accumulators with every operation rounded on its own (numpy never fuses a multiply into an add), candidates summed in list order.
-Engine level: the CPU oracle's Stabilizer frame by frame; state() after each process() gives T_i, its success flag and the accumulated
-correction of the frame just put out; the candidates of output frame k are the frames j = k+1 .. with
-
-    chain_j = compose(T_{k+1}, ..., T_j)                 # t_compose(t1, t2) = t1 then t2
-    cand_t  = inverse(chain_j)                           # the fill's F_j without the correction
+Engine level: tests/_engine_model.py (the candidate lists: its lookahead_candidates(); the pass is the first of its chain).
 
 Test infrastructure only: the only product code used is the host algebra (cv_inverse_matrix), handed in by the caller.
 """
@@ -107,73 +102,6 @@ def deblur_frame(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensiti
 def deblur_batch(cvinv, src, sharp, cand_frame, cand_t, bits, max_value, sensitivity=2.0, max_ratio=4.0):
     return np.stack([deblur_frame(cvinv, src, sharp, list(cf), list(ct), bits, max_value, sensitivity, max_ratio)
                      for cf, ct in zip(cand_frame, cand_t)])
-
-
-def measure(O, frames, **params):
-    """the oracle's Stabilizer over one clip -> (meas, succ, due): T_i and its success flag per input frame, and
-    {k: (plain output frame k, accumulated correction it was warped with)}"""
-    st = O.Stabilizer(**params)
-    lag = st.params.lag
-    meas, succ, due = [], [], {}
-    for i in range(len(frames)):
-        o = st.process(frames[i])
-        m, a, s = st.state()
-        meas.append(O.Transform.of(*m.tup()))
-        succ.append(s)
-        if o is not None:
-            due[i - lag] = (o, O.Transform.of(*a.tup()))
-    return meas, succ, due, st.params
-
-
-def candidates(O, k, ahead, meas, succ, mode="right"):
-    """(cand_frame, cand_t) of output frame k.  mode: "right"; "flip" = the chain un-inverted (the wrong direction)"""
-    cf, ct = [k], [O.Transform.of()]
-    chain = O.Transform.of()
-    for j in range(k + 1, k + ahead + 1):               # (frame k + lag has arrived when frame k is put out: all of them exist)
-        if j >= len(meas) or not succ[j]:
-            break
-        chain = O.t_compose(chain, meas[j])
-        cf.append(j)
-        ct.append(chain if mode == "flip" else O.t_inverse(chain))
-    while len(cf) < ahead + 1:
-        cf.append(-1)
-        ct.append(O.Transform.of())
-    return cf, ct
-
-
-def engine_model(O, cvinv, frames, ahead, bits=None, max_value=None, sensitivity=2.0, max_ratio=4.0, mode="right", fill=0, fill_ref=None, **params):
-    """the oracle's Stabilizer over one clip with every frame deblurred before its warp -> {k: output frame k} (cropped like the engine's)
-    and {k: the deblurred frame k}.  fill > 0 (fill_ref = tests/_fill_ref): the border fill behind it, its candidate 0 the deblurred frame"""
-    n, h, w, _ = frames.shape
-    if bits is None:
-        bits = 8 if frames.dtype == np.uint8 else 10
-    if max_value is None:
-        max_value = (1 << bits) - 1
-    meas, succ, due, p = measure(O, frames, **params)
-    crop = max(p.crop_pixels, 0)
-    sharp = sharpness_batch(frames, bits)
-    outs, sharpened = {}, {}
-    for k, (plain, acc) in due.items():
-        cf, ct = candidates(O, k, ahead, meas, succ, mode)
-        d = deblur_frame(cvinv, frames, sharp, cf, ct, bits, max_value, sensitivity, max_ratio)
-        sharpened[k] = d
-        Ck = O.t_inverse(acc)
-        if fill > 0:
-            ff, ft = [0], [Ck]
-            chain = O.Transform.of()
-            for j in range(k + 1, k + fill + 1):
-                if not succ[j]:
-                    break
-                chain = O.t_compose(chain, meas[j])
-                ff.append(j + 1)
-                ft.append(O.t_compose(O.t_inverse(chain), Ck))
-            stack = np.concatenate([d[None], frames])       # (frame 0 of the stack: the deblurred frame; frame j + 1: input frame j)
-            full = fill_ref.fill_frame(O, stack, ff, ft, p.warp_border, max_value)
-        else:
-            t = Ck if p.warp_mode == O.WARP_BILINEAR_CV else O.t_inverse(Ck)
-            full = O.bgr_image_warp(d, t, p.warp_mode, border=p.warp_border, max_value=max_value)
-        outs[k] = full[crop:h - crop, crop:w - crop] if crop else full
-    return outs, sharpened
 
 
 def blurred_clip(synth, w, h, n, seed, blurred, blur_px=6.0, angle=0.5, noise=1.0, bits=8, margin=128, **path_kw):

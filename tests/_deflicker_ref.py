@@ -6,14 +6,13 @@ oracle's vs_cv_inverse_matrix, with Python integers for the sums and the divisio
     apply_gain / gain_batch                    the applied sample
     whole_frame_stats                          NOT the rule: whole-frame channel sums laid out as statistics, for the quality pin that shows why
                                                the rule measures at the same scene points
-    window_gains                               the engine's candidate lists (tests/_deblur_ref.py's candidates(): chain_j = compose(T_{k+1} .. T_j),
-                                               cand_t = inverse(chain_j)) -> the gains of output frame k
+    window_gains                               the engine's candidate lists (tests/_engine_model.py's lookahead_candidates()) -> the gains of output frame k
 
 Test infrastructure only: nothing of the product is used here.
 """
 import numpy as np
 
-import _deblur_ref as DB
+from _engine_model import lookahead_candidates
 
 UNIT = 32768
 
@@ -142,6 +141,6 @@ def window_gains(O, frames, k, ahead, meas, succ, bits, step=4, mode="right", wh
     """the gains of output frame k from the window k .. k + ahead under the engine's candidate lists.  mode "flip": the chain un-inverted (the
     wrong direction); whole: whole-frame sums in place of the pair statistics"""
     _, h, w, _ = frames.shape
-    cf, ct = DB.candidates(O, k, ahead, meas, succ, mode)
+    cf, ct = lookahead_candidates(O, k, ahead, meas, succ, mode)
     rows = whole_frame_stats(frames, cf, step) if whole else stats_frame(O, frames, cf, ct, bits, step)
     return gains(rows, w, h, step)

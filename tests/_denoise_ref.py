@@ -1,17 +1,14 @@
-"""The temporal-denoise rule (include/vs_amd.h: vs_bgr_denoise_batch) in numpy on top of the CPU oracle, and the engine's model of it.
+"""The temporal-denoise rule (include/vs_amd.h: vs_bgr_denoise_batch) in numpy on top of the CPU oracle.
 
 Kernel level: every candidate's samples are the oracle's own WARP_BILINEAR_CV warp of that frame, its coverage is tests/_fill_ref.py's
 covered() (all four taps of the warp's integer source position inside the frame); weights, sums and the rounded division are int64 numpy
-(every value of the rule fits 32 bits: the header's bound, asserted here).  Engine level: the CPU oracle's Stabilizer frame by frame
-(tests/_deblur_ref.py's measure() and candidates(): chain_j = compose(T_{k+1}, ..., T_j), cand_t = inverse(chain_j)); order deblur, denoise,
-warp, fill.
+(every value of the rule fits 32 bits: the header's bound, asserted here).  Engine level: tests/_engine_model.py (the candidate lists: its
+lookahead_candidates(); the pass comes behind deblur: its target is the deblurred frame, its candidates stay the input frames).
 
-Test infrastructure only: nothing of the product is used here (the deblur stage of the engine model takes the host algebra's
-cv_inverse_matrix from its caller, as tests/_deblur_ref.py does).
+Test infrastructure only: nothing of the product is used here.
 """
 import numpy as np
 
-import _deblur_ref as DB
 import _fill_ref as FR
 
 
@@ -54,47 +51,6 @@ def denoise_frame(O, src, cand_frame, cand_t, bits, max_value, strength=24, want
 
 def denoise_batch(O, src, cand_frame, cand_t, bits, max_value, strength=24):
     return np.stack([denoise_frame(O, src, list(cf), list(ct), bits, max_value, strength) for cf, ct in zip(cand_frame, cand_t)])
-
-
-def engine_model(O, frames, ahead, strength=24, bits=None, max_value=None, mode="right", deblur=0, cvinv=None, fill=0, **params):
-    """the oracle's Stabilizer over one clip with every frame denoised before its warp -> {k: output frame k} (cropped like the engine's) and
-    {k: the denoised frame k}.  deblur > 0 (cvinv: the host algebra's cv_inverse_matrix): the deblur in front of it, default parameters -- the
-    denoise target is the deblurred frame, its candidates stay the input frames.  fill > 0: the border fill behind the warp, its candidate 0
-    the denoised frame, its other candidates the input frames."""
-    n, h, w, _ = frames.shape
-    if bits is None:
-        bits = 8 if frames.dtype == np.uint8 else 10
-    if max_value is None:
-        max_value = (1 << bits) - 1
-    meas, succ, due, p = DB.measure(O, frames, **params)
-    crop = max(p.crop_pixels, 0)
-    sharp = DB.sharpness_batch(frames, bits) if deblur else None
-    outs, clean = {}, {}
-    for k, (plain, acc) in due.items():
-        tgt = frames[k]
-        if deblur:
-            cf, ct = DB.candidates(O, k, deblur, meas, succ)
-            tgt = DB.deblur_frame(cvinv, frames, sharp, cf, ct, bits, max_value)
-        cf, ct = DB.candidates(O, k, ahead, meas, succ, mode)
-        d = denoise_target(O, tgt, [(frames[f], t) for f, t in zip(cf[1:], ct[1:]) if f >= 0], bits, max_value, strength)
-        clean[k] = d
-        Ck = O.t_inverse(acc)
-        if fill > 0:
-            ff, ft = [0], [Ck]
-            chain = O.Transform.of()
-            for j in range(k + 1, k + fill + 1):
-                if not succ[j]:
-                    break
-                chain = O.t_compose(chain, meas[j])
-                ff.append(j + 1)
-                ft.append(O.t_compose(O.t_inverse(chain), Ck))
-            stack = np.concatenate([d[None], frames])       # (frame 0 of the stack: the denoised frame; frame j + 1: input frame j)
-            full = FR.fill_frame(O, stack, ff, ft, p.warp_border, max_value)
-        else:
-            t = Ck if p.warp_mode == O.WARP_BILINEAR_CV else O.t_inverse(Ck)
-            full = O.bgr_image_warp(d, t, p.warp_mode, border=p.warp_border, max_value=max_value)
-        outs[k] = full[crop:h - crop, crop:w - crop] if crop else full
-    return outs, clean
 
 
 def noisy_clip(synth, w, h, n, seed, noise, bits=8, margin=128, **path_kw):

@@ -1,5 +1,5 @@
 """The fill's blend rule (include/vs_amd.h: vs_bgr_image_warp_fill_blend_batch) in numpy on top of tests/_fill_ref.py and the CPU oracle's
-WARP_BILINEAR_CV warp, and the engine's model of it.
+WARP_BILINEAR_CV warp.  Engine level: tests/_engine_model.py (blend=(feather, match) on its fill).
 
 Gains in Python ints (unbounded: the rule's unsigned 64-bit terms stay below 2^63, asserted), everything else in int64.  Candidates, coverage
 and positions are _fill_ref's; the plain value p and the sample q of a covering candidate are the oracle's own warp.
@@ -96,51 +96,3 @@ def blend_frame(O, src, cand_frame, cand_t, sums, feather, match, border, max_va
 
 def blend_batch(O, src, cand_frame, cand_t, sums, feather, match, border, max_value=None, roi=None):
     return np.stack([blend_frame(O, src, list(cf), list(ct), sums, feather, match, border, max_value, roi) for cf, ct in zip(cand_frame, cand_t)])
-
-
-def engine_candidates(O, frames, ahead, **params):
-    """the oracle's Stabilizer over one clip -> ({k: (plain output k, candidate frames, candidate transforms)}, roi, border): _fill_ref.engine_model's
-    candidate lists"""
-    n, h, w, _ = frames.shape
-    st = O.Stabilizer(**params)
-    lag, crop = st.params.lag, max(st.params.crop_pixels, 0)
-    assert st.params.warp_mode == O.WARP_BILINEAR_CV
-    meas, succ, due = [], [], {}
-    for i in range(n):
-        o = st.process(frames[i])
-        m, a, s = st.state()
-        meas.append(O.Transform.of(*m.tup()))
-        succ.append(s)
-        if o is not None:
-            due[i - lag] = (o, O.Transform.of(*a.tup()))
-    lists = {}
-    for k, (o, acc) in due.items():
-        Ck = O.t_inverse(acc)
-        cf, ct = [k], [Ck]
-        chain = O.Transform.of()
-        for j in range(k + 1, k + ahead + 1):
-            if not succ[j]:
-                break
-            chain = O.t_compose(chain, meas[j])
-            cf.append(j)
-            ct.append(O.t_compose(O.t_inverse(chain), Ck))
-        lists[k] = (o, cf, ct)
-    return lists, (crop, crop, w - 2 * crop, h - 2 * crop), st.params.warp_border
-
-
-def engine_model(O, frames, ahead, feather, match, max_value=None, want_masks=False, pixels=None, **params):
-    """the engine with the blend applied -> {k: output frame k} (cropped like the engine's; want_masks: blend_frame's tuple).  pixels: another
-    clip of the same shape whose samples (and sums) are used under the transforms measured on `frames`"""
-    if max_value is None:
-        max_value = 255 if frames.dtype == np.uint8 else 1023
-    lists, roi, border = engine_candidates(O, frames, ahead, **params)
-    pix = frames if pixels is None else pixels
-    sums = channel_sums(pix)
-    outs = {}
-    for k, (o, cf, ct) in lists.items():
-        res = blend_frame(O, pix, cf, ct, sums, feather, match, border, max_value, roi, want_masks=True)
-        if pixels is None:                           # outside the band the covered pixels are the plain output
-            keep = res[1] & ~res[3]
-            assert np.array_equal(np.where(keep[..., None], res[0], o), o), k
-        outs[k] = res if want_masks else res[0]
-    return outs

@@ -1,12 +1,8 @@
-"""The border-fill rule (include/vs_amd.h: vs_bgr_image_warp_fill_batch) in numpy on top of the CPU oracle, and the engine's model of it.
+"""The border-fill rule (include/vs_amd.h: vs_bgr_image_warp_fill_batch) in numpy on top of the CPU oracle.
 
 Kernel level: coverage from the oracle's output -> source matrix and cv::warpAffine's table rule (the coding of
 tests/test_bilinear_vs_opencv_fixed_point.py), every candidate's pixels from the oracle's own WARP_BILINEAR_CV warp, first covering candidate
-wins.  Engine level: the oracle's Stabilizer frame by frame; state() after each process() gives T_i, its success flag and the accumulated
-correction of the frame just put out; the candidates of output frame k are the frames j = k+1 .. with
-
-    chain_j = compose(T_{k+1}, ..., T_j)                 # t_compose(t1, t2) = t1 then t2
-    F_j     = compose(inverse(chain_j), C_k)             # C_k = inverse(accum): what frame k itself is warped with
+wins.  Engine level: tests/_engine_model.py (the candidate lists: its fill_candidates(); the fill takes the place of the plain warp).
 
 Test infrastructure only: nothing of the product is used here.
 """
@@ -100,40 +96,3 @@ def fill_frame(O, src, cand_frame, cand_t, border, max_value=None, roi=None, wan
 
 def fill_batch(O, src, cand_frame, cand_t, border, max_value=None, roi=None):
     return np.stack([fill_frame(O, src, list(cf), list(ct), border, max_value, roi) for cf, ct in zip(cand_frame, cand_t)])
-
-
-def engine_model(O, frames, ahead, flip=False, max_value=None, want_masks=False, **params):
-    """the oracle's Stabilizer over one clip with the fill applied -> {k: output frame k} (cropped like the engine's), and with
-    want_masks {k: (out, cov0, still_open)} on the cropped window.  flip: chain_j un-inverted (the wrong direction, for the direction test)"""
-    n, h, w, _ = frames.shape
-    st = O.Stabilizer(**params)
-    lag, crop = st.params.lag, max(st.params.crop_pixels, 0)
-    border = st.params.warp_border
-    assert st.params.warp_mode == O.WARP_BILINEAR_CV
-    if max_value is None:
-        max_value = 255 if frames.dtype == np.uint8 else 1023
-    meas, succ, due = [], [], {}
-    for i in range(n):
-        o = st.process(frames[i])
-        m, a, s = st.state()
-        meas.append(O.Transform.of(*m.tup()))
-        succ.append(s)
-        if o is not None:
-            due[i - lag] = (o, O.Transform.of(*a.tup()))
-    roi = (crop, crop, w - 2 * crop, h - 2 * crop)
-    outs = {}
-    for k, (o, acc) in due.items():
-        Ck = O.t_inverse(acc)
-        cf, ct = [k], [Ck]
-        chain = O.Transform.of()
-        for j in range(k + 1, k + ahead + 1):           # (frame k + lag has arrived when frame k is put out: all of them exist)
-            if not succ[j]:
-                break
-            chain = O.t_compose(chain, meas[j])
-            rel = chain if flip else O.t_inverse(chain)
-            cf.append(j)
-            ct.append(O.t_compose(rel, Ck))
-        res = fill_frame(O, frames, cf, ct, border, max_value, roi, want_masks=True)
-        assert np.array_equal(np.where(res[1][..., None], res[0], o), o), k       # covered pixels are the plain output
-        outs[k] = res if want_masks else res[0]
-    return outs

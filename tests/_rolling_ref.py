@@ -1,17 +1,15 @@
-"""The rolling-shutter rule (include/vs_amd.h: vs_bgr_rolling_batch) in numpy, and the engine's model of it.
+"""The rolling-shutter rule (include/vs_amd.h: vs_bgr_rolling_batch) in numpy.
 
 Kernel level: the row time, the row matrix and the int32 position are float64 / int64 numpy, one ufunc per rounded operation, in the order the
 rule writes them, on the helpers of tests/_fill_ref.py (cv_round_sat, wrap32); the two blends of VS_WARP_BILINEAR_CV are restated here (8-bit
-containers: int64; 16-bit containers: float32 ufuncs, one per rounded operation).  Engine level: the CPU oracle's Stabilizer frame by frame
-(tests/_deblur_ref.py's measure() and candidates()); order deblur, denoise, rolling shutter, warp, fill.
+containers: int64; 16-bit containers: float32 ufuncs, one per rounded operation).  Engine level: tests/_engine_model.py (the motion is
+candidate 1 of its lookahead_candidates(); the pass is the last before the warp).
 
 Test infrastructure only: nothing of the product is used here (cvinv, the host algebra's cv_inverse_matrix, comes from the caller, as in
 tests/_deblur_ref.py).
 """
 import numpy as np
 
-import _deblur_ref as DB
-import _denoise_ref as DN
 import _fill_ref as FR
 
 F32 = np.float32
@@ -89,58 +87,6 @@ def model_positions(M, w, h, rho):
     xs, ys = np.arange(w, dtype=np.float64)[None, :], np.arange(h, dtype=np.float64)[:, None]
     mx, my = M[0] * xs + M[1] * ys + M[2], M[3] * xs + M[4] * ys + M[5]
     return xs + tau * (mx - xs), ys + tau * (my - ys)
-
-
-def engine_model(O, frames, rho, cvinv=None, bits=None, max_value=None, deblur=0, denoise=0, fill=0, inpaint=None, **params):
-    """the oracle's Stabilizer over one clip with every frame corrected before its warp -> {k: output frame k} (cropped like the engine's) and
-    {k: the corrected frame k}.  Order: deblur (cvinv: the host algebra's cv_inverse_matrix; default parameters), denoise (default strength),
-    rolling shutter (the motion: candidate 1 of the look-ahead list, inverse(T_{k+1}); a failed alignment or lag 0: none), warp, fill (its
-    candidate 0 the corrected frame, its other candidates the input frames), inpaint (with the fill only: tests/_inpaint_ref.py's
-    inpaint(window, keep mask) on what the fill leaves open in the output window)."""
-    n, h, w, _ = frames.shape
-    if bits is None:
-        bits = 8 if frames.dtype == np.uint8 else 10
-    if max_value is None:
-        max_value = (1 << bits) - 1
-    if cvinv is None:
-        cvinv = O.cv_inverse_matrix
-    meas, succ, due, p = DB.measure(O, frames, **params)
-    crop = max(p.crop_pixels, 0)
-    sharp = DB.sharpness_batch(frames, bits) if deblur else None
-    outs, fixed = {}, {}
-    for k, (plain, acc) in due.items():
-        tgt = frames[k]
-        if deblur:
-            cf, ct = DB.candidates(O, k, deblur, meas, succ)
-            tgt = DB.deblur_frame(cvinv, frames, sharp, cf, ct, bits, max_value)
-        if denoise:
-            cf, ct = DB.candidates(O, k, denoise, meas, succ)
-            tgt = DN.denoise_target(O, tgt, [(frames[f], t) for f, t in zip(cf[1:], ct[1:]) if f >= 0], bits, max_value)
-        cf, ct = DB.candidates(O, k, min(1, p.lag), meas, succ)
-        M = cvinv(ct[1], w, h) if len(cf) > 1 and cf[1] >= 0 else None
-        d = rolling_frame(tgt, M, rho, max_value) if rho != 0 else tgt
-        fixed[k] = d
-        Ck = O.t_inverse(acc)
-        if fill > 0:
-            ff, ft = [0], [Ck]
-            chain = O.Transform.of()
-            for j in range(k + 1, k + fill + 1):
-                if not succ[j]:
-                    break
-                chain = O.t_compose(chain, meas[j])
-                ff.append(j + 1)
-                ft.append(O.t_compose(O.t_inverse(chain), Ck))
-            stack = np.concatenate([d[None], frames])       # (frame 0 of the stack: the corrected frame; frame j + 1: input frame j)
-            full, _, still_open = FR.fill_frame(O, stack, ff, ft, p.warp_border, max_value, want_masks=True)
-            if inpaint is not None:                         # (the window is the cropped frame: the push-pull sees nothing outside it)
-                full = full.copy()
-                win = (slice(crop, h - crop), slice(crop, w - crop))
-                full[win] = inpaint(full[win], ~still_open[win])
-        else:
-            t = Ck if p.warp_mode == O.WARP_BILINEAR_CV else O.t_inverse(Ck)
-            full = O.bgr_image_warp(d, t, p.warp_mode, border=p.warp_border, max_value=max_value)
-        outs[k] = full[crop:h - crop, crop:w - crop] if crop else full
-    return outs, fixed
 
 
 # ---- the direction test's renders ---------------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@ import gc
 import numpy as np
 import pytest
 
+from _stab_routes import walk
+
 pytestmark = pytest.mark.gpu
 
 W, H = 320, 240
@@ -27,42 +29,6 @@ def _tr(ts):
     return [t.tup() for t in ts]
 
 
-def _walk(vs, make, call, min_fired, throwing=False, stride=1):
-    """returns the number of allocations that were failed; asserts the contract at every one of them.
-    throwing: the allocation THROWS std::bad_alloc instead (vs_test_fail_alloc(-k)) -- a host allocation failing at that point of the call: the
-    exception must stop at the C boundary (VS_ERR_NOMEM = -5) and leave the handle exactly as an error code does; stride: every stride-th k only"""
-    vs.test_fail_alloc(0)
-    call(make())                                   # process-wide one-time allocations (the warp's parameter ring) happen here
-    ref = call(make())
-    fired, k = 0, 1
-    while True:
-        h = make()
-        vs.test_fail_alloc(-k if throwing else k)
-        try:
-            got, failed = call(h), False
-        except vs.VsError as e:
-            failed = True
-            if throwing:
-                assert "error -5" in str(e) and "bad_alloc" in str(e), str(e)
-            else:
-                assert "error -2" in str(e) and "out of memory" in str(e).lower(), str(e)
-        seen = vs.test_fail_alloc(0)
-        if not failed:
-            assert seen < k, "allocation %d was failed (of %d made) but the call reported success" % (k, seen)
-            assert got == ref
-            break
-        assert seen >= k
-        fired += 1
-        assert call(h) == ref, "k = %d: the call after the failed one differs from a fresh handle" % k
-        assert call(h) is not None                 # and the handle keeps working (state carried over from a good call)
-        del h
-        gc.collect()
-        k += stride
-        assert k < 400, "the walk does not terminate"
-    assert fired >= min_fired, "only %d allocations were failed: the hook does not see the call's allocations" % fired
-    return fired
-
-
 def test_align_batch_device_resident_every_allocation(gpu_vs):
     import torch
     vs = gpu_vs
@@ -72,7 +38,7 @@ def test_align_batch_device_resident_every_allocation(gpu_vs):
     def call(h):
         st, ts = h.align_batch_device(dev.data_ptr(), 6, W, H, vs.FMT_BGR8)
         return list(st), _tr(ts)
-    n = _walk(vs, lambda: vs.Aligner(device=0), call, min_fired=14)      # 10 device + 4 pinned slabs of ensure_capacity
+    n = walk(vs, lambda: vs.Aligner(device=0), call, min_fired=14)      # 10 device + 4 pinned slabs of ensure_capacity
     print("align_batch (device frames): %d allocations failed one by one" % n)
 
 
@@ -83,7 +49,7 @@ def test_align_batch_host_frames_and_host_selection(gpu_vs):
     def call(h):
         st, ts = h.align_batch(frames)
         return list(st), _tr(ts)
-    n = _walk(vs, lambda: vs.Aligner(device=0, select_mode=vs.SELECT_STL_HOST), call, min_fired=15)   # + the upload area
+    n = walk(vs, lambda: vs.Aligner(device=0, select_mode=vs.SELECT_STL_HOST), call, min_fired=15)   # + the upload area
     print("align_batch (host frames, host selection): %d allocations" % n)
 
 
@@ -94,7 +60,7 @@ def test_align_batch_phase_correlate_every_allocation(gpu_vs):
     def call(h):
         st, ts = h.align_batch(frames)
         return list(st), _tr(ts)
-    n = _walk(vs, lambda: vs.Aligner(device=0, phase_correlate=1), call, min_fired=20)    # + twiddles, spectra, surfaces, candidates
+    n = walk(vs, lambda: vs.Aligner(device=0, phase_correlate=1), call, min_fired=20)    # + twiddles, spectra, surfaces, candidates
     print("align_batch (phase_correlate): %d allocations" % n)
 
 
@@ -130,7 +96,7 @@ def test_stabilizer_process_batch_every_allocation(gpu_vs, bits):
     def call(s):
         out, has = s.process_batch(frames)
         return list(has), out.tobytes()
-    n = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, warp_mode=vs.WARP_LANCZOS2), call, min_fired=17)
+    n = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, warp_mode=vs.WARP_LANCZOS2), call, min_fired=17)
     print("process_batch (%d-bit host frames): %d allocations" % (bits, n))
 
 
@@ -149,7 +115,7 @@ def test_stabilizer_process_clips_device_every_allocation(gpu_vs):
         r, has = s.process_clips_device(dev.data_ptr(), n_clips, fpc, W, H, vs.FMT_BGR8, out.data_ptr())
         torch.cuda.synchronize()
         return r, list(has), out.cpu().numpy().tobytes()
-    n = _walk(vs, lambda: vs.Stabilizer(device=0, lag=5, crop_pixels=crop, warp_mode=vs.WARP_LANCZOS2), call, min_fired=14)
+    n = walk(vs, lambda: vs.Stabilizer(device=0, lag=5, crop_pixels=crop, warp_mode=vs.WARP_LANCZOS2), call, min_fired=14)
     print("process_clips (device frames, overlapped groups): %d allocations" % n)
 
 
@@ -164,13 +130,13 @@ def test_exceptions_stop_at_the_c_boundary(gpu_vs):
     def align(h):
         st, ts = h.align_batch_device(dev.data_ptr(), 6, W, H, vs.FMT_BGR8)
         return list(st), _tr(ts)
-    n1 = _walk(vs, lambda: vs.Aligner(device=0), align, min_fired=14, throwing=True)
+    n1 = walk(vs, lambda: vs.Aligner(device=0), align, min_fired=14, throwing=True)
     host = _clip(16, seed=7)
 
     def batch(s):
         out, has = s.process_batch(host)
         return list(has), out.tobytes()
-    n2 = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), batch, min_fired=17, throwing=True)   # (library defaults: the fixed-point bilinear warp)
+    n2 = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), batch, min_fired=17, throwing=True)   # (library defaults: the fixed-point bilinear warp)
     # device-resident clips: the overlapped groups (warps on their own stream, the next group's alignment prefetched; exclusive solver build beside this warp)
     n_clips, fpc, crop = 4, 34, 8
     cdev = torch.from_numpy(np.concatenate([_clip(fpc, seed=20 + c) for c in range(n_clips)])).cuda()
@@ -181,7 +147,7 @@ def test_exceptions_stop_at_the_c_boundary(gpu_vs):
         r, has = st.process_clips_device(cdev.data_ptr(), n_clips, fpc, W, H, vs.FMT_BGR8, cout.data_ptr())
         torch.cuda.synchronize()
         return r, list(has), cout.cpu().numpy().tobytes()
-    n3 = _walk(vs, lambda: vs.Stabilizer(device=0, lag=5, crop_pixels=crop), clips, min_fired=14, throwing=True)
+    n3 = walk(vs, lambda: vs.Stabilizer(device=0, lag=5, crop_pixels=crop), clips, min_fired=14, throwing=True)
     print("exceptions stopped at the boundary: %d (align_batch, device frames) + %d (process_batch, host frames) + %d (process_clips, device frames)" % (n1, n2, n3))
     # a kernel-level call: the parameter ring's first allocation on a fresh thread would be the natural case; any allocation will do
     vs.test_fail_alloc(-1)

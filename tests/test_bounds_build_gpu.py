@@ -10,31 +10,11 @@ bit-identical to the oracle (the checks change no arithmetic) and after every te
 (tests/conftest.py::_bounds_record_stays_clean).  The regular library carries no checks: its kernels are instruction for
 instruction what they were (compared with hipcc -S when the accessor was introduced).
 """
-import os
-import subprocess
-import sys
-
 import pytest
 
+from _bounds_child import bounds_lib, child_pytest, child_python
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "video_stabilizer_amd", "variants", "libvs_amd_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def bounds_lib(gpu_vs):
-    # (built on demand, and again whenever a source of the library is newer than it: a stale variant would test yesterday's kernels)
-    csrc = os.path.join(ROOT, "video_stabilizer_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc", ".cpp"))] + [os.path.join(ROOT, "include", "vs_amd.h")]
-    if not os.path.exists(LIB) or max(os.path.getmtime(f) for f in srcs) > os.path.getmtime(LIB):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "bounds"])
-    assert os.path.exists(LIB)
-    return LIB
-
-
-def _child(code, lib):
-    env = dict(os.environ, VS_AMD_LIB=lib, VS_BOUNDS_BUILD="1")
-    return subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r)\n" % ROOT + code], env=env, capture_output=True, text=True, timeout=600)
 
 
 def test_regular_library_has_no_bounds_build_entry_points(gpu_vs):
@@ -43,13 +23,12 @@ def test_regular_library_has_no_bounds_build_entry_points(gpu_vs):
 
 
 def test_the_checker_reports_a_deliberate_violation_and_does_not_execute_it(bounds_lib):
-    out = _child("from video_stabilizer_amd import capi\n"
-                 "L = capi.lib()\n"
-                 "print('clean', capi.debug_bounds_check())\n"
-                 "print('selftest', L.vs_debug_bounds_selftest())\n"
-                 "print('after', capi.debug_bounds_check())\n"
-                 "print('again', capi.debug_bounds_check())\n", bounds_lib)
-    assert out.returncode == 0, out.stderr[-2000:]
+    out = child_python("from video_stabilizer_amd import capi\n"
+                       "L = capi.lib()\n"
+                       "print('clean', capi.debug_bounds_check())\n"
+                       "print('selftest', L.vs_debug_bounds_selftest())\n"
+                       "print('after', capi.debug_bounds_check())\n"
+                       "print('again', capi.debug_bounds_check())\n", bounds_lib)
     assert "clean (0, '')" in out.stdout
     assert "selftest 202" in out.stdout                      # element 0 (100) stood in for element 11, + element 2 (102)
     assert "after (1, " in out.stdout and "site 900, index 11, limit 8, workgroup 0, thread 3" in out.stdout and "vs_capi.hip" in out.stdout
@@ -62,7 +41,6 @@ def test_selection_warp_phase_and_config_tests_pass_on_the_bounds_build_with_a_c
     global scratch, sixteen pairs with helper workgroups (exchange arrays), a 4K frame and the 10-bit stabilizer share at full size.
     (The WHOLE -m gpu suite has been run against this build once per round: profiles/r04_bounds_build.md.)"""
     # (every fresh device allocation of these runs starts filled with 0xA5: nothing compared against the oracle may depend on it)
-    env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1", VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")
     # (round 5: the separable Lanczos2 tests replace the contracted ones -- the two forms share the tile, fill and store code, the sweeps below still
     # draw all three -- and the fixed-point bilinear kernels' tests join: byte / word tiles, coordinate tables, sites 211-216; then the float-tile warps' table
     # tests and their hostile suite -- far rows, every staged shape's limits, the routes without extents and without tables: sites 201-209)
@@ -76,9 +54,5 @@ def test_selection_warp_phase_and_config_tests_pass_on_the_bounds_build_with_a_c
              "not allocation_failure and not video_test"),
             # the dense flow (sites 401-420): everything but the two-chunk 1080p clips, whose kernels and indices the smaller clips run as well
             (["tests/test_flow_gpu.py", "tests/test_flow_hostile_gpu.py", "tests/test_flow_routes_gpu.py"], "not chunked_clip and not two_chunks")]
-    for mods, expr in runs:
-        cmd = [sys.executable, "-m", "pytest", *mods, "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"] + (["-k", expr] if expr else [])
-        out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
-        tail = out.stdout[-3000:] + out.stderr[-1500:]
-        assert out.returncode == 0, tail
-        assert " passed" in out.stdout and "failed" not in out.stdout, tail
+    for mods, expr in runs:                         # (every module here is marked gpu as a whole)
+        child_pytest(mods, expr, bounds_lib, 1200, VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 
 import _deblur_ref as R
+import _engine_model as EM
 
 
 def _cvinv(vs):
@@ -120,7 +121,7 @@ def test_direction_and_centre_of_the_engine_maps(vs, oracle):
     O = oracle
     frames, truth, _ = R.blurred_clip(synth, **CLIP)
     k = CLIP["blurred"][0]
-    meas, succ, due, _ = R.measure(O, frames, lag=10, crop_pixels=0)
+    meas, succ, due, _ = EM.measure(O, frames, lag=10, crop_pixels=0)
     assert all(succ[k + 1:k + 5])
     S = R.sharpness_batch(frames, 8)
     assert all(S[j] > S[k] for j in range(k + 1, k + 5))
@@ -131,7 +132,7 @@ def test_direction_and_centre_of_the_engine_maps(vs, oracle):
         return M[:2].reshape(6)
 
     def ratio(mode, cvinv):
-        cf, ct = R.candidates(O, k, 4, meas, succ, mode)
+        cf, ct = EM.lookahead_candidates(O, k, 4, meas, succ, mode)
         d = R.deblur_frame(cvinv, frames, S, cf, ct, 8, 255)
         return np.abs(d.astype(np.float64) - truth[k]).mean() / e_in
     right, flip, other = ratio("right", _cvinv(vs)), ratio("flip", _cvinv(vs)), ratio("right", corner)
@@ -141,7 +142,7 @@ def test_direction_and_centre_of_the_engine_maps(vs, oracle):
     assert other > 0.7
     # the sharpest frame of its window comes back bit for bit
     ks = max(range(1, 10), key=lambda j: int(S[j]))
-    cf, ct = R.candidates(O, ks, 4, meas, succ)
+    cf, ct = EM.lookahead_candidates(O, ks, 4, meas, succ)
     if all(S[j] <= S[ks] for j in cf[1:] if j >= 0):
         assert np.array_equal(R.deblur_frame(_cvinv(vs), frames, S, cf, ct, 8, 255), frames[ks])
 

@@ -4,7 +4,6 @@ with candidates built here from a capi.Aligner's measurements: np.array_equal (t
 engine model on the CPU oracle's transforms: the two engines' transforms agree to about 1e-12 but not bit for bit and a nearest-sample decision
 can flip on that, so the gate there is DESIGN section 14's share -- at most 1e-4 of the samples differ.  Engine routes against each other:
 np.array_equal."""
-import gc
 import hashlib
 import os
 import subprocess
@@ -14,7 +13,8 @@ import numpy as np
 import pytest
 
 import _deblur_ref as R
-import _fill_ref as RF
+import _engine_model as EM
+from _stab_routes import assert_every_route_equals, frame_by_frame, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -203,25 +203,13 @@ def _plain_clip(n, seed, w=W, h=H, **kw):
     return synth.make_clip(w, h, n, seed=seed, channels=3, **kw)[0]
 
 
-def _frame_by_frame(st, frames, states=None):
-    out = {}
-    for i, f in enumerate(frames):
-        o = st.process(f)
-        if states is not None:
-            m, a, s = st.state()
-            states.append((m.tup(), a.tup(), s, o is not None))
-        if o is not None:
-            out[i - st.params.lag] = o
-    return out
-
-
 def test_deblur_leaves_transforms_state_and_has_output_alone(gpu_vs):
     vs = gpu_vs
     frames = _clip()
     kw = dict(device=0, lag=6, crop_pixels=8, select_mode=vs.SELECT_DEVICE)
     s_on, s_off = [], []
-    on = _frame_by_frame(vs.Stabilizer(deblur=4, **kw), frames, s_on)
-    off = _frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
+    on = frame_by_frame(vs.Stabilizer(deblur=4, **kw), frames, s_on)
+    off = frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
     assert s_on == s_off
     assert not all(s[2] for s in s_off[1:]), "the jump no longer makes the alignment fail: the test input has to change"
     assert sorted(on) == sorted(off) and any(not np.array_equal(on[k], off[k]) for k in on)
@@ -271,7 +259,7 @@ def _kernel_level(vs, frames, fmt, ahead, fill, kw):
     ks = sorted(due)
     cf, ct = [], []
     for k in ks:
-        f, t = R.candidates(vs, k, ahead, meas, status)
+        f, t = EM.lookahead_candidates(vs, k, ahead, meas, status)
         cf.append(f)
         ct.append(t)
     sharpened = vs.bgr_deblur_batch(frames, S, cf, ct, fmt=fmt)
@@ -280,15 +268,8 @@ def _kernel_level(vs, frames, fmt, ahead, fill, kw):
     for i, k in enumerate(ks):
         Ck = vs.t_inverse(due[k])
         if fill:
-            ff, ft = [0], [Ck]
-            chain = vs.Transform.of()
-            for j in range(k + 1, k + fill + 1):
-                if not status[j]:
-                    break
-                chain = vs.t_compose(chain, meas[j])
-                ff.append(j + 1)
-                ft.append(vs.t_compose(vs.t_inverse(chain), Ck))
-            ff += [-1] * (fill + 1 - len(ff))
+            ff, ft = EM.fill_candidates(vs, k, fill, meas, status, Ck)
+            ff = [0] + [j + 1 for j in ff[1:]] + [-1] * (fill + 1 - len(ff))
             ft += [vs.Transform.of()] * (fill + 1 - len(ft))
             stack = np.concatenate([sharpened[i][None], frames])
             outs[k] = vs.bgr_image_warp_fill_batch(stack, [ff], [ft], roi=roi, border=kw.get("warp_border", vs.BORDER_CONSTANT), max_value=maxv)[0]
@@ -309,7 +290,7 @@ def test_engine_equals_the_kernel_level_calls(gpu_vs, case):
         kw["warp_mode"] = vs.WARP_LANCZOS2
     fill = 3 if case == "cv_fill" else 0
     want = _kernel_level(vs, frames, fmt, 4, fill, kw)
-    got = _frame_by_frame(vs.Stabilizer(device=0, select_mode=vs.SELECT_DEVICE, deblur=4, border_fill=fill, **kw), frames)
+    got = frame_by_frame(vs.Stabilizer(device=0, select_mode=vs.SELECT_DEVICE, deblur=4, border_fill=fill, **kw), frames)
     assert sorted(got) == sorted(want)
     for k in want:
         assert np.array_equal(got[k], want[k]), (k, int((got[k] != want[k]).sum()))
@@ -321,9 +302,9 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, case):
     frames = _clip()
     fill = 3 if case == "cv_fill" else 0
     kw = dict(lag=6, crop_pixels=0 if fill else 8)
-    model, _ = R.engine_model(O, _cvinv(vs), frames, 4, fill=fill, fill_ref=RF, **kw)
-    got = _frame_by_frame(vs.Stabilizer(device=0, deblur=4, border_fill=fill, **kw), frames)
-    plain = _frame_by_frame(vs.Stabilizer(device=0, **kw), frames)
+    model = EM.engine_model(O, frames, cvinv=_cvinv(vs), deblur=4, fill=fill, **kw).outs
+    got = frame_by_frame(vs.Stabilizer(device=0, deblur=4, border_fill=fill, **kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(device=0, **kw), frames)
     assert sorted(got) == sorted(model)
     diff = sum(int((got[k] != model[k]).sum()) for k in model)
     total = sum(model[k].size for k in model)
@@ -336,7 +317,6 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, case):
 @pytest.mark.parametrize("case", ["cv", "cv_fill", "lanczos2_sep", "cv_10bit"])
 def test_every_route_gives_the_same_frames(gpu_vs, case):
     """process frame by frame == process_batch (one call; split calls) == device memory, with deblur on; a scene cut in the middle"""
-    import torch
     vs = gpu_vs
     bits = 10 if case == "cv_10bit" else 8
     frames = _clip(bits)
@@ -346,34 +326,8 @@ def test_every_route_gives_the_same_frames(gpu_vs, case):
         kw["border_fill"] = 3
     if case == "lanczos2_sep":
         kw["warp_mode"] = vs.WARP_LANCZOS2_SEP
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames)
-    out, has = vs.Stabilizer(**kw).process_batch(frames)
-    assert [i - 6 for i, hh in enumerate(has) if hh] == sorted(ref)
-    for i, hh in enumerate(has):
-        if hh:
-            assert np.array_equal(out[i], ref[i - 6]), i
-    # split calls: queued frames become buffers of the handle between the calls and are candidates of the next call's jobs
-    st = vs.Stabilizer(**kw)
-    pos = 0
-    for m in (3, 1, 9, 2, 11, n - 26):
-        o, hs = st.process_batch(frames[pos:pos + m])
-        for i, hh in enumerate(hs):
-            if hh:
-                assert np.array_equal(o[i], ref[pos + i - 6]), (pos, i)
-        pos += m
-    assert pos == n
-    # device-resident frames
-    fmt = vs.FMT_BGR8 if bits == 8 else vs.FMT_BGR10
-    dev = torch.from_numpy(frames.view(np.int16) if bits != 8 else frames).cuda()
-    dout = torch.zeros((n, H - 16, W - 16, 3), dtype=dev.dtype, device="cuda")
-    st = vs.Stabilizer(**kw)
-    r, hs = st.process_batch_device(dev.data_ptr(), n, W, H, fmt, dout.data_ptr())
-    torch.cuda.synchronize()
-    res = dout.cpu().numpy().view(frames.dtype)
-    assert r == len(ref)
-    for i, hh in enumerate(hs):
-        if hh:
-            assert np.array_equal(res[i], ref[i - 6]), i
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames)
+    assert_every_route_equals(vs, kw, frames, ref, (3, 1, 9, 2, 11, n - 26))
 
 
 @pytest.mark.parametrize("fill", [0, 3])
@@ -414,7 +368,7 @@ def test_process_clips_and_size_change(gpu_vs):
     n_clips, fpc = 4, 34
     clips = [_plain_clip(fpc, 20 + c) for c in range(n_clips)]
     kw = dict(device=0, lag=5, crop_pixels=8, deblur=4)
-    ref = [_frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
+    ref = [frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
     allf = np.concatenate(clips)
     out, has = vs.Stabilizer(**kw).process_clips(allf, n_clips)
     dev = torch.from_numpy(allf).cuda()
@@ -434,44 +388,9 @@ def test_process_clips_and_size_change(gpu_vs):
     st = vs.Stabilizer(**kw)
     for f in clips[0][:9]:
         st.process(f)
-    got = _frame_by_frame(st, small)
-    want = _frame_by_frame(vs.Stabilizer(**kw), small)
+    got = frame_by_frame(st, small)
+    want = frame_by_frame(vs.Stabilizer(**kw), small)
     assert sorted(got) == sorted(want) and all(np.array_equal(got[k], want[k]) for k in want)
-
-
-def _walk(vs, make, call, min_fired, throwing):
-    """the protocol of tests/test_alloc_failure_gpu.py: every allocation of the call failed once; the call reports it, the next call on the handle
-    equals a fresh handle's, the handle keeps working"""
-    vs.test_fail_alloc(0)
-    call(make())
-    ref = call(make())
-    fired, k = 0, 1
-    while True:
-        h = make()
-        vs.test_fail_alloc(-k if throwing else k)
-        try:
-            got, failed = call(h), False
-        except vs.VsError as e:
-            failed = True
-            if throwing:
-                assert "error -5" in str(e) and "bad_alloc" in str(e), str(e)
-            else:
-                assert "error -2" in str(e) and "out of memory" in str(e).lower(), str(e)
-        seen = vs.test_fail_alloc(0)
-        if not failed:
-            assert seen < k, "allocation %d was failed (of %d made) but the call reported success" % (k, seen)
-            assert got == ref
-            break
-        assert seen >= k
-        fired += 1
-        assert call(h) == ref, "k = %d: the call after the failed one differs from a fresh handle" % k
-        assert call(h) is not None
-        del h
-        gc.collect()
-        k += 1
-        assert k < 400, "the walk does not terminate"
-    assert fired >= min_fired, "only %d allocations were failed" % fired
-    return fired
 
 
 @pytest.mark.parametrize("throwing", [False, True])
@@ -482,8 +401,8 @@ def test_deblurred_process_batch_survives_every_allocation_failure(gpu_vs, throw
     def call(s):
         out, has = s.process_batch(frames)
         return list(has), out.tobytes()
-    plain = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), call, 1, throwing)
-    n = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, deblur=3, border_fill=2), call, plain + 2, throwing)
+    plain = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), call, 1, throwing)
+    n = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, deblur=3, border_fill=2), call, plain + 2, throwing)
     print("deblurred process_batch: %d allocations failed one by one (%s); %d without deblur" % (n, "throwing" if throwing else "error code", plain))
 
 

@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
-import _deblur_ref as DB
+import _engine_model as EM
 import _deflicker_ref as R
 
 FORMATS = ((np.uint8, 8, 255), (np.uint16, 10, 1023), (np.uint16, 12, 4095), (np.uint16, 16, 65535))
@@ -163,7 +163,7 @@ def clean_clip(oracle):
     def get(seed):
         if seed not in cache:
             clean, _ = synth.make_clip(320, 240, 40, seed=seed, channels=3)
-            meas, succ, _, _ = DB.measure(oracle, clean, lag=10, crop_pixels=0)
+            meas, succ, _, _ = EM.measure(oracle, clean, lag=10, crop_pixels=0)
             cache[seed] = (clean, meas, succ)
         return cache[seed]
     return get
@@ -213,7 +213,7 @@ def test_quality_pin_pan_and_direction(oracle):
     Measured with this restatement: the rule 227, whole-frame sums 876, wrong direction 1393 (of 32768: 0.7 %, 2.7 %, 4.3 %)."""
     O = oracle
     frames = pan_clip()
-    meas, succ, _, _ = DB.measure(O, frames, lag=10, crop_pixels=0)
+    meas, succ, _, _ = EM.measure(O, frames, lag=10, crop_pixels=0)
     assert all(succ[1:])
 
     def dev(**kw):

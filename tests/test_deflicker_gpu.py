@@ -10,9 +10,9 @@ import sys
 import numpy as np
 import pytest
 
-import _deblur_ref as DB
+import _engine_model as EM
 import _deflicker_ref as R
-from test_deblur_gpu import _frame_by_frame, _walk
+from _stab_routes import frame_by_frame, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -295,7 +295,7 @@ def _kernel_level(vs, O, frames, fmt, ahead, step, off, lag):
     status, meas = vs.Aligner(device=0, select_mode=vs.SELECT_DEVICE).align_batch(frames, fmt=fmt)
     p = vs.deflicker_params(step=step)
     ks = sorted(off)
-    lists = [DB.candidates(vs, k, ahead, meas, status) for k in ks]
+    lists = [EM.lookahead_candidates(vs, k, ahead, meas, status) for k in ks]
     ended_early = sum(l[0][-1] < 0 for l in lists)
     st = vs.exposure_stats_batch(frames, [l[0] for l in lists], [l[1] for l in lists], params=p, fmt=fmt)
     want_s = R.stats_batch(O, frames, [l[0] for l in lists], [[_o(O, t) for t in l[1]] for l in lists], bits, step)
@@ -330,12 +330,12 @@ def test_every_route_equals_the_kernel_level_calls(gpu_vs, oracle, case):
     kw = _case_kw(vs, case)
     crop = kw["crop_pixels"]
     s_on, s_off = [], []
-    off = _frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
+    off = frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
     want, gains, ended_early = _kernel_level(vs, O, frames, fmt, 4, 4, off, LAG)
     assert ended_early > 0, "the fall no longer makes an alignment fail: the test input has to change"
     assert (gains[:, 3] == 4).sum() > 5 and (np.abs(gains[:, :3].astype(np.int64) - UNIT) > 300).any()
     kw = dict(kw, deflicker=4)
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames, s_on)
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames, s_on)
     assert s_on == s_off                                             # transforms, state and has_output do not depend on the setting
     assert sorted(ref) == sorted(want)
     for k in want:
@@ -396,8 +396,8 @@ def test_switching_in_mid_clip_and_a_reset(gpu_vs):
     for f in frames[:9]:
         st.process(f)
     st.reset()
-    got = _frame_by_frame(st, frames[14:])
-    want = _frame_by_frame(vs.Stabilizer(deflicker=4, **kw), frames[14:])
+    got = frame_by_frame(st, frames[14:])
+    want = frame_by_frame(vs.Stabilizer(deflicker=4, **kw), frames[14:])
     assert sorted(got) == sorted(want) and len(want) > 3 and all(np.array_equal(got[k], want[k]) for k in want)
 
 
@@ -446,7 +446,7 @@ def test_process_clips_and_size_change(gpu_vs, case):
     if case == "all_passes":
         kw.update(border_fill=3, fill_blend=(2, 1), crop_pixels=0, deblur=3, denoise=2)
     crop = kw["crop_pixels"]
-    ref = [_frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
+    ref = [frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
     allf = np.concatenate(clips)
     out, has = vs.Stabilizer(**kw).process_clips(allf, n_clips)
     dev = torch.from_numpy(allf).cuda()
@@ -455,7 +455,7 @@ def test_process_clips_and_size_change(gpu_vs, case):
     torch.cuda.synchronize()
     dres = dout.cpu().numpy()
     assert has == dhas
-    off = _frame_by_frame(vs.Stabilizer(**dict(kw, deflicker=0)), clips[0])
+    off = frame_by_frame(vs.Stabilizer(**dict(kw, deflicker=0)), clips[0])
     assert any(not np.array_equal(off[k], ref[0][k]) for k in off)   # the pass does something on these clips
     for c in range(n_clips):
         for i in range(fpc):
@@ -467,8 +467,8 @@ def test_process_clips_and_size_change(gpu_vs, case):
     st = vs.Stabilizer(**kw)
     for f in clips[0][:9]:
         st.process(f)
-    got = _frame_by_frame(st, small)
-    want = _frame_by_frame(vs.Stabilizer(**kw), small)
+    got = frame_by_frame(st, small)
+    want = frame_by_frame(vs.Stabilizer(**kw), small)
     assert sorted(got) == sorted(want) and len(want) > 3 and all(np.array_equal(got[k], want[k]) for k in want)
 
 
@@ -497,7 +497,7 @@ def test_deflickered_process_batch_survives_every_allocation_failure(gpu_vs, thr
         return vs.test_fail_alloc(0)
     n_never, n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(off_again), allocations(lambda: vs.Stabilizer(deflicker=3, **kw))
     assert n_off == n_never and n_on == n_off + 1
-    on = _walk(vs, lambda: vs.Stabilizer(deflicker=3, **kw), call, n_on, throwing)
+    on = walk(vs, lambda: vs.Stabilizer(deflicker=3, **kw), call, n_on, throwing)
     print("deflickered process_batch: %d allocations failed one by one (%s); %d with deflicker off" % (on, "throwing" if throwing else "error code", n_off))
     assert on == n_on
 

@@ -11,7 +11,7 @@ import pytest
 
 import _denoise_direct as D
 import _denoise_ref as R
-import _deblur_ref as DB
+import _engine_model as EM
 import _fill_ref as FR
 
 FORMATS = ((np.uint8, 8, 255), (np.uint16, 10, 1023), (np.uint16, 16, 65535))
@@ -135,12 +135,12 @@ def test_direction_of_the_engine_maps(oracle, case):
     O = oracle
     frames, truth, _ = R.noisy_clip(synth, 320, 240, 20, noise=4.0, **DIRECTION[case])
     k = 4
-    meas, succ, due, _ = DB.measure(O, frames, lag=10, crop_pixels=0)
+    meas, succ, due, _ = EM.measure(O, frames, lag=10, crop_pixels=0)
     assert all(succ[k + 1:k + 5])
     e_in = np.abs(frames[k].astype(np.float64) - truth[k]).mean()
 
     def ratio(mode):
-        cf, ct = DB.candidates(O, k, 4, meas, succ, mode)
+        cf, ct = EM.lookahead_candidates(O, k, 4, meas, succ, mode)
         assert all(f >= 0 for f in cf)
         d = R.denoise_frame(O, frames, cf, ct, 8, 255, 24)
         return np.abs(d.astype(np.float64) - truth[k]).mean() / e_in

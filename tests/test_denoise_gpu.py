@@ -11,9 +11,10 @@ import sys
 import numpy as np
 import pytest
 
-import _deblur_ref as DB
 import _denoise_ref as R
-from test_deblur_gpu import _frame_by_frame, _plain_clip, _walk
+import _engine_model as EM
+from _stab_routes import assert_every_route_equals, frame_by_frame, walk
+from test_deblur_gpu import _plain_clip
 
 pytestmark = pytest.mark.gpu
 
@@ -191,8 +192,8 @@ def test_denoise_leaves_transforms_state_and_has_output_alone(gpu_vs):
     frames = _clip()
     kw = dict(device=0, lag=5, crop_pixels=8, select_mode=vs.SELECT_DEVICE)
     s_on, s_off = [], []
-    on = _frame_by_frame(vs.Stabilizer(denoise=4, **kw), frames, s_on)
-    off = _frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
+    on = frame_by_frame(vs.Stabilizer(denoise=4, **kw), frames, s_on)
+    off = frame_by_frame(vs.Stabilizer(**kw), frames, s_off)
     assert s_on == s_off
     assert not all(s[2] for s in s_off[1:]), "the jump no longer makes the alignment fail: the test input has to change"
     assert sorted(on) == sorted(off) and any(not np.array_equal(on[k], off[k]) for k in on)
@@ -225,8 +226,8 @@ def test_denoise_off_is_the_plain_stabilizer_and_a_reset_ends_the_list(gpu_vs):
     for f in frames[:9]:
         st.process(f)
     st.reset()
-    got = _frame_by_frame(st, frames[9:])
-    want = _frame_by_frame(vs.Stabilizer(denoise=4, **kw), frames[9:])
+    got = frame_by_frame(st, frames[9:])
+    want = frame_by_frame(vs.Stabilizer(denoise=4, **kw), frames[9:])
     assert sorted(got) == sorted(want) and len(want) > 3 and all(np.array_equal(got[k], want[k]) for k in want)
 
 
@@ -249,26 +250,19 @@ def _kernel_level(vs, frames, fmt, ahead, deblur, fill, kw):
     targets = frames[ks]
     if deblur:
         S = vs.sharpness_batch(frames, fmt=fmt)
-        lists = [DB.candidates(vs, k, deblur, meas, status) for k in ks]
+        lists = [EM.lookahead_candidates(vs, k, deblur, meas, status) for k in ks]
         targets = vs.bgr_deblur_batch(frames, S, [l[0] for l in lists], [l[1] for l in lists], fmt=fmt)
     roi = (crop, crop, w - 2 * crop, h - 2 * crop)
     outs = {}
     for i, k in enumerate(ks):
-        cf, ct = DB.candidates(vs, k, ahead, meas, status)
+        cf, ct = EM.lookahead_candidates(vs, k, ahead, meas, status)
         ended_early += cf[-1] < 0
         stack = np.concatenate([targets[i][None], frames])          # (frame 0 of the stack: the target; frame j + 1: input frame j)
         clean = vs.denoise_batch(stack, [[0] + [f + 1 if f >= 0 else -1 for f in cf[1:]]], [ct], fmt=fmt)[0]
         Ck = vs.t_inverse(due[k])
         if fill:
-            ff, ft = [0], [Ck]
-            chain = vs.Transform.of()
-            for j in range(k + 1, k + fill + 1):
-                if not status[j]:
-                    break
-                chain = vs.t_compose(chain, meas[j])
-                ff.append(j + 1)
-                ft.append(vs.t_compose(vs.t_inverse(chain), Ck))
-            ff += [-1] * (fill + 1 - len(ff))
+            ff, ft = EM.fill_candidates(vs, k, fill, meas, status, Ck)
+            ff = [0] + [j + 1 for j in ff[1:]] + [-1] * (fill + 1 - len(ff))
             ft += [vs.Transform.of()] * (fill + 1 - len(ft))
             stack = np.concatenate([clean[None], frames])
             outs[k] = vs.bgr_image_warp_fill_batch(stack, [ff], [ft], roi=roi, border=kw.get("warp_border", vs.BORDER_CONSTANT), max_value=maxv)[0]
@@ -293,49 +287,22 @@ def _case_kw(case):
 def test_every_route_equals_the_kernel_level_calls(gpu_vs, case):
     """process frame by frame == process_batch (one call; split calls) == device memory == the kernel-level calls, with and without the fill,
     with and without deblur, once with a Lanczos2 warp; a scene cut in the middle"""
-    import torch
     vs = gpu_vs
     bits = 10 if case == "cv_10bit" else 8
     frames = _clip(bits)
     n = len(frames)
     fmt = vs.FMT_BGR8 if bits == 8 else vs.FMT_BGR10
     kw = _case_kw(case)
-    crop = kw["crop_pixels"]
     want = _kernel_level(vs, frames, fmt, 4, kw.get("deblur", 0), kw.get("border_fill", 0),
                          {k: v for k, v in kw.items() if k not in ("deblur", "border_fill")})
     kw = dict(device=0, select_mode=vs.SELECT_DEVICE, denoise=4, **kw)
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames)
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames)
     assert sorted(ref) == sorted(want)
     for k in want:
         assert np.array_equal(ref[k], want[k]), (k, int((ref[k] != want[k]).sum()))
-    off = _frame_by_frame(vs.Stabilizer(**dict(kw, denoise=0)), frames)
+    off = frame_by_frame(vs.Stabilizer(**dict(kw, denoise=0)), frames)
     assert sum(int((ref[k] != off[k]).sum()) for k in ref) > 0.2 * sum(ref[k].size for k in ref)      # the pass did something
-    out, has = vs.Stabilizer(**kw).process_batch(frames)
-    assert [i - 5 for i, hh in enumerate(has) if hh] == sorted(ref)
-    for i, hh in enumerate(has):
-        if hh:
-            assert np.array_equal(out[i], ref[i - 5]), i
-    # split calls: queued frames become buffers of the handle between the calls and are candidates of the next call's jobs
-    st = vs.Stabilizer(**kw)
-    pos = 0
-    for m in (3, 1, 9, 2, n - 15):
-        o, hs = st.process_batch(frames[pos:pos + m])
-        for i, hh in enumerate(hs):
-            if hh:
-                assert np.array_equal(o[i], ref[pos + i - 5]), (pos, i)
-        pos += m
-    assert pos == n
-    # device-resident frames
-    dev = torch.from_numpy(frames.view(np.int16) if bits != 8 else frames).cuda()
-    dout = torch.zeros((n, H - 2 * crop, W - 2 * crop, 3), dtype=dev.dtype, device="cuda")
-    st = vs.Stabilizer(**kw)
-    r, hs = st.process_batch_device(dev.data_ptr(), n, W, H, fmt, dout.data_ptr())
-    torch.cuda.synchronize()
-    res = dout.cpu().numpy().view(frames.dtype)
-    assert r == len(ref)
-    for i, hh in enumerate(hs):
-        if hh:
-            assert np.array_equal(res[i], ref[i - 5]), i
+    assert_every_route_equals(vs, kw, frames, ref, (3, 1, 9, 2, n - 15))
 
 
 @pytest.mark.parametrize("case", ["cv", "cv_fill_deblur"])
@@ -345,9 +312,9 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, case):
     kw = _case_kw(case)
     fill, deblur = kw.pop("border_fill", 0), kw.pop("deblur", 0)
     cvinv = lambda t, w, h: vs.cv_inverse_matrix(vs.Transform.of(*t.tup()), w, h)
-    model, _ = R.engine_model(O, frames, 4, deblur=deblur, cvinv=cvinv, fill=fill, **kw)
-    got = _frame_by_frame(vs.Stabilizer(device=0, denoise=4, deblur=deblur, border_fill=fill, **kw), frames)
-    plain = _frame_by_frame(vs.Stabilizer(device=0, deblur=deblur, border_fill=fill, **kw), frames)
+    model = EM.engine_model(O, frames, cvinv=cvinv, deblur=deblur, denoise=4, fill=fill, **kw).outs
+    got = frame_by_frame(vs.Stabilizer(device=0, denoise=4, deblur=deblur, border_fill=fill, **kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(device=0, deblur=deblur, border_fill=fill, **kw), frames)
     assert sorted(got) == sorted(model)
     diff = sum(int((got[k] != model[k]).sum()) for k in model)
     total = sum(model[k].size for k in model)
@@ -402,7 +369,7 @@ def test_process_clips_and_size_change(gpu_vs, case):
     clips = [_plain_clip(fpc, 20 + c) for c in range(n_clips)]
     kw = dict(dict(device=0, lag=5, crop_pixels=8, denoise=4), **CLIP_CASES[case])
     crop = kw["crop_pixels"]
-    ref = [_frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
+    ref = [frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
     allf = np.concatenate(clips)
     out, has = vs.Stabilizer(**kw).process_clips(allf, n_clips)
     dev = torch.from_numpy(allf).cuda()
@@ -411,7 +378,7 @@ def test_process_clips_and_size_change(gpu_vs, case):
     torch.cuda.synchronize()
     dres = dout.cpu().numpy()
     assert has == dhas
-    off = _frame_by_frame(vs.Stabilizer(**dict(kw, denoise=0)), clips[0])
+    off = frame_by_frame(vs.Stabilizer(**dict(kw, denoise=0)), clips[0])
     assert any(not np.array_equal(off[k], ref[0][k]) for k in off)   # the pass does something on these clips
     for c in range(n_clips):
         for i in range(fpc):
@@ -424,8 +391,8 @@ def test_process_clips_and_size_change(gpu_vs, case):
     st = vs.Stabilizer(**kw)
     for f in clips[0][:9]:
         st.process(f)
-    got = _frame_by_frame(st, small)
-    want = _frame_by_frame(vs.Stabilizer(**kw), small)
+    got = frame_by_frame(st, small)
+    want = frame_by_frame(vs.Stabilizer(**kw), small)
     assert sorted(got) == sorted(want) and all(np.array_equal(got[k], want[k]) for k in want)
 
 
@@ -446,10 +413,10 @@ def test_denoised_process_batch_survives_every_allocation_failure(gpu_vs, throwi
         s = vs.Stabilizer(denoise=3, **kw)
         s.set_denoise(0)
         return s
-    plain = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), call, 1, throwing)
-    never = _walk(vs, lambda: vs.Stabilizer(**kw), call, plain + 2, throwing)
-    off = _walk(vs, off_again, call, plain + 2, throwing)
-    on = _walk(vs, lambda: vs.Stabilizer(denoise=3, **kw), call, plain + 3, throwing)
+    plain = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8), call, 1, throwing)
+    never = walk(vs, lambda: vs.Stabilizer(**kw), call, plain + 2, throwing)
+    off = walk(vs, off_again, call, plain + 2, throwing)
+    on = walk(vs, lambda: vs.Stabilizer(denoise=3, **kw), call, plain + 3, throwing)
     print("denoised process_batch: %d allocations failed one by one (%s); %d with denoise off, %d plain" % (on, "throwing" if throwing else "error code", off, plain))
     assert off == never
     assert on == off + 1

@@ -6,6 +6,7 @@ import ctypes
 
 import numpy as np
 
+import _engine_model as EM
 import _fill_blend_ref as B
 import _fill_ref as R
 
@@ -138,8 +139,10 @@ def test_quality_pin_exposure_drift(oracle):
     def expose(clip):
         return np.clip(np.rint(clip.astype(np.float64) * gain[:, None, None, None]), 0, 255).astype(np.uint8)
     dim, dim_big = expose(small), expose(big)
-    lists, roi, border = B.engine_candidates(O, small, 4, crop_pixels=0, lag=10)
-    assert roi == (0, 0, W, H)
+    meas, succ, due, p = EM.measure(O, small, crop_pixels=0, lag=10)
+    assert p.warp_mode == O.WARP_BILINEAR_CV and max(p.crop_pixels, 0) == 0
+    lists = {k: EM.fill_candidates(O, k, 4, meas, succ, O.t_inverse(acc)) for k, (_, acc) in due.items()}
+    border = p.warp_border
     sums = B.channel_sums(dim)
     st = O.Stabilizer(crop_pixels=0, lag=10)
     accum = {}
@@ -151,7 +154,7 @@ def test_quality_pin_exposure_drift(oracle):
 
     def run(feather, match):
         errs, steps = [], []
-        for k, (_, cf, ct) in lists.items():
+        for k, (cf, ct) in lists.items():
             out, cov0, still_open, _ = B.blend_frame(O, dim, cf, ct, sums, feather, match, border, 255, want_masks=True)
             o, t = out.astype(np.int64), truth[k]
             fm = ~cov0 & ~still_open

@@ -4,17 +4,18 @@ np.array_equal, on device memory inside guard bands (tests/_fill_blend_direct.py
 (tests/test_fill_gpu.py: at most 1e-4 of the samples differ, the two engines' transforms agree to about 1e-12 but not bit for bit); against the
 model fed with the engine's OWN transforms (they agree exactly): np.array_equal.  Engine routes against each other: np.array_equal."""
 import ctypes as C
-import gc
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import _engine_model as EM
 import _fill_blend_direct as D
 import _fill_blend_ref as B
 import _fill_ref as R
 import _hostile_maps as HM
+from _stab_routes import assert_every_route_equals, frame_by_frame, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -229,10 +230,6 @@ def _cut_clip(bits):
     return np.concatenate([a[:14], _clip(3, 77, bits), a[14:]])
 
 
-def _frame_by_frame(st, frames):
-    return {i - st.params.lag: o for i, o in ((i, st.process(f)) for i, f in enumerate(frames)) if o is not None}
-
-
 def _own_transform_model(vs, O, frames, ahead, feather, match, maxv, plain=None, **kw):
     """the engine frame by frame, and the rule applied with the engine's OWN measurements and corrections (vs_stabilizer_state after every frame,
     composed with the library's vs_transform_compose / _inverse as the engine composes them) -> (engine outputs, modelled outputs).  plain: {k: the
@@ -251,15 +248,7 @@ def _own_transform_model(vs, O, frames, ahead, feather, match, maxv, plain=None,
     sums = B.channel_sums(frames)
     want = {}
     for k, acc in due.items():
-        Ck = vs.t_inverse(acc)
-        cf, ct = [k], [Ck]
-        chain = vs.Transform.of()
-        for j in range(k + 1, k + ahead + 1):
-            if not succ[j]:
-                break
-            chain = vs.t_compose(chain, meas[j])
-            cf.append(j)
-            ct.append(vs.t_compose(vs.t_inverse(chain), Ck))
+        cf, ct = EM.fill_candidates(vs, k, ahead, meas, succ, vs.t_inverse(acc))
         want[k] = B.blend_frame(O, frames, cf, [O.Transform.of(*t.tup()) for t in ct], sums, feather, match, st.params.warp_border, maxv,
                                 (crop, crop, w - 2 * crop, h - 2 * crop), plain=None if plain is None else plain[k])
     return got, want
@@ -272,7 +261,7 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, bits, crop):
     frames = _cut_clip(bits)
     maxv = 255 if bits == 8 else 1023
     kw = dict(lag=6, crop_pixels=crop)
-    model = B.engine_model(O, frames, 4, 4, 1, want_masks=True, **kw)
+    model = EM.engine_model(O, frames, fill=4, blend=(4, 1), want_masks=True, **kw)
     st = O.Stabilizer(**kw)
     succ = []
     for f in frames:
@@ -280,9 +269,10 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, bits, crop):
         succ.append(st.state()[2])
     assert not all(succ[1:]), "the scene cut no longer makes the alignment fail: the test input has to change"
     got, own = _own_transform_model(vs, O, frames, 4, 4, 1, maxv, **kw)
-    assert sorted(got) == sorted(model) == sorted(own)
+    assert sorted(got) == sorted(model.outs) == sorted(own)
     diff = total = filled = banded = 0
-    for k, (want, cov0, still_open, band) in model.items():
+    for k, want in model.outs.items():
+        cov0, still_open, band = model.masks[k]
         diff += int((got[k] != want).sum())
         total += want.size
         filled += int((~cov0 & ~still_open).sum())
@@ -294,7 +284,7 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, bits, crop):
     # where the transforms agree (the engine's own): bit for bit
     bad = [k for k in own if not np.array_equal(got[k], own[k])]
     assert not bad, bad
-    plain = _frame_by_frame(vs.Stabilizer(device=0, border_fill=4, **kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(device=0, border_fill=4, **kw), frames)
     if crop == 0:
         assert any(not np.array_equal(plain[k], got[k]) for k in got)
 
@@ -307,37 +297,15 @@ def test_every_route_gives_the_same_frames(gpu_vs, bits):
     frames = _cut_clip(bits)
     n = len(frames)
     kw = dict(device=0, lag=6, crop_pixels=8, border_fill=4, fill_blend=(3, 1))
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames)
-    plain = _frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=8, border_fill=4), frames)
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=8, border_fill=4), frames)
     assert any(not np.array_equal(ref[k], plain[k]) for k in ref)
-    out, has = vs.Stabilizer(**kw).process_batch(frames)
-    assert [i - 6 for i, hh in enumerate(has) if hh] == sorted(ref)
-    for i, hh in enumerate(has):
-        if hh:
-            assert np.array_equal(out[i], ref[i - 6]), i
-    st = vs.Stabilizer(**kw)                                         # split calls: queued frames keep their sums between the calls
-    pos = 0
-    for m in (3, 1, 9, 2, 11, n - 26):
-        o, hs = st.process_batch(frames[pos:pos + m])
-        for i, hh in enumerate(hs):
-            if hh:
-                assert np.array_equal(o[i], ref[pos + i - 6]), (pos, i)
-        pos += m
-    assert pos == n
+    assert_every_route_equals(vs, kw, frames, ref, (3, 1, 9, 2, 11, n - 26))         # (split calls: queued frames keep their sums between the calls)
     fmt = vs.FMT_BGR8 if bits == 8 else vs.FMT_BGR10
-    dev = torch.from_numpy(frames.view(np.int16) if bits != 8 else frames).cuda()
-    dout = torch.zeros((n, H - 16, W - 16, 3), dtype=dev.dtype, device="cuda")
-    r, hs = vs.Stabilizer(**kw).process_batch_device(dev.data_ptr(), n, W, H, fmt, dout.data_ptr())
-    torch.cuda.synchronize()
-    res = dout.cpu().numpy().view(frames.dtype)
-    assert r == len(ref)
-    for i, hh in enumerate(hs):
-        if hh:
-            assert np.array_equal(res[i], ref[i - 6]), i
     # process_clips: two clips, host and device memory
     half = n // 2
     two = np.concatenate([frames[:half], frames[:half]])
-    one = _frame_by_frame(vs.Stabilizer(**kw), frames[:half])
+    one = frame_by_frame(vs.Stabilizer(**kw), frames[:half])
     out, has = vs.Stabilizer(**kw).process_clips(two, 2)
     dev = torch.from_numpy(two.view(np.int16) if bits != 8 else two).cuda()
     dout = torch.zeros((2 * half, H - 16, W - 16, 3), dtype=dev.dtype, device="cuda")
@@ -387,14 +355,14 @@ def test_with_deblur_and_denoise_on(gpu_vs, oracle):
     vs, O = gpu_vs, oracle
     frames = _cut_clip(8)
     base = dict(device=0, lag=6, crop_pixels=0, border_fill=4, deblur=3, denoise=3)
-    plain = _frame_by_frame(vs.Stabilizer(**base), frames)
+    plain = frame_by_frame(vs.Stabilizer(**base), frames)
     off = vs.Stabilizer(**base)
     off.set_fill_blend(0, 0)
-    got = _frame_by_frame(off, frames)
+    got = frame_by_frame(off, frames)
     assert all(np.array_equal(got[k], plain[k]) for k in plain)
-    nofill = _frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=0, deblur=3, denoise=3), frames)
+    nofill = frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=0, deblur=3, denoise=3), frames)
     for blend in ((4, 0), (4, 1), (0, 1)):
-        ref = _frame_by_frame(vs.Stabilizer(fill_blend=blend, **base), frames)
+        ref = frame_by_frame(vs.Stabilizer(fill_blend=blend, **base), frames)
         assert any(not np.array_equal(ref[k], plain[k]) for k in ref), blend
         out, has = vs.Stabilizer(fill_blend=blend, **base).process_batch(frames)
         for i, hh in enumerate(has):
@@ -449,41 +417,6 @@ def test_switching_on_mid_clip_equals_on_from_the_start(gpu_vs):
             assert np.array_equal(o2[i], ref[13 + i]), i
 
 
-def _walk(vs, make, call, min_fired, throwing):
-    """the protocol of tests/test_alloc_failure_gpu.py: every allocation of the call failed once; the call reports it, the next call on the handle
-    equals a fresh handle's, the handle keeps working"""
-    vs.test_fail_alloc(0)
-    call(make())
-    ref = call(make())
-    fired, k = 0, 1
-    while True:
-        h = make()
-        vs.test_fail_alloc(-k if throwing else k)
-        try:
-            got, failed = call(h), False
-        except vs.VsError as e:
-            failed = True
-            if throwing:
-                assert "error -5" in str(e) and "bad_alloc" in str(e), str(e)
-            else:
-                assert "error -2" in str(e) and "out of memory" in str(e).lower(), str(e)
-        seen = vs.test_fail_alloc(0)
-        if not failed:
-            assert seen < k, "allocation %d was failed (of %d made) but the call reported success" % (k, seen)
-            assert got == ref
-            break
-        assert seen >= k
-        fired += 1
-        assert call(h) == ref, "k = %d: the call after the failed one differs from a fresh handle" % k
-        assert call(h) is not None
-        del h
-        gc.collect()
-        k += 1
-        assert k < 400, "the walk does not terminate"
-    assert fired >= min_fired, "only %d allocations were failed" % fired
-    return fired
-
-
 @pytest.mark.parametrize("throwing", [False, True])
 def test_blended_process_batch_survives_every_allocation_failure(gpu_vs, throwing):
     """(the plain fill's walk fails 17 allocations at least on this call: tests/test_fill_gpu.py; the sums' block is one more)"""
@@ -493,7 +426,7 @@ def test_blended_process_batch_survives_every_allocation_failure(gpu_vs, throwin
     def call(s):
         out, has = s.process_batch(frames)
         return list(has), out.tobytes()
-    n = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, border_fill=3, fill_blend=(3, 1)), call, 18, throwing)
+    n = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, border_fill=3, fill_blend=(3, 1)), call, 18, throwing)
     print("blended process_batch: %d allocations failed one by one (%s)" % (n, "throwing" if throwing else "error code"))
 
 

@@ -6,6 +6,7 @@ import ctypes
 
 import numpy as np
 
+import _engine_model as EM
 import _fill_ref as R
 
 
@@ -75,10 +76,11 @@ def test_candidate_chain_direction(oracle):
         for i in range(N):
             if st.process(small[i]) is not None:
                 accum[i - 10] = O.Transform.of(*st.state()[1].tup())
-        outs = R.engine_model(O, small, 4, flip=flip, want_masks=True, crop_pixels=0, lag=10)
-        assert sorted(outs) == sorted(accum)
+        m = EM.engine_model(O, small, fill=4, flip=flip, want_masks=True, crop_pixels=0, lag=10)
+        assert sorted(m.outs) == sorted(accum)
         errs, unc, filled = [], 0, 0
-        for k, (out, cov0, still_open) in outs.items():
+        for k, out in m.outs.items():
+            cov0, still_open = m.masks[k]
             truth = O.bgr_image_warp(big[k], O.t_inverse(accum[k]), O.WARP_BILINEAR_CV, border=O.BORDER_CONSTANT)[P:-P, P:-P]
             fm = ~cov0 & ~still_open
             unc += int((~cov0).sum())

@@ -4,14 +4,15 @@ two engines agree to about 1e-12 but not bit for bit and a coverage decision can
 most 1e-4 of the samples differ (the reference alone moves no sample under a 1e-12 perturbation of every transform and at most 4.4e-7 of them
 under 1e-9).  Engine routes against each other: np.array_equal."""
 import ctypes as C
-import gc
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import _engine_model as EM
 import _fill_ref as R
+from _stab_routes import assert_every_route_equals, frame_by_frame, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -179,10 +180,6 @@ def _cut_clip(bits):
     return np.concatenate([a[:14], _clip(3, 77, bits), a[14:]])
 
 
-def _frame_by_frame(st, frames):
-    return {i - st.params.lag: o for i, o in ((i, st.process(f)) for i, f in enumerate(frames)) if o is not None}
-
-
 def test_fill_off_after_on_is_a_handle_that_never_had_it(gpu_vs):
     vs = gpu_vs
     frames = _clip(30, 5)
@@ -211,17 +208,18 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, bits, crop):
     vs, O = gpu_vs, oracle
     frames = _cut_clip(bits)
     kw = dict(lag=6, crop_pixels=crop)
-    model = R.engine_model(O, frames, 4, want_masks=True, **kw)
+    model = EM.engine_model(O, frames, fill=4, want_masks=True, **kw)
     st = O.Stabilizer(**kw)
     succ = []
     for f in frames:
         st.process(f)
         succ.append(st.state()[2])
     assert not all(succ[1:]), "the scene cut no longer makes the alignment fail: the test input has to change"
-    got = _frame_by_frame(vs.Stabilizer(device=0, border_fill=4, **kw), frames)
-    assert sorted(got) == sorted(model)
+    got = frame_by_frame(vs.Stabilizer(device=0, border_fill=4, **kw), frames)
+    assert sorted(got) == sorted(model.outs)
     diff = total = filled = 0
-    for k, (want, cov0, still_open) in model.items():
+    for k, want in model.outs.items():
+        cov0, still_open = model.masks[k]
         diff += int((got[k] != want).sum())
         total += want.size
         filled += int((~cov0 & ~still_open).sum())
@@ -235,41 +233,14 @@ def test_engine_equals_the_engine_model(gpu_vs, oracle, bits, crop):
 @pytest.mark.parametrize("bits", [8, 10])
 def test_every_route_gives_the_same_frames(gpu_vs, bits):
     """process frame by frame == process_batch (one call; split calls) == device memory, with the fill on; a scene cut in the middle"""
-    import torch
     vs = gpu_vs
     frames = _cut_clip(bits)
     n = len(frames)
     kw = dict(device=0, lag=6, crop_pixels=8, border_fill=4)
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames)
-    plain = _frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=8), frames)
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(device=0, lag=6, crop_pixels=8), frames)
     assert any(not np.array_equal(ref[k], plain[k]) for k in ref)
-    out, has = vs.Stabilizer(**kw).process_batch(frames)
-    assert [i - 6 for i, hh in enumerate(has) if hh] == sorted(ref)
-    for i, hh in enumerate(has):
-        if hh:
-            assert np.array_equal(out[i], ref[i - 6]), i
-    # split calls: queued frames become buffers of the handle between the calls and are candidates of the next call's jobs
-    st = vs.Stabilizer(**kw)
-    pos = 0
-    for m in (3, 1, 9, 2, 11, n - 26):
-        o, hs = st.process_batch(frames[pos:pos + m])
-        for i, hh in enumerate(hs):
-            if hh:
-                assert np.array_equal(o[i], ref[pos + i - 6]), (pos, i)
-        pos += m
-    assert pos == n
-    # device-resident frames
-    fmt = vs.FMT_BGR8 if bits == 8 else vs.FMT_BGR10
-    dev = torch.from_numpy(frames.view(np.int16) if bits != 8 else frames).cuda()
-    dout = torch.zeros((n, H - 16, W - 16, 3), dtype=dev.dtype, device="cuda")
-    st = vs.Stabilizer(**kw)
-    r, hs = st.process_batch_device(dev.data_ptr(), n, W, H, fmt, dout.data_ptr())
-    torch.cuda.synchronize()
-    res = dout.cpu().numpy().view(frames.dtype)
-    assert r == len(ref)
-    for i, hh in enumerate(hs):
-        if hh:
-            assert np.array_equal(res[i], ref[i - 6]), i
+    assert_every_route_equals(vs, kw, frames, ref, (3, 1, 9, 2, 11, n - 26))
 
 
 def test_chunked_and_pipelined_batches(gpu_vs, monkeypatch):
@@ -305,7 +276,7 @@ def test_process_clips_and_size_change(gpu_vs):
     n_clips, fpc = 4, 34
     clips = [_clip(fpc, 20 + c) for c in range(n_clips)]
     kw = dict(device=0, lag=5, crop_pixels=8, border_fill=4)
-    ref = [_frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
+    ref = [frame_by_frame(vs.Stabilizer(**kw), c) for c in clips]
     allf = np.concatenate(clips)
     out, has = vs.Stabilizer(**kw).process_clips(allf, n_clips)
     dev = torch.from_numpy(allf).cuda()
@@ -325,44 +296,9 @@ def test_process_clips_and_size_change(gpu_vs):
     st = vs.Stabilizer(**kw)
     for f in clips[0][:9]:
         st.process(f)
-    got = _frame_by_frame(st, small)
-    want = _frame_by_frame(vs.Stabilizer(**kw), small)
+    got = frame_by_frame(st, small)
+    want = frame_by_frame(vs.Stabilizer(**kw), small)
     assert sorted(got) == sorted(want) and all(np.array_equal(got[k], want[k]) for k in want)
-
-
-def _walk(vs, make, call, min_fired, throwing):
-    """the protocol of tests/test_alloc_failure_gpu.py: every allocation of the call failed once; the call reports it, the next call on the handle
-    equals a fresh handle's, the handle keeps working"""
-    vs.test_fail_alloc(0)
-    call(make())
-    ref = call(make())
-    fired, k = 0, 1
-    while True:
-        h = make()
-        vs.test_fail_alloc(-k if throwing else k)
-        try:
-            got, failed = call(h), False
-        except vs.VsError as e:
-            failed = True
-            if throwing:
-                assert "error -5" in str(e) and "bad_alloc" in str(e), str(e)
-            else:
-                assert "error -2" in str(e) and "out of memory" in str(e).lower(), str(e)
-        seen = vs.test_fail_alloc(0)
-        if not failed:
-            assert seen < k, "allocation %d was failed (of %d made) but the call reported success" % (k, seen)
-            assert got == ref
-            break
-        assert seen >= k
-        fired += 1
-        assert call(h) == ref, "k = %d: the call after the failed one differs from a fresh handle" % k
-        assert call(h) is not None
-        del h
-        gc.collect()
-        k += 1
-        assert k < 400, "the walk does not terminate"
-    assert fired >= min_fired, "only %d allocations were failed" % fired
-    return fired
 
 
 @pytest.mark.parametrize("throwing", [False, True])
@@ -373,7 +309,7 @@ def test_filled_process_batch_survives_every_allocation_failure(gpu_vs, throwing
     def call(s):
         out, has = s.process_batch(frames)
         return list(has), out.tobytes()
-    n = _walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, border_fill=3), call, 17, throwing)
+    n = walk(vs, lambda: vs.Stabilizer(device=0, lag=4, smoother_memory=2, crop_pixels=8, border_fill=3), call, 17, throwing)
     print("filled process_batch: %d allocations failed one by one (%s)" % (n, "throwing" if throwing else "error code"))
 
 

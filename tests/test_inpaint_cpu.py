@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import _engine_model as EM
 import _fill_ref as F
 import _inpaint_direct as D
 import _inpaint_ref as R
@@ -100,15 +101,16 @@ def test_quality_on_the_fills_own_scene(oracle):
     for i in range(N):
         if st.process(small[i]) is not None:
             accum[i - 10] = O.Transform.of(*st.state()[1].tup())
-    const = F.engine_model(O, small, 4, want_masks=True, crop_pixels=0, lag=10, warp_border=O.BORDER_CONSTANT)
-    clamp = F.engine_model(O, small, 4, want_masks=True, crop_pixels=0, lag=10, warp_border=O.BORDER_CLAMP)
+    const = EM.engine_model(O, small, fill=4, want_masks=True, crop_pixels=0, lag=10, warp_border=O.BORDER_CONSTANT)
+    clamp = EM.engine_model(O, small, fill=4, want_masks=True, crop_pixels=0, lag=10, warp_border=O.BORDER_CLAMP)
     err = {"inpaint": 0, "constant": 0, "clamp": 0}
     n_open = 0
-    for k, (out, _, still_open) in const.items():
+    for k, out in const.outs.items():
+        still_open = const.masks[k][1]
         truth = O.bgr_image_warp(big[k], O.t_inverse(accum[k]), O.WARP_BILINEAR_CV, border=O.BORDER_CONSTANT)[P:-P, P:-P].astype(np.int64)
-        assert np.array_equal(still_open, clamp[k][2])
+        assert np.array_equal(still_open, clamp.masks[k][1])
         n_open += 3 * int(still_open.sum())
-        for name, res in (("inpaint", R.inpaint(out, ~still_open)), ("constant", out), ("clamp", clamp[k][0])):
+        for name, res in (("inpaint", R.inpaint(out, ~still_open)), ("constant", out), ("clamp", clamp.outs[k])):
             err[name] += int(np.abs(res.astype(np.int64) - truth)[still_open].sum())
     assert n_open > 0
     mae = {k: v / n_open for k, v in err.items()}

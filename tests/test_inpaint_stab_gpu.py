@@ -1,8 +1,7 @@
 """The stabilizer's inpaint (include/vs_amd.h: vs_stabilizer_set_inpaint) on the GPU: every route gives the same bytes; on and off differ only
 where the model says nothing covers; the inpaint-on output IS the rule applied to the inpaint-off output under the model's still-open mask
-(tests/_inpaint_ref.py on tests/_fill_ref.py's engine model); the default crop pays nothing; the deflicker's gain stays last; allocation
+(tests/_inpaint_ref.py on tests/_engine_model.py's masks); the default crop pays nothing; the deflicker's gain stays last; allocation
 failures and poisoned fresh allocations.  Frames without zero samples throughout, so that a black border cannot coincide with a sample."""
-import gc
 import os
 import subprocess
 import sys
@@ -10,8 +9,9 @@ import sys
 import numpy as np
 import pytest
 
-import _fill_ref as F
+import _engine_model as EM
 import _inpaint_ref as R
+from _stab_routes import assert_every_route_equals, frame_by_frame, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +30,6 @@ def _cut_clip(bits):
     return np.concatenate([a[:14], _clip(3, 77, bits), a[14:]])
 
 
-def _frame_by_frame(st, frames):
-    return {i - st.params.lag: o for i, o in ((i, st.process(f)) for i, f in enumerate(frames)) if o is not None}
-
-
 @pytest.mark.parametrize("bits", [8, 10])
 def test_every_route_gives_the_same_frames(gpu_vs, bits):
     """process frame by frame == process_batch (one call; split calls) == device memory == process_clips (host, device), inpaint on"""
@@ -42,36 +38,15 @@ def test_every_route_gives_the_same_frames(gpu_vs, bits):
     frames = _cut_clip(bits)
     n = len(frames)
     kw = dict(device=0, lag=6, crop_pixels=0, border_fill=4, inpaint=1)
-    ref = _frame_by_frame(vs.Stabilizer(**kw), frames)
-    plain = _frame_by_frame(vs.Stabilizer(**dict(kw, inpaint=0)), frames)
+    ref = frame_by_frame(vs.Stabilizer(**kw), frames)
+    plain = frame_by_frame(vs.Stabilizer(**dict(kw, inpaint=0)), frames)
     assert any(not np.array_equal(ref[k], plain[k]) for k in ref)    # the pass did something
-    out, has = vs.Stabilizer(**kw).process_batch(frames)
-    assert [i - 6 for i, hh in enumerate(has) if hh] == sorted(ref)
-    for i, hh in enumerate(has):
-        if hh:
-            assert np.array_equal(out[i], ref[i - 6]), i
-    st = vs.Stabilizer(**kw)
-    pos = 0
-    for m in (3, 1, 9, 2, 11, n - 26):
-        o, hs = st.process_batch(frames[pos:pos + m])
-        for i, hh in enumerate(hs):
-            if hh:
-                assert np.array_equal(o[i], ref[pos + i - 6]), (pos, i)
-        pos += m
+    assert_every_route_equals(vs, kw, frames, ref, (3, 1, 9, 2, 11, n - 26))
     fmt = vs.FMT_BGR8 if bits == 8 else vs.FMT_BGR10
-    dev = torch.from_numpy(frames.view(np.int16) if bits != 8 else frames).cuda()
-    dout = torch.zeros((n, H, W, 3), dtype=dev.dtype, device="cuda")
-    r, hs = vs.Stabilizer(**kw).process_batch_device(dev.data_ptr(), n, W, H, fmt, dout.data_ptr())
-    torch.cuda.synchronize()
-    res = dout.cpu().numpy().view(frames.dtype)
-    assert r == len(ref)
-    for i, hh in enumerate(hs):
-        if hh:
-            assert np.array_equal(res[i], ref[i - 6]), i
     # two clips of 16 frames through process_clips: each equals the clip on a handle of its own
     fpc = 16
     two = np.ascontiguousarray(frames[:2 * fpc])
-    refs = [_frame_by_frame(vs.Stabilizer(**kw), two[:fpc]), _frame_by_frame(vs.Stabilizer(**kw), two[fpc:])]
+    refs = [frame_by_frame(vs.Stabilizer(**kw), two[:fpc]), frame_by_frame(vs.Stabilizer(**kw), two[fpc:])]
     out, has = vs.Stabilizer(**kw).process_clips(two, 2)
     dtwo = torch.from_numpy(two.view(np.int16) if bits != 8 else two).cuda()
     dout2 = torch.zeros((2 * fpc, H, W, 3), dtype=dtwo.dtype, device="cuda")
@@ -122,12 +97,13 @@ def test_inpaint_on_is_the_rule_on_the_inpaint_off_output(gpu_vs, oracle, bits, 
     vs, O = gpu_vs, oracle
     frames = _cut_clip(bits)
     kw = dict(lag=6, crop_pixels=0)
-    model = F.engine_model(O, frames, fill, want_masks=True, **kw)
-    off = _frame_by_frame(vs.Stabilizer(device=0, border_fill=fill, **kw), frames)
-    on = _frame_by_frame(vs.Stabilizer(device=0, border_fill=fill, inpaint=1, **kw), frames)
-    assert sorted(off) == sorted(model) == sorted(on)
+    model = EM.engine_model(O, frames, fill=fill, want_masks=True, **kw)
+    off = frame_by_frame(vs.Stabilizer(device=0, border_fill=fill, **kw), frames)
+    on = frame_by_frame(vs.Stabilizer(device=0, border_fill=fill, inpaint=1, **kw), frames)
+    assert sorted(off) == sorted(model.outs) == sorted(on)
     left_out, open_px, changed = [], 0, 0
-    for k, (want, _, still_open) in model.items():
+    for k, want in model.outs.items():
+        still_open = model.masks[k][1]
         if not np.array_equal(off[k], want):
             left_out.append(k)
             continue
@@ -136,7 +112,7 @@ def test_inpaint_on_is_the_rule_on_the_inpaint_off_output(gpu_vs, oracle, bits, 
         assert np.array_equal(on[k], R.inpaint(off[k], ~still_open)), k
         open_px += int(still_open.sum())
         changed += int((on[k] != off[k]).any(-1).sum())
-    print("%d-bit fill %d: %d frames, %d left out, %d open pixels, %d changed" % (bits, fill, len(model), len(left_out), open_px, changed))
+    print("%d-bit fill %d: %d frames, %d left out, %d open pixels, %d changed" % (bits, fill, len(model.outs), len(left_out), open_px, changed))
     assert len(left_out) <= 1, left_out
     assert open_px > 0 and 0.9 * open_px < changed <= open_px        # (no sample is zero: an inpainted pixel differs from a black one)
 
@@ -170,10 +146,10 @@ def test_the_deflickers_gain_stays_last(gpu_vs):
     frames = _clip(30, 5).astype(np.float64)
     frames = np.clip(frames * (0.8 + 0.15 * np.sin(np.arange(30) * 1.3))[:, None, None, None], 1, 255).astype(np.uint8)
     kw = dict(device=0, lag=6, crop_pixels=0, border_fill=2)
-    w_ = _frame_by_frame(vs.Stabilizer(**kw), frames)                              # warp
-    y_ = _frame_by_frame(vs.Stabilizer(deflicker=4, **kw), frames)                 # gain(warp)
-    z_ = _frame_by_frame(vs.Stabilizer(inpaint=1, **kw), frames)                   # inpaint(warp)
-    x_ = _frame_by_frame(vs.Stabilizer(inpaint=1, deflicker=4, **kw), frames)      # both
+    w_ = frame_by_frame(vs.Stabilizer(**kw), frames)                              # warp
+    y_ = frame_by_frame(vs.Stabilizer(deflicker=4, **kw), frames)                 # gain(warp)
+    z_ = frame_by_frame(vs.Stabilizer(inpaint=1, **kw), frames)                   # inpaint(warp)
+    x_ = frame_by_frame(vs.Stabilizer(inpaint=1, deflicker=4, **kw), frames)      # both
     checked = scaled = 0
     for k in w_:
         open_ = (z_[k] != w_[k]).any(-1)
@@ -188,41 +164,6 @@ def test_the_deflickers_gain_stays_last(gpu_vs):
             scaled += int((table[zi][known] != zi[known]).sum())
         assert np.array_equal(x_[k][~open_], y_[k][~open_])
     assert checked > 1000 and scaled > 0
-
-
-def _walk(vs, make, call, min_fired, throwing):
-    """the protocol of tests/test_alloc_failure_gpu.py: every allocation of the call failed once; the call reports it, the next call on the handle
-    equals a fresh handle's, the handle keeps working"""
-    vs.test_fail_alloc(0)
-    call(make())
-    ref = call(make())
-    fired, k = 0, 1
-    while True:
-        h = make()
-        vs.test_fail_alloc(-k if throwing else k)
-        try:
-            got, failed = call(h), False
-        except vs.VsError as e:
-            failed = True
-            if throwing:
-                assert "error -5" in str(e) and "bad_alloc" in str(e), str(e)
-            else:
-                assert "error -2" in str(e) and "out of memory" in str(e).lower(), str(e)
-        seen = vs.test_fail_alloc(0)
-        if not failed:
-            assert seen < k, "allocation %d was failed (of %d made) but the call reported success" % (k, seen)
-            assert got == ref
-            break
-        assert seen >= k
-        fired += 1
-        assert call(h) == ref, "k = %d: the call after the failed one differs from a fresh handle" % k
-        assert call(h) is not None
-        del h
-        gc.collect()
-        k += 1
-        assert k < 400, "the walk does not terminate"
-    assert fired >= min_fired, "only %d allocations were failed" % fired
-    return fired
 
 
 @pytest.mark.parametrize("throwing", [False, True])
@@ -243,7 +184,7 @@ def test_inpainted_process_batch_survives_every_allocation_failure(gpu_vs, throw
     allocations(lambda: vs.Stabilizer(**kw))                         # (the process-wide staging pool fills on the first call)
     n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(lambda: vs.Stabilizer(inpaint=1, **kw))
     assert n_on == n_off + 1                                         # the scratch block joins the protocol
-    fired = _walk(vs, lambda: vs.Stabilizer(inpaint=1, **kw), call, n_on, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(inpaint=1, **kw), call, n_on, throwing)
     print("inpainted process_batch: %d allocations failed one by one (%s)" % (fired, "throwing" if throwing else "error code"))
     assert fired == n_on
 

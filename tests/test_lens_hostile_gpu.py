@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import _lens_ref as L
-from test_inpaint_stab_gpu import _walk
+from _stab_routes import walk
 from test_lens_cpu import COEFFS
 
 pytestmark = pytest.mark.gpu
@@ -212,7 +212,7 @@ def test_corrected_process_batch_survives_every_allocation_failure(gpu_vs, throw
     allocations(lambda: vs.Stabilizer(**kw))                         # (the process-wide staging pool fills on the first call)
     n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(lambda: vs.Stabilizer(lens=(lens, 96, 64), **kw))
     assert n_on == n_off + 2                                         # the map and the staged span join the protocol (batch_in is there either way)
-    fired = _walk(vs, lambda: vs.Stabilizer(lens=(lens, 96, 64), **kw), call, n_on, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(lens=(lens, 96, 64), **kw), call, n_on, throwing)
     assert fired == n_on
 
 
@@ -229,4 +229,4 @@ def test_remap_batch_survives_every_allocation_failure(gpu_vs, throwing):
     def call(_):
         return vs.remap_batch(src, pos).tobytes()
     assert call(None) == want.tobytes()
-    _walk(vs, lambda: None, call, 0, throwing)
+    walk(vs, lambda: None, call, 0, throwing)

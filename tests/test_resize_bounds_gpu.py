@@ -3,39 +3,21 @@ store offsets go through VS_IDX, sites 637-648).  The resize modules run in a ch
 variants/libvs_amd_bounds.so, set up the way tests/test_ycbcr_bounds_gpu.py sets up its children: every result must still be bit-identical
 (the checks change no arithmetic) and after every test the bounds record must be clean (tests/conftest.py::_bounds_record_stays_clean).  The
 kernel-level modules run three times: with the form the library picks, and with each kernel form named through the test hooks."""
-import os
-import subprocess
-import sys
-
 import pytest
 
+from _bounds_child import bounds_lib, child_pytest, child_python
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "video_stabilizer_amd", "variants", "libvs_amd_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def bounds_lib(gpu_vs):
-    # (built on demand, and again whenever a source of the library is newer than it: a stale variant would test yesterday's kernels)
-    csrc = os.path.join(ROOT, "video_stabilizer_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc", ".cpp"))] + [os.path.join(ROOT, "include", "vs_amd.h")]
-    if not os.path.exists(LIB) or max(os.path.getmtime(f) for f in srcs) > os.path.getmtime(LIB):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "bounds"])
-    assert os.path.exists(LIB)
-    return LIB
 
 
 def test_the_bounds_build_carries_the_resize_record(bounds_lib):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from video_stabilizer_amd import capi\n"
+    code = ("from video_stabilizer_amd import capi\n"
             "import numpy as np\n"
             "src = np.arange(2 * 9 * 14 * 3, dtype=np.uint8).reshape(2, 9, 14, 3)\n"
             "capi.resize_batch(src, 5, 4, capi.RESIZE_AREA)\n"
             "capi.resize_batch(src, 20, 13, capi.RESIZE_LINEAR)\n"
-            "print('clean', capi.debug_bounds_check())\n" % ROOT)
-    env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
+            "print('clean', capi.debug_bounds_check())\n")
+    out = child_python(code, bounds_lib)
     assert "clean (0, '')" in out.stdout
 
 
@@ -44,16 +26,9 @@ def test_the_resize_modules_pass_on_the_bounds_build_with_a_clean_record(bounds_
     """the hostile module first, then the kernel-level grid, without the allocation-failure walks, the 65 537-frame case and the tests that
     start children of their own; with the library's own pick of the kernel form the stabilizer's module and the CPU module ride along"""
     # (every fresh device allocation of these runs starts filled with 0xA5: nothing compared against the restatement may depend on it)
-    env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1", VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")
-    env.pop("VS_TEST_RESIZE_FORM", None)
     mods = ["tests/test_resize_hostile_gpu.py", "tests/test_resize_gpu.py"]
     if form is None:
         mods += ["tests/test_resize_stab_gpu.py", "tests/test_resize_cpu.py"]
-    else:
-        env["VS_TEST_RESIZE_FORM"] = str(form)
     expr = "not allocation_failure and not fresh_allocations and not more_frames_than_a_grid and not scheduling_switch"
-    cmd = [sys.executable, "-m", "pytest", *mods, "-x", "-q", "-p", "no:cacheprovider", "-k", expr]
-    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
-    tail = out.stdout[-3000:] + out.stderr[-1500:]
-    assert out.returncode == 0, tail
-    assert " passed" in out.stdout and "failed" not in out.stdout, tail
+    child_pytest(mods, expr, bounds_lib, 1200, VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1",
+                 VS_TEST_RESIZE_FORM=None if form is None else str(form))         # (None: the variable is taken out of the child's environment)

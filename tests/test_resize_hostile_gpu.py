@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import _resize_ref as R
-from test_inpaint_stab_gpu import _walk
+from _stab_routes import walk
 from test_resize_gpu import FORMATS, dev_resize
 
 pytestmark = pytest.mark.gpu
@@ -110,4 +110,4 @@ def test_resize_batch_survives_every_allocation_failure(gpu_vs, throwing):
     def call(_):
         return vs.resize_batch(src, 101, 17, vs.RESIZE_AREA).tobytes()
     assert call(None) == want.tobytes()
-    _walk(vs, lambda: None, call, 0, throwing)
+    walk(vs, lambda: None, call, 0, throwing)

@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_deblur_gpu import _frame_by_frame, _walk
+from _stab_routes import batches, frame_by_frame, same, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -30,27 +30,11 @@ def clip8():
     return _clip()
 
 
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
-
-
 def _want(vs, frames, size, filt, fmt=None, **kw):
     """{k: vs_bgr_resize_batch of the off handle's output k}, and the off handle's states"""
     states = []
-    off = _frame_by_frame(vs.Stabilizer(**dict(KW, **kw)), frames, states)
+    off = frame_by_frame(vs.Stabilizer(**dict(KW, **kw)), frames, states)
     return {k: vs.resize_batch(off[k][None], size[0], size[1], filt, fmt=fmt)[0] for k in off}, off, states
-
-
-def _batches(st, frames, sizes, fmt=None):
-    out, i, k = {}, 0, 0
-    while i < len(frames):
-        m = min(sizes[k % len(sizes)], len(frames) - i)
-        o, has = st.process_batch(frames[i:i + m], fmt=fmt)
-        for j in range(m):
-            if has[j]:
-                out[i + j - st.params.lag] = o[j].copy()
-        i, k = i + m, k + 1
-    return out
 
 
 def test_off_is_the_handle_that_was(gpu_vs, clip8):
@@ -62,7 +46,7 @@ def test_off_is_the_handle_that_was(gpu_vs, clip8):
     assert never.get_output_size() is None and null.get_output_size() is None and null.delivered_size(W, H) == (W - 16, H - 16)
     assert vs.Stabilizer(output_size=(-1, -1), **KW).get_output_size() == (-1, -1, vs.RESIZE_LINEAR)
     s0, s1 = [], []
-    assert _same(_frame_by_frame(never, clip8, s0), _frame_by_frame(null, clip8, s1)) and s0 == s1
+    assert same(frame_by_frame(never, clip8, s0), frame_by_frame(null, clip8, s1)) and s0 == s1
 
     # allocation for allocation: switched on and off again is never switched on; on: the scratch block more.  A window that already has the
     # requested size is off: nothing launched (the same bytes), nothing allocated
@@ -99,18 +83,18 @@ def test_on_is_the_resize_of_the_off_handle_on_every_route(gpu_vs, clip8, size, 
         assert len(want) == N - LAG and all(v.shape == (dh, dw, 3) for v in want.values())
         kw = dict(KW, output_size=size + (filt,))
         s_on = []
-        assert _same(_frame_by_frame(vs.Stabilizer(**kw), clip8, s_on), want)
+        assert same(frame_by_frame(vs.Stabilizer(**kw), clip8, s_on), want)
         assert s_on == s_off                                 # transforms, state and has_output are left alone
-        assert _same(_batches(vs.Stabilizer(**kw), clip8, (N,)), want)
-        assert _same(_batches(vs.Stabilizer(**kw), clip8, (5,)), want)
-        assert _same(_batches(vs.Stabilizer(**kw), clip8, (13, 1)), want)
+        assert same(batches(vs.Stabilizer(**kw), clip8, (N,)), want)
+        assert same(batches(vs.Stabilizer(**kw), clip8, (5,)), want)
+        assert same(batches(vs.Stabilizer(**kw), clip8, (13, 1)), want)
         dev = torch.from_numpy(clip8).cuda()
         dout = torch.zeros((N, dh, dw, 3), dtype=torch.uint8, device="cuda")
         st = vs.Stabilizer(**kw)
         r, hs = st.process_batch_device(dev.data_ptr(), N, W, H, vs.FMT_BGR8, dout.data_ptr())
         torch.cuda.synchronize()
         res = dout.cpu().numpy()
-        assert r == len(want) and _same({i - LAG: res[i] for i, hh in enumerate(hs) if hh}, want)
+        assert r == len(want) and same({i - LAG: res[i] for i, hh in enumerate(hs) if hh}, want)
     # two clips through process_clips, host and device memory: each equals the clip on a handle of its own
     second = _clip(seed=9)
     want2, _, _ = _want(vs, second, delivered, filt)
@@ -136,10 +120,10 @@ def test_behind_fill_inpaint_sharpen_and_deflicker(gpu_vs):
     extra = dict(crop_pixels=8, border_fill=3, inpaint=1, sharpen=True, deflicker=3, deblur=2, denoise=2)
     for size, delivered in SIZES:
         want, off, _ = _want(vs, frames, delivered, vs.RESIZE_LINEAR, **extra)
-        plain = _frame_by_frame(vs.Stabilizer(**KW), frames)
-        assert not _same(off, plain)                         # premise: the passes did something
-        assert _same(_frame_by_frame(vs.Stabilizer(**dict(KW, output_size=size, **extra)), frames), want)
-        assert _same(_batches(vs.Stabilizer(**dict(KW, output_size=size, **extra)), frames, (5, 13)), want)
+        plain = frame_by_frame(vs.Stabilizer(**KW), frames)
+        assert not same(off, plain)                         # premise: the passes did something
+        assert same(frame_by_frame(vs.Stabilizer(**dict(KW, output_size=size, **extra)), frames), want)
+        assert same(batches(vs.Stabilizer(**dict(KW, output_size=size, **extra)), frames, (5, 13)), want)
 
 
 @pytest.mark.parametrize("mode", ["WARP_LANCZOS2", "WARP_LANCZOS2_FAST", "WARP_BILINEAR"])
@@ -147,8 +131,8 @@ def test_the_other_warp_modes(gpu_vs, clip8, mode):
     vs = gpu_vs
     extra = dict(warp_mode=getattr(vs, mode))
     want, _, _ = _want(vs, clip8, (W, H), vs.RESIZE_LINEAR, **extra)
-    assert _same(_batches(vs.Stabilizer(**dict(KW, output_size=(-1, -1), **extra)), clip8, (N,)), want)
-    assert _same(_frame_by_frame(vs.Stabilizer(**dict(KW, output_size=(-1, -1), **extra)), clip8), want)
+    assert same(batches(vs.Stabilizer(**dict(KW, output_size=(-1, -1), **extra)), clip8, (N,)), want)
+    assert same(frame_by_frame(vs.Stabilizer(**dict(KW, output_size=(-1, -1), **extra)), clip8), want)
 
 
 def test_ten_bit(gpu_vs):
@@ -159,8 +143,8 @@ def test_ten_bit(gpu_vs):
         want, off, _ = _want(vs, frames, delivered, vs.RESIZE_LINEAR, fmt=vs.FMT_BGR10)
         assert max(int(v.max()) for v in want.values()) > 255
         kw = dict(KW, output_size=size)
-        assert _same(_frame_by_frame(vs.Stabilizer(**kw), frames), want)
-        assert _same(_batches(vs.Stabilizer(**kw), frames, (5,), fmt=vs.FMT_BGR10), want)
+        assert same(frame_by_frame(vs.Stabilizer(**kw), frames), want)
+        assert same(batches(vs.Stabilizer(**kw), frames, (5,), fmt=vs.FMT_BGR10), want)
 
 
 @pytest.mark.parametrize("lag", [0, 6])
@@ -170,8 +154,8 @@ def test_lag_0_and_6(gpu_vs, clip8, lag):
         want, _, _ = _want(vs, clip8, delivered, vs.RESIZE_AREA if delivered[0] < W - 16 else vs.RESIZE_LINEAR, lag=lag)
         assert len(want) == N - lag
         kw = dict(KW, lag=lag, output_size=size + (vs.RESIZE_AREA if delivered[0] < W - 16 else vs.RESIZE_LINEAR,))
-        assert _same(_frame_by_frame(vs.Stabilizer(**kw), clip8), want)
-        assert _same(_batches(vs.Stabilizer(**kw), clip8, (13, 1)), want)
+        assert same(frame_by_frame(vs.Stabilizer(**kw), clip8), want)
+        assert same(batches(vs.Stabilizer(**kw), clip8, (13, 1)), want)
 
 
 def test_the_ycbcr_wrapper_equals_its_three_calls(gpu_vs, clip8):
@@ -224,32 +208,32 @@ def test_refusals_leave_the_state_alone(gpu_vs, clip8):
         states.append((m.tup(), a.tup(), s, o is not None))
         if o is not None:
             got[i - LAG] = o
-    assert _same(got, want) and states == s_off
+    assert same(got, want) and states == s_off
 
 
 def test_reset_and_a_size_change(gpu_vs, clip8):
     vs = gpu_vs
     want, _, _ = _want(vs, clip8, (W, H), vs.RESIZE_LINEAR)
     st = vs.Stabilizer(output_size=(-1, -1), **KW)
-    _frame_by_frame(st, _clip(seed=11))
+    frame_by_frame(st, _clip(seed=11))
     st.reset()
     assert st.get_output_size() == (-1, -1, vs.RESIZE_LINEAR)            # the size is a setting, not state
-    assert _same(_frame_by_frame(st, clip8), want)
+    assert same(frame_by_frame(st, clip8), want)
     # frames of another size: a new clip, delivered at ITS source size; then a fixed size mid-clip takes effect with the next call
     from video_stabilizer_amd import synth
     other = np.maximum(synth.make_clip(192, 144, N, seed=4, channels=3, pan=1.0, jitter_t=2.0)[0], 1)
-    off = _frame_by_frame(vs.Stabilizer(**KW), other)
-    on = _frame_by_frame(st, other)
-    assert _same(on, {k: vs.resize_batch(off[k][None], 192, 144)[0] for k in off})
+    off = frame_by_frame(vs.Stabilizer(**KW), other)
+    on = frame_by_frame(st, other)
+    assert same(on, {k: vs.resize_batch(off[k][None], 192, 144)[0] for k in off})
     st2, got = vs.Stabilizer(**KW), {}
-    off8 = _frame_by_frame(vs.Stabilizer(**KW), clip8)
+    off8 = frame_by_frame(vs.Stabilizer(**KW), clip8)
     for i, f in enumerate(clip8):
         if i == 8:
             st2.set_output_size(200, 150)
         o = st2.process(f)
         if o is not None:
             got[i - LAG] = o
-    assert _same(got, {k: (off8[k] if k + LAG < 8 else vs.resize_batch(off8[k][None], 200, 150)[0]) for k in off8})
+    assert same(got, {k: (off8[k] if k + LAG < 8 else vs.resize_batch(off8[k][None], 200, 150)[0]) for k in off8})
 
 
 CHILD = r'''
@@ -318,5 +302,5 @@ def test_resized_process_batch_survives_every_allocation_failure(gpu_vs, clip8, 
     allocations(lambda: vs.Stabilizer(output_size=(-1, -1), **kw))       # (the process-wide staging pool and rings fill on the first call)
     n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(lambda: vs.Stabilizer(output_size=(-1, -1), **kw))
     assert n_on == n_off + 1                                             # the scratch block joins the protocol
-    fired = _walk(vs, lambda: vs.Stabilizer(output_size=(-1, -1), **kw), call, n_on, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(output_size=(-1, -1), **kw), call, n_on, throwing)
     assert fired == n_on

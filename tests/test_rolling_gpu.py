@@ -6,9 +6,11 @@ import numpy as np
 import pytest
 
 import _denoise_ref as DN
+import _engine_model as EM
 import _hostile_maps as HM
 import _inpaint_ref as IP
 import _rolling_ref as R
+from _stab_routes import frame_by_frame
 from test_rolling_cpu import direction_errors
 
 pytestmark = pytest.mark.gpu
@@ -181,10 +183,6 @@ def _clip():
     return _clips["c"]
 
 
-def _frame_by_frame(st, frames):
-    return {i - st.params.lag: o for i, o in ((i, st.process(f)) for i, f in enumerate(frames)) if o is not None}
-
-
 ENGINE = {"alone": (dict(lag=4, crop_pixels=8), dict()),
           "all": (dict(lag=4, crop_pixels=0), dict(deblur=3, denoise=3, border_fill=4, inpaint=1))}
 
@@ -195,10 +193,10 @@ def test_the_engine_equals_the_engine_model(gpu_vs, oracle, case):
     frames = _clip()
     params, passes = ENGINE[case]
     rho = 0.8
-    want, fixed = R.engine_model(O, frames, rho, cvinv=HM.cvinv(vs), deblur=passes.get("deblur", 0), denoise=passes.get("denoise", 0),
-                                 fill=passes.get("border_fill", 0), inpaint=IP.inpaint if passes.get("inpaint") else None, **params)
-    got = _frame_by_frame(vs.Stabilizer(device=0, rolling_shutter=rho, **passes, **params), frames)
-    off = _frame_by_frame(vs.Stabilizer(device=0, **passes, **params), frames)
+    want = EM.engine_model(O, frames, cvinv=HM.cvinv(vs), deblur=passes.get("deblur", 0), denoise=passes.get("denoise", 0), rolling=rho,
+                           fill=passes.get("border_fill", 0), inpaint=IP.inpaint if passes.get("inpaint") else None, **params).outs
+    got = frame_by_frame(vs.Stabilizer(device=0, rolling_shutter=rho, **passes, **params), frames)
+    off = frame_by_frame(vs.Stabilizer(device=0, **passes, **params), frames)
     assert sorted(got) == sorted(want) == sorted(off) and len(want) > 8
     assert sum(int((got[k] != off[k]).sum()) for k in got) > 0.2 * sum(got[k].size for k in got)      # the pass did something
     same = [k for k in got if np.array_equal(got[k], off[k])]
@@ -229,8 +227,8 @@ def test_lag_0_and_a_failed_alignment_give_the_uncorrected_frame(gpu_vs):
     vs = gpu_vs
     frames = _clip()
     kw = dict(device=0, crop_pixels=8)
-    on = _frame_by_frame(vs.Stabilizer(lag=0, rolling_shutter=0.8, **kw), frames)
-    off = _frame_by_frame(vs.Stabilizer(lag=0, **kw), frames)
+    on = frame_by_frame(vs.Stabilizer(lag=0, rolling_shutter=0.8, **kw), frames)
+    off = frame_by_frame(vs.Stabilizer(lag=0, **kw), frames)
     assert sorted(on) == sorted(off) and len(on) > 8
     assert all(np.array_equal(on[k], off[k]) for k in on)
     # lag 4: frame k passes uncorrected exactly where the alignment of frame k + 1 failed
@@ -241,7 +239,7 @@ def test_lag_0_and_a_failed_alignment_give_the_uncorrected_frame(gpu_vs):
         states.append(st.state()[2])
         if o is not None:
             on[i - 4] = o
-    off = _frame_by_frame(vs.Stabilizer(lag=4, **kw), frames)
+    off = frame_by_frame(vs.Stabilizer(lag=4, **kw), frames)
     failed = [k for k in on if not states[k + 1]]
     assert failed and len(failed) < len(on)
     for k in on:

@@ -13,7 +13,7 @@ import pytest
 import _fill_ref as RF
 import _hostile_maps as HM
 import _rolling_ref as R
-from test_inpaint_stab_gpu import _walk
+from _stab_routes import walk
 
 pytestmark = pytest.mark.gpu
 
@@ -242,5 +242,5 @@ def test_corrected_process_batch_survives_every_allocation_failure(gpu_vs, throw
     allocations(lambda: vs.Stabilizer(**kw))                         # (the process-wide staging pool fills on the first call)
     n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(lambda: vs.Stabilizer(rolling_shutter=0.7, **kw))
     assert n_on == n_off + 1                                         # the scratch block joins the protocol
-    fired = _walk(vs, lambda: vs.Stabilizer(rolling_shutter=0.7, **kw), call, n_on, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(rolling_shutter=0.7, **kw), call, n_on, throwing)
     assert fired == n_on

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import _scene_ref as R
-from test_deblur_gpu import _frame_by_frame, _walk
+from _stab_routes import frame_by_frame, same, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +39,7 @@ def clips():
 def _run(st, frames, chunks=None):
     """-> {input frame index: output} through process (chunks None) or process_batch in chunks of the given sizes, cyclically"""
     if chunks is None:
-        return _frame_by_frame(st, frames)
+        return frame_by_frame(st, frames)
     out, i, k = {}, 0, 0
     while i < len(frames):
         m = min(chunks[k % len(chunks)], len(frames) - i)
@@ -49,10 +49,6 @@ def _run(st, frames, chunks=None):
                 out[i + j - st.params.lag] = o[j].copy()
         i, k = i + m, k + 1
     return out
-
-
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_off_is_the_plain_stabilizer(gpu_vs, clips):
@@ -65,8 +61,8 @@ def test_off_is_the_plain_stabilizer(gpu_vs, clips):
     p = on.get_scene_cut()
     assert (p.step, p.threshold) == (4, 32)
     s0, s1, s2 = [], [], []
-    o0, o1, o2 = _frame_by_frame(never, frames, s0), _frame_by_frame(null, frames, s1), _frame_by_frame(on, frames, s2)
-    assert len(o0) == 2 * N - KW["lag"] and _same(o0, o1) and _same(o0, o2)
+    o0, o1, o2 = frame_by_frame(never, frames, s0), frame_by_frame(null, frames, s1), frame_by_frame(on, frames, s2)
+    assert len(o0) == 2 * N - KW["lag"] and same(o0, o1) and same(o0, o2)
     assert s0 == s1 == s2
     followed = sum(1 for s in s0[1:] if s[2])
     print("the aligner follows %d of the shaky clip's %d steps" % (followed, len(s0) - 1))
@@ -74,7 +70,7 @@ def test_off_is_the_plain_stabilizer(gpu_vs, clips):
     assert on.scene_cuts() == (0, []) and never.scene_cuts() == (0, [])
     # the cut clip too: a handle that had detection switched on and off again is one that never had it
     null.reset()
-    assert _same(_frame_by_frame(vs.Stabilizer(**KW), clips["ab"]), _frame_by_frame(null, clips["ab"]))
+    assert same(frame_by_frame(vs.Stabilizer(**KW), clips["ab"]), frame_by_frame(null, clips["ab"]))
     assert null.scene_cuts() == (0, [])
 
 
@@ -132,11 +128,11 @@ def test_a_cut_is_detected_and_resets_the_path(gpu_vs, clips, case):
     c = kw["crop_pixels"]
     if case != "lanczos2":                                               # (the fixed-point warp under the identity is the copy)
         assert np.array_equal(got[N], frames[N][c:H - c, c:W - c])
-    assert _same(got, want)
+    assert same(got, want)
     # the batched forms: frame by frame, batches of 5, 12 and 13 (the cut last, first and second in its chunk), host memory
     for chunks in ([5], [12], [13], [1, 24]):
         s2 = vs.Stabilizer(scene_cut=p, **kw)
-        assert _same(_run(s2, frames, chunks), want), (case, chunks)
+        assert same(_run(s2, frames, chunks), want), (case, chunks)
         assert s2.scene_cuts() == (1, [N])
 
 
@@ -145,7 +141,7 @@ def test_device_memory_gives_the_same_bytes(gpu_vs, clips):
     vs = gpu_vs
     frames = clips["ab"]
     c, lag = KW["crop_pixels"], KW["lag"]
-    want = _frame_by_frame(vs.Stabilizer(scene_cut=True, **KW), frames)
+    want = frame_by_frame(vs.Stabilizer(scene_cut=True, **KW), frames)
     dev = torch.from_numpy(frames).cuda()
     for chunk in (24, 13, 5):
         st = vs.Stabilizer(scene_cut=True, **KW)
@@ -158,7 +154,7 @@ def test_device_memory_gives_the_same_bytes(gpu_vs, clips):
         torch.cuda.synchronize()
         o = out.cpu().numpy()
         got = {i - lag: o[i] for i in range(len(frames)) if has[i]}
-        assert _same(got, want), chunk
+        assert same(got, want), chunk
         assert st.scene_cuts() == (1, [N])
 
 
@@ -188,24 +184,24 @@ def test_the_leak_is_closed(gpu_vs, clips):
     assert len(found) == 2, "the aligner no longer follows two of the calm clips: the test input has to change"
     print("scene A is followed by seeds", [f[0] for f in found])
     clips = {"ab": found[0][1], "ab2": found[1][1]}
-    off_b, off_b2 = _frame_by_frame(vs.Stabilizer(**kw), clips["ab"]), _frame_by_frame(vs.Stabilizer(**kw), clips["ab2"])
+    off_b, off_b2 = frame_by_frame(vs.Stabilizer(**kw), clips["ab"]), frame_by_frame(vs.Stabilizer(**kw), clips["ab2"])
     leaked = [k for k in range(N) if not np.array_equal(off_b[k], off_b2[k])]
     print("without detection the following scene changes frames", leaked)
     assert leaked, "the following scene no longer reaches scene A's frames without detection: the test input has to change"
     on_b, on_b2 = vs.Stabilizer(scene_cut=True, **kw), vs.Stabilizer(scene_cut=True, **kw)
-    got_b, got_b2 = _frame_by_frame(on_b, clips["ab"]), _frame_by_frame(on_b2, clips["ab2"])
+    got_b, got_b2 = frame_by_frame(on_b, clips["ab"]), frame_by_frame(on_b2, clips["ab2"])
     assert on_b.scene_cuts() == (1, [N]) and on_b2.scene_cuts() == (1, [N])
     assert all(np.array_equal(got_b[k], got_b2[k]) for k in range(N))
     # ... and they are what scene A alone gives for the frames that finish before the cut frame arrives
-    alone = _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"][:N])
+    alone = frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"][:N])
     assert all(np.array_equal(got_b[k], alone[k]) for k in alone)
     # in batches too
-    assert _same(_run(vs.Stabilizer(scene_cut=True, **kw), clips["ab"], [13]), got_b)
+    assert same(_run(vs.Stabilizer(scene_cut=True, **kw), clips["ab"], [13]), got_b)
     # With the smoother on, frame k's correction is made when frame k + lag arrives, from the measurements up to that frame: frames 0 .. 12 - lag
     # see nothing behind the cut frame (whose measurement is the identity whatever follows) and stay identical; the rest of scene A may move
     # with the next scene's camera path (known limits) -- but only move: their candidate lists still end at the cut
     kw = dict(KW, crop_pixels=0, **PASSES)
-    sm_b, sm_b2 = _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"]), _frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab2"])
+    sm_b, sm_b2 = frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab"]), frame_by_frame(vs.Stabilizer(scene_cut=True, **kw), clips["ab2"])
     print("with the smoother on the following scene's motion reaches frames", [k for k in range(N) if not np.array_equal(sm_b[k], sm_b2[k])])
     assert all(np.array_equal(sm_b[k], sm_b2[k]) for k in range(N + 1 - kw["lag"]))
 
@@ -224,14 +220,14 @@ def test_state_changes(gpu_vs, clips):
     vs = gpu_vs
     frames = clips["ab"]
     st = vs.Stabilizer(scene_cut=True, **KW)
-    _frame_by_frame(st, frames)
+    frame_by_frame(st, frames)
     assert st.scene_cuts() == (1, [N]) and st.scene_cuts(cap=0) == (1, [])
     st.reset()
     assert st.scene_cuts() == (0, [])
     # after the reset the first frame has no predecessor: the second scene alone shows no cut, and indices count from the reset
-    _frame_by_frame(st, frames[N:])
+    frame_by_frame(st, frames[N:])
     assert st.scene_cuts() == (0, [])
-    _frame_by_frame(st, frames[:N])                                      # ... scene A behind scene B, without a reset: a cut at index 12
+    frame_by_frame(st, frames[:N])                                      # ... scene A behind scene B, without a reset: a cut at index 12
     assert st.scene_cuts() == (1, [N])
     # switched on between frames 11 and 12: the cut frame is the next frame, and is detected; switched on after it: nothing to detect
     for at, want in ((N, (1, [N])), (N + 1, (0, []))):
@@ -244,7 +240,7 @@ def test_state_changes(gpu_vs, clips):
     # a flash frame is two cuts; more than the list holds
     flash = np.concatenate([frames[:5], frames[N:N + 1], frames[5:N]])
     s3 = vs.Stabilizer(scene_cut=True, **KW)
-    _frame_by_frame(s3, flash)
+    frame_by_frame(s3, flash)
     assert s3.scene_cuts() == (2, [5, 6]) and s3.scene_cuts(cap=1) == (2, [6])
     # the parameter boundary at the handle
     for kw in (dict(step=0), dict(step=65), dict(threshold=0), dict(threshold=256)):
@@ -287,8 +283,8 @@ def test_process_batch_survives_every_allocation_failure(gpu_vs, clips, throwing
         return list(has), list(has2), out.tobytes(), out2.tobytes(), s.scene_cuts()
     for lag in (0, 4):
         kw = dict(KW, lag=lag, smoother_memory=2)
-        plain = _walk(vs, lambda: vs.Stabilizer(**kw), call, 1, throwing)
-        n = _walk(vs, lambda: vs.Stabilizer(scene_cut=True, **kw), call, plain + (1 if lag == 0 else 0), throwing)
+        plain = walk(vs, lambda: vs.Stabilizer(**kw), call, 1, throwing)
+        n = walk(vs, lambda: vs.Stabilizer(scene_cut=True, **kw), call, plain + (1 if lag == 0 else 0), throwing)
         print("lag %d: %d allocations failed one by one with detection (%s); %d without" % (lag, n, "throwing" if throwing else "error code", plain))
 
 

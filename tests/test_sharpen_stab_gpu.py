@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import _sharpen_ref as R
-from test_deblur_gpu import _frame_by_frame, _walk
+from _stab_routes import batches, frame_by_frame, same, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -40,27 +40,11 @@ def _sequence(vs, frames, fmt=None, **kw):
     strength = kw.pop("strength", 16)
     st = vs.Stabilizer(**kw)
     states = []
-    off = _frame_by_frame(st, frames, states)
+    off = frame_by_frame(st, frames, states)
     corr = {i - kw["lag"]: vs.t_inverse(vs.Transform.of(*a)) for i, (_, a, _, has) in enumerate(states) if has}
     assert sorted(corr) == sorted(off)
     want = {k: vs.sharpen_batch(off[k][None], [corr[k]], W, H, crop, crop, params=vs.sharpen_params(strength=strength), fmt=fmt)[0] for k in off}
     return off, want, corr
-
-
-def _same(a, b):
-    return sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
-
-
-def _batches(st, frames, sizes):
-    out, i, k = {}, 0, 0
-    while i < len(frames):
-        m = min(sizes[k % len(sizes)], len(frames) - i)
-        o, has = st.process_batch(frames[i:i + m])
-        for j in range(m):
-            if has[j]:
-                out[i + j - st.params.lag] = o[j].copy()
-        i, k = i + m, k + 1
-    return out
 
 
 def test_off_is_the_handle_that_was(gpu_vs, clip8):
@@ -72,7 +56,7 @@ def test_off_is_the_handle_that_was(gpu_vs, clip8):
     assert never.get_sharpen() is None and null.get_sharpen() is None
     assert vs.Stabilizer(sharpen=True, **KW).get_sharpen().strength == 16
     s0, s1 = [], []
-    assert _same(_frame_by_frame(never, clip8, s0), _frame_by_frame(null, clip8, s1)) and s0 == s1
+    assert same(frame_by_frame(never, clip8, s0), frame_by_frame(null, clip8, s1)) and s0 == s1
 
     # allocation for allocation: a handle that had the pass switched on and off again allocates what one that never had it does; on: one block more
     def allocations(make):
@@ -111,17 +95,17 @@ def test_on_is_the_kernel_level_sequence_on_every_route(gpu_vs, clip8, strength)
     assert np.array_equal(want[k0], R.sharpen(vs, off[k0], corr[k0], W, H, (8, 8, W - 16, H - 16), strength, 255))
     kw = dict(KW, sharpen=vs.sharpen_params(strength=strength))
     s_on, s_off = [], []
-    assert _same(_frame_by_frame(vs.Stabilizer(**kw), clip8, s_on), want)
-    _frame_by_frame(vs.Stabilizer(**KW), clip8, s_off)
+    assert same(frame_by_frame(vs.Stabilizer(**kw), clip8, s_on), want)
+    frame_by_frame(vs.Stabilizer(**KW), clip8, s_off)
     assert s_on == s_off                                                 # transforms, state and has_output are left alone
-    assert _same(_batches(vs.Stabilizer(**kw), clip8, (N,)), want)
-    assert _same(_batches(vs.Stabilizer(**kw), clip8, (3, 1, 5, 2)), want)
+    assert same(batches(vs.Stabilizer(**kw), clip8, (N,)), want)
+    assert same(batches(vs.Stabilizer(**kw), clip8, (3, 1, 5, 2)), want)
     dev = torch.from_numpy(clip8).cuda()
     dout = torch.zeros((N, H - 16, W - 16, 3), dtype=torch.uint8, device="cuda")
     r, hs = vs.Stabilizer(**kw).process_batch_device(dev.data_ptr(), N, W, H, vs.FMT_BGR8, dout.data_ptr())
     torch.cuda.synchronize()
     res = dout.cpu().numpy()
-    assert r == len(want) and _same({i - LAG: res[i] for i, hh in enumerate(hs) if hh}, want)
+    assert r == len(want) and same({i - LAG: res[i] for i, hh in enumerate(hs) if hh}, want)
     # two clips through process_clips: each equals the clip on a handle of its own
     second = _clip(seed=9)
     off2, want2, _ = _sequence(vs, second, strength=strength)
@@ -144,11 +128,11 @@ def test_ten_bit(gpu_vs):
     frames = _clip(bits=10)
     assert frames.dtype == np.uint16 and frames.max() > 255
     off, want, _ = _sequence(vs, frames, fmt=vs.FMT_BGR10)
-    assert not _same(off, want)
+    assert not same(off, want)
     kw = dict(KW, sharpen=True)
-    assert _same(_frame_by_frame(vs.Stabilizer(**kw), frames), want)     # (uint16 numpy frames are 10-bit unless the caller says otherwise)
+    assert same(frame_by_frame(vs.Stabilizer(**kw), frames), want)     # (uint16 numpy frames are 10-bit unless the caller says otherwise)
     out, has = vs.Stabilizer(**kw).process_batch(frames, fmt=vs.FMT_BGR10)
-    assert _same({i - LAG: out[i] for i, hh in enumerate(has) if hh}, want)
+    assert same({i - LAG: out[i] for i, hh in enumerate(has) if hh}, want)
 
 
 def test_fill_and_inpaint_pixels_are_unchanged_at_crop_0(gpu_vs, clip8):
@@ -158,9 +142,9 @@ def test_fill_and_inpaint_pixels_are_unchanged_at_crop_0(gpu_vs, clip8):
     frames = _clip(20, 5, pan=2.0, jitter_t=4.0)
     extra = dict(crop_pixels=0, border_fill=3, inpaint=1)
     off, want, corr = _sequence(vs, frames, **extra)
-    on = _frame_by_frame(vs.Stabilizer(**dict(KW, sharpen=True, **extra)), frames)
-    assert _same(on, want)
-    plain = _frame_by_frame(vs.Stabilizer(**dict(KW, crop_pixels=0)), frames)
+    on = frame_by_frame(vs.Stabilizer(**dict(KW, sharpen=True, **extra)), frames)
+    assert same(on, want)
+    plain = frame_by_frame(vs.Stabilizer(**dict(KW, crop_pixels=0)), frames)
     open_px = kept = 0
     for k in off:
         X, Y = R.positions(vs, corr[k], W, H)
@@ -179,10 +163,10 @@ def test_the_deflickers_gain_stays_last(gpu_vs):
     vs = gpu_vs
     frames = _clip(16, 5).astype(np.float64)
     frames = np.clip(frames * (0.8 + 0.15 * np.sin(np.arange(16) * 1.3))[:, None, None, None], 1, 255).astype(np.uint8)
-    w_ = _frame_by_frame(vs.Stabilizer(**KW), frames)                                   # warp
-    y_ = _frame_by_frame(vs.Stabilizer(deflicker=3, **KW), frames)                      # gain(warp)
-    z_ = _frame_by_frame(vs.Stabilizer(sharpen=True, **KW), frames)                     # sharpen(warp)
-    x_ = _frame_by_frame(vs.Stabilizer(sharpen=True, deflicker=3, **KW), frames)        # both
+    w_ = frame_by_frame(vs.Stabilizer(**KW), frames)                                   # warp
+    y_ = frame_by_frame(vs.Stabilizer(deflicker=3, **KW), frames)                      # gain(warp)
+    z_ = frame_by_frame(vs.Stabilizer(sharpen=True, **KW), frames)                     # sharpen(warp)
+    x_ = frame_by_frame(vs.Stabilizer(sharpen=True, deflicker=3, **KW), frames)        # both
     checked = scaled = 0
     for k in w_:
         for c in range(3):
@@ -195,17 +179,17 @@ def test_the_deflickers_gain_stays_last(gpu_vs):
             checked += int(known.sum())
             scaled += int((table[zi][known] != zi[known]).sum())
     assert checked > 100000 and scaled > 1000
-    assert not _same(z_, w_) and not _same(x_, y_)
+    assert not same(z_, w_) and not same(x_, y_)
 
 
 def test_reset_and_refusals(gpu_vs, clip8):
     vs = gpu_vs
     _, want, _ = _sequence(vs, clip8)
     st = vs.Stabilizer(sharpen=True, **KW)
-    _frame_by_frame(st, _clip(seed=11))
+    frame_by_frame(st, _clip(seed=11))
     st.reset()
     assert st.get_sharpen().strength == 16                               # the switch is a setting, not state
-    assert _same(_frame_by_frame(st, clip8), want)
+    assert same(frame_by_frame(st, clip8), want)
     # a Lanczos2 handle is refused with the fill's wording; a strength outside 1 .. 32 is an argument error and leaves the setting alone
     lz = vs.Stabilizer(warp_mode=vs.WARP_LANCZOS2_FAST, **KW)
     with pytest.raises(vs.VsError, match="error -3.*sharpen: VS_WARP_BILINEAR_CV handles only"):
@@ -304,6 +288,6 @@ def test_sharpened_process_batch_survives_every_allocation_failure(gpu_vs, clip8
     allocations(lambda: vs.Stabilizer(**kw))                             # (the process-wide staging pool fills on the first call)
     n_off, n_on = allocations(lambda: vs.Stabilizer(**kw)), allocations(lambda: vs.Stabilizer(sharpen=True, **kw))
     assert n_on == n_off + 1                                             # the scratch block joins the protocol
-    fired = _walk(vs, lambda: vs.Stabilizer(sharpen=True, **kw), call, n_on, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(sharpen=True, **kw), call, n_on, throwing)
     print("sharpened process_batch: %d allocations failed one by one (%s)" % (fired, "throwing" if throwing else "error code"))
     assert fired == n_on

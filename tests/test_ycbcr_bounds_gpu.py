@@ -2,40 +2,22 @@
 offsets go through VS_IDX, sites 602-615).  The ycbcr modules run in a child pytest with VS_AMD_LIB pointing at variants/libvs_amd_bounds.so, set
 up the way tests/test_lens_bounds_gpu.py sets up its children: every result must still be bit-identical (the checks change no arithmetic)
 and after every test the bounds record must be clean (tests/conftest.py::_bounds_record_stays_clean)."""
-import os
-import subprocess
-import sys
-
 import pytest
 
+from _bounds_child import bounds_lib, child_pytest, child_python
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "video_stabilizer_amd", "variants", "libvs_amd_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def bounds_lib(gpu_vs):
-    # (built on demand, and again whenever a source of the library is newer than it: a stale variant would test yesterday's kernels)
-    csrc = os.path.join(ROOT, "video_stabilizer_amd", "csrc")
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc", ".cpp"))] + [os.path.join(ROOT, "include", "vs_amd.h")]
-    if not os.path.exists(LIB) or max(os.path.getmtime(f) for f in srcs) > os.path.getmtime(LIB):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "bounds"])
-    assert os.path.exists(LIB)
-    return LIB
 
 
 def test_the_bounds_build_carries_the_ycbcr_record(bounds_lib):
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from video_stabilizer_amd import capi\n"
+    code = ("from video_stabilizer_amd import capi\n"
             "import numpy as np\n"
             "y = np.arange(2 * 5 * 8, dtype=np.uint8).reshape(2, 5, 8)\n"
             "c = np.arange(2 * 3 * 4, dtype=np.uint8).reshape(2, 3, 4)\n"
             "bgr = capi.ycbcr_to_bgr_batch(y, c, c)\n"
             "capi.bgr_to_ycbcr_batch(bgr, interleaved='nv12')\n"
-            "print('clean', capi.debug_bounds_check())\n" % ROOT)
-    env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
+            "print('clean', capi.debug_bounds_check())\n")
+    out = child_python(code, bounds_lib)
     assert "clean (0, '')" in out.stdout
 
 
@@ -44,11 +26,6 @@ def test_the_ycbcr_modules_pass_on_the_bounds_build_with_a_clean_record(bounds_l
     and the stabilizer's wrapper, without the allocation-failure walks, the 65 537-frame case and the tests that start children of their
     own; the CPU module rides along"""
     # (every fresh device allocation of these runs starts filled with 0xA5: nothing compared against the restatement may depend on it)
-    env = dict(os.environ, VS_AMD_LIB=bounds_lib, VS_BOUNDS_BUILD="1", VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")
     mods = ["tests/test_ycbcr_hostile_gpu.py", "tests/test_ycbcr_gpu.py", "tests/test_ycbcr_stab_gpu.py", "tests/test_ycbcr_cpu.py"]
     expr = "not allocation_failure and not fresh_allocations and not more_frames_than_a_grid"
-    cmd = [sys.executable, "-m", "pytest", *mods, "-x", "-q", "-p", "no:cacheprovider", "-k", expr]
-    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
-    tail = out.stdout[-3000:] + out.stderr[-1500:]
-    assert out.returncode == 0, tail
-    assert " passed" in out.stdout and "failed" not in out.stdout, tail
+    child_pytest(mods, expr, bounds_lib, 1200, VS_TEST_POISON_ALLOC="165", VS_TEST_HOOKS="1")

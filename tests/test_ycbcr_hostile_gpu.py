@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import _ycbcr_ref as R
-from test_inpaint_stab_gpu import _walk
+from _stab_routes import walk
 from test_lens_hostile_gpu import G, _banded
 
 pytestmark = pytest.mark.gpu
@@ -245,8 +245,8 @@ def test_the_batch_calls_survive_every_allocation_failure(gpu_vs, throwing):
     def to_ycbcr(_):
         return b"".join(p.tobytes() for p in vs.bgr_to_ycbcr_batch(want, interleaved="nv12"))
     assert to_bgr(None) == want.tobytes() and to_ycbcr(None) == b"".join(p.tobytes() for p in wantp)
-    _walk(vs, lambda: None, to_bgr, 0, throwing)
-    _walk(vs, lambda: None, to_ycbcr, 0, throwing)
+    walk(vs, lambda: None, to_bgr, 0, throwing)
+    walk(vs, lambda: None, to_ycbcr, 0, throwing)
 
 
 @pytest.mark.parametrize("throwing", [False, True])
@@ -271,5 +271,5 @@ def test_process_batch_ycbcr_survives_every_allocation_failure(gpu_vs, throwing)
     allocations(call)                                                              # (the process-wide staging pool fills on the first call)
     n = allocations(call)
     assert n >= 2                                                                  # a fresh handle's two BGR buffers at the least
-    fired = _walk(vs, lambda: vs.Stabilizer(**kw), call, n, throwing)
+    fired = walk(vs, lambda: vs.Stabilizer(**kw), call, n, throwing)
     assert fired == n
